@@ -1,6 +1,6 @@
 """Benchmark of the hot path: env-steps/s of the vectorised Go2 joystick_pgtt step on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--envs 4096] [--workload level4|flat|level13_dr|wfc_dr|curriculum]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--envs 4096] [--workload level4|flat|level13_dr|wfc_dr|curriculum] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 A "step" is one control step (4 physics substeps + 13x9 scan + obs + 21 rewards + bookkeeping, with the
@@ -18,11 +18,19 @@ nothing in the timed window loads a code object or creates an event for the firs
 ms_per_step / (physics + observe + the interval reduction's share of a step); "cold": true (and exit code 3) when it exceeds 1.5.
 
 Prints ONE JSON line (rank 0).  `roofline` is for the dominant kernel (physics_kernel) with ITS share of the algorithmic work
-(1.2 MFLOP, 0.8 KB per env-step), `roofline_observe` / `roofline_step` the scan kernel and the whole step; `cpu_baseline` is the
-build's own CPU restatement (oracle/, kind "port") timed on this box's host cores on a bounded sample.  With one GPU the line
-also carries `other_configs`: BASELINE configs[1] (flat, 4096), configs[3] (WFC + DR, 8192), level4 at 32768 envs, the seven per-rank
-workloads of configs[4] (one curriculum level file each, 4096 envs), the step loop replayed as ONE HIP graph per 20 steps, the roll-out row
-and the 1-ulp-division side build, 100 steps each after the headline window (never part of `value`; --no-other-configs skips them).
+(1.2 MFLOP, 0.8 KB per env-step), `roofline_observe` / `roofline_step` the scan kernel and the whole step (all from the headline window's
+own kernel events, no run of their own).  A plain run does nothing else: set-up, warm-up, the K timed steps, the outputs, the line.
+
+--full adds what takes runs of its own, after the headline window (never part of `value`): `cpu_baseline`, the build's own CPU
+restatement (oracle/, kind "port") timed on the host's cores on a bounded sample (--no-cpu-baseline skips it), and with one GPU
+`other_configs`: BASELINE configs[1] (flat, 4096), configs[3] (WFC + DR, 8192), level4 at 32768 envs, the seven per-rank workloads of
+configs[4] (one curriculum level file each, 4096 envs), the step loop replayed as ONE HIP graph per 20 steps, the roll-out row and the
+1-ulp-division side build, 100 steps each (--no-other-configs skips them).
+
+--dump-outputs DIR writes what the last timed step returned to its caller (env.step: observations, reward, done, info) as DIR/<name>.npy,
+float32, at most 64 MB in all (above that, the same seeded sample of envs from every array, its indices in DIR/env_index.npy); with
+more than one rank each rank writes <name>_rank<r>.npy.  Inputs (reset seed, terrain variants, action pool) are fixed by the arguments,
+so two builds can be compared output for output.
 
 `roofline.traffic` / `valu_busy` / `mfma_ops` come from the rocprofv3 --pmc passes committed under profiles/ (hbm_traffic.json, which
 records the SHA-256 of the kernel sources it was measured on); when the sources of the library being timed differ they are null and
@@ -76,6 +84,8 @@ def parse_args(argv=None):
     ap.add_argument("--envs", type=int, default=4096, help="envs per GPU")
     ap.add_argument("--workload", default="level4", choices=["level4", "flat", "level13_dr", "wfc_dr", "curriculum"])
     ap.add_argument("--stage", type=int, default=None, help="curriculum workload: index into the level list (default: the rank)")
+    ap.add_argument("--full", action="store_true", help="also the measurements that take runs of their own: cpu_baseline and other_configs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's outputs as DIR/<name>.npy (float32, <= 64 MB)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-sample-steps", type=int, default=200)
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"], help="gloo: CPU test hook with a stub env (not a result)")
@@ -170,9 +180,10 @@ WORKLOAD_TEXT = {
 OTHER_CONFIGS = [("flat", 4096, "BASELINE configs[1]"), ("wfc_dr", 8192, "BASELINE configs[3]"), ("level4", 32768, "single-GPU saturation of configs[2]")]
 
 
-def timed_window(env, n, steps, warmup, dev, rank, world, stub, sync, prime_steps=PRIME_STEPS):
+def timed_window(env, n, steps, warmup, dev, rank, world, stub, sync, prime_steps=PRIME_STEPS, keep_outputs=False):
     """prime every code path, W untimed warm-up steps, then EXACTLY `steps` steps between barrier + synchronize on both sides.
-    -> dict(dt = max-over-ranks wall seconds, ranks, physics_ms, observe_ms, launches, gemv_ms, env_steps)"""
+    -> dict(dt = max-over-ranks wall seconds, ranks, physics_ms, observe_ms, launches, gemv_ms, env_steps
+    [, outputs = host copies of what the last timed step returned, keep_outputs only])"""
     import torch
     import torch.distributed as dist
     from phase_guided_terrain_traversal_amd.distributed import MetricReducer
@@ -189,9 +200,11 @@ def timed_window(env, n, steps, warmup, dev, rank, world, stub, sync, prime_step
         out = reducer.reduce_env(env, float(nsteps) * n) if native_reduce else reducer.reduce_block(sums, float(nsteps) * n)
         env_steps_seen.add_(out["env_steps"])
 
+    last = [None]
+
     def run(k0, k1):
         for k in range(k0, k1):
-            env.step(pool[k % len(pool)])
+            last[0] = env.step(pool[k % len(pool)])
             if (k + 1) % REDUCE_EVERY == 0:
                 flush(REDUCE_EVERY)
 
@@ -247,6 +260,7 @@ def timed_window(env, n, steps, warmup, dev, rank, world, stub, sync, prime_step
         dist.barrier()
     sync()
     dt = time.perf_counter() - t0
+    outputs = step_outputs(last[0]) if keep_outputs else None      # before the tail reduction below touches any buffer
     ranks, ranks_dt = 1, [dt_own]
     if steps % REDUCE_EVERY:
         flush(steps % REDUCE_EVERY)                    # the tail of the last interval (outside the clock)
@@ -262,7 +276,33 @@ def timed_window(env, n, steps, warmup, dev, rank, world, stub, sync, prime_step
     phys_ms, obs_ms, ntimed = env.kernel_ms_mean()
     env.enable_timing(False)
     return {"dt": dt, "ranks": ranks, "ranks_dt": ranks_dt, "untimed_steps": untimed, "physics_ms": phys_ms, "observe_ms": obs_ms, "launches": ntimed, "gemv_ms": gemv_ms,
-            "env_steps": float(env_steps_seen.item()), "done_frac": float(env.buffers["done"].mean().item())}
+            "env_steps": float(env_steps_seen.item()), "done_frac": float(env.buffers["done"].mean().item()), "outputs": outputs}
+
+
+DUMP_BYTES = 64 * 10 ** 6              # --dump-outputs: every file of one run together, .npy headers included
+
+
+def step_outputs(ret):
+    """env.step's return (obs dict, reward, done, info dict) -> {name: host float32 array}: obs_state, obs_privileged_state, reward, done,
+    info_metrics, info_episode_metrics (the stub env of the gloo hook returns reward and done only)"""
+    obs, reward, done, info = ret
+    named = [(f"obs_{k}", v) for k, v in (obs or {}).items()] + [("reward", reward), ("done", done)] + [(f"info_{k}", v) for k, v in (info or {}).items()]
+    return {k: v.detach().cpu().numpy().astype(np.float32) for k, v in named if v is not None}
+
+
+def dump_outputs(out_dir, outputs, n, rank, world):
+    """DIR/<name>.npy for every output (<name>_rank<r>.npy with several ranks).  The env axis is the one of length n (the last one of the
+    [rows][N] arrays, the first one otherwise); above this rank's share of DUMP_BYTES every array keeps the same seeded sample of envs."""
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = f"_rank{rank}" if world > 1 else ""
+    total = sum(a.nbytes for a in outputs.values())
+    budget = DUMP_BYTES // max(world, 1) - 8 * n - 256 * (len(outputs) + 1)       # room for env_index.npy and the headers
+    if total > budget:
+        keep = np.sort(np.random.default_rng(0).choice(n, max(1, int(n * budget / total)), replace=False))
+        outputs = {k: np.take(a, keep, axis=a.ndim - 1 if a.shape[-1] == n else 0) for k, a in outputs.items()}
+        np.save(os.path.join(out_dir, f"env_index{suffix}.npy"), keep.astype(np.float64))
+    for k, a in outputs.items():
+        np.save(os.path.join(out_dir, f"{k}{suffix}.npy"), np.ascontiguousarray(a))
 
 
 def profile_record(workload, n):
@@ -538,9 +578,11 @@ def worker(args):
         env, cfg, terrain, task, dr = build_env(args, rank, world, local)
         sync = torch.cuda.synchronize
     n = args.envs
-    w = timed_window(env, n, args.steps, args.warmup, dev, rank, world, stub, sync, args.prime_steps)
+    w = timed_window(env, n, args.steps, args.warmup, dev, rank, world, stub, sync, args.prime_steps, keep_outputs=args.dump_outputs is not None)
     dt, ranks, env_steps = w["dt"], w["ranks"], w["env_steps"]
     env.close()
+    if args.dump_outputs is not None:
+        dump_outputs(args.dump_outputs, w["outputs"], n, rank, world)
 
     rc = 0
     if rank == 0:
@@ -571,9 +613,9 @@ def worker(args):
         if env_steps != float(n) * world * args.steps or ranks != world:
             out["error"] = f"all-reduce saw {env_steps} env-steps from {ranks} ranks, expected {float(n) * world * args.steps} from {world}"
             rc = 4
-        if world == 1 and not stub and not args.no_other_configs:
+        if world == 1 and not stub and args.full and not args.no_other_configs:
             out["other_configs"] = other_configs(args, local, dev, sync)
-        if world == 1 and not args.no_cpu_baseline and not stub:
+        if world == 1 and args.full and not args.no_cpu_baseline and not stub:
             out["cpu_baseline"] = cpu_baseline(args, cfg, terrain, task, n)
         print(json.dumps(out), flush=True)
         if out["cold"] and not stub:

@@ -125,6 +125,26 @@ def test_bench_loop_world2_spawned_gloo():
     assert abs(d["value"] - d["env_steps_allreduced"] / (d["ms_per_step"] * 1e-3 * 45)) < 1e-6 * d["value"]
 
 
+def test_bench_dump_outputs_gloo(tmp_path):
+    """--dump-outputs on the gloo test hook: every rank writes what its last timed step returned (the stub's reward and done rows) as float32
+    <name>_rank<r>.npy; the same arguments give the same files"""
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    dumps = []
+    for i in range(2):
+        out = tmp_path / f"run{i}"
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "21", "--warmup", "3",
+                            "--envs", "32", "--dump-outputs", str(out)], env=env, capture_output=True, text=True, timeout=300)
+        assert p.returncode == 0, p.stderr[-2000:]
+        d = _bench_line(p.stdout)
+        assert d["steps"] == 21 and "cpu_baseline" not in d and "other_configs" not in d
+        assert sorted(os.listdir(out)) == ["done_rank0.npy", "done_rank1.npy", "reward_rank0.npy", "reward_rank1.npy"]
+        dumps.append({f: np.load(out / f) for f in os.listdir(out)})
+    for f, a in dumps[0].items():
+        assert a.dtype == np.float32 and a.shape == (32,) and np.array_equal(a, dumps[1][f]), f
+    assert (dumps[0]["reward_rank0.npy"] == 1.0).all() and (dumps[0]["reward_rank1.npy"] == 2.0).all()      # the stub's rank-dependent reward row
+
+
 def test_bench_loop_world8_spawned_gloo():
     """the shape of the run the driver makes on an 8-GPU node (BASELINE configs[4]: eight ranks), on the gloo test hook: eight spawned ranks, every one's
     env-steps in the all-reduced count, one JSON line, one `ranks_dt` entry per rank"""

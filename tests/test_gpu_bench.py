@@ -1,11 +1,14 @@
-"""The driver's own command, `python bench.py --gpus 1 --steps 20 --warmup 5`, on the GPU box: ONE JSON line with the contract's fields, the metric of
-BASELINE.json on its configuration, `roofline` and `cpu_baseline`, and the side rows this repository adds (other single-GPU configs, the roll-out
-row, one-HIP-graph row, the seven curriculum levels of configs[4], the 1-ulp-division side build).  A guard for the measurement, not a benchmark: thresholds are far below the measured values."""
+"""The driver's own command, `python bench.py --gpus 1 --steps 20 --warmup 5`, on the GPU: ONE JSON line with the contract's fields and the metric of
+BASELINE.json on its configuration, nothing beyond the headline window, and the outputs of its last timed step with --dump-outputs.  With --full the same
+line also carries `cpu_baseline` and the side rows this repository adds (other single-GPU configs, the roll-out row, one-HIP-graph row, the seven
+curriculum levels of configs[4], the 1-ulp-division side build).  A guard for the measurement, not a benchmark: thresholds are far below the measured values."""
 import json
 import os
 import subprocess
 import sys
+import time
 
+import numpy as np
 import pytest
 
 torch = pytest.importorskip("torch")
@@ -14,14 +17,60 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def test_driver_command_line_contract():
+DRIVER = ["--gpus", "1", "--steps", "20", "--warmup", "5"]
+OUTPUTS = {"obs_state": (4096, None), "obs_privileged_state": (4096, None), "reward": (4096,), "done": (4096,), "info_metrics": (None, 4096),
+           "info_episode_metrics": (None, 4096)}
+
+
+def _bench(extra, timeout):
+    """-> (JSON line, wall seconds of the whole process)"""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "PGTT_LIB")}
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--cpu-sample-steps", "25"],
-                       env=env, capture_output=True, text=True, timeout=1500)
+    t0 = time.perf_counter()
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + DRIVER + extra, env=env, capture_output=True, text=True, timeout=timeout)
+    wall = time.perf_counter() - t0
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
-    d = json.loads(lines[0])
+    return json.loads(lines[0]), wall
+
+
+def _load_outputs(d):
+    got = {f[:-4]: np.load(os.path.join(d, f)) for f in os.listdir(d)}
+    assert set(got) == set(OUTPUTS), sorted(got)
+    for k, shape in OUTPUTS.items():
+        a = got[k]
+        assert a.dtype == np.float32 and a.ndim == len(shape) and all(s is None or s == t for s, t in zip(shape, a.shape)), (k, a.shape)
+        assert np.isfinite(a).all(), k
+    assert sum(os.path.getsize(os.path.join(d, f)) for f in os.listdir(d)) <= 64 * 10 ** 6
+    return got
+
+
+@pytest.fixture(scope="module")
+def plain_run(tmp_path_factory):
+    out = str(tmp_path_factory.mktemp("plain") / "outputs")
+    d, wall = _bench(["--dump-outputs", out], 600)
+    return d, wall, out
+
+
+def test_plain_run_is_lean_and_dumps_the_last_step(plain_run):
+    """the plain command times the headline workload and nothing else: no cpu_baseline, no other_configs, at most 30 s of the process outside
+    its warm-up and timed steps; --dump-outputs leaves what the last timed step returned to its caller"""
+    d, wall, out = plain_run
+    assert d["steps"] == 20 and d["warmup"] == 5 and "cpu_baseline" not in d and "other_configs" not in d and "error" not in d
+    assert d["env_steps_allreduced"] == d["env_steps_expected"] == 4096 * 20
+    assert abs(d["value"] - d["env_steps_allreduced"] / (d["ms_per_step"] * 1e-3 * 20)) < 1e-6 * d["value"]
+    assert d["unit"] == "env-steps/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert wall - (20 + 5) * d["ms_per_step"] * 1e-3 < 30, wall
+    got = _load_outputs(out)
+    assert set(np.unique(got["done"])) <= {0.0, 1.0}
+
+
+def test_driver_command_line_contract(plain_run, tmp_path):
+    d, _ = _bench(["--full", "--cpu-sample-steps", "25", "--dump-outputs", str(tmp_path / "full")], 1500)
+    # --full changes nothing about the headline window: the same inputs, the same outputs, bit for bit
+    ref = _load_outputs(plain_run[2])
+    for k, a in _load_outputs(str(tmp_path / "full")).items():
+        assert np.array_equal(a, ref[k]), k
     base = json.load(open(os.path.join(ROOT, "BASELINE.json")))
     assert d["metric"] == base["metric"] and d["unit"] == "env-steps/s" and d["n_gpus"] == 1 and d["steps"] == 20
     assert d["higher_is_better"] is True and d["scaling"] == "weak" and d["vs_baseline"] is None and d["dtype"] == "f32" and d["data"] == "synthetic"

@@ -2,8 +2,8 @@
 # bench lines (the driver's exact command first, its stdout KEPT), rocprofv3 kernel trace of the default bench, PMC passes (separate runs,
 # counters only) -> gpurun_out/$ROUND_TAG/ ; tools/collect_profiles.py copies the summaries into profiles/
 cd $GRAFT_REPO_ROOT; export TMPDIR=/tmp; O=gpurun_out/${ROUND_TAG:-r02}; mkdir -p $O
-python bench.py --gpus 1 --steps 20 --warmup 5 > $O/driver_cmd_bench.json 2>$O/driver_cmd_bench.err; echo "driver command rc=$?"; cat $O/driver_cmd_bench.json
-python bench.py --no-other-configs > $O/bench_level4.json 2>$O/bench_level4.err
+python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/driver_cmd_bench.json 2>$O/driver_cmd_bench.err; echo "driver command rc=$?"; cat $O/driver_cmd_bench.json
+python bench.py --full --no-other-configs > $O/bench_level4.json 2>$O/bench_level4.err
 python bench.py --workload flat --no-cpu-baseline --no-other-configs > $O/bench_flat.json 2>/dev/null
 python bench.py --workload wfc_dr --envs 8192 --no-cpu-baseline --no-other-configs > $O/bench_wfc_dr_8192.json 2>/dev/null
 python bench.py --layout quad --no-cpu-baseline --no-other-configs > $O/bench_level4_quad.json 2>/dev/null
@@ -26,7 +26,7 @@ done
 cp $O/kt/*kernel_stats.csv $O/kernel_stats.csv
 # round 4: the caller of the hot path on the record - kernel trace of the driver's command WITH its other_configs rows (the 'rollout' row: policy_act_kernel,
 # rollout_record_kernel next to the two env kernels) and of a short train.py run (acting step + PPO update)
-rocprofv3 --kernel-trace --stats -d $O/kt_rollout -o kt --output-format csv -- python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > $O/kt_rollout_bench.json 2>/dev/null
+rocprofv3 --kernel-trace --stats -d $O/kt_rollout -o kt --output-format csv -- python bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu-baseline > $O/kt_rollout_bench.json 2>/dev/null
 cp $O/kt_rollout/*kernel_stats.csv $O/train_rollout_kernel_stats.csv
 rocprofv3 --kernel-trace --stats -d $O/kt_train -o kt --output-format csv -- python train.py --task_name stairs --terrain_file level4 --num_envs 4096 --num_timesteps 6553600 --num_evals 5 --index 904 > $O/train_run.txt 2>&1
 cp $O/kt_train/*kernel_stats.csv $O/train_ppo_kernel_stats.csv; tail -5 $O/train_run.txt
