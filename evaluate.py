@@ -54,6 +54,48 @@ def load_policy_from_args(args, tmp_dir):
     return PolicyMLP(os.path.join(args.checkpoint_folder, npz[-1])).to(DEVICE)
 
 
+class VideoRecorder:
+    """--video: renders the first --video_envs evaluation envs with a tracking camera before every --video_every-th control step (frames stay
+    on the device: [H, K * W, 3] per frame, the envs side by side, a progress bar of the episode along the bottom rows) and writes them at
+    the end (render.save_gif: a GIF, or a PNG sequence where PIL is missing).  Only reads the env."""
+
+    def __init__(self, args, env, episode_length):
+        from phase_guided_terrain_traversal_amd.render import Camera, Renderer
+        w, h = (int(x) for x in args.video_size.lower().split("x"))
+        self.env, self.path, self.every, self.L = env, args.video, max(1, int(args.video_every)), episode_length
+        self.ids = list(range(min(int(args.video_envs), env.num_envs)))
+        self.scan = bool(args.video_scan)
+        self.renderer = Renderer(env, w, h, shadows=True)
+        self.camera = Camera("track", target=(0.0, 0.0, 0.0), distance=2.2, azimuth=120.0, elevation=-25.0, fovy=45.0)
+        self.frames = []
+
+    def capture(self, t):
+        if t % self.every:
+            return
+        from phase_guided_terrain_traversal_amd.render import scan_points
+        markers = None
+        if self.scan:
+            p = scan_points(self.env, self.ids)
+            markers = torch.cat([p, torch.full_like(p[..., :1], 0.012)], -1)
+        rgb = self.renderer.render(self.ids, camera=self.camera, markers=markers)["rgb"]
+        v, h, w, _ = rgb.shape
+        frame = rgb.permute(1, 0, 2, 3).reshape(h, v * w, 3).clone()
+        bar = max(1, h // 80)
+        frame[h - bar:, : int(round(v * w * (t + 1) / self.L))] = 255
+        self.frames.append(frame)
+
+    def write(self, verbose=True):
+        from phase_guided_terrain_traversal_amd.render import save_gif
+        frames = torch.stack(self.frames).cpu().numpy()
+        d = os.path.dirname(os.path.abspath(self.path))
+        os.makedirs(d, exist_ok=True)
+        out = save_gif(self.path, frames, fps=1.0 / (self.env.dt * self.every))
+        self.renderer.close()
+        if verbose:
+            print(f"video: {len(frames)} frames of {frames.shape[2]}x{frames.shape[1]} -> {out}")
+        return out
+
+
 def run_evaluation(args, num_eval_envs=NUM_EVAL_ENVS, seed=0, verbose=True):
     """-> dict(survivors, num_eval_envs, episode_reward, avg_episode_length, tracking_lin_vel, tracking_ang_vel)"""
     if args.method not in ("pgtt", "baseline"):
@@ -77,7 +119,10 @@ def run_evaluation(args, num_eval_envs=NUM_EVAL_ENVS, seed=0, verbose=True):
     first = torch.ones(n, dtype=torch.bool, device=dev)                           # still inside its first episode
     ret = torch.zeros(n, device=dev); length = torch.zeros(n, device=dev); fell = torch.zeros(n, dtype=torch.bool, device=dev)
     terms = torch.zeros(abi.NMETRIC, n, device=dev)
-    for _ in range(L):
+    video = VideoRecorder(args, env, L) if getattr(args, "video", None) else None
+    for t in range(L):
+        if video is not None:
+            video.capture(t)
         _, reward, done, info = env.step(pi(env.buffers["obs_state"]))
         w = first.float()
         ret += reward * w; length += w; terms += info["metrics"] * w
@@ -89,6 +134,8 @@ def run_evaluation(args, num_eval_envs=NUM_EVAL_ENVS, seed=0, verbose=True):
     sc = cfg["reward_config"]["scales"]
     out = {"survivors": survivors, "num_eval_envs": n, "episode_reward": float(ret.mean()), "avg_episode_length": float(length.mean()),
            "tracking_lin_vel": float(terms[i_lin].mean()) / (sc["tracking_lin_vel"] * L), "tracking_ang_vel": float(terms[i_ang].mean()) / (sc["tracking_ang_vel"] * L)}
+    if video is not None:
+        out["video"] = video.write(verbose)
     env.close()
     if verbose:                                                                    # training/evaluate.py:212,226
         print(out["episode_reward"])
@@ -116,6 +163,11 @@ def make_parser():
     ap.add_argument("--num_timesteps", type=int, default=1)
     ap.add_argument("--num_evals", type=int, default=2)
     ap.add_argument("--index", type=int, default=32)
+    ap.add_argument("--video", type=str, default=None, help="write a rollout video of the first --video_envs envs here (.gif; a PNG sequence where PIL is missing)")
+    ap.add_argument("--video_envs", type=int, default=4)
+    ap.add_argument("--video_size", type=str, default="320x240", help="WxH of each env's tile")
+    ap.add_argument("--video_every", type=int, default=2, help="one frame every n control steps")
+    ap.add_argument("--video_scan", action="store_true", help="overlay the 117 height-scan hits as marker spheres")
     return ap
 
 

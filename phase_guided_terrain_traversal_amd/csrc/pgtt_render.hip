@@ -1,0 +1,452 @@
+// pgtt_render.hip — libpgtt_render.so: batched brute-force ray casting of env frames (include/pgtt_render.h).
+//
+// Two kernels per call, both on the caller's stream:
+//   render_setup_kernel : one workgroup per view.  Lane 0 runs the forward kinematics of the 13 bodies from the env's qpos (the formulas
+//                         of mjcf.kinematics_np) and builds the camera basis; lanes g < ngeom then place the robot primitives.  The result
+//                         is one ViewRec per view in the caller's workspace.
+//   render_pixel_kernel : grid (16x16 pixel tiles, views).  The prologue stages the view record, the env's terrain variant (ray-ready boxes)
+//                         and the view's markers into LDS; every lane then walks the same primitive list (wave-uniform bounds, LDS
+//                         broadcasts), takes the closest hit, casts one shadow ray toward the light and stores one packed RGBA dword.
+// Nothing is shared between views and nothing is atomic, so a view renders to the same bits whatever else is in the batch.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../../include/pgtt_render.h"
+
+#ifndef PGTT_RENDER_SRC
+#define PGTT_RENDER_SRC "unknown"
+#endif
+
+namespace {
+
+thread_local std::string g_err;
+
+int fail(int code, const std::string& msg) { g_err = msg; return code; }
+
+#define HIP_TRY(expr)                                                                              \
+  do {                                                                                             \
+    hipError_t _e = (expr);                                                                        \
+    if (_e != hipSuccess) return fail(PGTT_E_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
+  } while (0)
+
+constexpr int kTile = 16;               // pixel tile edge: 256 lanes per workgroup
+constexpr int kChunk = 64;              // views per setup launch (their cameras travel as launch arguments)
+constexpr int kBoxWords = 16;           // ray-ready box: centre[3], local axes in world coordinates r0[3] r1[3] r2[3], half extents[3], pad
+constexpr int kGeomWords = 20;          // placed geom: centre[3], local axes r0 r1 r2 [9], size[3], rgb[3], type, pad
+constexpr int kHeadWords = 16;          // camera pos[3] fwd[3] right[3] up[3], tan(fovy / 2), env, variant, pad
+constexpr int kViewWords = kHeadWords + PGTT_RENDER_MAX_GEOM * kGeomWords;
+
+struct ViewArg {
+  int32_t env;
+  PgttRenderCamera cam;
+};
+struct SetupChunk {
+  ViewArg v[kChunk];
+};
+
+struct V3 { float x, y, z; };
+__device__ __forceinline__ V3 v3(float x, float y, float z) { return {x, y, z}; }
+__device__ __forceinline__ V3 operator+(V3 a, V3 b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
+__device__ __forceinline__ V3 operator-(V3 a, V3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
+__device__ __forceinline__ V3 operator*(float s, V3 a) { return {s * a.x, s * a.y, s * a.z}; }
+__device__ __forceinline__ float dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
+__device__ __forceinline__ V3 cross(V3 a, V3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
+__device__ __forceinline__ V3 ld3(const float* p) { return {p[0], p[1], p[2]}; }
+
+struct Q4 { float w, x, y, z; };
+__device__ __forceinline__ Q4 qmul(Q4 a, Q4 b) {
+  return {a.w * b.w - a.x * b.x - a.y * b.y - a.z * b.z, a.w * b.x + a.x * b.w + a.y * b.z - a.z * b.y,
+          a.w * b.y - a.x * b.z + a.y * b.w + a.z * b.x, a.w * b.z + a.x * b.y - a.y * b.x + a.z * b.w};
+}
+// columns of the rotation matrix of q: the body's local axes in world coordinates
+__device__ __forceinline__ void qaxes(Q4 q, V3& c0, V3& c1, V3& c2) {
+  const float w = q.w, x = q.x, y = q.y, z = q.z;
+  c0 = v3(w * w + x * x - y * y - z * z, 2.f * (x * y + w * z), 2.f * (x * z - w * y));
+  c1 = v3(2.f * (x * y - w * z), w * w - x * x + y * y - z * z, 2.f * (y * z + w * x));
+  c2 = v3(2.f * (x * z + w * y), 2.f * (y * z - w * x), w * w - x * x - y * y + z * z);
+}
+__device__ __forceinline__ V3 qrot(Q4 q, V3 v) {
+  V3 c0, c1, c2; qaxes(q, c0, c1, c2);
+  return v.x * c0 + v.y * c1 + v.z * c2;
+}
+
+// ---------------------------------------------------------------- setup: kinematics, camera, placed geoms
+__global__ void __launch_bounds__(64) render_setup_kernel(SetupChunk chunk, int first_view, const float* __restrict__ state, const float* __restrict__ params,
+                                                          const int32_t* __restrict__ variant, int N, int T, const PgttModel* __restrict__ m,
+                                                          const PgttRenderGeom* __restrict__ geoms, int ngeom, float* __restrict__ ws,
+                                                          float* __restrict__ body_pose) {
+  __shared__ float sh_pose[PGTT_NBODY][8];      // xpos[3], xquat[4]
+  const int lv = blockIdx.x, vi = first_view + lv;
+  float* rec = ws + (size_t)vi * kViewWords;
+  if (threadIdx.x == 0) {
+    const int e = chunk.v[lv].env;
+    const PgttRenderCamera cam = chunk.v[lv].cam;
+    auto row = [&](int r) { return state[(size_t)r * N + e]; };
+    V3 xpos[PGTT_NBODY]; Q4 xq[PGTT_NBODY];
+    xpos[0] = v3(row(PGTT_S_QPOS + 0), row(PGTT_S_QPOS + 1), row(PGTT_S_QPOS + 2));
+    {
+      Q4 q = {row(PGTT_S_QPOS + 3), row(PGTT_S_QPOS + 4), row(PGTT_S_QPOS + 5), row(PGTT_S_QPOS + 6)};
+      const float n = sqrtf(q.w * q.w + q.x * q.x + q.y * q.y + q.z * q.z);
+      xq[0] = {q.w / n, q.x / n, q.y / n, q.z / n};
+    }
+#pragma unroll
+    for (int b = 1; b < PGTT_NBODY; b++) {
+      const int k = (b - 1) % 3, parent = k == 0 ? 0 : b - 1;
+      const V3 pos = xpos[parent] + qrot(xq[parent], ld3(m->body_pos[b]));
+      const Q4 quat = qmul(xq[parent], Q4{m->body_quat[b][0], m->body_quat[b][1], m->body_quat[b][2], m->body_quat[b][3]});
+      const float q0 = params ? params[(size_t)(PGTT_P_QPOS0 + b - 1) * N + e] : m->qpos0[7 + b - 1];
+      const float ang = row(PGTT_S_QPOS + 7 + b - 1) - q0;
+      float s, c; sincosf(0.5f * ang, &s, &c);
+      xq[b] = qmul(quat, Q4{c, m->jnt_axis[b - 1][0] * s, m->jnt_axis[b - 1][1] * s, m->jnt_axis[b - 1][2] * s});
+      xpos[b] = pos;
+    }
+#pragma unroll
+    for (int b = 0; b < PGTT_NBODY; b++) {
+      sh_pose[b][0] = xpos[b].x; sh_pose[b][1] = xpos[b].y; sh_pose[b][2] = xpos[b].z;
+      sh_pose[b][3] = xq[b].w; sh_pose[b][4] = xq[b].x; sh_pose[b][5] = xq[b].y; sh_pose[b][6] = xq[b].z;
+    }
+    // camera (MuJoCo free camera): fwd = (cos el cos az, cos el sin az, sin el), up = (-sin el cos az, -sin el sin az, cos el), right = fwd x up
+    const float deg = 3.14159265358979323846f / 180.f;
+    float az = cam.azimuth_deg;
+    V3 look = ld3(cam.target);
+    if (cam.mode != PGTT_CAM_FIXED) look = look + xpos[0];
+    if (cam.mode == PGTT_CAM_TRACK_YAW) {
+      const Q4 q = xq[0];
+      az += atan2f(2.f * (q.w * q.z + q.x * q.y), 1.f - 2.f * (q.y * q.y + q.z * q.z)) / deg;
+    }
+    float sa, ca, se, ce;
+    sincosf(az * deg, &sa, &ca); sincosf(cam.elevation_deg * deg, &se, &ce);
+    const V3 fwd = v3(ce * ca, ce * sa, se), up = v3(-se * ca, -se * sa, ce), right = cross(fwd, up);
+    const V3 pos = look - cam.distance * fwd;
+    const float hd[kHeadWords] = {pos.x, pos.y, pos.z, fwd.x, fwd.y, fwd.z, right.x, right.y, right.z, up.x, up.y, up.z,
+                                  tanf(0.5f * cam.fovy_deg * deg), __int_as_float(e),
+                                  __int_as_float((T > 0 && variant) ? min(max(variant[e], 0), T - 1) : 0), 0.f};
+#pragma unroll
+    for (int i = 0; i < kHeadWords; i++) rec[i] = hd[i];
+  }
+  __syncthreads();
+  if (body_pose)
+    for (int i = threadIdx.x; i < PGTT_NBODY * 7; i += blockDim.x) body_pose[(size_t)vi * PGTT_NBODY * 7 + i] = sh_pose[i / 7][i % 7];
+  const int g = threadIdx.x;
+  if (g < ngeom) {
+    const PgttRenderGeom G = geoms[g];
+    const int b = min(max(G.body, 0), PGTT_NBODY - 1);
+    const V3 bp = v3(sh_pose[b][0], sh_pose[b][1], sh_pose[b][2]);
+    const Q4 bq = {sh_pose[b][3], sh_pose[b][4], sh_pose[b][5], sh_pose[b][6]};
+    const V3 c = bp + qrot(bq, ld3(G.pos));
+    V3 r0, r1, r2; qaxes(qmul(bq, Q4{G.quat[0], G.quat[1], G.quat[2], G.quat[3]}), r0, r1, r2);
+    const float gw[kGeomWords] = {c.x, c.y, c.z, r0.x, r0.y, r0.z, r1.x, r1.y, r1.z, r2.x, r2.y, r2.z,
+                                  G.size[0], G.size[1], G.size[2], G.rgb[0], G.rgb[1], G.rgb[2], __int_as_float(G.type), 0.f};
+    float* dst = rec + kHeadWords + g * kGeomWords;
+#pragma unroll
+    for (int i = 0; i < kGeomWords; i++) dst[i] = gw[i];
+  }
+}
+
+// ---------------------------------------------------------------- primitives (ray o + t d, |d| = 1; a hit needs t > 0)
+// oriented box: slab test in the box frame; t = entry distance (a ray that starts inside the box does not see it)
+__device__ __forceinline__ float hit_box(V3 o, V3 d, const float* __restrict__ bx, int& axis, float& sgn) {
+  const V3 rel = o - ld3(bx);
+  const V3 r0 = ld3(bx + 3), r1 = ld3(bx + 6), r2 = ld3(bx + 9);
+  const float ol[3] = {dot(r0, rel), dot(r1, rel), dot(r2, rel)};
+  const float dl[3] = {dot(r0, d), dot(r1, d), dot(r2, d)};
+  float tn = -INFINITY, tf = INFINITY;
+  axis = 0;
+#pragma unroll
+  for (int a = 0; a < 3; a++) {
+    const float inv = 1.f / dl[a], h = bx[12 + a];
+    const float t1 = (-h - ol[a]) * inv, t2 = (h - ol[a]) * inv;
+    const float lo = fminf(t1, t2), hi = fmaxf(t1, t2);
+    if (lo > tn) { tn = lo; axis = a; }
+    tf = fminf(tf, hi);
+  }
+  sgn = dl[axis] < 0.f ? 1.f : -1.f;
+  return (tn <= tf && tn > 0.f) ? tn : INFINITY;
+}
+__device__ __forceinline__ float hit_sphere(V3 o, V3 d, V3 c, float r) {
+  const V3 oc = o - c;
+  const float b = dot(oc, d), cc = dot(oc, oc) - r * r, disc = b * b - cc;
+  if (disc < 0.f) return INFINITY;
+  const float t = -b - sqrtf(disc);
+  return t > 0.f ? t : INFINITY;
+}
+// capsule: segment c +- hl * ax, radius r (cylinder body, then the nearer end cap)
+__device__ __forceinline__ float hit_capsule(V3 o, V3 d, V3 c, V3 ax, float r, float hl) {
+  const V3 pa = c - hl * ax, ba = (2.f * hl) * ax, oa = o - pa;
+  const float baba = dot(ba, ba), bard = dot(ba, d), baoa = dot(ba, oa), rdoa = dot(d, oa), oaoa = dot(oa, oa);
+  const float a = baba - bard * bard, b = baba * rdoa - baoa * bard, cc = baba * oaoa - baoa * baoa - r * r * baba;
+  const float h = b * b - a * cc;
+  if (h < 0.f) return INFINITY;
+  const float t = (-b - sqrtf(h)) / a, y = baoa + t * bard;
+  if (y > 0.f && y < baba) return t > 0.f ? t : INFINITY;
+  return hit_sphere(o, d, y <= 0.f ? pa : pa + ba, r);
+}
+__device__ __forceinline__ V3 capsule_normal(V3 p, V3 c, V3 ax, float r, float hl) {
+  const float s = fminf(fmaxf(dot(p - c, ax), -hl), hl);
+  return (1.f / r) * (p - (c + s * ax));
+}
+__device__ __forceinline__ float hit_geom(V3 o, V3 d, const float* __restrict__ g) {
+  const int type = __float_as_int(g[18]);
+  if (type == PGTT_RENDER_SPHERE) return hit_sphere(o, d, ld3(g), g[12]);
+  if (type == PGTT_RENDER_CAPSULE) return hit_capsule(o, d, ld3(g), ld3(g + 9), g[12], g[13]);
+  float bx[kBoxWords];
+#pragma unroll
+  for (int i = 0; i < 15; i++) bx[i] = g[i];
+  int axis; float sgn;
+  return hit_box(o, d, bx, axis, sgn);
+}
+
+// ---------------------------------------------------------------- pixels
+__global__ void __launch_bounds__(kTile * kTile) render_pixel_kernel(const float* __restrict__ ws, const float* __restrict__ boxes, int B,
+                                                                     const float* __restrict__ markers, int M, int ngeom, int W, int H, int tiles_x,
+                                                                     int shadows, uint32_t* __restrict__ rgba, float* __restrict__ depth,
+                                                                     int32_t* __restrict__ seg) {
+  __shared__ float sh_view[kViewWords];
+  __shared__ float sh_box[PGTT_MAX_BOX * kBoxWords];
+  __shared__ float sh_mk[PGTT_RENDER_MAX_MARKER * 4];
+  const int vi = blockIdx.y, tid = threadIdx.x;
+  const float* rec = ws + (size_t)vi * kViewWords;
+  for (int i = tid; i < kHeadWords + ngeom * kGeomWords; i += blockDim.x) sh_view[i] = rec[i];
+  if (B > 0) {
+    const int v = __float_as_int(rec[14]);
+    const float* src = boxes + (size_t)v * B * kBoxWords;
+    for (int i = tid; i < B * kBoxWords; i += blockDim.x) sh_box[i] = src[i];
+  }
+  if (M > 0) {
+    const float* src = markers + (size_t)vi * M * 4;
+    for (int i = tid; i < M * 4; i += blockDim.x) sh_mk[i] = src[i];
+  }
+  __syncthreads();
+
+  const int tx = blockIdx.x % tiles_x, ty = blockIdx.x / tiles_x;
+  const int px = tx * kTile + (tid % kTile), py = ty * kTile + (tid / kTile);
+  const V3 o = ld3(sh_view), fwd = ld3(sh_view + 3), right = ld3(sh_view + 6), up = ld3(sh_view + 9);
+  const float tan_y = sh_view[12];
+  const float u = (2.f * ((float)px + 0.5f) / (float)W - 1.f) * tan_y * ((float)W / (float)H);
+  const float vv = (1.f - 2.f * ((float)py + 0.5f) / (float)H) * tan_y;
+  V3 d = fwd + u * right + vv * up;
+  d = (1.f / sqrtf(dot(d, d))) * d;
+
+  // closest hit
+  float best = INFINITY;
+  int id = PGTT_SEG_SKY;
+  V3 n = v3(0.f, 0.f, 1.f);
+  if (d.z != 0.f) {
+    const float t = -o.z / d.z;
+    if (t > 0.f) { best = t; id = PGTT_SEG_PLANE; }
+  }
+  for (int b = 0; b < B; b++) {
+    const float* bx = sh_box + b * kBoxWords;
+    int axis; float sgn;
+    const float t = hit_box(o, d, bx, axis, sgn);
+    if (t < best) { best = t; id = PGTT_SEG_BOX + b; n = sgn * ld3(bx + 3 + 3 * axis); }
+  }
+  for (int g = 0; g < ngeom; g++) {
+    const float* G = sh_view + kHeadWords + g * kGeomWords;
+    const float t = hit_geom(o, d, G);
+    if (t < best) { best = t; id = PGTT_SEG_GEOM + g; }
+  }
+  for (int k = 0; k < M; k++) {
+    const float t = hit_sphere(o, d, ld3(sh_mk + 4 * k), sh_mk[4 * k + 3]);
+    if (t < best) { best = t; id = PGTT_SEG_MARKER + k; }
+  }
+
+  V3 col;
+  if (id == PGTT_SEG_SKY) {
+    const float s = fmaxf(d.z, 0.f);
+    col = v3(PGTT_RENDER_SKY_HORIZON_R + (PGTT_RENDER_SKY_ZENITH_R - PGTT_RENDER_SKY_HORIZON_R) * s,
+             PGTT_RENDER_SKY_HORIZON_G + (PGTT_RENDER_SKY_ZENITH_G - PGTT_RENDER_SKY_HORIZON_G) * s,
+             PGTT_RENDER_SKY_HORIZON_B + (PGTT_RENDER_SKY_ZENITH_B - PGTT_RENDER_SKY_HORIZON_B) * s);
+  } else {
+    const V3 p = o + best * d;
+    V3 alb;
+    if (id == PGTT_SEG_PLANE) {
+      const int par = ((int)floorf(p.x / PGTT_RENDER_CHECKER) + (int)floorf(p.y / PGTT_RENDER_CHECKER)) & 1;
+      alb = par ? v3(PGTT_RENDER_FLOOR_B_R, PGTT_RENDER_FLOOR_B_G, PGTT_RENDER_FLOOR_B_B) : v3(PGTT_RENDER_FLOOR_A_R, PGTT_RENDER_FLOOR_A_G, PGTT_RENDER_FLOOR_A_B);
+    } else if (id < PGTT_SEG_GEOM) {
+      alb = v3(PGTT_RENDER_BOX_R, PGTT_RENDER_BOX_G, PGTT_RENDER_BOX_B);
+    } else if (id < PGTT_SEG_MARKER) {
+      const float* G = sh_view + kHeadWords + (id - PGTT_SEG_GEOM) * kGeomWords;
+      alb = ld3(G + 15);
+      const int type = __float_as_int(G[18]);
+      if (type == PGTT_RENDER_SPHERE) n = (1.f / G[12]) * (p - ld3(G));
+      else if (type == PGTT_RENDER_CAPSULE) n = capsule_normal(p, ld3(G), ld3(G + 9), G[12], G[13]);
+      else {
+        float bx[kBoxWords];
+#pragma unroll
+        for (int i = 0; i < 15; i++) bx[i] = G[i];
+        int axis; float sgn;
+        hit_box(o, d, bx, axis, sgn);
+        n = sgn * ld3(G + 3 + 3 * axis);
+      }
+    } else {
+      const float* mk = sh_mk + 4 * (id - PGTT_SEG_MARKER);
+      alb = v3(PGTT_RENDER_MARKER_R, PGTT_RENDER_MARKER_G, PGTT_RENDER_MARKER_B);
+      n = (1.f / mk[3]) * (p - ld3(mk));
+    }
+    if (dot(n, d) > 0.f) n = -1.f * n;
+    V3 l = v3(PGTT_RENDER_LIGHT_X, PGTT_RENDER_LIGHT_Y, PGTT_RENDER_LIGHT_Z);
+    l = (1.f / sqrtf(dot(l, l))) * l;
+    const float ndl = fmaxf(dot(n, l), 0.f);
+    float vis = 1.f;
+    if (shadows && ndl > 0.f) {
+      // any hit toward the light among the boxes and the robot geoms
+      const V3 so = p + PGTT_RENDER_SHADOW_EPS * n;
+      bool occ = false;
+      for (int b = 0; b < B && !occ; b++) {
+        int axis; float sgn;
+        occ = hit_box(so, l, sh_box + b * kBoxWords, axis, sgn) < INFINITY;
+      }
+      for (int g = 0; g < ngeom && !occ; g++) occ = hit_geom(so, l, sh_view + kHeadWords + g * kGeomWords) < INFINITY;
+      vis = occ ? 0.f : 1.f;
+    }
+    const float s = PGTT_RENDER_AMBIENT + PGTT_RENDER_DIFFUSE * ndl * vis;
+    col = v3(alb.x * s, alb.y * s, alb.z * s);
+  }
+  if (px < W && py < H) {
+    const size_t idx = ((size_t)vi * H + py) * W + px;
+    auto q8 = [](float c) { return (uint32_t)rintf(255.f * fminf(fmaxf(c, 0.f), 1.f)); };
+    rgba[idx] = q8(col.x) | (q8(col.y) << 8) | (q8(col.z) << 16) | (255u << 24);
+    if (depth) depth[idx] = id == PGTT_SEG_SKY ? INFINITY : best * dot(d, fwd);
+    if (seg) seg[idx] = id;
+  }
+}
+
+}  // namespace
+
+struct pgtt_renderer {
+  int device = 0;
+  int ngeom = 0;
+  PgttModel* d_model = nullptr;
+  PgttRenderGeom* d_geoms = nullptr;
+  float* d_boxes = nullptr;      // [T][B][kBoxWords]
+  int T = 0, B = 0;
+};
+
+extern "C" {
+
+const char* pgtt_render_last_error(void) { return g_err.c_str(); }
+const char* pgtt_render_build_info(void) { return "src=" PGTT_RENDER_SRC ";flavor=product"; }
+int pgtt_render_sizeof_geom(void) { return (int)sizeof(PgttRenderGeom); }
+int pgtt_render_sizeof_camera(void) { return (int)sizeof(PgttRenderCamera); }
+int pgtt_render_sizeof_views(void) { return (int)sizeof(PgttRenderViews); }
+
+int64_t pgtt_render_workspace_bytes(int num_views) {
+  if (num_views < 1 || num_views > PGTT_RENDER_MAX_VIEWS) return 0;
+  return (int64_t)num_views * kViewWords * (int64_t)sizeof(float);
+}
+
+int pgtt_render_create(const PgttModel* model, const PgttRenderGeom* geoms, int ngeom, int device, pgtt_render_handle* out) {
+  if (!model || !out || (ngeom > 0 && !geoms)) return fail(PGTT_E_ARG, "pgtt_render_create: null argument");
+  *out = nullptr;
+  if (ngeom < 0 || ngeom > PGTT_RENDER_MAX_GEOM) return fail(PGTT_E_ARG, "pgtt_render_create: ngeom must be in [0, PGTT_RENDER_MAX_GEOM]");
+  for (int g = 0; g < ngeom; g++) {
+    if (geoms[g].body < 0 || geoms[g].body >= PGTT_NBODY) return fail(PGTT_E_ARG, "pgtt_render_create: geom body outside [0, PGTT_NBODY)");
+    if (geoms[g].type < PGTT_RENDER_SPHERE || geoms[g].type > PGTT_RENDER_BOX) return fail(PGTT_E_ARG, "pgtt_render_create: unknown geom type");
+    if (!(geoms[g].size[0] > 0.f) || (geoms[g].type != PGTT_RENDER_SPHERE && !(geoms[g].size[1] > 0.f)) ||
+        (geoms[g].type == PGTT_RENDER_BOX && !(geoms[g].size[2] > 0.f)))
+      return fail(PGTT_E_ARG, "pgtt_render_create: geom sizes must be positive");
+  }
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(PGTT_E_NODEVICE, "pgtt_render_create: no HIP device (this library has no CPU path)");
+  if (device < 0 || device >= ndev) return fail(PGTT_E_ARG, "pgtt_render_create: device index out of range");
+  HIP_TRY(hipSetDevice(device));
+  pgtt_renderer* h = new pgtt_renderer();
+  h->device = device; h->ngeom = ngeom;
+  auto built = [&]() -> int {
+    HIP_TRY(hipMalloc(&h->d_model, sizeof(PgttModel)));
+    HIP_TRY(hipMalloc(&h->d_geoms, PGTT_RENDER_MAX_GEOM * sizeof(PgttRenderGeom)));
+    HIP_TRY(hipMemcpy(h->d_model, model, sizeof(PgttModel), hipMemcpyHostToDevice));
+    if (ngeom > 0) HIP_TRY(hipMemcpy(h->d_geoms, geoms, ngeom * sizeof(PgttRenderGeom), hipMemcpyHostToDevice));
+    return PGTT_OK;
+  };
+  if (int rc = built()) { pgtt_render_destroy(h); return rc; }
+  *out = h;
+  return PGTT_OK;
+}
+
+int pgtt_render_destroy(pgtt_render_handle h) {
+  if (!h) return PGTT_OK;
+  hipSetDevice(h->device);
+  if (h->d_model) hipFree(h->d_model);
+  if (h->d_geoms) hipFree(h->d_geoms);
+  if (h->d_boxes) hipFree(h->d_boxes);
+  delete h;
+  return PGTT_OK;
+}
+
+int pgtt_render_set_terrain(pgtt_render_handle h, const float* boxes, int T, int B) {
+  if (!h) return fail(PGTT_E_ARG, "null handle");
+  if (T < 0 || B < 0 || B > PGTT_MAX_BOX) return fail(PGTT_E_ARG, "pgtt_render_set_terrain: need 0 <= B <= PGTT_MAX_BOX, T >= 0");
+  if (T > 0 && (!boxes || B == 0)) return fail(PGTT_E_ARG, "pgtt_render_set_terrain: null table");
+  HIP_TRY(hipSetDevice(h->device));
+  if (h->d_boxes) { HIP_TRY(hipFree(h->d_boxes)); h->d_boxes = nullptr; }
+  h->T = 0; h->B = 0;
+  if (T == 0) return PGTT_OK;
+  // ray-ready form: centre, the box's local axes in world coordinates (columns of the rotation of the NORMALISED quaternion, in double),
+  // half extents
+  std::vector<float> tab((size_t)T * B * kBoxWords, 0.f);
+  for (size_t i = 0; i < (size_t)T * B; i++) {
+    const float* r = boxes + 10 * i;
+    float* t = tab.data() + kBoxWords * i;
+    double w = r[3], x = r[4], y = r[5], z = r[6];
+    const double qn = std::sqrt(w * w + x * x + y * y + z * z);
+    if (!(qn > 0.0)) return fail(PGTT_E_ARG, "pgtt_render_set_terrain: zero quaternion");
+    w /= qn; x /= qn; y /= qn; z /= qn;
+    const double ax[9] = {w * w + x * x - y * y - z * z, 2 * (x * y + w * z), 2 * (x * z - w * y),
+                          2 * (x * y - w * z), w * w - x * x + y * y - z * z, 2 * (y * z + w * x),
+                          2 * (x * z + w * y), 2 * (y * z - w * x), w * w - x * x - y * y + z * z};
+    t[0] = r[0]; t[1] = r[1]; t[2] = r[2];
+    for (int k = 0; k < 9; k++) t[3 + k] = (float)ax[k];
+    t[12] = r[7]; t[13] = r[8]; t[14] = r[9];
+  }
+  HIP_TRY(hipMalloc(&h->d_boxes, tab.size() * sizeof(float)));
+  HIP_TRY(hipMemcpy(h->d_boxes, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice));
+  h->T = T; h->B = B;
+  return PGTT_OK;
+}
+
+int pgtt_render(pgtt_render_handle h, const PgttRenderViews* v, void* stream) {
+  if (!h || !v) return fail(PGTT_E_ARG, "pgtt_render: null argument");
+  if (!v->state || !v->rgba || !v->workspace || !v->env_ids || !v->cameras) return fail(PGTT_E_ARG, "pgtt_render: state, rgba, workspace, env_ids and cameras are required");
+  if ((uintptr_t)v->workspace % 16 != 0) return fail(PGTT_E_ARG, "pgtt_render: workspace must be 16-byte aligned");
+  if (v->num_envs < 1) return fail(PGTT_E_ARG, "pgtt_render: num_envs must be >= 1");
+  if (v->num_views < 1 || v->num_views > PGTT_RENDER_MAX_VIEWS) return fail(PGTT_E_ARG, "pgtt_render: num_views outside [1, PGTT_RENDER_MAX_VIEWS]");
+  if (v->width < 1 || v->height < 1 || v->width > PGTT_RENDER_MAX_DIM || v->height > PGTT_RENDER_MAX_DIM)
+    return fail(PGTT_E_ARG, "pgtt_render: width and height must be in [1, PGTT_RENDER_MAX_DIM]");
+  if (v->num_markers < 0 || v->num_markers > PGTT_RENDER_MAX_MARKER) return fail(PGTT_E_ARG, "pgtt_render: num_markers outside [0, PGTT_RENDER_MAX_MARKER]");
+  if (v->num_markers > 0 && !v->markers) return fail(PGTT_E_ARG, "pgtt_render: num_markers > 0 needs a markers buffer");
+  for (int i = 0; i < v->num_views; i++) {
+    if (v->env_ids[i] < 0 || v->env_ids[i] >= v->num_envs) return fail(PGTT_E_ARG, "pgtt_render: env id outside [0, num_envs)");
+    const PgttRenderCamera& c = v->cameras[i];
+    if (c.mode < PGTT_CAM_FIXED || c.mode > PGTT_CAM_TRACK_YAW) return fail(PGTT_E_ARG, "pgtt_render: unknown camera mode");
+    if (!(c.distance > 0.f) || !std::isfinite(c.distance)) return fail(PGTT_E_ARG, "pgtt_render: camera distance must be positive");
+    if (!(c.fovy_deg > 0.f) || !(c.fovy_deg < 180.f)) return fail(PGTT_E_ARG, "pgtt_render: fovy must be in (0, 180) degrees");
+    if (!std::isfinite(c.azimuth_deg) || !std::isfinite(c.elevation_deg) || !std::isfinite(c.target[0]) || !std::isfinite(c.target[1]) || !std::isfinite(c.target[2]))
+      return fail(PGTT_E_ARG, "pgtt_render: camera angles and target must be finite");
+  }
+  HIP_TRY(hipSetDevice(h->device));
+  hipStream_t st = (hipStream_t)stream;
+  float* ws = (float*)v->workspace;
+  for (int first = 0; first < v->num_views; first += kChunk) {
+    const int nv = std::min(kChunk, v->num_views - first);
+    SetupChunk chunk;
+    std::memset(&chunk, 0, sizeof(chunk));
+    for (int i = 0; i < nv; i++) { chunk.v[i].env = v->env_ids[first + i]; chunk.v[i].cam = v->cameras[first + i]; }
+    hipLaunchKernelGGL(render_setup_kernel, dim3(nv), dim3(64), 0, st, chunk, first, v->state, v->params, v->variant, v->num_envs, h->T,
+                       h->d_model, h->d_geoms, h->ngeom, ws, v->body_pose);
+  }
+  const int tiles_x = (v->width + kTile - 1) / kTile, tiles_y = (v->height + kTile - 1) / kTile;
+  hipLaunchKernelGGL(render_pixel_kernel, dim3(tiles_x * tiles_y, v->num_views), dim3(kTile * kTile), 0, st, ws, h->d_boxes, h->B, v->markers,
+                     v->num_markers, h->ngeom, v->width, v->height, tiles_x, (v->flags & PGTT_RENDER_SHADOWS) ? 1 : 0, v->rgba, v->depth,
+                     v->segmentation);
+  HIP_TRY(hipGetLastError());
+  return PGTT_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,175 @@
+"""The renderer's host side (phase_guided_terrain_traversal_amd/render.py, include/pgtt_render.h) without a GPU: struct layouts, the
+stick-figure robot, the camera convention, the height-scan overlay and the PNG writer."""
+import ctypes as C
+import os
+import re
+import struct
+import zlib
+
+import numpy as np
+import pytest
+import torch
+
+from phase_guided_terrain_traversal_amd import abi, mjcf, render
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HEADER = os.path.join(ROOT, "include", "pgtt_render.h")
+
+
+def test_struct_sizes_match_the_library():
+    if not os.path.exists(render.LIB_PATH):
+        pytest.skip("libpgtt_render.so not built (run __graft_entry__.build())")
+    L = render.lib()
+    assert L.pgtt_render_sizeof_geom() == C.sizeof(render.PgttRenderGeom)
+    assert L.pgtt_render_sizeof_camera() == C.sizeof(render.PgttRenderCamera)
+    assert L.pgtt_render_sizeof_views() == C.sizeof(render.PgttRenderViews)
+    assert L.pgtt_render_workspace_bytes(0) == 0 and L.pgtt_render_workspace_bytes(render.MAX_VIEWS + 1) == 0
+    assert L.pgtt_render_workspace_bytes(3) == 3 * L.pgtt_render_workspace_bytes(1) > 0
+    for n in render.EXPORTS:
+        assert hasattr(L, n), n
+    info = render.build_info()
+    assert info["flavor"] == "product" and re.fullmatch(r"[0-9a-f]{64}", info["src"])
+
+
+def test_header_constants_match_the_mirror():
+    text = open(HEADER).read()
+    num = lambda name: int(re.search(rf"#define PGTT_{name}\s+\(?(-?\d+)\)?", text).group(1))
+    assert (num("RENDER_MAX_GEOM"), num("RENDER_MAX_MARKER"), num("RENDER_MAX_DIM"), num("RENDER_MAX_VIEWS")) == \
+        (render.MAX_GEOM, render.MAX_MARKER, render.MAX_DIM, render.MAX_VIEWS)
+    assert (num("SEG_SKY"), num("SEG_PLANE"), num("SEG_BOX"), num("SEG_GEOM"), num("SEG_MARKER")) == \
+        (render.SEG_SKY, render.SEG_PLANE, render.SEG_BOX, render.SEG_GEOM, render.SEG_MARKER)
+    assert sorted(set(re.findall(r"\b(pgtt_render[a-z_0-9]*)\s*\(", text))) == sorted(render.EXPORTS)
+    # the renderer is its own library: the env ABI keeps exactly its function set
+    from phase_guided_terrain_traversal_amd import native
+    assert not set(render.EXPORTS) & set(native.EXPORTS)
+
+
+def test_library_exports_nothing_of_libpgtt():
+    if not os.path.exists(render.LIB_PATH):
+        pytest.skip("libpgtt_render.so not built")
+    import subprocess
+    out = subprocess.run(["nm", "-D", "--defined-only", render.LIB_PATH], capture_output=True, text=True)
+    if out.returncode != 0:
+        pytest.skip("nm not available")
+    names = {ln.split()[-1] for ln in out.stdout.splitlines() if " T " in ln and ln.split()[-1].startswith("pgtt")}
+    assert names == set(render.EXPORTS)
+
+
+def test_default_robot_geoms_hang_on_the_body_chain():
+    m = mjcf.load_model("stairs")
+    geoms = render.default_robot_geoms(m)
+    assert 0 < len(geoms) <= render.MAX_GEOM
+    for g in geoms:
+        assert 0 <= g["body"] < abi.NBODY and g["type"] in (render.SPHERE, render.CAPSULE, render.BOX)
+        assert abs(np.linalg.norm(g["quat"]) - 1) < 1e-12 and (np.asarray(g["size"])[:1] > 0).all()
+    feet = [g for g in geoms if g["type"] == render.SPHERE]
+    assert len(feet) == abi.NLEG
+    for leg, g in enumerate(sorted(feet, key=lambda g: g["body"])):
+        assert g["body"] == 3 + 3 * leg                                     # the calf of leg FL, FR, RL, RR
+        assert np.array_equal(g["pos"], np.asarray(m["foot_geom_pos"][leg], float))
+        assert g["size"][0] == float(m["foot_radius"][leg])
+    # each capsule runs from its body's origin to the next body's origin (or the foot centre), along its local z axis
+    bp = np.asarray(m["body_pos"], float)
+    for g in geoms:
+        if g["type"] != render.CAPSULE:
+            continue
+        b = g["body"]; k = (b - 1) % 3
+        end = bp[b + 1] if k < 2 else np.asarray(m["foot_geom_pos"][(b - 1) // 3], float)
+        w, x, y, z = g["quat"]
+        axis = np.array([2 * (x * z + w * y), 2 * (y * z - w * x), w * w - x * x - y * y + z * z])
+        hl = g["size"][1]
+        assert np.allclose(g["pos"] - hl * axis, 0, atol=1e-12) and np.allclose(g["pos"] + hl * axis, end, atol=1e-12)
+    base = [g for g in geoms if g["type"] == render.BOX]
+    assert len(base) == 1 and base[0]["body"] == 0
+    hips = bp[[1, 4, 7, 10]]
+    assert np.all(np.abs(hips[:, :2] - base[0]["pos"][:2]) <= base[0]["size"][:2] + 1e-12)     # spans the hip origins
+    arr = render.geom_array(geoms)
+    assert [s.body for s in arr] == [g["body"] for g in geoms]
+
+
+@pytest.mark.parametrize("mode", ["fixed", "track", "track_yaw"])
+def test_camera_basis_is_orthonormal_and_looks_at_its_target(mode):
+    rng = np.random.default_rng(0)
+    base = np.array([0.7, -1.2, 0.3])
+    q = rng.normal(size=4); q /= np.linalg.norm(q)
+    for az in np.linspace(-180, 180, 13):
+        for el in (-89.0, -60.0, -25.0, 0.0, 30.0, 89.0):
+            cam = render.Camera(mode, target=(0.1, 0.2, -0.05), distance=1.7, azimuth=az, elevation=el, fovy=50)
+            pos, fwd, right, up = render.camera_basis(cam, base, q)
+            B = np.stack([fwd, right, up])
+            assert np.allclose(B @ B.T, np.eye(3), atol=1e-12)
+            assert np.allclose(np.cross(up, right), fwd, atol=1e-12)            # right = fwd x up, so up x right = fwd
+            assert right[2] == pytest.approx(0, abs=1e-12)                      # no roll: right stays horizontal
+            look = np.asarray(cam.target) + (0 if mode == "fixed" else base)
+            assert np.allclose(pos + cam.distance * fwd, look, atol=1e-12)
+            yaw = np.degrees(render.base_yaw(q)) if mode == "track_yaw" else 0.0
+            a, e = np.radians(az + yaw), np.radians(el)
+            assert np.allclose(fwd, [np.cos(e) * np.cos(a), np.cos(e) * np.sin(a), np.sin(e)], atol=1e-12)
+    # the centre pixel of an odd-sized image looks along the optical axis; row 0 is the top
+    cam = render.Camera("fixed", target=(0, 0, 0), distance=2, azimuth=30, elevation=-40, fovy=60)
+    pos, d = render.camera_rays(cam, 5, 3)
+    _, fwd, _, up = render.camera_basis(cam)
+    assert np.allclose(d[1, 2], fwd, atol=1e-12)
+    assert np.dot(d[0, 2], up) > 0 > np.dot(d[2, 2], up)
+    assert np.dot(d[0, 2], up) / np.dot(d[0, 2], fwd) * 3 / 2 == pytest.approx(np.tan(np.radians(30)), abs=1e-12)   # row 0's centre: 2/3 of tan(fovy / 2)
+
+
+def test_scan_points_xy_match_the_scan_grid_fixture(golden_dir):
+    g = np.load(os.path.join(golden_dir, "scan_grid.npz"))
+    n = len(g["yaws"])
+
+    class StubEnv:                      # scan_points only reads the state rows, scan_z and the config
+        config = {"scan_dist_x": 0.1, "scan_dist_y": 0.1}
+        buffers = {"state": torch.zeros((abi.NSTATE, n), dtype=torch.float64), "scan_z": torch.from_numpy(np.arange(n * abi.NSCAN, dtype=np.float64).reshape(n, abi.NSCAN))}
+
+    S = StubEnv.buffers["state"]
+    S[abi.S_QPOS:abi.S_QPOS + 3] = torch.from_numpy(g["centers"].T)
+    S[abi.S_QPOS + 3] = torch.from_numpy(np.cos(g["yaws"] / 2)) * 2.0        # un-normalised on purpose: scan_points normalises
+    S[abi.S_QPOS + 6] = torch.from_numpy(np.sin(g["yaws"] / 2)) * 2.0
+    p = render.scan_points(StubEnv()).numpy()
+    assert p.shape == (n, abi.NSCAN, 3)
+    assert np.abs(p[..., :2] - g["origins"][..., :2].reshape(n, abi.NSCAN, 2)).max() < 1e-6
+    assert np.array_equal(p[..., 2], StubEnv.buffers["scan_z"].numpy())
+    sub = render.scan_points(StubEnv(), [2, 0]).numpy()
+    assert np.array_equal(sub, p[[2, 0]])
+    # numpy inputs give the same grid
+    xy = render.scan_grid_xy(g["centers"][:, :2], g["yaws"])
+    assert np.abs(xy - g["origins"][..., :2].reshape(n, abi.NSCAN, 2)).max() < 1e-6
+
+
+def _decode_png(data: bytes) -> np.ndarray:
+    assert data[:8] == b"\x89PNG\r\n\x1a\n"
+    pos, chunks = 8, {}
+    while pos < len(data):
+        (n,) = struct.unpack(">I", data[pos:pos + 4])
+        tag, body = data[pos + 4:pos + 8], data[pos + 8:pos + 8 + n]
+        assert struct.unpack(">I", data[pos + 8 + n:pos + 12 + n])[0] == zlib.crc32(tag + body) & 0xFFFFFFFF
+        chunks[tag] = chunks.get(tag, b"") + body
+        pos += 12 + n
+    w, h, depth, ctype = struct.unpack(">IIBB", chunks[b"IHDR"][:10])
+    assert depth == 8
+    ch = {0: 1, 2: 3, 6: 4}[ctype]
+    raw = zlib.decompress(chunks[b"IDAT"])
+    rows = np.frombuffer(raw, np.uint8).reshape(h, 1 + w * ch)
+    assert (rows[:, 0] == 0).all()                       # filter type 0 (None) on every row
+    return rows[:, 1:].reshape(h, w, ch)
+
+
+@pytest.mark.parametrize("ch", [1, 3, 4])
+def test_png_round_trip_is_bit_exact(tmp_path, ch):
+    img = np.random.default_rng(ch).integers(0, 256, size=(37, 53, ch), dtype=np.uint8)
+    p = render.save_png(str(tmp_path / "x.png"), img if ch > 1 else img[..., 0])
+    assert np.array_equal(_decode_png(open(p, "rb").read()), img)
+
+
+def test_gif_or_png_sequence(tmp_path):
+    frames = np.random.default_rng(0).integers(0, 256, size=(3, 16, 24, 3), dtype=np.uint8)
+    out = render.save_gif(str(tmp_path / "v.gif"), frames, fps=10)
+    try:
+        from PIL import Image
+    except ImportError:
+        files = sorted(os.listdir(out))
+        assert len(files) == 3 and np.array_equal(_decode_png(open(os.path.join(out, files[1]), "rb").read()), frames[1])
+        return
+    im = Image.open(out)
+    assert im.n_frames == 3 and im.size == (24, 16)
