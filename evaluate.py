@@ -108,6 +108,9 @@ def run_evaluation(args, num_eval_envs=NUM_EVAL_ENVS, seed=0, verbose=True):
     kw = {"params": torch.from_numpy(dr["params"])}
     if terrain is not None:
         kw.update(variant=torch.from_numpy(dr["variant"]), box_friction=torch.from_numpy(dr["box_friction"]))
+    push = configs.push_from_args(args)                           # --push_*: random kicks of the torso (off unless one is given)
+    if push is not None:
+        kw["push"] = push
     env = Joystick(args.task_name, cfg, num_envs=n, terrain=terrain, device=DEVICE, autoreset=True, **kw)
     tmp = os.path.join(ROOT, "plots"); os.makedirs(tmp, exist_ok=True)
     pi = load_policy_from_args(args, tmp)
@@ -168,6 +171,7 @@ def make_parser():
     ap.add_argument("--video_size", type=str, default="320x240", help="WxH of each env's tile")
     ap.add_argument("--video_every", type=int, default=2, help="one frame every n control steps")
     ap.add_argument("--video_scan", action="store_true", help="overlay the 117 height-scan hits as marker spheres")
+    configs.add_push_args(ap)
     return ap
 
 

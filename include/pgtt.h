@@ -153,6 +153,12 @@ typedef struct PgttConfig {
                                    * the wave holds four box contacts (multiples of 4 envs then). */
   int32_t observe_form;           /* PGTT_OBSERVE_*: scan + obs + rewards as one kernel or as observe + task kernels */
   int32_t test_hooks;             /* non-zero: pgtt_set_test_overrides is allowed on this handle (fixture replay); 0 in production */
+  /* random pushes (pgtt_push; MuJoCo Playground Go2 joystick pert_config, no counterpart in the reference).  0 = off: the fields below are not read.
+   * When on, PgttBuffers.xfrc and .push_state must be bound, every range needs 0 <= lo <= hi, and push_duration_s[0] >= ctrl_dt. */
+  int32_t push_enable;
+  float push_wait_s[2];           /* seconds between kicks, uniform (kick_wait_times) */
+  float push_duration_s[2];       /* seconds a kick lasts, uniform (kick_durations) */
+  float push_velocity[2];         /* velocity change of the torso a kick aims at, m/s, uniform (velocity_kick) */
 } PgttConfig;
 enum { PGTT_LAYOUT_AUTO = 0, PGTT_LAYOUT_QUAD = 1, PGTT_LAYOUT_OCT = 2, PGTT_LAYOUT_HEX = 4 };   /* 4, 8, 16 lanes per env */
 enum { PGTT_OBSERVE_FUSED = 0, PGTT_OBSERVE_SPLIT = 1 };
@@ -217,7 +223,21 @@ enum {
   PGTT_RS_GYRO = 0, PGTT_RS_GRAVITY = 1, PGTT_RS_QPOS = 2, PGTT_RS_QVEL = 3, PGTT_RS_SCAN = 4,
   PGTT_RS_CMD_Y = 5, PGTT_RS_CMD_W = 6, PGTT_RS_CMD_Z = 7, PGTT_RS_TIMER = 8,
   PGTT_RS_RESET_XY = 16, PGTT_RS_RESET_YAW = 17, PGTT_RS_RESET_VEL = 18, PGTT_RS_RESET_TIMER = 19,
-  PGTT_RS_RESET_CMD = 20, PGTT_RS_RESET_FREQ = 21
+  PGTT_RS_RESET_CMD = 20, PGTT_RS_RESET_FREQ = 21,
+  PGTT_RS_PUSH_WAIT = 24,          /* i = 0: wait before the next kick */
+  PGTT_RS_PUSH_KICK = 25           /* i = 0 duration, 1 velocity, 2 direction of a kick */
+};
+
+/* per-env push scheduler state rows (float SoA [PGTT_NPUSH][N], PgttBuffers.push_state; counts are whole numbers held in floats) */
+enum {
+  PGTT_PU_WAIT = 0,                /* control steps still to wait before the next kick; < 0: restart (pgtt_reset writes -1) */
+  PGTT_PU_STEP = 1,                /* step of the running kick, 0 .. LEN - 1; -1 while waiting */
+  PGTT_PU_LEN = 2,                 /* steps of the running kick, round(DURATION / ctrl_dt) */
+  PGTT_PU_DURATION = 3,            /* drawn duration, s */
+  PGTT_PU_VELOCITY = 4,            /* drawn velocity, m/s */
+  PGTT_PU_DIR_X = 5,               /* cos a, sin a of the drawn direction a */
+  PGTT_PU_DIR_Y = 6,
+  PGTT_NPUSH = 7
 };
 
 /* device pointers, all caller-owned, all sized for N = num_envs given to pgtt_create */
@@ -249,6 +269,12 @@ typedef struct PgttBuffers {
    * cleared the block.  The reference's trainer averages the Episode-wrapper metrics per log interval (training/train.py:198-229);
    * with the sums kept by the step itself a logging interval costs ONE reduction over the envs instead of one per step. */
   float*   interval_sums;
+  /* [6][N] or NULL: external wrench on the torso, MuJoCo's xfrc_applied[torso]: rows 0..2 a world-frame force, rows 3..5 a world-frame torque, applied
+   * at the torso's centre of mass (per-env PGTT_P_BASE_IPOS under domain randomisation) in every substep of pgtt_step / pgtt_physics; not by the
+   * reset's forward pass.  Rows 0..2 are also privileged extras 41..43 of the step's observation.  An env whose six values are all zero computes
+   * exactly what it computes with xfrc = NULL.  With push_enable = 0 the library only reads it; with push_enable = 1 pgtt_push writes it. */
+  float*   xfrc;
+  float*   push_state;   /* [PGTT_NPUSH][N] or NULL: the push scheduler's per-env state (PGTT_PU_*), written by pgtt_reset and pgtt_push */
 } PgttBuffers;
 
 #define PGTT_DBG_PEN_OVERFLOW 0x10000
@@ -281,6 +307,14 @@ int pgtt_step(pgtt_handle h, const float* action_Nx12, void* stream);
 int pgtt_physics(pgtt_handle h, const float* action_Nx12, void* stream);  /* 4 x mjx.step + sensors + contact flags */
 int pgtt_observe(pgtt_handle h, const float* action_Nx12, void* stream);  /* scan + obs + rewards + bookkeeping */
 int pgtt_scan(pgtt_handle h, float yaw_override_or_nan, void* stream);     /* K11 alone -> scan_z */
+
+/* Random pushes (PgttConfig.push_enable): one launch, one thread per env, writes PgttBuffers.xfrc and .push_state for the coming control step.
+ * pgtt_step calls it first when push_enable is set; callers of pgtt_physics / pgtt_observe call it themselves before pgtt_physics.  Per env:
+ * wait round(U(push_wait_s) / ctrl_dt) steps with a zero wrench, then kick for d = round(D / ctrl_dt) steps, D ~ U(push_duration_s), with
+ * force(t) = 0.5 sin(pi t ctrl_dt / D) m_torso v / D (cos a, sin a, 0), t = 0 .. d - 1, v ~ U(push_velocity), a ~ U(0, 2 pi), zero torque, then
+ * wait again.  An env whose done was set by the previous step, or that pgtt_reset reset, restarts its wait.  Draws: PGTT_RS_PUSH_* at the
+ * env's current epoch.  PGTT_E_STATE when push_enable is 0. */
+int pgtt_push(pgtt_handle h, void* stream);
 
 /* Interval reduction of the running sums the step kernels keep (PgttBuffers.interval_sums, [PGTT_NMETRIC + 2][N]: metrics, reward, done)
  * into out_dev[PGTT_NMETRIC + 3]: entry k < PGTT_NMETRIC + 2 receives the sum over the envs of row k, the last entry `env_steps` (the

@@ -39,6 +39,10 @@ F_GYRO, F_ACCEL, F_GLOBAL_LINVEL, F_GLOBAL_ANGVEL, F_LOCAL_LINVEL, F_UPVECTOR, F
 F_FEET_POS, F_FEET_VEL, F_ACT_FORCE, F_CONTACT, F_FOOT_SITE_Z, NFRAME = 21, 33, 45, 57, 61, 65
 P_BODY_MASS, P_BASE_IPOS, P_QPOS0, P_ARMATURE, P_DAMPING, P_GAIN, P_BIAS1, P_FLOOR_FRICTION, NPARAM = \
     0, 13, 16, 28, 40, 52, 64, 76, 77
+# push scheduler rows (PgttBuffers.push_state, float SoA) and the Philox streams of its draws
+PU_WAIT, PU_STEP, PU_LEN, PU_DURATION, PU_VELOCITY, PU_DIR_X, PU_DIR_Y, NPUSH = 0, 1, 2, 3, 4, 5, 6, 7
+RS_PUSH_WAIT, RS_PUSH_KICK = 24, 25
+NXFRC = 6                                       # PgttBuffers.xfrc rows: world force xyz, world torque xyz on the torso
 
 f, i32 = C.c_float, C.c_int32
 
@@ -76,6 +80,7 @@ class PgttConfig(C.Structure):
         ("phase_sigma", f), ("cmd_u_max", f * 3), ("cmd_u_min", f * 3), ("cmd_b", f * 3),
         ("gait_freq", f * 2), ("scan_dist_x", f), ("scan_dist_y", f), ("scan_z_offset", f),
         ("autoreset", i32), ("method", i32), ("lane_layout", i32), ("observe_form", i32), ("test_hooks", i32),
+        ("push_enable", i32), ("push_wait_s", f * 2), ("push_duration_s", f * 2), ("push_velocity", f * 2),
     ]
 
 
@@ -83,7 +88,7 @@ class PgttBuffers(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in (
         "state", "istate", "frame", "scan_z", "obs_state", "obs_priv", "reward", "done", "metrics",
         "first_state", "first_obs", "ep_metrics", "params", "variant", "box_friction", "dbg_contact",
-        "dbg_dist", "dbg_niter", "interval_sums")]
+        "dbg_dist", "dbg_niter", "interval_sums", "xfrc", "push_state")]
 
 
 # (name, rows-or-cols, dtype, layout) ; layout "soa" => [rows][N], "aos" => [N][cols]
@@ -156,4 +161,28 @@ def config_struct(cfg: Dict[str, Any]) -> PgttConfig:
     s.lane_layout = LAYOUTS[cfg.get("lane_layout", "auto")]
     s.observe_form = OBSERVE_FORMS[cfg.get("observe_form", "fused")]
     s.test_hooks = int(bool(cfg.get("test_hooks", False)))
+    push = push_ranges(cfg)
+    if push is not None:
+        s.push_enable = 1
+        for k, name in (("wait", "push_wait_s"), ("duration", "push_duration_s"), ("velocity", "push_velocity")):
+            getattr(s, name)[0], getattr(s, name)[1] = push[k]
     return s
+
+
+# MuJoCo Playground's Go2 joystick names of the kick ranges (pert_config) -> the keys of Joystick(push=...)
+PERT_KEYS = {"kick_wait_times": "wait", "kick_durations": "duration", "velocity_kick": "velocity"}
+
+
+def push_ranges(cfg: Dict[str, Any]):
+    """{"wait": (lo, hi) s, "duration": (lo, hi) s, "velocity": (lo, hi) m/s} of the random pushes a config asks for, or None (pushes off).
+    cfg["push"] holds them under these names; cfg["pert_config"] under Playground's (enable, kick_wait_times, kick_durations, velocity_kick)."""
+    p = cfg.get("push")
+    if p is None:
+        pc = cfg.get("pert_config")
+        if not pc or not pc.get("enable", False):
+            return None
+        p = {PERT_KEYS[k]: v for k, v in pc.items() if k in PERT_KEYS}
+    missing = {"wait", "duration", "velocity"} - set(p)
+    if missing:
+        raise ValueError(f"push ranges need wait, duration and velocity; missing {sorted(missing)}")
+    return {k: (float(p[k][0]), float(p[k][1])) for k in ("wait", "duration", "velocity")}

@@ -7,7 +7,7 @@ values are the reference's.  ``scan_*`` come from go2/go2_constants.py:90-94 and
 from __future__ import annotations
 
 import copy
-from typing import Any, Dict
+from typing import Any, Dict, Optional
 
 
 def default_config() -> Dict[str, Any]:
@@ -64,6 +64,34 @@ def evaluation_config(method: str = "pgtt") -> Dict[str, Any]:
     cfg["command_config"]["u_min"] = [-0.4, -0.4, -0.7]
     cfg["gait_freq"] = [1, 3]
     return cfg
+
+
+# random pushes (Joystick(push=...), PgttConfig.push_*): MuJoCo Playground's Go2 joystick pert_config ranges, used for the ranges a command line leaves out
+PUSH_DEFAULTS = {"wait": (1.0, 3.0), "duration": (0.05, 0.2), "velocity": (0.0, 3.0)}
+
+
+def add_push_args(ap) -> None:
+    """--push_velocity / --push_wait / --push_duration lo,hi of train.py and evaluate.py (none given: no pushes)"""
+    ap.add_argument("--push_velocity", type=str, default=None, help="random pushes: torso velocity change of a kick, lo,hi m/s (e.g. 0,1.5)")
+    ap.add_argument("--push_wait", type=str, default=None, help="random pushes: seconds between kicks, lo,hi (default 1,3)")
+    ap.add_argument("--push_duration", type=str, default=None, help="random pushes: seconds a kick lasts, lo,hi (default 0.05,0.2)")
+
+
+def push_from_args(args) -> Optional[Dict[str, Any]]:
+    """the Joystick(push=...) dict of --push_* (PUSH_DEFAULTS for the ranges not given), or None when none of them is given"""
+    given = {k: getattr(args, "push_" + k, None) for k in PUSH_DEFAULTS}
+    if all(v is None for v in given.values()):
+        return None
+    out = {}
+    for k, v in given.items():
+        if v is None:
+            out[k] = PUSH_DEFAULTS[k]
+            continue
+        parts = [float(x) for x in str(v).split(",")]
+        if len(parts) != 2:
+            raise ValueError(f"--push_{k} takes lo,hi (got {v!r})")
+        out[k] = (parts[0], parts[1])
+    return out
 
 
 def with_overrides(cfg: Dict[str, Any], **kw) -> Dict[str, Any]:

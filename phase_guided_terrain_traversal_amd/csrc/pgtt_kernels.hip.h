@@ -76,7 +76,9 @@ PG_INL int exp_timer(unsigned long long seed, unsigned env, unsigned epoch, unsi
   return (int)rint(t / (double)ctrl_dt);
 }
 
-enum { MODE_STEP = 0, MODE_FORWARD = 1 };
+// MODE_STEP_XFRC: MODE_STEP with PgttBuffers.xfrc bound (the torso wrench enters qfrc_smooth); a kernel of its own, so that the two step
+// kernels without a wrench buffer are the code they were before it existed (same instructions, same roundings)
+enum { MODE_STEP = 0, MODE_FORWARD = 1, MODE_STEP_XFRC = 2 };
 constexpr int kHandover = 128;                 // floats per env (512 bytes: four lines)
 enum { HO_QPOS = 0, HO_QVEL = 19, HO_MOTOR = 37, HO_FRAME = 49, HO_END = HO_FRAME + PGTT_NFRAME };
 static_assert(HO_END <= kHandover, "hand-over record");
@@ -94,6 +96,7 @@ PG_INL int xcd_block(int bid, int nblocks) {
 template <int MODE, bool HAS_DR, bool HAS_TERRAIN, int SUBS>
 __global__ __launch_bounds__(64) void physics_kernel(KArgs a, const float* __restrict__ action) {
   static_assert(SUBS == kSubs, "one lane layout per translation unit");
+  constexpr bool kStep = MODE != MODE_FORWARD;         // MODE_STEP or MODE_STEP_XFRC
   const int N = a.N;
 #ifdef PGTT_TIME
   const long long t0_cyc = __builtin_readcyclecounter(), t0_real = wall_clock64();
@@ -103,7 +106,7 @@ __global__ __launch_bounds__(64) void physics_kernel(KArgs a, const float* __res
   int e = blk * kEnvsPerWave + lane_env();
   bool valid = e < N;
   if (!valid) e = N - 1;                               // keep whole quads running (DPP), suppress the stores
-  if (MODE != MODE_STEP && a.mask && !a.mask[e]) valid = false;
+  if (!kStep && a.mask && !a.mask[e]) valid = false;
   // Hex layout: the model constants (sizeof(PgttModel) = 2.5 KB, read ~100 times per substep through uniform or per-leg addresses) are staged
   // in LDS once per launch: with one wave per SIMD every wait for a vector-memory round trip is exposed, and an LDS read returns in about
   // half the time of an L1 hit (80 global loads of the step kernel became LDS reads: bit-identical, level4 168.0 -> 166.7 us, flat 118.1 ->
@@ -143,7 +146,7 @@ __global__ __launch_bounds__(64) void physics_kernel(KArgs a, const float* __res
     s.ql[k] = PG_ROW(S, PGTT_S_QPOS + 7 + j, N, e);
     s.vl[k] = PG_ROW(S, PGTT_S_QVEL + 6 + j, N, e);
     s.wl[k] = PG_ROW(S, PGTT_S_QWARM + 6 + j, N, e);
-    if (MODE == MODE_STEP) s.ctrl[k] = gm->key_qpos[7 + ac] + PG_REC(action, e, 12, ac) * cfg->action_scale;
+    if (kStep) s.ctrl[k] = gm->key_qpos[7 + ac] + PG_REC(action, e, 12, ac) * cfg->action_scale;
     else s.ctrl[k] = PG_ROW(S, PGTT_S_QPOS + 7 + ac, N, e);          // mjx_env.init(ctrl = qpos[7:])
   }
   const TerrainBox* boxes = nullptr;
@@ -187,7 +190,7 @@ __global__ __launch_bounds__(64) void physics_kernel(KArgs a, const float* __res
 #ifdef PGTT_TRACE
   if (valid && e == 0 && a.trace && lane_sub() == 0) s.tr = a.trace + l;
 #endif
-  const int nsub = MODE == MODE_STEP ? cfg->n_substeps : 1;
+  const int nsub = kStep ? cfg->n_substeps : 1;
   const float dt = m->timestep;
   PG_TICK(s, 15);          // launch prologue: state rows, per-env model, LDS staging of the terrain variant
   for (int sub = 0; sub < nsub; sub++) {
@@ -198,7 +201,7 @@ __global__ __launch_bounds__(64) void physics_kernel(KArgs a, const float* __res
     PG_TICK(s, 16);
     ph.inertia();
     PG_TICK(s, 0);
-    ph.velocity_stage();
+    ph.velocity_stage<MODE == MODE_STEP_XFRC>(a.buf.xfrc, N, e);      // the reset's forward pass applies no wrench
     PG_TICK(s, 1);
     ph.constraint_stage(HAS_TERRAIN && boxes != nullptr && nbox > 0, a.buf.box_friction, N, e, slots);
     PG_TICK(s, 2);
@@ -221,7 +224,7 @@ __global__ __launch_bounds__(64) void physics_kernel(KArgs a, const float* __res
       V3 a0 = mtmul(s.R0, cacc.l - cross(dif, cacc.a)) + cross(gyro, llin);
       acc0[0] = a0.x; acc0[1] = a0.y; acc0[2] = a0.z;
       float* __restrict__ Ho = &PG_REC(a.handover_w, ee, kHandover, HO_FRAME);      // MODE_STEP: the same values, env-major, for this step's observe launch
-      auto put1 = [&](int row, float v) { PG_ROW(Fr, row, N, ee) = v; if (MODE == MODE_STEP) Ho[row] = v; };
+      auto put1 = [&](int row, float v) { PG_ROW(Fr, row, N, ee) = v; if (kStep) Ho[row] = v; };
       auto put3 = [&](int row, V3 v) { put1(row, v.x); put1(row + 1, v.y); put1(row + 2, v.z); };
       if (lead) {
         put3(PGTT_F_GYRO, gyro); put3(PGTT_F_GLOBAL_LINVEL, glin); put3(PGTT_F_GLOBAL_ANGVEL, w); put3(PGTT_F_LOCAL_LINVEL, llin);
@@ -279,11 +282,11 @@ __global__ __launch_bounds__(64) void physics_kernel(KArgs a, const float* __res
 #pragma unroll
         for (int k = 0; k < 6; k++) v += accA[r][k] * s.qacc_b[k];
         PG_ROW(Fr, PGTT_F_ACCEL + r, N, ee) = v;
-        if (MODE == MODE_STEP) PG_REC(a.handover_w, ee, kHandover, HO_FRAME + PGTT_F_ACCEL + r) = v;
+        if (kStep) PG_REC(a.handover_w, ee, kHandover, HO_FRAME + PGTT_F_ACCEL + r) = v;
       }
       if (a.buf.dbg_niter) a.buf.dbg_niter[ee] = s.niter_max | (pen_ovf > 0 ? PGTT_DBG_PEN_OVERFLOW : 0);
     }
-    if (MODE == MODE_STEP) {
+    if (kStep) {
       // ---- semi-implicit Euler (eulerdamp disabled)
 #pragma unroll
       for (int i = 0; i < 6; i++) s.vb[i] = s.vb[i] + s.qacc_b[i] * dt;
@@ -337,13 +340,13 @@ __global__ __launch_bounds__(64) void physics_kernel(KArgs a, const float* __res
 #else
   const int lq = l;
 #endif
-  if (MODE == MODE_STEP || a.write_qpos) {
+  if (kStep || a.write_qpos) {
 #pragma unroll
     for (int i = 0; i < 7; i++) PG_ROW(S, PGTT_S_QPOS + i, N, e) = s.qb[i];
 #pragma unroll
     for (int k = 0; k < 3; k++) PG_ROW(S, PGTT_S_QPOS + 7 + 3 * lq + k, N, e) = s.ql[k];
   }
-  if (MODE == MODE_STEP) {
+  if (kStep) {
 #pragma unroll
     for (int i = 0; i < 6; i++) PG_ROW(S, PGTT_S_QVEL + i, N, e) = s.vb[i];
 #pragma unroll
@@ -394,6 +397,69 @@ __global__ __launch_bounds__(64) void reset_pose_kernel(KArgs a) {
     S[(PGTT_S_QVEL + i) * (long)N + e] = i < 6 ? rng_uniform(a.seed, id, ep, PGTT_RS_RESET_VEL, i, a.rng_fix) * 0.2f + -0.1f : 0.f;
     S[(PGTT_S_QWARM + i) * (long)N + e] = 0.f;
   }
+  if (a.buf.push_state && a.buf.xfrc && a.cfg->push_enable) {
+    // the push scheduler of a reset env starts over (pgtt_push draws its wait), and the reset state carries no wrench
+    a.buf.push_state[PGTT_PU_WAIT * (long)N + e] = -1.f;
+    a.buf.push_state[PGTT_PU_STEP * (long)N + e] = -1.f;
+#pragma unroll
+    for (int r = 0; r < 6; r++) a.buf.xfrc[r * (long)N + e] = 0.f;
+  }
+}
+
+// ------------------------------------------------------------------ push scheduler: one env per thread (pgtt_push; include/pgtt.h)
+// MuJoCo Playground's Go2 joystick kicks (_maybe_apply_perturbation), recalled: wait, then a half-sine force pulse of the drawn duration whose
+// integral is m_torso v / pi.  Runs before the step's physics launch and draws at the env's epoch of that step (streams PGTT_RS_PUSH_*).
+// The affine maps of the draws are not contracted to an fma, so that a host replay in fp32 gets the same bits.
+PG_INL float push_draw(const float* r, float u) {
+#pragma clang fp contract(off)
+  return u * (r[1] - r[0]) + r[0];
+}
+template <int UNUSED>
+__global__ __launch_bounds__(64) void push_kernel(KArgs a) {
+  const int e = blockIdx.x * 64 + threadIdx.x;
+  const int N = a.N;
+  if (e >= N) return;
+  const PgttConfig* __restrict__ cfg = a.cfg;
+  float* __restrict__ P = a.buf.push_state;
+  float* __restrict__ X = a.buf.xfrc;
+  const unsigned id = (unsigned)(a.env_off + e);
+  const unsigned ep = (unsigned)a.buf.istate[PGTT_I_RNG_CTR * (long)N + e];
+  const float dt = cfg->ctrl_dt;
+  float wait = P[PGTT_PU_WAIT * (long)N + e], kstep = P[PGTT_PU_STEP * (long)N + e], len = P[PGTT_PU_LEN * (long)N + e];
+  float dur = P[PGTT_PU_DURATION * (long)N + e], vel = P[PGTT_PU_VELOCITY * (long)N + e];
+  float dx = P[PGTT_PU_DIR_X * (long)N + e], dy = P[PGTT_PU_DIR_Y * (long)N + e];
+  // a new wait after a reset (WAIT < 0), after a finished episode (done of the previous step) and after the last step of a kick
+  const bool restart = wait < 0.f || a.buf.done[e] != 0.f;
+  if (restart || (kstep >= 0.f && kstep >= len)) {
+    wait = rintf(push_draw(cfg->push_wait_s, rng_uniform(a.seed, id, ep, PGTT_RS_PUSH_WAIT, 0, a.rng_fix)) / dt);
+    kstep = -1.f;
+  }
+  if (kstep < 0.f) {
+    if (wait > 0.f) {
+      wait -= 1.f;
+    } else {
+      dur = push_draw(cfg->push_duration_s, rng_uniform(a.seed, id, ep, PGTT_RS_PUSH_KICK, 0, a.rng_fix));
+      vel = push_draw(cfg->push_velocity, rng_uniform(a.seed, id, ep, PGTT_RS_PUSH_KICK, 1, a.rng_fix));
+      const float ang = rng_uniform(a.seed, id, ep, PGTT_RS_PUSH_KICK, 2, a.rng_fix) * (float)(2.0 * M_PI);
+      sincosf(ang, &dy, &dx);
+      len = rintf(dur / dt);
+      kstep = 0.f;
+    }
+  }
+  float fx = 0.f, fy = 0.f;
+  if (kstep >= 0.f) {
+    const float mass = a.buf.params ? a.buf.params[PGTT_P_BODY_MASS * (long)N + e] : a.model->body_mass[0];
+    const float u = 0.5f * sinf((float)M_PI * (kstep * dt) / dur);
+    const float mag = u * mass * vel / dur;
+    fx = mag * dx; fy = mag * dy;
+    kstep += 1.f;
+  }
+  P[PGTT_PU_WAIT * (long)N + e] = wait; P[PGTT_PU_STEP * (long)N + e] = kstep; P[PGTT_PU_LEN * (long)N + e] = len;
+  P[PGTT_PU_DURATION * (long)N + e] = dur; P[PGTT_PU_VELOCITY * (long)N + e] = vel;
+  P[PGTT_PU_DIR_X * (long)N + e] = dx; P[PGTT_PU_DIR_Y * (long)N + e] = dy;
+  X[0 * (long)N + e] = fx; X[1 * (long)N + e] = fy;
+#pragma unroll
+  for (int r = 2; r < 6; r++) X[r * (long)N + e] = 0.f;
 }
 
 // ------------------------------------------------------------------ observe: one env per wave
@@ -1072,6 +1138,9 @@ __global__ __launch_bounds__(64, 4) void observe_kernel(KArgs a, const float* __
     sh_obs[io] = noisy - offs;
   }
   if (lane < PGTT_PRIV - PGTT_OBS) sh_obs[OBSD + OBSD + lane] = *reinterpret_cast<const float*>(srcb + psrc);
+  // privileged extras 41..43: the force on the torso during this step (xfrc_applied[torso, :3], joystick_pgtt.py:364); 0 without a wrench buffer
+  // and in the observation of a reset
+  if ((OMODE == OBS_STEP || OMODE == OBS_STEP_OBS) && a.buf.xfrc && lane >= 41 && lane < 44) sh_obs[OBSD + OBSD + lane] = a.buf.xfrc[(lane - 41) * (long)N + e];
   // history buffers (joystick_pgtt.py:319-334): motor_targets in sh_st was written by the physics kernel
   float hist_q = 0.f, hist_v = 0.f; const bool upd = (step_ctr % cfg->history_update_steps) == 0;
   if (lane < 24) {

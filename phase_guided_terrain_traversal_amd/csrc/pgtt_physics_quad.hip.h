@@ -558,7 +558,9 @@ struct QPhysics {
     qarrow_factor(s.LM);
   }
 
-  PG_INL void velocity_stage() {
+  // XFRC: the step kernel with a wrench buffer bound (PgttBuffers.xfrc, [6][N]); without it the arguments are not read
+  template <bool XFRC>
+  PG_INL void velocity_stage(const float* __restrict__ xfrc, int N, int e) {
     S6 cv0{v3(0, 0, 0), v3(s.vb[0], s.vb[1], s.vb[2])};
 #pragma unroll
     for (int k = 0; k < 3; k++) s.cddr[k] = motion_cross(cv0, s.cdr[k]);
@@ -600,6 +602,23 @@ struct QPhysics {
       force = fminf(fmaxf(force, m->act_forcerange[a][0]), m->act_forcerange[a][1]);
       s.act_force[k] = force;
       s.qfs_l[k] = -em.damping[k] * s.vl[k] - bias_l[k] + force;
+    }
+    if (XFRC) {
+      // external wrench on the torso (mj_xfrcAccumulate: qfrc_smooth += J_torso^T w, J at the torso COM xipos).  The spatial force in the
+      // c-frame (origin s.com) is (torque + (xipos - com) x f, f); a free-joint dof takes its cdof's projection of it: f itself on the
+      // translational dofs; on rotational dof k, cdr[k] = (a_k, a_k x (com - p0)) with a_k = column k of R0, the projection is
+      // a_k . (torque + (xipos - p0) x f) = (R0^T torque + base_ipos x R0^T f)_k since xipos - p0 = R0 base_ipos.  That form reads only
+      // values that are live here anyway (R0, the env's base_ipos: no register is held from the inertia stage); the hinges get nothing (the
+      // torso is the root).  Reloaded in every substep rather than kept live across the solve; every lane of the env reads the same six
+      // floats and forms the same values (the base block is replicated).  An all-zero wrench leaves qfrc_smooth as it is.
+      int ee = e; asm volatile("" : "+v"(ee));      // opaque env index: the loads cannot be hoisted out of the substep loop
+      const V3 f = v3(PG_ROW(xfrc, 0, N, ee), PG_ROW(xfrc, 1, N, ee), PG_ROW(xfrc, 2, N, ee));
+      const V3 t = v3(PG_ROW(xfrc, 3, N, ee), PG_ROW(xfrc, 4, N, ee), PG_ROW(xfrc, 5, N, ee));
+      const bool any = f.x != 0.f || f.y != 0.f || f.z != 0.f || t.x != 0.f || t.y != 0.f || t.z != 0.f;
+      const V3 rb = mtmul(s.R0, t) + cross(em.base_ipos, mtmul(s.R0, f));
+      const float jw[6] = {f.x, f.y, f.z, rb.x, rb.y, rb.z};
+#pragma unroll
+      for (int i = 0; i < 6; i++) s.qfs_b[i] = any ? s.qfs_b[i] + jw[i] : s.qfs_b[i];
     }
     qarrow_solve(s.LM, s.qfs_b, s.qfs_l, s.qas_b, s.qas_l);
 #ifdef PGTT_TRACE

@@ -27,10 +27,12 @@ class Joystick:
                  variant: Optional[torch.Tensor] = None, box_friction: Optional[torch.Tensor] = None,
                  autoreset: bool = False, debug_contacts: bool = False, env_id_offset: int = 0,
                  model: Optional[Dict[str, Any]] = None, layout: Optional[str] = None, observe_form: Optional[str] = None,
-                 test_hooks: bool = False, interval_sums: bool = False):
+                 test_hooks: bool = False, interval_sums: bool = False, push: Optional[Dict[str, Any]] = None, xfrc: bool = False):
         """layout: "auto" | "quad" | "oct" | "hex" lane layout of physics_kernel (PgttConfig.lane_layout; results are bit-identical
         across batch sizes and shards within one layout); observe_form: "fused" | "split"; test_hooks: allow set_test_overrides
-        (fixture replay only); interval_sums: keep per-env running sums of the step outputs for a logging trainer (PgttBuffers.interval_sums)."""
+        (fixture replay only); interval_sums: keep per-env running sums of the step outputs for a logging trainer (PgttBuffers.interval_sums);
+        push: random pushes, dict(wait=(lo, hi) s, duration=(lo, hi) s, velocity=(lo, hi) m/s) (or config["pert_config"] with MuJoCo
+        Playground's keys): the step kicks the torso (pgtt_push); xfrc: allocate the torso-wrench buffer without pushes (apply_wrench)."""
         self._config = dict(configs.default_config() if config is None else config)
         self._config["autoreset"] = int(autoreset)
         if layout is not None:
@@ -39,6 +41,9 @@ class Joystick:
             self._config["observe_form"] = observe_form
         if test_hooks:
             self._config["test_hooks"] = True
+        if push is not None:
+            self._config["push"] = dict(push)
+        self.push = abi.push_ranges(self._config)          # None: no pushes
         self.method = self._config.get("method", "pgtt")     # "pgtt" = go2/joystick_pgtt.py, "baseline" = go2/joystick.py
         self.task = task
         self.num_envs = int(num_envs)
@@ -86,6 +91,11 @@ class Joystick:
             self.buffers["dbg_contact"] = torch.zeros((n, abi.NCON * 2), dtype=torch.int32, device=self.device)
             self.buffers["dbg_dist"] = torch.zeros((n, abi.NCON), dtype=torch.float32, device=self.device)
             self.buffers["dbg_niter"] = torch.zeros((n,), dtype=torch.int32, device=self.device)
+        # external wrench on the torso ([6][N]: world force, world torque; PgttBuffers.xfrc) and the push scheduler's state ([NPUSH][N])
+        if xfrc or self.push is not None:
+            self.buffers["xfrc"] = torch.zeros((abi.NXFRC, n), dtype=torch.float32, device=self.device)
+        if self.push is not None:
+            self.buffers["push_state"] = torch.full((abi.NPUSH, n), -1.0, dtype=torch.float32, device=self.device)
         self._bind()
         self._seed = 0
 
@@ -132,6 +142,33 @@ class Joystick:
             t = self.buffers.get(name)
             setattr(b, name, None if t is None else t.data_ptr())
         native.check(self._lib.pgtt_bind(self._h, C.byref(b)))
+
+    @property
+    def xfrc(self) -> Optional[torch.Tensor]:
+        """[6][N] view of the wrench on each env's torso (rows 0..2 world force, 3..5 world torque, at the torso COM), or None when the env has
+        no wrench buffer (Joystick(..., xfrc=True) or push=... allocate it; apply_wrench does on first use)"""
+        return self.buffers.get("xfrc")
+
+    def apply_wrench(self, force, torque=None, env_ids=None) -> torch.Tensor:
+        """Set the torso wrench that the following steps apply (held until changed; MuJoCo's xfrc_applied[torso]).  force / torque: [3] or
+        [len(env_ids), 3] world-frame values (torque None = zero); env_ids: the envs to set (None = all).  Not with random pushes, which own
+        the buffer."""
+        if self.push is not None:
+            raise native.PgttError("apply_wrench: this env has random pushes enabled; the push scheduler writes the wrench")
+        if "xfrc" not in self.buffers:
+            self.buffers["xfrc"] = torch.zeros((abi.NXFRC, self.num_envs), dtype=torch.float32, device=self.device)
+            self._bind()
+        x = self.buffers["xfrc"]
+        ids = slice(None) if env_ids is None else torch.as_tensor(env_ids, device=self.device, dtype=torch.long)
+        f = torch.as_tensor(force, dtype=torch.float32, device=self.device)
+        t = torch.zeros_like(f) if torque is None else torch.as_tensor(torque, dtype=torch.float32, device=self.device)
+        x[0:3, ids] = f.T if f.ndim == 2 else f[:, None]
+        x[3:6, ids] = t.T if t.ndim == 2 else t[:, None]
+        return x
+
+    def push_step(self) -> None:
+        """the push scheduler alone (pgtt_push): what step() runs first when pushes are on; for callers of physics() / observe()"""
+        native.check(self._lib.pgtt_push(self._h, self._stream()))
 
     def set_terrain(self, terrain: np.ndarray) -> None:
         t = np.ascontiguousarray(terrain, dtype=np.float32)

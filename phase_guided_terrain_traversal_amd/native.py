@@ -13,7 +13,7 @@ LIB_PATH = os.environ.get("PGTT_LIB", os.path.join(_HERE, "libpgtt.so"))   # PGT
 _LIB: Optional[C.CDLL] = None
 
 EXPORTS = ["pgtt_create", "pgtt_destroy", "pgtt_set_terrain", "pgtt_bind", "pgtt_reset", "pgtt_step",
-           "pgtt_physics", "pgtt_observe", "pgtt_scan", "pgtt_interval_reduce", "pgtt_set_test_overrides", "pgtt_enable_timing", "pgtt_last_kernel_ms", "pgtt_kernel_ms_mean",
+           "pgtt_physics", "pgtt_observe", "pgtt_scan", "pgtt_push", "pgtt_interval_reduce", "pgtt_set_test_overrides", "pgtt_enable_timing", "pgtt_last_kernel_ms", "pgtt_kernel_ms_mean",
            "pgtt_obs_dims", "pgtt_sizeof_model", "pgtt_sizeof_config", "pgtt_sizeof_buffers", "pgtt_version", "pgtt_build_info", "pgtt_last_error"]
 TRAIN_EXPORTS = ["pgtt_ppo_policy_loss", "pgtt_ppo_linear_backward", "pgtt_policy_act", "pgtt_policy_packed_floats", "pgtt_rollout_record",
                  "pgtt_sizeof_policy_act_args", "pgtt_sizeof_rollout_record_args"]      # include/pgtt_train.h: trainer helpers, not the env boundary
@@ -69,6 +69,7 @@ def lib() -> C.CDLL:
         for fn in ("pgtt_step", "pgtt_physics", "pgtt_observe"):
             getattr(L, fn).argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.pgtt_scan.argtypes = [C.c_void_p, C.c_float, C.c_void_p]
+        L.pgtt_push.argtypes = [C.c_void_p, C.c_void_p]
         L.pgtt_interval_reduce.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_void_p]
         L.pgtt_enable_timing.argtypes = [C.c_void_p, C.c_int]
         L.pgtt_set_test_overrides.argtypes = [C.c_void_p, C.c_float, C.c_int]

@@ -50,6 +50,9 @@ def run_training(args):
     kw = {"params": torch.from_numpy(dr["params"])}
     if terrain is not None:
         kw.update(variant=torch.from_numpy(dr["variant"]), box_friction=torch.from_numpy(dr["box_friction"]))
+    push = configs.push_from_args(args)                           # --push_*: random kicks of the torso (off unless one is given)
+    if push is not None:
+        kw["push"] = push
     env = Joystick(args.task_name, cfg, num_envs=hi - lo, terrain=terrain, device=DEVICE, autoreset=True, env_id_offset=lo, **kw)
     ckpt = os.path.join(ROOT, "checks_stairs", f"checkpoint_{args.index}")
     if rank == 0:
@@ -113,4 +116,5 @@ if __name__ == "__main__":
     ap.add_argument("--num_timesteps", type=int, default=1)
     ap.add_argument("--num_evals", type=int, default=31)
     ap.add_argument("--index", type=int, default=32)
+    configs.add_push_args(ap)
     run_training(ap.parse_args())
