@@ -44,9 +44,6 @@ struct KArgs {
   // between pgtt_physics and pgtt_observe called on their own the caller may have edited the rows).
   float* handover_w;
   const float* handover_r;
-#if defined(PGTT_TRACE) || defined(PGTT_TIME)
-  float* trace;                // debugging builds only: per-iteration solver record of env 0
-#endif
 };
 
 // ------------------------------------------------------------------ Philox4x32-10 (independent of the oracle's C)
@@ -98,9 +95,6 @@ __global__ __launch_bounds__(64) void physics_kernel(KArgs a, const float* __res
   static_assert(SUBS == kSubs, "one lane layout per translation unit");
   constexpr bool kStep = MODE != MODE_FORWARD;         // MODE_STEP or MODE_STEP_XFRC
   const int N = a.N;
-#ifdef PGTT_TIME
-  const long long t0_cyc = __builtin_readcyclecounter(), t0_real = wall_clock64();
-#endif
   const int l = lane_leg();                            // leg FL,FR,RL,RR
   const int blk = xcd_block(blockIdx.x, gridDim.x);
   int e = blk * kEnvsPerWave + lane_env();
@@ -133,9 +127,6 @@ __global__ __launch_bounds__(64) void physics_kernel(KArgs a, const float* __res
   QEnvModel em;
   qload_env_model<HAS_DR>(gm, a.buf.params, N, e, l, em);
   QSim s;
-#ifdef PGTT_TIME
-  s.tlast = t0_cyc;
-#endif
 #pragma unroll
   for (int i = 0; i < 7; i++) s.qb[i] = PG_ROW(S, PGTT_S_QPOS + i, N, e);
 #pragma unroll
@@ -187,24 +178,14 @@ __global__ __launch_bounds__(64) void physics_kernel(KArgs a, const float* __res
   QPhysics ph(m, em, s, l);
   QSolver sol(m, s, slots);
   sol.lds_slots = HAS_TERRAIN && nbox > 0;
-#ifdef PGTT_TRACE
-  if (valid && e == 0 && a.trace && lane_sub() == 0) s.tr = a.trace + l;
-#endif
   const int nsub = kStep ? cfg->n_substeps : 1;
   const float dt = m->timestep;
-  PG_TICK(s, 15);          // launch prologue: state rows, per-env model, LDS staging of the terrain variant
   for (int sub = 0; sub < nsub; sub++) {
-    PG_TICK(s, 9);
     ph.kinematics();
-    PG_TICK(s, 0);
     if (HAS_TERRAIN) ph.collide(boxes, box0, nbox, sh_box, sh_box2, slots, quad, grid_v, cell0, a.grid_E, a.grid_inv); else s.nbox = 0;
-    PG_TICK(s, 16);
     ph.inertia();
-    PG_TICK(s, 0);
     ph.velocity_stage<MODE == MODE_STEP_XFRC>(a.buf.xfrc, N, e);      // the reset's forward pass applies no wrench
-    PG_TICK(s, 1);
     ph.constraint_stage(HAS_TERRAIN && boxes != nullptr && nbox > 0, a.buf.box_friction, N, e, slots);
-    PG_TICK(s, 2);
     // ---- sensors of the last forward (pre-integration state), written BEFORE the solve; the accelerometer is an affine map of
     //      qacc[0:6]: its constant part is kept across the solve (3 values), the 3 x 6 matrix is formed after it from frames that are
     //      still live (R0, cdr, imu, com) - 18 registers less across the Newton loop of a kernel that spills to scratch
@@ -304,34 +285,7 @@ __global__ __launch_bounds__(64) void physics_kernel(KArgs a, const float* __res
       for (int k = 0; k < 3; k++) s.ql[k] = s.ql[k] + dt * s.vl[k];
     }
   }
-#ifdef PGTT_TIME
-  // stage ticks of the wave that owns env PGTT_TIME (e.g. -DPGTT_TIME=0): 0 position 1 velocity 2 constraint 3 sensors
-  // 4 solver init x3 5 first gradient 6 line search 7 update_constraint 8 update_gradient 9 rest 10 #iterations
-  if (e == PGTT_TIME && a.trace) {
-    for (int i = 0; i < 20; i++) a.trace[i] = s.cyc[i];
-    for (int i = 20; i < 28; i++) a.trace[4 + i] = s.cyc[i];      // line-search sub-stages at [24..31]
-    // whole-kernel span of this wave in shader-clock ticks and in ticks of the constant 100 MHz clock (gives the shader clock rate)
-    a.trace[20] = (float)(__builtin_readcyclecounter() - t0_cyc); a.trace[21] = (float)(wall_clock64() - t0_real);
-  }
-  if (a.trace) {      // per-wave totals: [32 + block] ticks of the whole kernel, [32 + 4096 + block] sum over substeps of nslots
-    float tot = 0.f;
-    for (int i = 0; i < 10; i++) tot += i == 9 ? 0.f : s.cyc[i];
-    for (int i = 11; i < 17; i++) tot += s.cyc[i];
-    a.trace[32 + blockIdx.x] = tot; a.trace[32 + 4096 + blockIdx.x] = s.cyc[17];
-    // placement and timeline of the wave (blocks < 1024): HW_ID, XCC_ID, start / end on the constant 100 MHz clock
-    if (blockIdx.x < 1024) {
-      unsigned* tw = (unsigned*)(a.trace + 32 + 8192 + 4 * blockIdx.x);
-      tw[0] = __builtin_amdgcn_s_getreg((31 << 11) | 4); tw[1] = __builtin_amdgcn_s_getreg((31 << 11) | 20);
-      tw[2] = (unsigned)t0_real; tw[3] = (unsigned)wall_clock64();
-      for (int i = 0; i < 20; i++) a.trace[16384 + 24 * blockIdx.x + i] = s.cyc[i];      // stage ticks of every wave
-    }
-  }
-#endif
   if (!valid) return;
-#ifdef PGTT_EFFORT
-  if (a.buf.dbg_contact) { a.buf.dbg_contact[(long)e * 16 + 14] = (int)(unsigned)s.eff; a.buf.dbg_contact[(long)e * 16 + 15] = (int)(unsigned)(s.eff >> 32);
-    a.buf.dbg_contact[(long)e * 16 + 12] = s.eff_hess; a.buf.dbg_contact[(long)e * 16 + 13] = s.eff_hess_same; }       // the same for every env of the wave
-#endif
   // The compiler would otherwise keep the ~50 row addresses formed for the loads at the top alive (spilled to scratch)
   // until these stores: an opaque copy of the env index makes it re-form them here (one mad each).
   asm volatile("" : "+v"(e));
@@ -721,20 +675,6 @@ PG_INL void task_rewards(const float* sh_st, const float* sh_fr, const float* sh
     metrics[PGTT_NREW] = sp / 4;
 }
 
-#ifdef PGTT_TIME
-// -DPGTT_TIME=<env> builds (tools/gpu_observe_time.py): phase ticks of the observe wave of that env at a.trace[60000 + i]
-#define PG_OTICK(i) do { if (OMODE == OBS_STEP && a.trace) { long long t_ = __builtin_readcyclecounter(); if (lane == 0) { if (e == PGTT_TIME) a.trace[60000 + (i)] = (float)(t_ - ot0_); \
-    if (blockIdx.x < 512) a.trace[61000 + 8 * blockIdx.x + (i)] = (float)(t_ - ot0_); } } } while (0)        /* [61000 + 8 block + i]: the boundaries of the first 512 waves (inside trace segment 0, clear of the physics records) */
-#elif defined(PGTT_OBS_STOP)
-// -DPGTT_OBS_STOP builds (tools/gpu_observe_instr.py): the step's observe wave leaves at phase boundary i when the test-hook integer says so
-#define PG_OTICK(i) do { if (OMODE == OBS_STEP && a.scan_preset == 100 + (i)) return; } while (0)
-#define PG_SCAN_PRESET(a) ((a).scan_preset == 1)
-#else
-#define PG_OTICK(i) ((void)0)
-#endif
-#ifndef PG_SCAN_PRESET
-#define PG_SCAN_PRESET(a) ((a).scan_preset != 0)
-#endif
 // ---- observation rows as a table.  Every row of the state observation is (source value [- zmin]) [+ noise] [- offset]; which source, which
 // word of the noise draws, which noise scale and which offset is a function of the row number alone.  The kernel used to find them through a
 // chain of row-range tests that every lane of every pass walked (the vector ALU is what the four waves of a SIMD share); now lane io reads
@@ -800,10 +740,6 @@ template <int OMODE, bool HAS_TERRAIN>
 // four waves per SIMD (128 VGPRs): the kernel is latency-bound, a launch lasts as long as the resident waves of a SIMD take in turn
 __global__ __launch_bounds__(64, 4) void observe_kernel(KArgs a, const float* __restrict__ action) {
   const int e = xcd_block(blockIdx.x, gridDim.x), lane = threadIdx.x, N = a.N;
-#ifdef PGTT_TIME
-  const long long ot0_ = __builtin_readcyclecounter();
-  const unsigned ow0_ = (unsigned)wall_clock64();
-#endif
   if (OMODE != OBS_STEP && OMODE != OBS_STEP_OBS && a.mask && !a.mask[e]) return;
   const PgttModel* __restrict__ m = a.model;
   const PgttConfig* __restrict__ cfg = a.cfg;
@@ -868,7 +804,6 @@ __global__ __launch_bounds__(64, 4) void observe_kernel(KArgs a, const float* __
     if (a.buf.interval_sums) ivs_old = a.buf.interval_sums[lane * (long)N + e];
   }
   __syncthreads();
-  PG_OTICK(0);
 
   // ---------------- height scan (heightmap.py:25-67)
   const float bx = sh_st[PGTT_S_QPOS + 0], by = sh_st[PGTT_S_QPOS + 1], bz = sh_st[PGTT_S_QPOS + 2];
@@ -1008,14 +943,13 @@ __global__ __launch_bounds__(64, 4) void observe_kernel(KArgs a, const float* __
       }
     }
   }
-  PG_OTICK(1);
   float z[2];
 #pragma unroll
   for (int h = 0; h < 2; h++) {
     float dist = hit[h] == INFINITY ? -1.0f : hit[h];
     z[h] = org[h].z + (-1.0f) * dist;
     int idx = lane + 64 * h;
-    if ((OMODE == OBS_STEP || OMODE == OBS_STEP_OBS) && PG_SCAN_PRESET(a)) z[h] = a.buf.scan_z[(long)e * PGTT_NSCAN + (idx < PGTT_NSCAN ? idx : 0)];   // test hook
+    if ((OMODE == OBS_STEP || OMODE == OBS_STEP_OBS) && a.scan_preset != 0) z[h] = a.buf.scan_z[(long)e * PGTT_NSCAN + (idx < PGTT_NSCAN ? idx : 0)];   // test hook
     if (idx < PGTT_NSCAN) { sh_scan[idx] = z[h]; a.buf.scan_z[(long)e * PGTT_NSCAN + idx] = z[h]; }
   }
   if (OMODE == OBS_SCAN_ONLY) return;
@@ -1043,7 +977,6 @@ __global__ __launch_bounds__(64, 4) void observe_kernel(KArgs a, const float* __
   }
   const float zmin = wave_min(fminf(z[0], v1 ? z[1] : INFINITY));
 
-  PG_OTICK(2);
   // ---------------- per-env scalars (computed redundantly by every lane from LDS)
   // method 1 = the baseline task go2/joystick.py: no phase / gait_freq rows in the observation (162 / 206 instead of
   // 171 / 215), H_max = quadrant max, world-frame clearance target, 0.5 s air-time threshold
@@ -1092,7 +1025,6 @@ __global__ __launch_bounds__(64, 4) void observe_kernel(KArgs a, const float* __
     }
   }
 
-  PG_OTICK(3);
   // ---------------- observation rows in LDS (joystick_pgtt.py:336-365)
   const float lvl = cfg->noise_level;
   // The noise draws of all rows in ONE Philox pass: the 147 noisy rows need 38 counter blocks (gyro 1, gravity 1, joint
@@ -1164,7 +1096,6 @@ __global__ __launch_bounds__(64, 4) void observe_kernel(KArgs a, const float* __
     return;
   }
 
-  PG_OTICK(4);
   // ---------------- rewards, termination, bookkeeping
   float reward = 0.f; bool done = false; float metrics[PGTT_NMETRIC];
 #pragma unroll
@@ -1187,7 +1118,6 @@ __global__ __launch_bounds__(64, 4) void observe_kernel(KArgs a, const float* __
     for (int k = 0; k < PGTT_NMETRIC; k++) metrics[k] = t.metrics[k];
     if (lane < 12) act_i = sh_act[lane];
   }
-  PG_OTICK(5);
   // ---------------- Episode / AutoReset wrapper semantics (UPSTREAM-RECALL)
   bool wdone = done;
   if (OMODE == OBS_STEP && cfg->autoreset) {
@@ -1236,7 +1166,6 @@ __global__ __launch_bounds__(64, 4) void observe_kernel(KArgs a, const float* __
   if (OMODE == OBS_STEP && cfg->autoreset && a.buf.ep_metrics && lane < PGTT_NMETRIC + 2)
     a.buf.ep_metrics[lane * (long)N + e] = (epm_old + sh_met[lane]) * (prev_done ? 0.f : 1.f);
 
-  PG_OTICK(6);
   // ---------------- stores: rows PGTT_S_CMD .. PGTT_NSTATE - 1 of the image (the step leaves the motor targets, which are the physics kernel's, alone)
   static_assert(PGTT_NSTATE - PGTT_S_CMD <= 128 && PGTT_NMETRIC + 2 <= 64, "two passes over the rows, one over the metrics");
 #pragma unroll
@@ -1266,13 +1195,6 @@ __global__ __launch_bounds__(64, 4) void observe_kernel(KArgs a, const float* __
   }
   for (int i = lane; i < OBSD; i += 64) a.buf.obs_state[(long)e * OBSD + i] = sh_obs[i];
   for (int i = lane; i < PRIVD; i += 64) a.buf.obs_priv[(long)e * PRIVD + i] = sh_obs[OBSD + i];
-  PG_OTICK(7);
-#ifdef PGTT_TIME
-  if (OMODE == OBS_STEP && a.trace && lane == 0 && blockIdx.x < 4096) {      // placement and timeline of every observe wave
-    unsigned* tw = (unsigned*)(a.trace + 40960 + 4 * blockIdx.x);
-    tw[0] = __builtin_amdgcn_s_getreg((31 << 11) | 4); tw[1] = __builtin_amdgcn_s_getreg((31 << 11) | 20); tw[2] = ow0_; tw[3] = (unsigned)wall_clock64();
-  }
-#endif
   if (OMODE == OBS_RESET) {
     if (a.buf.first_state) for (int r = lane; r < PGTT_S_CMD; r += 64) a.buf.first_state[r * (long)N + e] = sh_st[r];
     if (a.buf.first_obs) for (int i = lane; i < OBSD + PRIVD; i += 64) a.buf.first_obs[(long)e * (OBSD + PRIVD) + i] = sh_obs[i];

@@ -206,33 +206,9 @@ struct QSim {
   bool lim_active[3]; float lim_sign[3], lim_D[3], lim_aref[3];
   QContact con0;             // own foot vs the plane (registers)
   int nbox;                  // own box contacts; their records live in LDS (see BoxSlots)
-#ifdef PGTT_TRACE
-  float* tr = nullptr; int trn = 0;
-  PG_INL void rec(float v) { if (tr) tr[4 * trn] = v; trn++; }
-  PG_INL void rec(V3 v) { rec(v.x); rec(v.y); rec(v.z); }
-#endif
-#ifdef PGTT_TIME
-  // stage timer (-DPGTT_TIME builds): cyc[i] accumulates shader-clock ticks of stage i over the launch
-  long long tlast = 0; float cyc[28] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // 20..27: sub-stages of the line search (own clock)
-  long long tls = 0; PG_INL void ltick(int i) { long long t = __builtin_readcyclecounter(); cyc[i] += (float)(t - tls); tls = t; }
-#define PG_LTICK(sim, i) (sim).ltick(i)
-  PG_INL void tick(int stage) { long long t = __builtin_readcyclecounter(); cyc[stage] += (float)(t - tlast); tlast = t; }
-#define PG_TICK(sim, stage) (sim).tick(stage)
-  PG_INL void cyc_iter() { cyc[10] += 1.f; }
-#else
-#define PG_TICK(sim, stage) ((void)0)
-#define PG_LTICK(sim, i) ((void)0)
-  PG_INL void cyc_iter() {}
-#endif
   // outputs
   float qacc_b[6], qacc_l[3];
   int niter, niter_max;
-#ifdef PGTT_EFFORT
-  // -DPGTT_EFFORT builds (tools/gpu_effort.py): 1 + the line-search rounds THIS env needed, 3 bits per Newton trip, 5 trips per substep
-  unsigned long long eff = 0ull; int eff_pos = 0, eff_sub = 0;
-  // ... and how often the Hessian is rebuilt although NO lane of the wave has a row that changed sides since the last Newton trip
-  unsigned eff_pat = 0xffffffffu; int eff_hess = 0, eff_hess_same = 0;
-#endif
   bool pen_overflow;         // some substep of this call met more than kMaxPenQ simultaneously penetrating boxes under this foot (collide())
 };
 
@@ -257,22 +233,16 @@ PG_INL void qarrow_mul(const QArrow& A, const float* xb, const float* xl, float*
     yl[k] = s;
   }
 }
-// -DPGTT_EXACT_PIVOT side builds (profiles/r06_rsq_ab.txt): the inverse pivots from a correctly rounded square root and a correctly rounded division
-#ifdef PGTT_EXACT_PIVOT
-#define PG_RSQ(x) (1.0f / sqrtf(x))
-#else
-#define PG_RSQ(x) __builtin_amdgcn_rsqf(x)
-#endif
 PG_INL void qarrow_factor(QArrow& A) {
   float* c = A.ll;
   // The diagonal of a Cholesky factor is only ever used as a divisor (here and in qarrow_solve), so the factor keeps its
   // INVERSE: one v_rsq_f32 (1 ulp) per pivot and multiplications instead of a square root plus ~40 divisions (8
   // instructions each in the 1-ulp form) per factorisation + solve.
-  const float i00 = PG_RSQ(c[0]);
+  const float i00 = __builtin_amdgcn_rsqf(c[0]);
   float l10 = c[1] * i00, l20 = c[3] * i00;
-  const float i11 = PG_RSQ(c[2] - l10 * l10);
+  const float i11 = __builtin_amdgcn_rsqf(c[2] - l10 * l10);
   float l21 = (c[4] - l20 * l10) * i11;
-  const float i22 = PG_RSQ(c[5] - l20 * l20 - l21 * l21);
+  const float i22 = __builtin_amdgcn_rsqf(c[5] - l20 * l20 - l21 * l21);
   c[0] = i00; c[1] = l10; c[2] = i11; c[3] = l20; c[4] = l21; c[5] = i22;
   float* w = A.lb;
   if (kSubs != 4) {
@@ -333,7 +303,7 @@ PG_INL void qarrow_factor(QArrow& A) {
     float s = A.bb[tri(j, j)];
 #pragma unroll
     for (int k = 0; k < j; k++) s -= A.bb[tri(j, k)] * A.bb[tri(j, k)];
-    const float id = PG_RSQ(s);
+    const float id = __builtin_amdgcn_rsqf(s);
     A.bb[tri(j, j)] = id;
 #pragma unroll
     for (int i = j + 1; i < 6; i++) {
@@ -541,20 +511,6 @@ struct QPhysics {
       for (int kk = 0; kk <= k; kk++) s.M.bb[tri(k, kk)] = kk < 3 ? fl[kk] : dot6(s.cdr[kk - 3], f);
     }
     s.LM = s.M;
-#ifdef PGTT_TRACE
-    s.rec(400.f);
-    for (int i = 0; i < 7; i++) s.rec(s.qb[i]);            // 1..7
-    for (int i = 0; i < 3; i++) s.rec(s.ql[i]);            // 8..10
-    s.rec(em.mass0); for (int i = 0; i < 3; i++) s.rec(em.massl[i]);   // 11..14
-    s.rec(xi0); for (int i = 0; i < 6; i++) s.rec(Iw0[i]);             // 15..17, 18..23
-    for (int k = 0; k < 3; k++) s.rec(xil[k]);                          // 24..32
-    s.rec(part); s.rec(pm); s.rec(tot); s.rec(mt); s.rec(s.com);       // 33..35, 36, 37..39, 40, 41..43
-    for (int i = 0; i < 10; i++) s.rec(s.cin0.i[i]);                    // 44..53
-    for (int i = 0; i < 10; i++) s.rec(crb.i[i]);                       // 54..63
-    for (int i = 0; i < 10; i++) s.rec(crb_base.i[i]);                  // 64..73
-    for (int k = 0; k < 3; k++) { s.rec(s.cdr[k].a); s.rec(s.cdr[k].l); }   // 74..91
-    for (int i = 0; i < 21; i++) s.rec(s.M.bb[i]);                      // 92..112
-#endif
     qarrow_factor(s.LM);
   }
 
@@ -621,22 +577,6 @@ struct QPhysics {
       for (int i = 0; i < 6; i++) s.qfs_b[i] = any ? s.qfs_b[i] + jw[i] : s.qfs_b[i];
     }
     qarrow_solve(s.LM, s.qfs_b, s.qfs_l, s.qas_b, s.qas_l);
-#ifdef PGTT_TRACE
-    s.rec(500.f);
-    for (int i = 0; i < 21; i++) s.rec(s.LM.bb[i]);       // 1..21
-    for (int i = 0; i < 18; i++) s.rec(s.LM.lb[i]);       // 22..39
-    for (int i = 0; i < 6; i++) s.rec(s.LM.ll[i]);        // 40..45
-    for (int i = 0; i < 6; i++) s.rec(s.M.ll[i]);         // 46..51
-    for (int i = 0; i < 6; i++) s.rec(s.qfs_b[i]);        // 52..57
-    for (int i = 0; i < 3; i++) s.rec(s.qfs_l[i]);        // 58..60
-    for (int i = 0; i < 6; i++) s.rec(s.qas_b[i]);        // 61..66
-    for (int i = 0; i < 3; i++) s.rec(s.qas_l[i]);        // 67..69
-    for (int i = 0; i < 3; i++) s.rec(s.ctrl[i]);         // 70..72
-    for (int i = 0; i < 3; i++) s.rec(bias_l[i]);         // 73..75
-    for (int i = 0; i < 3; i++) s.rec(s.act_force[i]);    // 76..78
-    for (int i = 0; i < 6; i++) s.rec(s.vb[i]);           // 79..84
-    for (int i = 0; i < 3; i++) s.rec(s.vl[i]);           // 85..87
-#endif
   }
 
   PG_INL void contact_jac(QContact& c, V3 pos, V3 n, V3 t1, V3 t2, float sign) const {
@@ -767,7 +707,6 @@ struct QPhysics {
     const float rad = m->foot_radius[l];
     s.nbox = 0;
     if (boxes == nullptr || nbox <= 0) return;
-    PG_TICK(s, 11);
     // a slot that is not used in this substep must contribute exact zeros: no active row, D = 0, aref = 0.  Its other fields
     // (mu, offset, frame) only ever meet those zeros and keep whatever finite values they hold (the records are cleared in
     // full once per launch, BoxSlots::clear_all)
@@ -817,7 +756,6 @@ struct QPhysics {
       if (kSubs > 1) { cm[0] = sub_or(cm[0]); cm[1] = sub_or(cm[1]); cm[2] = sub_or(cm[2]); cm[3] = sub_or(cm[3]); }
     };
     candidates();
-    PG_TICK(s, 12);
     // pass 1b: narrow phase on the candidates in box order (every lane pops its own lowest set bit); penetrating pairs kept
     QPen pen[kMaxPenQ]; int npen = 0;
 #pragma unroll
@@ -990,7 +928,6 @@ struct QPhysics {
       }
       s.pen_overflow |= npenetr > kMaxPenQ;
     }
-    PG_TICK(s, 13);
     if (__ballot(npen > 0) == 0ull) return;
     // wave-uniform number of candidate columns that are in use anywhere
     int ncol = 0;
@@ -1023,9 +960,6 @@ struct QPhysics {
       // On the shipped terrains the count is ~3 of the 25 allowed, so R is generous (thr + 0.1 m) and the 100-box pass runs once per launch.
       {
         const bool holds = (thr2 < 0.f) | ((c2_thr >= 0.f) & ((norm(s.footc - c2_foot) + thr) * 1.0001f + 1e-5f <= c2_thr));      // own foot
-#ifdef PGTT_TIME
-        s.cyc[26] += __ballot(!holds) == 0ull ? 1.f : 0.f;       // substeps in which the wave carries the proof over
-#endif
         if (__ballot(!holds) == 0ull) goto counted;           // every foot of every env of the wave: need_exact stays false
       }
       {
@@ -1044,9 +978,6 @@ struct QPhysics {
         if (kSubs == 4) nearmask |= (in ? 1u : 0u) << t;     // own boxes that can sort before a candidate (pass 2b)
       }
       need_exact = quad_sum_i(sub_sum_i(cnt)) > maxp;
-#ifdef PGTT_TIME
-      s.cyc[25] += (float)quad_sum_i(sub_sum_i(cnt));      // pairs counted by the passes of this launch (own env)
-#endif
       // remember the wider count when it is a proof as well (an env without a candidate has thr2 < 0 and needs none)
       c2_foot = s.footc;
       c2_thr = (thr2 >= 0.f && quad_sum_i(sub_sum_i(cnt_r)) <= maxp) ? thr_r : -1.f;
@@ -1143,7 +1074,6 @@ struct QPhysics {
         }
       }
     }
-    PG_TICK(s, 14);
     // selection of the max_contact_points deepest survivors of the env (ties: lower broad-phase rank first, then the
     // scan order leg-major): MJX's sequential top-k picks exactly the pairs that fewer than max_contact_points others
     // beat, so every lane only ranks its OWN pairs against the table — no selection rounds.
@@ -1219,7 +1149,6 @@ struct QPhysics {
       }
     }
     s.nbox = nb;
-    PG_TICK(s, 16);
   }
 };
 
@@ -1263,23 +1192,6 @@ struct QSolver {
   bool any_lim, any_con0;   // wave-uniform: some lane has an active joint-limit row / an active plane contact.
                             // Inactive rows have D = 0 and aref = 0: they add exact zeros, so skipping them is bit-neutral.
   const BoxSlots slots;
-#ifdef PGTT_TRACE
-  float last_alpha = 0.f;
-  PG_INL void rec(float v) { s.rec(v); }
-  PG_INL void rec_state(float tag) {
-    rec(tag); rec(cost); rec(gauss); rec(prev_cost); rec(last_alpha);
-    for (int i = 0; i < 6; i++) rec(qb[i]);
-    for (int i = 0; i < 3; i++) rec(ql[i]);
-    for (int i = 0; i < 6; i++) rec(gb[i]);
-    for (int i = 0; i < 3; i++) rec(gl[i]);
-    for (int i = 0; i < 6; i++) rec(sb[i]);
-    for (int i = 0; i < 3; i++) rec(sl[i]);
-    for (int i = 0; i < 6; i++) rec(fcb[i]);
-    for (int i = 0; i < 3; i++) rec(fcl[i]);
-    for (int i = 0; i < 4; i++) rec(jar0[i]);
-    for (int i = 0; i < 3; i++) rec(jar_lim[i]);
-  }
-#endif
 
   PG_INL QSolver(const PgttModel* m_, QSim& s_, const BoxSlots& sl_) : m(m_), s(s_), slots(sl_) {}
 
@@ -1408,21 +1320,6 @@ struct QSolver {
   }
 
   PG_INL void update_gradient() {
-#ifdef PGTT_EFFORT
-    {
-      unsigned pat = 0u;
-#pragma unroll
-      for (int k = 0; k < 3; k++) pat |= (jar_lim[k] < 0.f ? 1u : 0u) << k;
-#pragma unroll
-      for (int r = 0; r < 4; r++) pat |= (jar0[r] < 0.f ? 1u : 0u) << (3 + r);
-      if (kSubs == 4) {
-#pragma unroll
-        for (int r = 0; r < 4; r++) pat |= ((own_on((int)(threadIdx.x & 3)) && mjar[r] < 0.f) ? 1u : 0u) << (7 + r);
-      }
-      s.eff_hess += 1; s.eff_hess_same += __ballot(pat != s.eff_pat) == 0ull ? 1 : 0;
-      s.eff_pat = pat;
-    }
-#endif
 #pragma unroll
     for (int i = 0; i < 6; i++) gb[i] = Mab[i] - s.qfs_b[i] - fcb[i];
 #pragma unroll
@@ -1559,13 +1456,6 @@ struct QSolver {
     }
 #pragma unroll
     for (int i = 0; i < 21; i++) H.bb[i] = s.M.bb[i] + quad_sum(Gbb[i]);
-#ifdef PGTT_TRACE
-    rec(300.f);
-    for (int i = 0; i < 21; i++) rec(H.bb[i]);
-    for (int i = 0; i < 21; i++) rec(s.M.bb[i]);
-    for (int i = 0; i < 18; i++) rec(H.lb[i]);
-    for (int i = 0; i < 6; i++) rec(H.ll[i]);
-#endif
     qarrow_factor(H);
     float mgb[6], mgl[3];
     qarrow_solve(H, gb, gl, mgb, mgl);
@@ -1673,7 +1563,6 @@ struct QSolver {
   }
 
   PG_INL void linesearch(bool frozen) {
-    PG_LTICK(s, 27);
     float snb = 0.f, snl = 0.f;
 #pragma unroll
     for (int i = 0; i < 6; i++) snb += sb[i] * sb[i];
@@ -1794,27 +1683,15 @@ struct QSolver {
       moved = u < u0;
       return r;
     };
-    PG_LTICK(s, 20);      // set-up: M s, J s, row hand-over, Gauss coefficients
     LSPoint p0, lo0;
     { const float a0 = 0.f; ls_points<1>(&a0, jv_lim, jv0, qg0, qg1, qg2, &p0); }
     { const float a1 = p0.alpha - div_normal(p0.d0, p0.d1); ls_points<1, false>(&a1, jv_lim, jv0, qg0, qg1, qg2, &lo0); }
     bool lesser = lo0.d0 < p0.d0;
     LSPoint hi = lesser ? p0 : lo0, lo = lesser ? lo0 : p0;
     bool swap = true; int it = 0;
-    PG_LTICK(s, 21);      // the two initial points
-#ifdef PGTT_EFFORT
-    int eff_need = frozen ? 0 : 1;        // 0: the env was not in this trip at all
-#endif
     for (;;) {
       bool done = it >= m->ls_iterations || !swap || ((lo.d0 < 0.f) && (lo.d0 > -gtol)) || ((hi.d0 > 0.f) && (hi.d0 < gtol));
       if (__ballot(!done) == 0ull) break;
-#ifdef PGTT_EFFORT
-      eff_need += (done || frozen) ? 0 : 1;
-#endif
-#ifdef PGTT_TIME
-      s.cyc[18] += 1.f;           // line-search rounds executed by this wave
-      s.cyc[19] += done ? 0.f : 1.f;   // ... of which this env needed
-#endif
       const float al3[3] = {lo.alpha - div_normal(lo.d0, lo.d1), hi.alpha - div_normal(hi.d0, hi.d1), 0.5f * (lo.alpha + hi.alpha)};
       LSPoint pt[3];
       ls_points<3, false>(al3, jv_lim, jv0, qg0, qg1, qg2, pt);
@@ -1824,23 +1701,15 @@ struct QSolver {
       // a finished env moves nothing, so swap turns false and keeps it finished (`done` is sticky through !swap); its count may run on
       swap = ml | mh; it++;
     }
-    PG_LTICK(s, 22);      // bracketing rounds
-#ifdef PGTT_EFFORT
-    s.eff |= (unsigned long long)eff_need << s.eff_pos; s.eff_pos += 3;
-#endif
     {   // costs of the two points the bracket ended with
       const float al2[2] = {lo.alpha, hi.alpha};
       LSPoint fin[2];
       ls_points<2, true>(al2, jv_lim, jv0, qg0, qg1, qg2, fin);
       lo.cost = fin[0].cost; hi.cost = fin[1].cost;
     }
-    PG_LTICK(s, 23);      // final costs
     bool improved = (lo.cost < p0.cost) || (hi.cost < p0.cost);
     float alpha = lo.cost < hi.cost ? lo.alpha : hi.alpha;
     float ia = (improved && !frozen) ? alpha : 0.f;
-#ifdef PGTT_TRACE
-    last_alpha = ia;
-#endif
 #pragma unroll
     for (int i = 0; i < 6; i++) { qb[i] += sb[i] * ia; Mab[i] += mvb[i] * ia; }
 #pragma unroll
@@ -1856,20 +1725,13 @@ struct QSolver {
         else { mjar[r] += mjv[r] * ia; slots.jar(k, r) = mjar[r]; }
       }
     }
-    PG_LTICK(s, 24);      // update of qacc, M qacc, J qacc - aref
   }
 
   PG_INL void solve() {
-#ifdef PGTT_EFFORT
-    s.eff_pos = 15 * s.eff_sub; s.eff_sub++; s.eff_pat = 0xffffffffu;
-#endif
     int nb = 0;
 #pragma unroll
     for (int k = 0; k < kMaxB; k++) if (__ballot(s.nbox > k) != 0ull) nb = k + 1;
     nslots = nb;
-#ifdef PGTT_TIME
-    s.cyc[17] += (float)nb;
-#endif
     any_lim = __ballot(s.lim_active[0] || s.lim_active[1] || s.lim_active[2]) != 0ull;
     any_con0 = __ballot(s.con0.row_active) != 0ull;
     plane_sub = kSubs == 4 && lds_slots && nb <= 3 && any_con0;
@@ -1882,7 +1744,6 @@ struct QSolver {
       if (plane_sub) slots.store(nb, s.con0);
     }
     if (kSubs == 4 && lds_slots) mine = slots.load((int)(threadIdx.x & 3));
-    PG_TICK(s, 3);
     // start from the cheaper of (unconstrained acceleration, warm start).  The warm start is evaluated LAST: when it wins
     // in every lane of the wave (the steady state) the solver state is already the one to continue from; only a wave
     // in which some env prefers the unconstrained acceleration pays a third evaluation of the per-env choice.
@@ -1898,12 +1759,7 @@ struct QSolver {
       for (int k = 0; k < 3; k++) kl[k] = usew ? s.wl[k] : s.qas_l[k];
       init(kb, kl); update_constraint();
     }
-    PG_TICK(s, 4);
     update_gradient();
-    PG_TICK(s, 5);
-#ifdef PGTT_TRACE
-    rec_state(100.f);
-#endif
     const float scale = m->meaninertia * 18.0f;
     int niter = 0, trip = 0;
     for (;;) {
@@ -1917,23 +1773,15 @@ struct QSolver {
       const bool d_it = niter >= m->iterations, d_imp = div_normal(prev_cost - cost, scale) < m->tolerance, d_grad = div_normal(sqrtf(gn), scale) < m->tolerance;
       bool done = d_it | d_imp | d_grad;
       if (__ballot(!done) == 0ull) break;
-      PG_TICK(s, 9);
       linesearch(done);
-      PG_TICK(s, 6);
       // "done" is sticky and every other lane counts up, so the loop makes at most `iterations` trips: the constraint
       // forces, cost, gradient, Hessian and search direction of the last possible trip would never be used (mjx
       // computes them all the same); qacc is final after its line search
       if (++trip < m->iterations) {
         update_constraint();
-        PG_TICK(s, 7);
         update_gradient();
       }
-      PG_TICK(s, 8);
-      s.cyc_iter();
       if (!done) niter++;
-#ifdef PGTT_TRACE
-      rec_state(200.f + niter);
-#endif
     }
 #pragma unroll
     for (int i = 0; i < 6; i++) { s.qacc_b[i] = qb[i]; s.wb[i] = qb[i]; }

@@ -256,7 +256,7 @@ def run_parity(task, n, terrain, steps, dr=False, autoreset=False, noise=1.0, me
             X.explain_step(ledger, k, ve, vkeys, ms, hb, terrain, S0, act, hb["state"][abi.S_MOTOR_TARGETS:abi.S_MOTOR_TARGETS + 12] if not autoreset else motor_targets(env, act),
                            fin, substeps, nsub, skip_final_check=was_reset, observed=eg, scan_ctx=dict(cs=cs, dev_scan=g["scan_z"], orc_scan=hb["scan_z"]))
             bad_now = [r for r in ledger.records[nrec:] if r["cause"] == "unexplained"]
-            if bad_now:           # keep the whole batch of that step: tools/gpu_explain_case.py replays it (trace builds, other layouts) on the GPU box
+            if bad_now:           # keep the whole batch of that step: tools/gpu_explain_case.py replays it (other layouts, other builds) on the GPU box
                 out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gpurun_out", "unexplained")
                 os.makedirs(out, exist_ok=True)
                 name = os.environ.get("PYTEST_CURRENT_TEST", "case").split("::")[-1].split(" ")[0].replace("[", "_").replace("]", "").replace("/", "_")

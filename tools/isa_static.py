@@ -1,5 +1,5 @@
-"""Static instruction mix of the headline kernel, physics_kernel<0,false,true,4> (variant 4_0_0_1), compiled with the product flags of csrc/Makefile and
--save-temps: how many of its vector-ALU instructions are PACKED fp32 (v_pk_*: two flops per lane per issue - what the 157.3 TFLOP/s peak assumes)?
+"""Static instruction mix of the headline kernel, physics_kernel<0,false,true,4> (variant 4_0_0_1), compiled with the product flags of csrc/Makefile
+(`make flags-4_0_0_1`) and -save-temps: how many of its vector-ALU instructions are PACKED fp32 (v_pk_*: two flops per lane per issue - what the 157.3 TFLOP/s peak assumes)?
 Writes profiles/isa_static.json with the hash of the kernel sources; bench.py quotes `valu_packed_share` and the roofline fraction against the UNPACKED
 ceiling (78.65 TFLOP/s) from it when the loaded library was built from the same sources.       python tools/isa_static.py      (here, no GPU)"""
 import collections, json, os, subprocess, sys, tempfile
@@ -7,9 +7,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from phase_guided_terrain_traversal_amd import srchash
 csrc = os.path.join(ROOT, "phase_guided_terrain_traversal_amd", "csrc")
-flags = "--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-value -fno-slp-vectorize -mllvm -amdgpu-sched-strategy=iterative-ilp -mllvm -amdgpu-load-store-vectorizer=0".split()
+flags = subprocess.run(["make", "-s", "--no-print-directory", "-C", csrc, "flags-4_0_0_1"], check=True, capture_output=True, text=True).stdout.split()
 with tempfile.TemporaryDirectory() as td:
-    subprocess.run(["hipcc"] + flags + ["-DPG_SUBS=4", "-DPG_MODE=0", "-DPG_DR=0", "-DPG_TERRAIN=1", "-save-temps", "-c", os.path.join(csrc, "pgtt_physics_inst.hip"), "-o", os.path.join(td, "p.o")],
+    subprocess.run(["hipcc"] + flags + ["-save-temps", "-c", os.path.join(csrc, "pgtt_physics_inst.hip"), "-o", os.path.join(td, "p.o")],
                    check=True, cwd=td, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
     asm = [f for f in os.listdir(td) if f.endswith(".s") and "gfx950" in f][0]
     c = collections.Counter()
