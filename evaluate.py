@@ -104,7 +104,13 @@ def run_evaluation(args, num_eval_envs=NUM_EVAL_ENVS, seed=0, verbose=True):
     model = mjcf.load_model(args.task_name)
     terrain = load_terrain(args.terrain_file) if args.task_name == "stairs" else None
     n = num_eval_envs
-    dr = domain_randomize(model, n, seed=seed, terrain=terrain)                   # the evaluator's env gets the same randomization_fn
+    level_start = None
+    if args.task_name == "stairs" and getattr(args, "terrain_files", None):
+        # the stacked table of a curriculum run, evaluated on ONE fixed level of it (--level), the curriculum off
+        from phase_guided_terrain_traversal_amd.curriculum import stack_levels
+        terrain, level_start = stack_levels([load_terrain(f) for f in args.terrain_files.split(",")])
+    dr = domain_randomize(model, n, seed=seed, terrain=terrain, level_start=level_start,      # the evaluator's env gets the same randomization_fn
+                          init_level=int(getattr(args, "level", 0)))
     kw = {"params": torch.from_numpy(dr["params"])}
     if terrain is not None:
         kw.update(variant=torch.from_numpy(dr["variant"]), box_friction=torch.from_numpy(dr["box_friction"]))
@@ -172,6 +178,8 @@ def make_parser():
     ap.add_argument("--video_every", type=int, default=2, help="one frame every n control steps")
     ap.add_argument("--video_scan", action="store_true", help="overlay the 117 height-scan hits as marker spheres")
     configs.add_push_args(ap)
+    ap.add_argument("--terrain_files", type=str, default=None, help="comma-separated level files stacked into one table (as train.py --terrain_files); evaluated on --level")
+    ap.add_argument("--level", type=int, default=0, help="with --terrain_files: the level every evaluation env stands on (no curriculum at evaluation)")
     return ap
 
 

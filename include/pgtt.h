@@ -52,6 +52,7 @@ extern "C" {
 #define PGTT_METHOD_BASELINE 1  /* go2/joystick.py + configs.baseline_config() */
 #define PGTT_NREW 21       /* configs.py:31-59 */
 #define PGTT_NMETRIC 22    /* 21 scaled reward terms + swing_peak (joystick_pgtt.py:122-125) */
+#define PGTT_MAX_LEVELS 16 /* terrain curriculum: levels of one stacked terrain table (pgtt_curriculum) */
 
 /* ---------------------------------------------------------------- errors */
 enum {
@@ -225,7 +226,14 @@ enum {
   PGTT_RS_RESET_XY = 16, PGTT_RS_RESET_YAW = 17, PGTT_RS_RESET_VEL = 18, PGTT_RS_RESET_TIMER = 19,
   PGTT_RS_RESET_CMD = 20, PGTT_RS_RESET_FREQ = 21,
   PGTT_RS_PUSH_WAIT = 24,          /* i = 0: wait before the next kick */
-  PGTT_RS_PUSH_KICK = 25           /* i = 0 duration, 1 velocity, 2 direction of a kick */
+  PGTT_RS_PUSH_KICK = 25,          /* i = 0 duration, 1 velocity, 2 direction of a kick */
+  PGTT_RS_CURRICULUM = 26          /* i = 0: the variant within the level a finished env stands on next */
+};
+
+/* PgttCurriculum.stats (int32): finished episodes per level (counted on the level the episode was played on), then three totals */
+enum {
+  PGTT_CS_PROMOTED = PGTT_MAX_LEVELS, PGTT_CS_DEMOTED = PGTT_MAX_LEVELS + 1, PGTT_CS_FINISHED = PGTT_MAX_LEVELS + 2,
+  PGTT_NCSTAT = PGTT_MAX_LEVELS + 3
 };
 
 /* per-env push scheduler state rows (float SoA [PGTT_NPUSH][N], PgttBuffers.push_state; counts are whole numbers held in floats) */
@@ -256,8 +264,9 @@ typedef struct PgttBuffers {
   float*   ep_metrics;   /* [PGTT_NMETRIC + 2][N] running episode sums: metrics, sum_reward, length */
   /* optional */
   const float*   params;        /* [PGTT_NPARAM][N] or NULL */
-  const int32_t* variant;       /* [N] terrain variant per env in [0, T), or NULL (=0).  pgtt_reset refuses labels outside the range (PGTT_E_ARG);
-                                 * the step kernels clamp them, so a label edited afterwards can never index past the terrain tables */
+  int32_t* variant;             /* [N] terrain variant per env in [0, T), or NULL (=0).  pgtt_reset refuses labels outside the range (PGTT_E_ARG);
+                                 * the step kernels clamp them, so a label edited afterwards can never index past the terrain tables.  Only
+                                 * pgtt_curriculum writes it (pgtt_set_curriculum); otherwise the library only reads it */
   const float*   box_friction;  /* [PGTT_MAX_BOX][N] sliding friction per env per box, or NULL */
   int32_t* dbg_contact;  /* [N][PGTT_NCON][2] (foot 0..3 FL,FR,RL,RR ; geom: -1 plane, box idx, -2 none) or NULL */
   float*   dbg_dist;     /* [N][PGTT_NCON] or NULL */
@@ -276,6 +285,18 @@ typedef struct PgttBuffers {
   float*   xfrc;
   float*   push_state;   /* [PGTT_NPUSH][N] or NULL: the push scheduler's per-env state (PGTT_PU_*), written by pgtt_reset and pgtt_push */
 } PgttBuffers;
+
+/* terrain curriculum (pgtt_set_curriculum / pgtt_curriculum; no counterpart in the reference): settings and caller-owned device buffers.  A struct of its
+ * own, so that PgttConfig and PgttBuffers - and with them the argument block of every step kernel - are what they were without it. */
+typedef struct PgttCurriculum {
+  int32_t levels;                 /* L, 1 .. PGTT_MAX_LEVELS */
+  int32_t level_start[PGTT_MAX_LEVELS + 1];   /* level l owns the variants [start[l], start[l + 1]) of the terrain table; start[0] = 0, strictly increasing */
+  float promote_tracking;         /* in [0, 1]: a TRUNCATED episode whose mean unscaled tracking_lin_vel term reaches it moves its env one level up */
+  float demote_length;            /* in [0, 1]: an episode TERMINATED before this share of episode_length moves its env one level down */
+  int32_t* level;                 /* [N] the env's current level in [0, L): the caller sets the initial levels (and, in PgttBuffers.variant, variants inside
+                                   * them), pgtt_curriculum keeps both afterwards */
+  int32_t* stats;                 /* [PGTT_NCSTAT] counters pgtt_curriculum adds to (PGTT_CS_*); the caller clears them; or NULL */
+} PgttCurriculum;
 
 #define PGTT_DBG_PEN_OVERFLOW 0x10000
 
@@ -315,6 +336,36 @@ int pgtt_scan(pgtt_handle h, float yaw_override_or_nan, void* stream);     /* K1
  * wait again.  An env whose done was set by the previous step, or that pgtt_reset reset, restarts its wait.  Draws: PGTT_RS_PUSH_* at the
  * env's current epoch.  PGTT_E_STATE when push_enable is 0. */
 int pgtt_push(pgtt_handle h, void* stream);
+
+/* Terrain curriculum: per env and at the end of each episode, the level the env stands on next, decided on the GPU.
+ * For an env whose `done` of the step just taken is 1, with steps = istate[PGTT_I_EP_STEPS], truncated = (steps >= episode_length) and
+ * trk = ep_metrics[PGTT_R_TRACKING_LIN_VEL] / (ep_metrics[PGTT_NMETRIC + 1] * reward_scale[PGTT_R_TRACKING_LIN_VEL]) (the episode mean of the unscaled
+ * term, in [0, 1]; 0 when the length row or the scale is 0):
+ *   truncated && trk >= curriculum_promote_tracking               -> level + 1, clamped to L - 1
+ *   !truncated && steps < curriculum_demote_length * episode_length -> level - 1, clamped to 0
+ *   otherwise                                                      -> the level stays
+ * and variant = level_start[l] + min(int(u * T_l), T_l - 1), u = uniform(seed, global env id, epoch, PGTT_RS_CURRICULUM, 0) at the env's epoch after
+ * the step.  curriculum_kernel (one thread per env) writes level, variant and stats (integer atomics); the call then runs pgtt_reset's
+ * masked sequence on the finished envs with the seed and env_id_offset of the last pgtt_reset, without a read-back: the whole call is asynchronous
+ * and can be captured.  So EVERY finished episode restarts from a fresh Joystick.reset on a freshly drawn variant of its (new) level - not from the
+ * AutoReset first state, which belongs to another variant.  done, reward and metrics of the step stay as the step wrote them (a trainer reads them,
+ * and the next step's wrapper multiplies its sums away as after any done); the observation of a finished env is the fresh reset's.
+ * pgtt_step calls it after the observe launch when the curriculum is on; callers of pgtt_physics / pgtt_observe call it themselves.
+ * A caller that must read done / ep_metrics of the step BEFORE the restart clears the sums (a roll-out recorder) sets
+ * pgtt_set_curriculum_deferred(h, 1): pgtt_step then leaves the call to the caller, who makes it after its read.
+ * PGTT_E_STATE when the curriculum is off.
+ * pgtt_set_curriculum switches it on (cur != NULL, copied) or off (NULL) on a bound handle.  It refuses (PGTT_E_ARG, handle unchanged) what
+ * pgtt_curriculum_check refuses - that one needs no handle and no device: a handle config with autoreset = 0, L outside 1 .. PGTT_MAX_LEVELS, a level_start
+ * that is not strictly increasing from 0, thresholds outside [0, 1] or non-finite, promote_tracking > 0 with reward_scale[PGTT_R_TRACKING_LIN_VEL] == 0, a
+ * NULL level - and a handle whose bound buffers lack variant or ep_metrics (PGTT_E_STATE before pgtt_bind); pgtt_bind refuses such buffers while it is on.
+ * The first pgtt_reset after pgtt_set_curriculum / pgtt_bind / pgtt_set_terrain, and every whole-batch one, refuses (PGTT_E_ARG, nothing written) a
+ * table whose T is not level_start[L], a level outside [0, L) and a variant outside its level's range: the same read-back as the label check of pgtt_reset,
+ * skipped during a capture like it. */
+int pgtt_curriculum_check(const PgttConfig* cfg, const PgttCurriculum* cur);
+int pgtt_set_curriculum(pgtt_handle h, const PgttCurriculum* cur_or_null);
+int pgtt_curriculum(pgtt_handle h, void* stream);
+int pgtt_set_curriculum_deferred(pgtt_handle h, int deferred);
+int pgtt_sizeof_curriculum(void);
 
 /* Interval reduction of the running sums the step kernels keep (PgttBuffers.interval_sums, [PGTT_NMETRIC + 2][N]: metrics, reward, done)
  * into out_dev[PGTT_NMETRIC + 3]: entry k < PGTT_NMETRIC + 2 receives the sum over the envs of row k, the last entry `env_steps` (the

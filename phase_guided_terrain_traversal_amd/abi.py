@@ -42,6 +42,9 @@ P_BODY_MASS, P_BASE_IPOS, P_QPOS0, P_ARMATURE, P_DAMPING, P_GAIN, P_BIAS1, P_FLO
 # push scheduler rows (PgttBuffers.push_state, float SoA) and the Philox streams of its draws
 PU_WAIT, PU_STEP, PU_LEN, PU_DURATION, PU_VELOCITY, PU_DIR_X, PU_DIR_Y, NPUSH = 0, 1, 2, 3, 4, 5, 6, 7
 RS_PUSH_WAIT, RS_PUSH_KICK = 24, 25
+# terrain curriculum (pgtt_curriculum): levels of one stacked table, the stream of its variant draw, the rows of PgttCurriculum.stats
+MAX_LEVELS, RS_CURRICULUM = 16, 26
+CS_PROMOTED, CS_DEMOTED, CS_FINISHED, NCSTAT = MAX_LEVELS, MAX_LEVELS + 1, MAX_LEVELS + 2, MAX_LEVELS + 3
 NXFRC = 6                                       # PgttBuffers.xfrc rows: world force xyz, world torque xyz on the torso
 
 f, i32 = C.c_float, C.c_int32
@@ -89,6 +92,12 @@ class PgttBuffers(C.Structure):
         "state", "istate", "frame", "scan_z", "obs_state", "obs_priv", "reward", "done", "metrics",
         "first_state", "first_obs", "ep_metrics", "params", "variant", "box_friction", "dbg_contact",
         "dbg_dist", "dbg_niter", "interval_sums", "xfrc", "push_state")]
+
+
+class PgttCurriculum(C.Structure):
+    """the terrain curriculum's settings and buffers (pgtt_set_curriculum): a struct of its own, PgttConfig / PgttBuffers stay as they are"""
+    _fields_ = [("levels", i32), ("level_start", i32 * (MAX_LEVELS + 1)), ("promote_tracking", f), ("demote_length", f),
+                ("level", C.c_void_p), ("stats", C.c_void_p)]
 
 
 # (name, rows-or-cols, dtype, layout) ; layout "soa" => [rows][N], "aos" => [N][cols]
@@ -167,6 +176,42 @@ def config_struct(cfg: Dict[str, Any]) -> PgttConfig:
         for k, name in (("wait", "push_wait_s"), ("duration", "push_duration_s"), ("velocity", "push_velocity")):
             getattr(s, name)[0], getattr(s, name)[1] = push[k]
     return s
+
+
+def curriculum_struct(cur: Dict[str, Any], level_ptr=None, stats_ptr=None) -> PgttCurriculum:
+    """dict from curriculum_settings (+ the device addresses of the level / stats buffers) -> PgttCurriculum"""
+    s = PgttCurriculum()
+    s.levels = len(cur["level_start"]) - 1
+    for i, v in enumerate(cur["level_start"]):
+        s.level_start[i] = v
+    s.promote_tracking, s.demote_length = cur["promote_tracking"], cur["demote_length"]
+    s.level, s.stats = level_ptr, stats_ptr
+    return s
+
+
+# seed: of the initial labels Joystick draws itself when the caller passes none (curriculum.initial_labels; randomize.domain_randomize(seed=s, level_start=...)
+# returns the same labels for seed = s).  promote_tracking: the reference's vel_percentage (go2/configs.py:11), the tracking level its trainer calls converged; both are parameters, not measurements
+CURRICULUM_DEFAULTS = {"promote_tracking": 0.65, "demote_length": 0.5, "init_level": 0, "seed": 0}
+
+
+def curriculum_settings(cfg: Dict[str, Any]):
+    """{"level_start": [L + 1 ints], "promote_tracking", "demote_length", "init_level"} of the terrain curriculum a config asks for
+    (cfg["curriculum"]), or None (off).  Shape errors are raised here; the value checks are pgtt_create's."""
+    c = cfg.get("curriculum")
+    if c is None:
+        return None
+    unknown = set(c) - set(CURRICULUM_DEFAULTS) - {"level_start"}
+    if unknown:
+        raise ValueError(f"unknown curriculum keys {sorted(unknown)}")
+    if "level_start" not in c:
+        raise ValueError("curriculum needs level_start (curriculum.stack_levels returns it; Joystick fills it in for a list of level tables)")
+    ls = [int(v) for v in c["level_start"]]
+    if not 2 <= len(ls) <= MAX_LEVELS + 1:
+        raise ValueError(f"curriculum: 1 .. {MAX_LEVELS} levels, level_start has {len(ls)} entries")
+    out = dict(CURRICULUM_DEFAULTS, **{k: v for k, v in c.items() if k != "level_start"})
+    out["level_start"] = ls
+    out["promote_tracking"], out["demote_length"] = float(out["promote_tracking"]), float(out["demote_length"])
+    return out
 
 
 # MuJoCo Playground's Go2 joystick names of the kick ranges (pert_config) -> the keys of Joystick(push=...)

@@ -3,7 +3,7 @@
     actor = FusedActor(env, T=20, seed=0)
     actor.load(policy_layers, mean, std)          # [(W [out, in], b [out])] x 4, observation statistics
     for t in range(T):
-        actor.act(); env.step(actor.action); actor.record()
+        actor.act(); env.step(actor.action); actor.record()          # = actor.step()
     actor.storage["obs" | "priv" | "u" | "logp" | "rew" | "done" | "trunc"]      # [T, N, ...]
 
 What the reference gets from Brax's `generate_unroll` with the networks of training/train.py:135-161 (the deployed form of the same
@@ -141,7 +141,15 @@ class FusedActor:
         native.check(self._L.pgtt_rollout_record(C.byref(self._rec_args), self._stream()))
 
     def step(self) -> None:
+        """one acting step.  With a terrain curriculum on the env the order is step (push, physics, observe) -> record -> curriculum: the record
+        reads done / ep_metrics of the step, and the curriculum's restart of the finished envs clears those sums, so env.step leaves the
+        curriculum call to this method (step(..., curriculum=False)), which makes it after the record.  All of it is capturable."""
         self.act()
+        if getattr(self.env, "curriculum", None) is not None:
+            self.env.step(self.action, curriculum=False)
+            self.record()
+            self.env.curriculum_step()
+            return
         self.env.step(self.action)
         self.record()
 

@@ -94,6 +94,30 @@ def push_from_args(args) -> Optional[Dict[str, Any]]:
     return out
 
 
+def add_curriculum_args(ap) -> None:
+    """--terrain_files a,b,c [--curriculum [--curriculum_promote P --curriculum_demote D --curriculum_init lo,hi]] of train.py"""
+    ap.add_argument("--terrain_files", type=str, default=None, help="comma-separated level files, easiest first: one stacked terrain table (a ladder of levels)")
+    ap.add_argument("--curriculum", action="store_true", help="in-run terrain curriculum over --terrain_files: each finished episode moves its env up / down the ladder")
+    ap.add_argument("--curriculum_promote", type=float, default=0.65, help="promote a truncated episode whose mean tracking_lin_vel term reaches this (0..1)")
+    ap.add_argument("--curriculum_demote", type=float, default=0.5, help="demote an episode terminated before this share of episode_length (0..1)")
+    ap.add_argument("--curriculum_init", type=str, default="0,0", help="initial levels lo,hi (uniform per env)")
+
+
+def curriculum_from_args(args, ap=None) -> Optional[Dict[str, Any]]:
+    """the Joystick(curriculum=...) dict of --curriculum*, or None; --curriculum without --terrain_files is a usage error"""
+    if not getattr(args, "curriculum", False):
+        return None
+    if not getattr(args, "terrain_files", None):
+        msg = "--curriculum needs --terrain_files (the ladder of level files)"
+        if ap is not None:
+            ap.error(msg)
+        raise ValueError(msg)
+    parts = [int(x) for x in str(args.curriculum_init).split(",")]
+    if len(parts) != 2:
+        raise ValueError(f"--curriculum_init takes lo,hi (got {args.curriculum_init!r})")
+    return {"promote_tracking": float(args.curriculum_promote), "demote_length": float(args.curriculum_demote), "init_level": (parts[0], parts[1])}
+
+
 def with_overrides(cfg: Dict[str, Any], **kw) -> Dict[str, Any]:
     out = copy.deepcopy(cfg)
     for k, v in kw.items():

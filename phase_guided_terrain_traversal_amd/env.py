@@ -16,7 +16,7 @@ from typing import Any, Dict, Optional
 import numpy as np
 import torch
 
-from . import abi, configs, mjcf, native
+from . import abi, configs, curriculum as _curriculum, mjcf, native
 
 
 class Joystick:
@@ -27,12 +27,22 @@ class Joystick:
                  variant: Optional[torch.Tensor] = None, box_friction: Optional[torch.Tensor] = None,
                  autoreset: bool = False, debug_contacts: bool = False, env_id_offset: int = 0,
                  model: Optional[Dict[str, Any]] = None, layout: Optional[str] = None, observe_form: Optional[str] = None,
-                 test_hooks: bool = False, interval_sums: bool = False, push: Optional[Dict[str, Any]] = None, xfrc: bool = False):
+                 test_hooks: bool = False, interval_sums: bool = False, push: Optional[Dict[str, Any]] = None, xfrc: bool = False,
+                 curriculum: Optional[Dict[str, Any]] = None, level: Optional[torch.Tensor] = None):
         """layout: "auto" | "quad" | "oct" | "hex" lane layout of physics_kernel (PgttConfig.lane_layout; results are bit-identical
         across batch sizes and shards within one layout); observe_form: "fused" | "split"; test_hooks: allow set_test_overrides
         (fixture replay only); interval_sums: keep per-env running sums of the step outputs for a logging trainer (PgttBuffers.interval_sums);
         push: random pushes, dict(wait=(lo, hi) s, duration=(lo, hi) s, velocity=(lo, hi) m/s) (or config["pert_config"] with MuJoCo
-        Playground's keys): the step kicks the torso (pgtt_push); xfrc: allocate the torso-wrench buffer without pushes (apply_wrench)."""
+        Playground's keys): the step kicks the torso (pgtt_push); xfrc: allocate the torso-wrench buffer without pushes (apply_wrench);
+        terrain: one (T, B, 10) table, or a list of level tables (stacked by curriculum.stack_levels; `level_start` says where each begins);
+        curriculum: dict(promote_tracking=0.65, demote_length=0.5, init_level=0 | (lo, hi), seed=0[, level_start=...]): the terrain curriculum
+        (pgtt_curriculum; needs autoreset): each finished episode moves its env up / down the levels and restarts it on a fresh variant.  With ONE
+        stacked table as `terrain`, `level_start` (from curriculum.stack_levels) is required.  level / variant: the initial labels ([N] each), e.g.
+        the "level" / "variant" of randomize.domain_randomize(seed=s, level_start=...); default: curriculum.initial_labels(curriculum["seed"], ...),
+        the same draws for seed = s.  None: nothing of it is allocated, bound or launched."""
+        self.level_start = None
+        if isinstance(terrain, (list, tuple)):
+            terrain, self.level_start = _curriculum.stack_levels(terrain)
         self._config = dict(configs.default_config() if config is None else config)
         self._config["autoreset"] = int(autoreset)
         if layout is not None:
@@ -44,6 +54,23 @@ class Joystick:
         if push is not None:
             self._config["push"] = dict(push)
         self.push = abi.push_ranges(self._config)          # None: no pushes
+        if curriculum is not None:
+            if task != "stairs" or terrain is None:
+                raise ValueError("the terrain curriculum needs task='stairs' and a terrain (a list of level tables)")
+            given = curriculum.get("level_start")
+            if self.level_start is None:
+                # one stacked table (curriculum.stack_levels done by the caller, as train.py does): the caller says where its levels begin
+                if given is None:
+                    raise ValueError("curriculum with one stacked terrain table needs curriculum['level_start'] (what curriculum.stack_levels "
+                                     "returned); or pass terrain=[level tables] and let Joystick stack them")
+                self.level_start = np.asarray(given, dtype=np.int32)
+            elif given is not None and [int(v) for v in given] != [int(v) for v in self.level_start]:
+                raise ValueError(f"curriculum['level_start'] {list(given)} does not match the stacked level tables {self.level_start.tolist()}")
+            if int(self.level_start[0]) != 0 or int(self.level_start[-1]) != np.asarray(terrain).shape[0]:
+                raise ValueError(f"curriculum level_start {self.level_start.tolist()} does not span the terrain table's {np.asarray(terrain).shape[0]} variants")
+            self._config["curriculum"] = dict(curriculum, level_start=[int(v) for v in self.level_start])
+        self.curriculum = abi.curriculum_settings(self._config)      # None: no curriculum
+        self._cur_deferred = False
         self.method = self._config.get("method", "pgtt")     # "pgtt" = go2/joystick_pgtt.py, "baseline" = go2/joystick.py
         self.task = task
         self.num_envs = int(num_envs)
@@ -82,6 +109,16 @@ class Joystick:
         if params is not None:
             self.buffers["params"] = params.to(self.device, torch.float32).contiguous()
             assert self.buffers["params"].shape == (abi.NPARAM, n)
+        if self.curriculum is not None:
+            # the curriculum's labels: caller-owned like every buffer, kept by the library after the first reset
+            if level is None:
+                lv, va = _curriculum.initial_labels(self.curriculum["seed"], self.env_id_offset, n, self.level_start, self.curriculum["init_level"])
+                level = torch.from_numpy(lv)
+                variant = torch.from_numpy(va) if variant is None else variant
+            elif variant is None:
+                raise ValueError("Joystick(level=...) needs variant=... as well (each env's variant inside its level)")
+            self.buffers["level"] = level.to(self.device, torch.int32).contiguous()
+            self.buffers["curriculum_stats"] = torch.zeros(abi.NCSTAT, dtype=torch.int32, device=self.device)
         if variant is not None:
             self.buffers["variant"] = variant.to(self.device, torch.int32).contiguous()
         if box_friction is not None:
@@ -97,6 +134,8 @@ class Joystick:
         if self.push is not None:
             self.buffers["push_state"] = torch.full((abi.NPUSH, n), -1.0, dtype=torch.float32, device=self.device)
         self._bind()
+        if self.curriculum is not None:
+            self._set_curriculum()
         self._seed = 0
 
     # ---- reference-compatible properties
@@ -143,6 +182,10 @@ class Joystick:
             setattr(b, name, None if t is None else t.data_ptr())
         native.check(self._lib.pgtt_bind(self._h, C.byref(b)))
 
+    def _set_curriculum(self) -> None:
+        cs = abi.curriculum_struct(self.curriculum, self.buffers["level"].data_ptr(), self.buffers["curriculum_stats"].data_ptr())
+        native.check(self._lib.pgtt_set_curriculum(self._h, C.byref(cs)))
+
     @property
     def xfrc(self) -> Optional[torch.Tensor]:
         """[6][N] view of the wrench on each env's torso (rows 0..2 world force, 3..5 world torque, at the torso COM), or None when the env has
@@ -170,6 +213,27 @@ class Joystick:
         """the push scheduler alone (pgtt_push): what step() runs first when pushes are on; for callers of physics() / observe()"""
         native.check(self._lib.pgtt_push(self._h, self._stream()))
 
+    @property
+    def level(self) -> Optional[torch.Tensor]:
+        """[N] int32 view of each env's current curriculum level, or None without a curriculum"""
+        return self.buffers.get("level")
+
+    def curriculum_step(self) -> None:
+        """the curriculum alone (pgtt_curriculum): what step() runs last when the curriculum is on; for callers of physics() / observe() and of
+        step(action, curriculum=False)"""
+        native.check(self._lib.pgtt_curriculum(self._h, self._stream()))
+
+    def curriculum_stats(self) -> Dict[str, Any]:
+        """{"finished_per_level": [L], "promoted", "demoted", "finished", "mean_level"} since the last call; clears the counters (one read-back)"""
+        if self.curriculum is None:
+            raise native.PgttError("curriculum_stats: this env has no terrain curriculum - create it with Joystick(..., curriculum=dict(...))")
+        st = self.buffers["curriculum_stats"]
+        s = st.tolist()
+        st.zero_()
+        L = len(self.level_start) - 1
+        return {"finished_per_level": s[:L], "promoted": s[abi.CS_PROMOTED], "demoted": s[abi.CS_DEMOTED], "finished": s[abi.CS_FINISHED],
+                "mean_level": float(self.buffers["level"].float().mean())}
+
     def set_terrain(self, terrain: np.ndarray) -> None:
         t = np.ascontiguousarray(terrain, dtype=np.float32)
         assert t.ndim == 3 and t.shape[2] == 10 and t.shape[1] <= abi.MAX_BOX
@@ -191,9 +255,14 @@ class Joystick:
         native.check(self._lib.pgtt_reset(self._h, self._seed, self.env_id_offset, mp, self._stream()))
         return self._obs()
 
-    def step(self, action: torch.Tensor):
+    def step(self, action: torch.Tensor, curriculum: bool = True):
+        """curriculum=False (only with a curriculum): leave pgtt_curriculum to the caller, who reads done / episode_metrics of the step first and
+        then calls curriculum_step() (the restart clears the episode sums; acting.FusedActor records in between)"""
         a = action.to(self.device, torch.float32).contiguous()
         assert a.shape == (self.num_envs, abi.NU)
+        if self.curriculum is not None and self._cur_deferred != (not curriculum):
+            native.check(self._lib.pgtt_set_curriculum_deferred(self._h, int(not curriculum)))
+            self._cur_deferred = not curriculum
         native.check(self._lib.pgtt_step(self._h, a.data_ptr(), self._stream()))
         info = {"metrics": self.buffers["metrics"], "episode_metrics": self.buffers["ep_metrics"]}
         return self._obs(), self.buffers["reward"], self.buffers["done"], info

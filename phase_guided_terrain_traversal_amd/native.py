@@ -13,7 +13,7 @@ LIB_PATH = os.environ.get("PGTT_LIB", os.path.join(_HERE, "libpgtt.so"))   # PGT
 _LIB: Optional[C.CDLL] = None
 
 EXPORTS = ["pgtt_create", "pgtt_destroy", "pgtt_set_terrain", "pgtt_bind", "pgtt_reset", "pgtt_step",
-           "pgtt_physics", "pgtt_observe", "pgtt_scan", "pgtt_push", "pgtt_interval_reduce", "pgtt_set_test_overrides", "pgtt_enable_timing", "pgtt_last_kernel_ms", "pgtt_kernel_ms_mean",
+           "pgtt_physics", "pgtt_observe", "pgtt_scan", "pgtt_push", "pgtt_curriculum", "pgtt_curriculum_check", "pgtt_set_curriculum", "pgtt_set_curriculum_deferred", "pgtt_sizeof_curriculum", "pgtt_interval_reduce", "pgtt_set_test_overrides", "pgtt_enable_timing", "pgtt_last_kernel_ms", "pgtt_kernel_ms_mean",
            "pgtt_obs_dims", "pgtt_sizeof_model", "pgtt_sizeof_config", "pgtt_sizeof_buffers", "pgtt_version", "pgtt_build_info", "pgtt_last_error"]
 TRAIN_EXPORTS = ["pgtt_ppo_policy_loss", "pgtt_ppo_linear_backward", "pgtt_policy_act", "pgtt_policy_packed_floats", "pgtt_rollout_record",
                  "pgtt_sizeof_policy_act_args", "pgtt_sizeof_rollout_record_args"]      # include/pgtt_train.h: trainer helpers, not the env boundary
@@ -70,6 +70,10 @@ def lib() -> C.CDLL:
             getattr(L, fn).argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.pgtt_scan.argtypes = [C.c_void_p, C.c_float, C.c_void_p]
         L.pgtt_push.argtypes = [C.c_void_p, C.c_void_p]
+        L.pgtt_curriculum.argtypes = [C.c_void_p, C.c_void_p]
+        L.pgtt_set_curriculum_deferred.argtypes = [C.c_void_p, C.c_int]
+        L.pgtt_set_curriculum.argtypes = [C.c_void_p, C.POINTER(abi.PgttCurriculum)]
+        L.pgtt_curriculum_check.argtypes = [C.POINTER(abi.PgttConfig), C.POINTER(abi.PgttCurriculum)]
         L.pgtt_interval_reduce.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_void_p]
         L.pgtt_enable_timing.argtypes = [C.c_void_p, C.c_int]
         L.pgtt_set_test_overrides.argtypes = [C.c_void_p, C.c_float, C.c_int]
@@ -77,6 +81,7 @@ def lib() -> C.CDLL:
         assert L.pgtt_sizeof_model() == C.sizeof(abi.PgttModel)
         assert L.pgtt_sizeof_config() == C.sizeof(abi.PgttConfig)
         assert L.pgtt_sizeof_buffers() == C.sizeof(abi.PgttBuffers)
+        assert L.pgtt_sizeof_curriculum() == C.sizeof(abi.PgttCurriculum)
         _LIB = L
     return _LIB
 

@@ -268,13 +268,16 @@ class _Actor:
         S["obs"].index_copy_(0, t, o[None]); S["priv"].index_copy_(0, t, p[None]); S["u"].index_copy_(0, t, u[None])
         S["logp"].index_copy_(0, t, self.model.log_prob(loc, scale, u)[None])
         self.act.copy_(torch.tanh(u))
-        _, reward, done, info = env.step(self.act)
+        cur = getattr(env, "curriculum", None) is not None      # terrain curriculum: its restart clears the episode sums read below, so it runs last
+        _, reward, done, info = env.step(self.act, curriculum=False) if cur else env.step(self.act)
         fallen = env.buffers["frame"][abi.F_UPVECTOR + 2] < 0
         trunc = (env.buffers["istate"][abi.I_EP_STEPS] >= self.L) & ~fallen
         S["rew"].index_copy_(0, t, (reward * cfg.reward_scaling)[None]); S["done"].index_copy_(0, t, done[None]); S["trunc"].index_copy_(0, t, trunc.float()[None])
         epm = info["episode_metrics"]
         self.ep_ret_sum += (epm[abi.NMETRIC] * done).sum(); self.ep_len_sum += (epm[abi.NMETRIC + 1] * done).sum(); self.ep_cnt += done.sum()
         self.ep_metric_sum += (epm[:abi.NMETRIC] * done).sum(1)
+        if cur:
+            env.curriculum_step()
         t += 1
 
     def rollout(self):
@@ -496,10 +499,19 @@ def train(env, cfg: PPOConfig, progress_fn: Optional[Callable[[int, Dict[str, fl
             log = torch.cat([torch.stack([ep_ret_sum, ep_len_sum, ep_cnt]), ep_metric_sum,
                              torch.stack([loss.detach().reshape(()), batch["rew"].mean()]),
                              torch.tensor([t_env, t_sgd], device=dev, dtype=ep_ret_sum.dtype)])
+            cur = getattr(env, "curriculum", None) is not None
+            if cur:
+                # terrain curriculum: [sum of the envs' levels, promoted, demoted] appended to the SAME buffer (one collective); small integers, exact in fp32
+                cs = env.buffers["curriculum_stats"]
+                log = torch.cat([log, torch.stack([env.buffers["level"].sum(), cs[abi.CS_PROMOTED], cs[abi.CS_DEMOTED]]).to(log.dtype)])
+                n_tail = 3
+            else:
+                n_tail = 0
             if dp:
                 dist.all_reduce(log)
-                log[3 + abi.NMETRIC:] /= world
+                log[3 + abi.NMETRIC:len(log) - n_tail] /= world
             log = log.tolist()
+            cur_tail, log = (log[-3:], log[:-3]) if cur else (None, log)
             c = max(log[2], 1.0)
             te, ts = (log[-2], log[-1]) if dp else (t_env, t_sgd)
             m = {"eval/episode_reward": log[0] / c, "eval/avg_episode_length": log[1] / c,
@@ -508,6 +520,9 @@ def train(env, cfg: PPOConfig, progress_fn: Optional[Callable[[int, Dict[str, fl
                  "loss": log[3 + abi.NMETRIC], "mean_step_reward": log[4 + abi.NMETRIC]}
             for i, k in enumerate(abi.REWARD_KEYS):
                 m[f"eval/episode_reward/{k}"] = log[3 + i] / c
+            if cur:
+                m["curriculum/mean_level"], m["curriculum/promoted"], m["curriculum/demoted"] = cur_tail[0] / (n * world), cur_tail[1], cur_tail[2]
+                env.buffers["curriculum_stats"].zero_()
             history.append((env_steps, m))
             ep_sums.zero_()
             if policy_params_fn is not None and rank == 0:

@@ -78,8 +78,11 @@ def grouped_variants(seed: int, first_env: int, n: int, T: int, total_envs: Opti
 
 def domain_randomize(model: Dict[str, Any], num_envs: int, seed: int = 0, terrain: Optional[np.ndarray] = None,
                      env_id_offset: int = 0, enable: bool = True, _frac: Optional[float] = None,
-                     group_variants: bool = True, total_envs: Optional[int] = None) -> Dict[str, np.ndarray]:
+                     group_variants: bool = True, total_envs: Optional[int] = None, level_start=None, init_level=0) -> Dict[str, np.ndarray]:
     """`group_variants` / `total_envs`: see the module text (`total_envs` = env count of the whole job when this call draws one shard of it).
+    `level_start` (with `terrain` the stacked table of curriculum.stack_levels): the env runs a terrain curriculum - the returned "variant" is drawn
+    inside each env's initial level ("level", `init_level` an int or (lo, hi)) per GLOBAL env id instead, and the ascending hand-out does not apply
+    (the labels move at run time); every other draw, the per-box friction rows included (per box index), is what it is without a curriculum.
     `_frac` (tests only): every draw returns lo + _frac * (hi - lo) instead of a Philox sample, which is how
     tests/golden/domain_randomize.npz was recorded from the reference's own functions."""
     n = int(num_envs)
@@ -125,4 +128,7 @@ def domain_randomize(model: Dict[str, Any], num_envs: int, seed: int = 0, terrai
         if enable:
             bf[:nbox] = u(0.4, 1.0, _D_BOXF, nbox).T
         out["box_friction"] = bf
+        if level_start is not None:
+            from . import curriculum
+            out["level"], out["variant"] = curriculum.initial_labels(seed, env_id_offset, n, level_start, init_level)
     return out

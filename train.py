@@ -6,6 +6,9 @@ driving the HIP environment through the reset()/step()/obs API.
     torchrun --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 train.py --num_envs 32768 ...      (data parallel)
 
 `--terrain_file` accepts a shipped level name (level1,2,3,4,7,10,13) or a path to a (T,100,10) .npy.
+`--terrain_files level1,level4,level7,level10,level13 --curriculum` trains ONE run over a ladder of levels (no counterpart in the reference, whose
+ladder is the three runs of training.sh): every env carries its own level, promoted / demoted on the GPU at the end of each of its episodes
+(DESIGN.md 12); the progress line then shows the mean level and the promoted / demoted counts.  `--terrain_file` alone behaves as before.
 With a torchrun environment (WORLD_SIZE > 1) the job is data parallel, one process per GPU over RCCL, the way the reference's
 Brax PPO spreads over its local devices: `--num_envs` and `--batch_size` stay the job's totals, rank r owns the contiguous
 global env ids of `distributed.shard_range` (DR and reset draws are keyed by global id, so a shard is the same whatever the
@@ -42,14 +45,22 @@ def run_training(args):
     cfg = configs.training_config(args.method)                    # train.py:120-129: config by method + overrides
     model = mjcf.load_model(args.task_name)
     terrain = load_terrain(args.terrain_file) if args.task_name == "stairs" else None
+    cur = configs.curriculum_from_args(args)
+    level_start = None
+    if args.task_name == "stairs" and getattr(args, "terrain_files", None):
+        from phase_guided_terrain_traversal_amd.curriculum import stack_levels
+        terrain, level_start = stack_levels([load_terrain(f) for f in args.terrain_files.split(",")])
     rank, _, world = init_from_env()
     lo, hi = shard_range(args.num_envs, rank, world)
     if (hi - lo) * world != args.num_envs:
         raise SystemExit(f"--num_envs {args.num_envs} must be a multiple of the world size {world}")
-    dr = domain_randomize(model, hi - lo, seed=args.index, terrain=terrain, env_id_offset=lo, total_envs=args.num_envs)      # once per env index
+    dr = domain_randomize(model, hi - lo, seed=args.index, terrain=terrain, env_id_offset=lo, total_envs=args.num_envs,      # once per env index
+                          level_start=level_start if cur is not None else None, init_level=cur["init_level"] if cur is not None else 0)
     kw = {"params": torch.from_numpy(dr["params"])}
     if terrain is not None:
         kw.update(variant=torch.from_numpy(dr["variant"]), box_friction=torch.from_numpy(dr["box_friction"]))
+    if cur is not None:                                           # per-env levels, promoted / demoted on the GPU (pgtt_curriculum)
+        kw.update(curriculum=dict(cur, level_start=[int(v) for v in level_start]), level=torch.from_numpy(dr["level"]))
     push = configs.push_from_args(args)                           # --push_*: random kicks of the torso (off unless one is given)
     if push is not None:
         kw["push"] = push
@@ -74,7 +85,9 @@ def run_training(args):
         av = m["eval/episode_reward/tracking_ang_vel"] / (cfg["reward_config"]["scales"]["tracking_ang_vel"] * L)
         lin.append(vel); ang.append(av)
         if rank == 0:
-            print(f"steps {num_steps:>12d}  reward/episode {y[-1]:9.3f}  len {m['eval/avg_episode_length']:7.1f}  lin {vel:.3f}  ang {av:.3f}  "
+            ladder = (f"level {m['curriculum/mean_level']:.3f}  promoted {int(m['curriculum/promoted'])}  demoted {int(m['curriculum/demoted'])}  "
+                      if "curriculum/mean_level" in m else "")
+            print(f"steps {num_steps:>12d}  reward/episode {y[-1]:9.3f}  len {m['eval/avg_episode_length']:7.1f}  lin {vel:.3f}  ang {av:.3f}  {ladder}"
                   f"rollout {m['env_steps_per_s_rollout'] / 1e6:.2f} M steps/s  total {m['env_steps_per_s_total'] / 1e6:.2f} M steps/s", flush=True)
         if len(y) >= 2 and y[-1] != 0:
             rel = abs((y[-1] - y[-2]) / y[-1])
@@ -117,4 +130,7 @@ if __name__ == "__main__":
     ap.add_argument("--num_evals", type=int, default=31)
     ap.add_argument("--index", type=int, default=32)
     configs.add_push_args(ap)
-    run_training(ap.parse_args())
+    configs.add_curriculum_args(ap)
+    args = ap.parse_args()
+    configs.curriculum_from_args(args, ap)                        # --curriculum without --terrain_files: a usage error
+    run_training(args)
