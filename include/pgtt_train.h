@@ -15,13 +15,20 @@ extern "C" {
  * policy head (loc | raw scale, scale = softplus(raw) + 1e-3; the Brax loss configured at training/train.py:135-161) and its
  * gradient with respect to the network output, in one launch + a single-wave finish instead of ~100 elementwise launches.
  * All pointers are device pointers (float32); partial holds 2 * ceil(B / 64) floats of scratch; loss_3 = {total, policy
- * term, mean entropy}; A must be 12.  Enqueued on `stream`, no synchronisation. */
+ * term, mean entropy}; A must be 12.  Enqueued on `stream`, no synchronisation.
+ * The trainer differentiates and logs loss_3[0] only.  loss_3[1] = -mean(surr) and loss_3[2] = mean(entropy) are the two sums the total is
+ * made of (total = [1] - entropy_cost * [2]): they are there so that each term can be held to a reference on its own - a wrong entropy
+ * weighs 1e-2 in the total and would hide behind the policy term (tests/test_gpu_ppo_kernels.py compares all three with fp64).
+ * Refused with PGTT_E_ARG, nothing written: a NULL pointer, B <= 0, A != 12. */
 int pgtt_ppo_policy_loss(const float* out_Bx2A, const float* u_BxA, const float* logp_old_B, const float* adv_B,
                          const float* eps_BxA, int B, int A, float clip_eps, float entropy_cost,
                          float* partial_2xceilB64, float* loss_3, float* grad_Bx2A, void* stream);
 /* Weight and bias gradient of a Linear layer over a long batch, dW[n][m] = sum_k dY[k][n] X[k][m],
  * db[n] = sum_k dY[k][n] (X [K][M], dY [K][N], dW in torch's [N][M] layout), K split over S workgroups per 64x64 tile on
- * fp32 MFMA, summed in a fixed order.  partial holds S * (N * M + N) floats of scratch.  Device pointers, caller's stream. */
+ * fp32 MFMA, summed in a fixed order.  partial holds S * (N * M + N) floats of scratch.  Device pointers, caller's stream.
+ * The chunk height is ceil(K / S) rounded up to an even number, so only Sused = ceil(K / chunk) <= S planes are written and summed
+ * (Sused < S whenever S > K / 2) - but the column-sum planes start at partial + S * N * M, so the scratch must have room for all S planes
+ * whatever Sused is.  Refused with PGTT_E_ARG, nothing written: a NULL pointer, K, M, N or S <= 0. */
 int pgtt_ppo_linear_backward(const float* x_KxM, const float* dy_KxN, int K, int M, int N, int S,
                              float* partial_Sx_NM_plus_N, float* dw_NxM, float* db_N, void* stream);
 
