@@ -1,8 +1,6 @@
 // pgtt_curriculum.hip — the terrain curriculum's kernels (pgtt_curriculum; include/pgtt.h).  A translation unit of its own: the step kernels
 // and the file they live in stay as they are.  Host launchers at the end; pgtt_api.hip holds the entry point and the masked reset that follows.
-#include <hip/hip_runtime.h>
-
-#include "pgtt_kernels.hip.h"
+#include "pgtt_common.hip.h"
 
 namespace pgtt {
 

@@ -15,23 +15,13 @@
 // Reference call sites this replaces: go2/joystick_pgtt.py:146-148 (mjx_env.step x n_substeps),
 // go2/base.py:153-171 (compute_contact), go2/base.py:116-149 (sensor getters).
 #pragma once
-#include <hip/hip_runtime.h>
-#include "../../include/pgtt.h"
+#include "pgtt_common.hip.h"
 
 namespace pgtt {
 
-#define PG_INL __device__ __forceinline__
 constexpr float kMinVal = 1e-15f;
 constexpr float kMinImp = 0.0001f;
 constexpr float kMaxImp = 0.9999f;
-
-struct TerrainBox {                 // resident terrain table entry (80 B), built once by pgtt_set_terrain
-  float px, py, pz, rb;             // centre, bounding radius |half-size|
-  float sx, sy, sz, m00;            // half-size, rotation matrix row-major
-  float m01, m02, m10, m11;
-  float m12, m20, m21, m22;
-  float hx, hy, hz, pad;            // half-extents of the WORLD-axis-aligned bounding box (|R| size, rounded up)
-};
 
 // Row `row` of an SoA block [rows][N] for env e (PG_ROW), element i of env e's record in an env-major array (PG_REC).  PG_ADDR32 (quad and oct
 // layouts): through a 32-bit BYTE offset from a wave-uniform base - the form global_load / global_store take as "SGPR base + zero-extended VGPR
@@ -55,69 +45,6 @@ template <class T> PG_INL T& pg_at(T* base, unsigned idx) { return *reinterpret_
 #define PG_REC(base, e, stride, i) ((base)[(long)(e) * (stride) + (i)])
 #endif
 
-// ------------------------------------------------------------------ small vector helpers
-struct V3 { float x, y, z; };
-PG_INL V3 v3(float x, float y, float z) { return V3{x, y, z}; }
-PG_INL V3 operator+(V3 a, V3 b) { return v3(a.x + b.x, a.y + b.y, a.z + b.z); }
-PG_INL V3 operator-(V3 a, V3 b) { return v3(a.x - b.x, a.y - b.y, a.z - b.z); }
-PG_INL V3 operator*(V3 a, float s) { return v3(a.x * s, a.y * s, a.z * s); }
-PG_INL V3 operator*(float s, V3 a) { return v3(a.x * s, a.y * s, a.z * s); }
-PG_INL float dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-PG_INL V3 cross(V3 a, V3 b) { return v3(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x); }
-PG_INL float norm(V3 a) { return sqrtf(dot(a, a)); }
-struct Q4 { float w, x, y, z; };
-PG_INL Q4 qmul(Q4 u, Q4 v) {
-  return Q4{u.w * v.w - u.x * v.x - u.y * v.y - u.z * v.z, u.w * v.x + u.x * v.w + u.y * v.z - u.z * v.y,
-            u.w * v.y - u.x * v.z + u.y * v.w + u.z * v.x, u.w * v.z + u.x * v.y - u.y * v.x + u.z * v.w};
-}
-struct M3 { float m[9]; };
-PG_INL M3 qmat(Q4 q) {
-  float q00 = q.w * q.w, q01 = q.w * q.x, q02 = q.w * q.y, q03 = q.w * q.z;
-  float q11 = q.x * q.x, q12 = q.x * q.y, q13 = q.x * q.z, q22 = q.y * q.y, q23 = q.y * q.z, q33 = q.z * q.z;
-  M3 r;
-  r.m[0] = q00 + q11 - q22 - q33; r.m[1] = 2 * (q12 - q03); r.m[2] = 2 * (q13 + q02);
-  r.m[3] = 2 * (q12 + q03); r.m[4] = q00 - q11 + q22 - q33; r.m[5] = 2 * (q23 - q01);
-  r.m[6] = 2 * (q13 - q02); r.m[7] = 2 * (q23 + q01); r.m[8] = q00 - q11 - q22 + q33;
-  return r;
-}
-PG_INL V3 qrot(V3 v, Q4 q) {        // mjx math.rotate
-  V3 u = v3(q.x, q.y, q.z);
-  float uv = dot(u, v), uu = dot(u, u);
-  V3 c = cross(u, v);
-  return 2.0f * (uv * u) + (q.w * q.w - uu) * v + (2.0f * q.w) * c;
-}
-PG_INL V3 mcol(const M3& a, int i) { return v3(a.m[i], a.m[3 + i], a.m[6 + i]); }
-PG_INL V3 mtmul(const M3& a, V3 v) {   // a^T v
-  return v3(a.m[0] * v.x + a.m[3] * v.y + a.m[6] * v.z, a.m[1] * v.x + a.m[4] * v.y + a.m[7] * v.z,
-            a.m[2] * v.x + a.m[5] * v.y + a.m[8] * v.z);
-}
-PG_INL V3 mmul(const M3& a, V3 v) {
-  return v3(a.m[0] * v.x + a.m[1] * v.y + a.m[2] * v.z, a.m[3] * v.x + a.m[4] * v.y + a.m[5] * v.z,
-            a.m[6] * v.x + a.m[7] * v.y + a.m[8] * v.z);
-}
-// normalise with MJX's zero guard (allclose(x, 0, atol=1e-8) -> treated as zero, norm 0)
-PG_INL float normalize3(V3& a) {
-  bool z = fabsf(a.x) <= 1e-8f && fabsf(a.y) <= 1e-8f && fabsf(a.z) <= 1e-8f;
-  if (z) a = v3(1.f, 1.f, 1.f);
-  float n = norm(a);
-  float d = n + (z ? 1.0f : 0.0f);
-  a = v3(a.x / d, a.y / d, a.z / d);
-  return z ? 0.0f : n;
-}
-PG_INL void normalize4(Q4& q) {
-  bool z = fabsf(q.w) <= 1e-8f && fabsf(q.x) <= 1e-8f && fabsf(q.y) <= 1e-8f && fabsf(q.z) <= 1e-8f;
-  if (z) q = Q4{1.f, 1.f, 1.f, 1.f};
-  float n = sqrtf(q.w * q.w + q.x * q.x + q.y * q.y + q.z * q.z) + (z ? 1.0f : 0.0f);
-  q = Q4{q.w / n, q.x / n, q.y / n, q.z / n};
-}
-PG_INL void make_frame(V3 a, V3& n, V3& t1, V3& t2) {
-  normalize3(a);
-  V3 y = (a.y > -0.5f && a.y < 0.5f) ? v3(0, 1, 0) : v3(0, 0, 1);
-  V3 b = y - a * dot(a, y);
-  normalize3(b);
-  n = a; t1 = b; t2 = cross(a, b);
-}
-
 // spatial 6-vectors [ang, lin] and 10-float spatial inertias [Ixx,Iyy,Izz,Ixy,Ixz,Iyz, m*off(3), m]
 struct S6 { V3 a, l; };
 PG_INL S6 operator+(S6 p, S6 q) { return S6{p.a + q.a, p.l + q.l}; }
@@ -136,7 +63,6 @@ PG_INL S6 motion_cross_force(S6 v, S6 f) { return S6{cross(v.a, f.a) + cross(v.l
 
 // ------------------------------------------------------------------ symmetric arrowhead matrix
 constexpr int tri(int i, int j) { return i * (i + 1) / 2 + j; }   // j <= i
-PG_INL float sel4(int l, float a, float b, float c, float d) { return l == 0 ? a : (l == 1 ? b : (l == 2 ? c : d)); }
 // impedance / stiffness / damping of a constraint row (mjx constraint._kbi); returns (k*imp, b, imp)
 PG_INL void kbi(float timestep, const float* solref, const float* solimp, float pos, float& k_imp, float& b, float& imp) {
   float timeconst = fmaxf(solref[0], 2.0f * timestep), dampratio = solref[1];

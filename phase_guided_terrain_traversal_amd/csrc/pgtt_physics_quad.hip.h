@@ -30,15 +30,11 @@ namespace pgtt {
 //                       layout for 4097..8192 envs: 1024 waves, still one per SIMD.
 // "quad_*" primitives act over the four LEGS of an env, "sub_*" over the sub-lanes of a leg.
 #ifndef PG_SUBS
-#define PG_SUBS 1
+#error "PG_SUBS (1 quad, 2 oct, 4 hex) selects the lane layout of a physics translation unit: compile with -DPG_SUBS=... (csrc/flags.mk, vflags)"
 #endif
 constexpr int kSubs = PG_SUBS;
-// this translation unit's kernel has box terrain (one TU per physics_kernel variant, pgtt_physics_inst.hip); 0 where the header is only parsed
-#ifdef PG_TERRAIN
+// this translation unit's kernel has box terrain (one TU per physics_kernel variant, pgtt_physics_inst.hip)
 constexpr bool kTerrainTU = PG_TERRAIN != 0;
-#else
-constexpr bool kTerrainTU = false;
-#endif
 constexpr int kEnvsPerWave = 16 / PG_SUBS;
 // centre / world-AABB half extents of the env's boxes staged in LDS per env (hex, oct) or read from the resident table where they are needed (quad:
 // 16 envs x 100 boxes x 24 B = 38 KB per workgroup were what kept a CU at two quad workgroups; without them four fit, one per SIMD - collide())
@@ -51,12 +47,6 @@ PG_INL int lane_leg() { return kSubs == 1 ? (int)(threadIdx.x & 3) : (int)((thre
 PG_INL int lane_env() { return kSubs == 1 ? (int)(threadIdx.x >> 2) : (kSubs == 4 ? (int)(threadIdx.x >> 4) : (int)(2 * (threadIdx.x >> 4) + ((threadIdx.x >> 1) & 1))); }
 PG_INL int lane_in_env() { return kSubs == 2 ? 2 * lane_leg() + lane_sub() : (int)(threadIdx.x % (4 * kSubs)); }
 PG_INL int lane_col() { return kSubs == 2 ? 4 * lane_env() + lane_leg() : (int)(threadIdx.x / kSubs); }
-template <int CTRL>
-PG_INL float dpp_f(float x) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), CTRL, 0xF, 0xF, true));
-}
-template <int CTRL>
-PG_INL int dpp_i(int x) { return __builtin_amdgcn_update_dpp(0, x, CTRL, 0xF, 0xF, true); }
 // The butterfly adds must stay plain adds: with contraction on, `p*q + dpp(p*q)` may be fused into
 // fma(p, q, dpp(round(p*q))), which differs between the two lanes of a pair and breaks the invariant that every
 // lane of an env holds the bit-identical sum (base-body quantities are replicated, never broadcast).
@@ -128,7 +118,6 @@ template <int J> PG_INL float quad_bcast(float x) { return __int_as_float(quad_b
 #endif
 
 constexpr int kMaxB = 4;          // box contacts one foot can hold (= max_contact_points of the reference)
-constexpr int kGridG = 16;        // cells per side of the terrain grid (pgtt_set_terrain): 128-bit box mask per cell and variant
 constexpr int kMaxPenQ = 4;       // penetrating (foot, box) pairs tracked per foot
 
 struct QArrow { float bb[21]; float lb[18]; float ll[6]; };

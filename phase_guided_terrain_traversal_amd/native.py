@@ -24,7 +24,8 @@ class PgttError(RuntimeError):
 
 
 def source_sha256() -> str:
-    """SHA-256 over the sources physics_kernel is built from, as they are ON DISK (srchash.py).  csrc/Makefile embeds the same hash in the library
+    """SHA-256 over what physics_kernel is built from, as it is ON DISK: the files csrc/pgtt_physics_inst.hip includes and its compile flags,
+    csrc/flags.mk - not the task kernels, the host code or the rules of the Makefile (srchash.py).  csrc/Makefile embeds the same hash in the library
     at build time (`build_info()`): tools/collect_profiles.py stores it next to the rocprofv3 counters of that kernel, bench.py compares the record
     with what the LOADED library says about itself before quoting them."""
     from . import srchash

@@ -1,22 +1,28 @@
-"""SHA-256 over the sources physics_kernel is built from (stdlib only: csrc/Makefile runs this file to embed the hash in libpgtt.so, native.py
-imports it).  What the translation unit csrc/pgtt_physics_inst.hip includes, plus the Makefile that holds its flags, with comments and white space
-removed (a comment edit does not change the kernel)."""
+"""SHA-256 over what physics_kernel is built from (stdlib only: csrc/Makefile runs this file to embed the hash in libpgtt.so, native.py imports
+it): the include closure of the translation unit csrc/pgtt_physics_inst.hip - itself, the two physics headers, the common header, include/pgtt.h -
+and csrc/flags.mk, the make fragment that holds the compile flags of that unit.  Comments and white space are removed (a comment edit does not
+change the kernel).  The task-side kernels, the host code and the other rules of the Makefile are not covered: a change there leaves the hash,
+and with it the counters recorded under profiles/, valid.  EXTRA flags and the 1-ulp division are what the build's flavor says."""
 import hashlib
 import os
 import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
+PHYSICS_SOURCES = ("pgtt_physics_inst.hip", "pgtt_physics.hip.h", "pgtt_physics_quad.hip.h", "pgtt_common.hip.h")
+FLAGS_FRAGMENT = "flags.mk"
 
 
-def source_sha256() -> str:
+def hashed_files(pkg: str = _HERE):
+    """the files the hash covers, for the package directory `pkg` (the checkout's by default)"""
+    return sorted([os.path.join(pkg, "csrc", f) for f in PHYSICS_SOURCES + (FLAGS_FRAGMENT,)] + [os.path.join(os.path.dirname(pkg), "include", "pgtt.h")])
+
+
+def source_sha256(pkg: str = _HERE) -> str:
     h = hashlib.sha256()
-    root = os.path.dirname(_HERE)
-    files = sorted([os.path.join(_HERE, "csrc", f) for f in ("pgtt_physics_inst.hip", "pgtt_physics.hip.h", "pgtt_physics_quad.hip.h", "pgtt_kernels.hip.h", "Makefile")]
-                   + [os.path.join(root, "include", "pgtt.h")])
-    for f in files:
+    for f in hashed_files(pkg):
         with open(f, "r") as fh:
             text = fh.read()
-        if f.endswith("Makefile"):
+        if f.endswith(".mk"):
             text = "\n".join(ln for ln in text.splitlines() if not ln.lstrip().startswith("#"))
         else:
             text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)

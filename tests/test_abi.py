@@ -150,3 +150,57 @@ def test_tools_and_entry_points_compile():
     assert len(files) > 10
     for f in files:
         compile(open(f).read(), f, "exec")
+
+
+def test_source_hash_covers_the_physics_translation_unit_and_nothing_else(tmp_path):
+    """srchash.py hashes what physics_kernel is built from: the project files its translation unit includes and the flags fragment.  An edit of
+    the task kernels, the curriculum kernels or another rule of the Makefile leaves the hash alone; an edit of a physics header or of a flag changes it."""
+    import shutil
+    import subprocess
+    from phase_guided_terrain_traversal_amd import srchash
+    pkg = os.path.join(ROOT, "phase_guided_terrain_traversal_amd")
+    csrc = os.path.join(pkg, "csrc")
+    hashed = {os.path.realpath(f) for f in srchash.hashed_files()}
+    assert os.path.realpath(os.path.join(csrc, "flags.mk")) in hashed
+    assert native.source_sha256() == srchash.source_sha256()
+    # on copies: what moves the hash and what does not
+    cp = tmp_path / "phase_guided_terrain_traversal_amd"
+    (cp / "csrc").mkdir(parents=True)
+    (tmp_path / "include").mkdir()
+    for f in os.listdir(csrc):
+        if f.endswith((".hip", ".h", ".mk")) or f == "Makefile":
+            shutil.copy(os.path.join(csrc, f), cp / "csrc" / f)
+    shutil.copy(os.path.join(ROOT, "include", "pgtt.h"), tmp_path / "include" / "pgtt.h")
+    h0 = srchash.source_sha256(str(cp))
+    assert h0 == srchash.source_sha256()
+
+    def appended(name, text):
+        p = cp / "csrc" / name
+        old = p.read_text()
+        p.write_text(old + text)
+        h = srchash.source_sha256(str(cp))
+        p.write_text(old)
+        return h
+    for name, text in (("pgtt_task.hip", "\nint pgtt_extra_statement;\n"), ("pgtt_curriculum.hip", "\nint pgtt_extra_statement;\n"), ("pgtt_api.hip", "\nint pgtt_extra_statement;\n"),
+                       ("Makefile", "\nextra-rule:\n\t@true\n")):
+        assert appended(name, text) == h0, name
+    for name, text in (("pgtt_physics.hip.h", "\nint pgtt_extra_statement;\n"), ("pgtt_physics_quad.hip.h", "\nint pgtt_extra_statement;\n"), ("pgtt_common.hip.h", "\nint pgtt_extra_statement;\n"),
+                       ("pgtt_physics_inst.hip", "\nint pgtt_extra_statement;\n"), ("flags.mk", "\nFLAGS += -O2\n")):
+        assert appended(name, text) != h0, name
+    assert appended("pgtt_physics_quad.hip.h", "\n// a comment\n") == h0 and appended("flags.mk", "\n# a comment\n") == h0
+
+
+def test_source_hash_files_are_the_include_closure_of_the_physics_translation_unit():
+    """the hashed files are exactly the project-local files the compiler reads for pgtt_physics_inst.hip, plus the flags fragment"""
+    import shutil
+    import subprocess
+    from phase_guided_terrain_traversal_amd import srchash
+    csrc = os.path.join(ROOT, "phase_guided_terrain_traversal_amd", "csrc")
+    hashed = {os.path.realpath(f) for f in srchash.hashed_files()}
+    if not (shutil.which("hipcc") and shutil.which("make")):
+        pytest.skip("hipcc / make not on PATH: the include closure cannot be listed")
+    flags = subprocess.run(["make", "-s", "flags-4_0_0_1"], cwd=csrc, check=True, capture_output=True, text=True).stdout.split()
+    mm = subprocess.run(["hipcc"] + flags + ["--cuda-host-only", "-MM", "pgtt_physics_inst.hip"], cwd=csrc, check=True, capture_output=True, text=True).stdout
+    deps = {os.path.realpath(os.path.join(csrc, t)) for t in mm.replace("\\\n", " ").split()[1:]}
+    local = {d for d in deps if d.startswith(os.path.realpath(ROOT) + os.sep)}
+    assert local | {os.path.realpath(os.path.join(csrc, "flags.mk"))} == hashed

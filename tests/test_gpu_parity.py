@@ -590,6 +590,47 @@ def test_library_refuses_without_bind():
     L.pgtt_destroy(h)
 
 
+_SIDE_BUILD_PROBE = """
+import os, sys
+import numpy as np, torch
+from phase_guided_terrain_traversal_amd import configs, native
+from phase_guided_terrain_traversal_amd.env import Joystick
+assert native.build_info()["flavor"] == "fastdiv", native.build_info()
+terrain = np.load(os.path.join(os.path.dirname(native.__file__), "assets", "terrains", "level4.npy"))
+msg = "does not contain the physics_kernel variant the call needs"
+for lay in ("quad", "oct"):                               # libpgtt_fastdiv.so holds the hex step / forward kernels on box terrain without DR only
+    env = Joystick("stairs", configs.training_config(), num_envs=64, terrain=terrain, device="cuda:0", layout=lay)
+    before = {k: v.clone() for k, v in env.buffers.items() if torch.is_tensor(v)}
+    for call in (lambda: env.reset(1), lambda: env.step(torch.zeros(64, 12, device="cuda:0"))):
+        try:
+            call()
+        except native.PgttError as err:
+            assert "libpgtt error -2" in str(err) and msg in str(err), str(err)     # PGTT_E_STATE
+        else:
+            raise AssertionError("a launch of a variant that was not built must fail: " + lay)
+    torch.cuda.synchronize()
+    assert all(torch.equal(v, env.buffers[k]) for k, v in before.items()), lay          # nothing was written
+    env.close()
+env = Joystick("stairs", configs.training_config(), num_envs=64, terrain=terrain, device="cuda:0", layout="hex")
+env.reset(1); env.step(torch.zeros(64, 12, device="cuda:0")); torch.cuda.synchronize()
+assert torch.isfinite(env.buffers["state"]).all()
+env.close()
+print("side build probe ok")
+"""
+
+
+def test_variant_missing_from_a_side_build_is_an_error_that_writes_nothing():
+    """libpgtt_fastdiv.so (csrc/Makefile `fastdiv`) compiles two of the 36 physics_kernel variants: a call that needs another one returns PGTT_E_STATE
+    before anything is launched; the variants it holds run.  In a child process: PGTT_LIB is read when the library is first loaded."""
+    import subprocess, sys
+    from phase_guided_terrain_traversal_amd import native
+    lib = os.path.join(os.path.dirname(native.__file__), "libpgtt_fastdiv.so")
+    assert os.path.exists(lib), f"{lib} missing: __graft_entry__.build() makes it (make -C csrc fastdiv)"
+    root = os.path.dirname(os.path.dirname(os.path.abspath(native.__file__)))
+    r = subprocess.run([sys.executable, "-c", _SIDE_BUILD_PROBE], cwd=root, env=dict(os.environ, PGTT_LIB=lib), capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0 and "side build probe ok" in r.stdout, (r.stdout[-1000:], r.stderr[-3000:])
+
+
 def nearest_boxes(terrain, B):
     """the B boxes of every variant whose centres lie nearest to the spawn area: a terrain table with FEWER than 100 boxes per variant"""
     out = np.zeros((terrain.shape[0], B, 10), np.float32)

@@ -61,6 +61,6 @@ from phase_guided_terrain_traversal_amd import native
 info = native.build_info()
 assert info["flavor"] == "product" and info["src"] == native.source_sha256(), "libpgtt.so is not the product build of the sources on disk: rebuild before collecting"
 t["_source"] = {"csrc_sha256": info["src"], "flavor": info["flavor"], "lib_sha256": native.library_sha256(), "tag": tag,
-                "what": "pgtt_build_info() of the libpgtt.so the counters were collected on: SHA-256 over the sources of physics_kernel (csrc/pgtt_physics_inst.hip and the headers it includes, csrc/Makefile, include/pgtt.h: srchash.py) embedded at build time; lib_sha256 = the file itself (informational)"}
+                "what": "pgtt_build_info() of the libpgtt.so the counters were collected on: SHA-256 over what physics_kernel is built from (csrc/pgtt_physics_inst.hip and the files it includes, include/pgtt.h among them, and its compile flags csrc/flags.mk: srchash.py) embedded at build time; lib_sha256 = the file itself (informational)"}
 json.dump(t, open(tp, "w"), indent=1)
 print("collected", tag, {k: (round(v["physics_bytes_per_launch"] / 1e6, 2), round(v.get("valu_busy", 0), 3)) for k, v in t.items() if not k.startswith("_")})
