@@ -105,17 +105,32 @@ __global__ __launch_bounds__(64) void push_kernel(KArgs a) {
 }
 
 // ------------------------------------------------------------------ observe: one env per wave
+// sums over the 16 lanes of a DPP row / the 4 lanes of a quad, the same bits in every lane (symmetric butterflies, plain adds)
+PG_INL float row16_sum(float x) {
+#pragma clang fp contract(off)
+  x = x + dpp_f<0xB1>(x); x = x + dpp_f<0x4E>(x); x = x + dpp_f<0x128>(x); x = x + dpp_f<0x124>(x);
+  return x;
+}
+PG_INL float quad4_sum(float x) {
+#pragma clang fp contract(off)
+  x = x + dpp_f<0xB1>(x); x = x + dpp_f<0x4E>(x);
+  return x;
+}
+PG_INL float quad4_min(float x) { x = fminf(x, dpp_f<0xB1>(x)); x = fminf(x, dpp_f<0x4E>(x)); return x; }
+// max / min over the 16 lanes of a DPP row, the same bits in every lane of the row
+PG_INL float row16_max(float x) { x = fmaxf(x, dpp_f<0xB1>(x)); x = fmaxf(x, dpp_f<0x4E>(x)); x = fmaxf(x, dpp_f<0x124>(x)); x = fmaxf(x, dpp_f<0x128>(x)); return x; }
+PG_INL float row16_min(float x) { x = fminf(x, dpp_f<0xB1>(x)); x = fminf(x, dpp_f<0x4E>(x)); x = fminf(x, dpp_f<0x124>(x)); x = fminf(x, dpp_f<0x128>(x)); return x; }
 // wave-wide max / min (all 64 lanes active): DPP butterflies inside the 16-lane rows, then the four row results through
 // scalar registers - no LDS crossbar (ds_bpermute) round trips
 PG_INL float wave_max(float v) {
-  v = fmaxf(v, dpp_f<0xB1>(v)); v = fmaxf(v, dpp_f<0x4E>(v)); v = fmaxf(v, dpp_f<0x124>(v)); v = fmaxf(v, dpp_f<0x128>(v));
+  v = row16_max(v);
   const int i = __float_as_int(v);
   const float r0 = __int_as_float(__builtin_amdgcn_readlane(i, 0)), r1 = __int_as_float(__builtin_amdgcn_readlane(i, 16));
   const float r2 = __int_as_float(__builtin_amdgcn_readlane(i, 32)), r3 = __int_as_float(__builtin_amdgcn_readlane(i, 48));
   return fmaxf(fmaxf(r0, r1), fmaxf(r2, r3));
 }
 PG_INL float wave_min(float v) {
-  v = fminf(v, dpp_f<0xB1>(v)); v = fminf(v, dpp_f<0x4E>(v)); v = fminf(v, dpp_f<0x124>(v)); v = fminf(v, dpp_f<0x128>(v));
+  v = row16_min(v);
   const int i = __float_as_int(v);
   const float r0 = __int_as_float(__builtin_amdgcn_readlane(i, 0)), r1 = __int_as_float(__builtin_amdgcn_readlane(i, 16));
   const float r2 = __int_as_float(__builtin_amdgcn_readlane(i, 32)), r3 = __int_as_float(__builtin_amdgcn_readlane(i, 48));
@@ -187,22 +202,21 @@ PG_INL float fmod_once(float x, float y) {
 // Rewards, termination and bookkeeping of one control step (joystick_pgtt.py:193-227 / joystick.py): shared by the fused
 // observe kernel (sh_* in LDS) and by task_kernel (sh_* = per-lane arrays, all indices compile-time constants).
 struct TaskScalars {
-  float cmd[3], phase[4], air[4], peak[4], hmax[4], last_contact[4], contact[4], first_contact[4];
-  float phase_dt; int step_ctr, timer;
+  float cmd[3], phase[4], air[4], peak[4], hmax[4], hmin[4], last_contact[4], contact[4], first_contact[4];
+  float gait_freq, phase_dt; int step_ctr, timer;
   bool done; float reward; float metrics[PGTT_NMETRIC];
 };
-// sums over the 16 lanes of a DPP row / the 4 lanes of a quad, the same bits in every lane (symmetric butterflies, plain adds)
-PG_INL float row16_sum(float x) {
-#pragma clang fp contract(off)
-  x = x + dpp_f<0xB1>(x); x = x + dpp_f<0x4E>(x); x = x + dpp_f<0x128>(x); x = x + dpp_f<0x124>(x);
-  return x;
+// the values a step starts with, from the env's state rows and sensor frame: contact bookkeeping of joystick_pgtt.py:193-203.  H_max / H_min are
+// the caller's: the fused form takes them from this scan's quadrant statistics, the split form from the state rows
+PG_INL void task_foot_start(const float* st, const float* fr, float dt, int f, TaskScalars& t) {
+  t.phase[f] = st[PGTT_S_PHASE + f];
+  t.last_contact[f] = st[PGTT_S_LAST_CONTACT + f];
+  t.contact[f] = fr[PGTT_F_CONTACT + f];
+  const bool filt = (t.contact[f] != 0.f) || (t.last_contact[f] != 0.f);
+  t.first_contact[f] = (st[PGTT_S_AIR_TIME + f] > 0.f ? 1.f : 0.f) * (filt ? 1.f : 0.f);
+  t.air[f] = st[PGTT_S_AIR_TIME + f] + dt;
+  t.peak[f] = fmaxf(st[PGTT_S_SWING_PEAK + f], fr[PGTT_F_FEET_POS + 3 * f + 2]);
 }
-PG_INL float quad4_sum(float x) {
-#pragma clang fp contract(off)
-  x = x + dpp_f<0xB1>(x); x = x + dpp_f<0x4E>(x);
-  return x;
-}
-PG_INL float quad4_min(float x) { x = fminf(x, dpp_f<0xB1>(x)); x = fminf(x, dpp_f<0x4E>(x)); return x; }
 // WAVE = true (fused observe kernel, one env per wave, every lane holds the same per-env scalars): the 12 joint terms and the
 // 4 foot terms are evaluated by the lanes of a row / a quad in parallel (lane & 15 = joint, lane & 3 = foot) and summed
 // with DPP butterflies - a fraction of the instructions of the serial loops and of the ~130 VGPRs their unrolled bodies keep
@@ -211,153 +225,149 @@ template <bool WAVE>
 PG_INL void task_rewards(const float* sh_st, const float* sh_fr, const float* sh_act, const PgttConfig* __restrict__ cfg,
                          const PgttModel* __restrict__ m, bool baseline, unsigned long long seed, unsigned id, unsigned ep, float dt,
                          float rng_fix, TaskScalars& t) {
-  float (&cmd)[3] = t.cmd; float (&phase)[4] = t.phase; float (&air)[4] = t.air; float (&peak)[4] = t.peak; float (&hmax)[4] = t.hmax;
-  float (&last_contact)[4] = t.last_contact; float (&contact)[4] = t.contact; float (&first_contact)[4] = t.first_contact;
-  float (&metrics)[PGTT_NMETRIC] = t.metrics;
-  const float phase_dt = t.phase_dt; int& step_ctr = t.step_ctr; int& timer = t.timer; bool& done = t.done; float& reward = t.reward;
-  struct { unsigned long long seed; } a{seed};
-    done = sh_fr[PGTT_F_UPVECTOR + 2] < 0.f;
-    float rew[PGTT_NREW];
-    const float cmd_norm = sqrtf(cmd[0] * cmd[0] + cmd[1] * cmd[1] + cmd[2] * cmd[2]);
-    // the three exponentials (both tracking terms, feet_phase): WAVE = true evaluates them in ONE expf expansion, lanes 0 / 1 / 2
-    float xlin, xang;
-    {
-      float e0 = cmd[0] - sh_fr[PGTT_F_LOCAL_LINVEL], e1 = cmd[1] - sh_fr[PGTT_F_LOCAL_LINVEL + 1];
-      xlin = -(e0 * e0 + e1 * e1) / cfg->tracking_sigma;
-      float ea = cmd[2] - sh_fr[PGTT_F_GYRO + 2];
-      xang = -(ea * ea) / cfg->tracking_sigma;
-    }
-    rew[PGTT_R_LIN_VEL_Z] = sh_fr[PGTT_F_GLOBAL_LINVEL + 2] * sh_fr[PGTT_F_GLOBAL_LINVEL + 2];
-    rew[PGTT_R_ANG_VEL_XY] = sh_fr[PGTT_F_GLOBAL_ANGVEL] * sh_fr[PGTT_F_GLOBAL_ANGVEL] + sh_fr[PGTT_F_GLOBAL_ANGVEL + 1] * sh_fr[PGTT_F_GLOBAL_ANGVEL + 1];
-    rew[PGTT_R_ORIENTATION] = sh_fr[PGTT_F_UPVECTOR] * sh_fr[PGTT_F_UPVECTOR] + sh_fr[PGTT_F_UPVECTOR + 1] * sh_fr[PGTT_F_UPVECTOR + 1];
-    {
-      float sa = 0.f, lim = 0.f, pose = 0.f, s2 = 0.f, s1 = 0.f, en = 0.f, ar = 0.f;
-      auto joint = [&](int i, float on) {
-        float q = sh_st[PGTT_S_QPOS + 7 + i], dq = q - m->key_qpos[7 + i];
-        sa += on * fabsf(dq);
-        pose += on * ((dq * dq) * ((i % 3) == 0 ? 1.0f : 0.1f));
-        float lo = m->jnt_range[i][0] * cfg->soft_joint_pos_limit_factor, hi = m->jnt_range[i][1] * cfg->soft_joint_pos_limit_factor;
-        lim += on * (-fminf(q - lo, 0.f) + fmaxf(q - hi, 0.f));
-        float f = sh_fr[PGTT_F_ACT_FORCE + i];
-        s2 += on * (f * f); s1 += on * fabsf(f);
-        en += on * (fabsf(sh_st[PGTT_S_QVEL + 6 + i]) * fabsf(f));
-        float da = sh_act[i] - sh_st[PGTT_S_LAST_ACT + i]; ar += on * (da * da);
-      };
-      if constexpr (WAVE) {
-        const int j = (int)(threadIdx.x & 15);
-        joint(j < 12 ? j : 0, j < 12 ? 1.0f : 0.0f);
-        sa = row16_sum(sa); lim = row16_sum(lim); pose = row16_sum(pose); s2 = row16_sum(s2); s1 = row16_sum(s1); en = row16_sum(en); ar = row16_sum(ar);
-      } else {
-#pragma unroll
-        for (int i = 0; i < 12; i++) joint(i, 1.0f);
-      }
-      rew[PGTT_R_STAND_STILL] = sa * (cmd_norm < 0.01f ? 1.f : 0.f);
-      rew[PGTT_R_POSE] = pose; rew[PGTT_R_DOF_POS_LIMITS] = lim;
-      rew[PGTT_R_TORQUES] = sqrtf(s2) + s1; rew[PGTT_R_ENERGY] = en; rew[PGTT_R_ACTION_RATE] = ar;
-    }
-    rew[PGTT_R_TERMINATION] = done ? 1.f : 0.f;
-    {
-      float slip = 0.f, clear = 0.f, perr = 0.f, swing = 0.f, airr = 0.f, con = 0.f, center = 0.f, fh = 0.f, minfoot = INFINITY;
-      auto foot = [&](int f, float contact_f, float hmax_f, float phase_f, float air_f, float first_f, float peak_f) {
-        float vx = sh_fr[PGTT_F_FEET_VEL + 3 * f], vy = sh_fr[PGTT_F_FEET_VEL + 3 * f + 1];
-        float v2 = vx * vx + vy * vy;
-        slip += v2 * contact_f;
-        float px = sh_fr[PGTT_F_FEET_POS + 3 * f], py = sh_fr[PGTT_F_FEET_POS + 3 * f + 1], pz = sh_fr[PGTT_F_FEET_POS + 3 * f + 2];
-        const float clr = baseline ? sh_fr[PGTT_F_FOOT_SITE_Z + f] - (hmax_f - cfg->base_feet_distance + cfg->swing_height)   // joystick.py:569-572
-                                   : pz - (hmax_f + cfg->swing_height);                                                  // joystick_pgtt.py:576-578
-        clear += fabsf(clr) * sqrtf(sqrtf(v2));
-        float rz = gait_get_z(phase_f, hmax_f + cfg->swing_height, cfg->base_feet_distance);
-        perr += (pz - rz) * (pz - rz);
-        bool swing_mask = phase_f / (float)(2 * M_PI) >= 0.5f;
-        swing += ((pz - cfg->swing_height) * (pz - cfg->swing_height)) * (swing_mask ? 1.f : 0.f);
-        con += (swing_mask && contact_f != 0.f) ? 1.f : 0.f;
-        airr += (air_f - (baseline ? 0.5f : 0.1f)) * first_f;        // joystick.py:591 / joystick_pgtt.py:597
-        center += px * px + py * py;
-        float er = peak_f / cfg->swing_height - 1.0f;
-        fh += (er * er) * first_f;
-        minfoot = fminf(minfoot, sh_fr[PGTT_F_FOOT_SITE_Z + f]);
-      };
-      if constexpr (WAVE) {
-        const int f = (int)(threadIdx.x & 3);
-        foot(f, sel4(f, contact[0], contact[1], contact[2], contact[3]), sel4(f, hmax[0], hmax[1], hmax[2], hmax[3]),
-             sel4(f, phase[0], phase[1], phase[2], phase[3]), sel4(f, air[0], air[1], air[2], air[3]),
-             sel4(f, first_contact[0], first_contact[1], first_contact[2], first_contact[3]), sel4(f, peak[0], peak[1], peak[2], peak[3]));
-        slip = quad4_sum(slip); clear = quad4_sum(clear); perr = quad4_sum(perr); swing = quad4_sum(swing); airr = quad4_sum(airr);
-        con = quad4_sum(con); center = quad4_sum(center); fh = quad4_sum(fh); minfoot = quad4_min(minfoot);
-      } else {
-#pragma unroll
-        for (int f = 0; f < 4; f++) foot(f, contact[f], hmax[f], phase[f], air[f], first_contact[f], peak[f]);
-      }
-      float moving = cmd_norm > 0.01f ? 1.f : 0.f;
-      rew[PGTT_R_FEET_SLIP] = slip * moving; rew[PGTT_R_FEET_CLEARANCE] = clear;
-      const float xph = -perr / cfg->phase_sigma;
-      if constexpr (WAVE) {
-        const int ln = (int)(threadIdx.x & 63);
-        const int ex = __float_as_int(expf(ln == 0 ? xlin : (ln == 1 ? xang : xph)));
-        rew[PGTT_R_TRACKING_LIN_VEL] = __int_as_float(__builtin_amdgcn_readlane(ex, 0));
-        rew[PGTT_R_TRACKING_ANG_VEL] = __int_as_float(__builtin_amdgcn_readlane(ex, 1));
-        rew[PGTT_R_FEET_PHASE] = __int_as_float(__builtin_amdgcn_readlane(ex, 2));
-      } else {
-        rew[PGTT_R_TRACKING_LIN_VEL] = expf(xlin); rew[PGTT_R_TRACKING_ANG_VEL] = expf(xang); rew[PGTT_R_FEET_PHASE] = expf(xph);
-      }
-      rew[PGTT_R_FEET_SWING] = swing;
-      rew[PGTT_R_FEET_AIR_TIME] = airr * moving; rew[PGTT_R_CONTACT] = -con; rew[PGTT_R_CENTER] = center;
-      rew[PGTT_R_FEET_HEIGHT] = fh * moving;
-      float bh = sh_st[PGTT_S_QPOS + 2] - minfoot - 0.27f;
-      rew[PGTT_R_BODY_HEIGHT] = bh * bh;
-    }
-    float sum = 0.f;
-#pragma unroll
-    for (int k = 0; k < PGTT_NREW; k++) { metrics[k] = rew[k] * cfg->reward_scale[k]; sum += metrics[k]; }
-    reward = fminf(fmaxf(sum * dt, 0.f), 10000.f);
-    // bookkeeping (joystick_pgtt.py:205-227)
-    step_ctr += 1;
-#pragma unroll
-    for (int f = 0; f < 4; f++) phase[f] = fmod_once(phase[f] + phase_dt, (float)(2 * M_PI));
-    timer -= 1;
+  const float phase_dt = t.phase_dt;       // by value, read here: read inside the loop below, task_kernel compiles to other registers
+  t.done = sh_fr[PGTT_F_UPVECTOR + 2] < 0.f;
+  float rew[PGTT_NREW];
+  const float cmd_norm = sqrtf(t.cmd[0] * t.cmd[0] + t.cmd[1] * t.cmd[1] + t.cmd[2] * t.cmd[2]);
+  // the three exponentials (both tracking terms, feet_phase): WAVE = true evaluates them in ONE expf expansion, lanes 0 / 1 / 2
+  float xlin, xang;
+  {
+    float e0 = t.cmd[0] - sh_fr[PGTT_F_LOCAL_LINVEL], e1 = t.cmd[1] - sh_fr[PGTT_F_LOCAL_LINVEL + 1];
+    xlin = -(e0 * e0 + e1 * e1) / cfg->tracking_sigma;
+    float ea = t.cmd[2] - sh_fr[PGTT_F_GYRO + 2];
+    xang = -(ea * ea) / cfg->tracking_sigma;
+  }
+  rew[PGTT_R_LIN_VEL_Z] = sh_fr[PGTT_F_GLOBAL_LINVEL + 2] * sh_fr[PGTT_F_GLOBAL_LINVEL + 2];
+  rew[PGTT_R_ANG_VEL_XY] = sh_fr[PGTT_F_GLOBAL_ANGVEL] * sh_fr[PGTT_F_GLOBAL_ANGVEL] + sh_fr[PGTT_F_GLOBAL_ANGVEL + 1] * sh_fr[PGTT_F_GLOBAL_ANGVEL + 1];
+  rew[PGTT_R_ORIENTATION] = sh_fr[PGTT_F_UPVECTOR] * sh_fr[PGTT_F_UPVECTOR] + sh_fr[PGTT_F_UPVECTOR + 1] * sh_fr[PGTT_F_UPVECTOR + 1];
+  {
+    float sa = 0.f, lim = 0.f, pose = 0.f, s2 = 0.f, s1 = 0.f, en = 0.f, ar = 0.f;
+    auto joint = [&](int i, float on) {
+      float q = sh_st[PGTT_S_QPOS + 7 + i], dq = q - m->key_qpos[7 + i];
+      sa += on * fabsf(dq);
+      pose += on * ((dq * dq) * ((i % 3) == 0 ? 1.0f : 0.1f));
+      float lo = m->jnt_range[i][0] * cfg->soft_joint_pos_limit_factor, hi = m->jnt_range[i][1] * cfg->soft_joint_pos_limit_factor;
+      lim += on * (-fminf(q - lo, 0.f) + fmaxf(q - hi, 0.f));
+      float f = sh_fr[PGTT_F_ACT_FORCE + i];
+      s2 += on * (f * f); s1 += on * fabsf(f);
+      en += on * (fabsf(sh_st[PGTT_S_QVEL + 6 + i]) * fabsf(f));
+      float da = sh_act[i] - sh_st[PGTT_S_LAST_ACT + i]; ar += on * (da * da);
+    };
     if constexpr (WAVE) {
-      // the waves that resample (1 - 2 % of a launch) are among the last to leave it: their four counter blocks (command y / z / w, timer)
-      // in ONE Philox pass, lanes 0..3, instead of four - same words as rng_uniform(.., stream, i) = word i of block 0 of the stream
-      if (done || timer <= 0) {
-        const int ln = (int)(threadIdx.x & 63);
-        unsigned c0 = id, c1 = ep, c2 = (unsigned)(ln == 0 ? PGTT_RS_CMD_Y : (ln == 1 ? PGTT_RS_CMD_Z : (ln == 2 ? PGTT_RS_CMD_W : PGTT_RS_TIMER))), c3 = 0u;
-        philox4x32_10((unsigned)a.seed, (unsigned)(a.seed >> 32), c0, c1, c2, c3);
-        auto uni = [&](unsigned w, int src) {
-          const float u = (float)((unsigned)__builtin_amdgcn_readlane((int)w, src) >> 8) * (1.0f / 16777216.0f);
-          return rng_fix == rng_fix ? rng_fix : u;
-        };
-        if (timer <= 0) {
-          const unsigned w[3] = {c0, c1, c2};
-#pragma unroll
-          for (int i = 0; i < 3; i++) {
-            float y = uni(w[i], 0) * (cfg->cmd_u_max[i] - cfg->cmd_u_min[i]) + cfg->cmd_u_min[i];
-            float zb = uni(w[i], 1) < cfg->cmd_b[i] ? 1.f : 0.f;
-            float wb = uni(w[i], 2) < 0.5f ? 1.f : 0.f;
-            cmd[i] = cmd[i] - wb * (cmd[i] - y * zb);
-          }
-        }
-        const double t = -log1p(-(double)uni(c0, 3)) * 5.0;           // exp_timer
-        timer = (int)rint(t / (double)dt);
-      }
+      const int j = (int)(threadIdx.x & 15);
+      joint(j < 12 ? j : 0, j < 12 ? 1.0f : 0.0f);
+      sa = row16_sum(sa); lim = row16_sum(lim); pose = row16_sum(pose); s2 = row16_sum(s2); s1 = row16_sum(s1); en = row16_sum(en); ar = row16_sum(ar);
     } else {
-      if (timer <= 0) {
+#pragma unroll
+      for (int i = 0; i < 12; i++) joint(i, 1.0f);
+    }
+    rew[PGTT_R_STAND_STILL] = sa * (cmd_norm < 0.01f ? 1.f : 0.f);
+    rew[PGTT_R_POSE] = pose; rew[PGTT_R_DOF_POS_LIMITS] = lim;
+    rew[PGTT_R_TORQUES] = sqrtf(s2) + s1; rew[PGTT_R_ENERGY] = en; rew[PGTT_R_ACTION_RATE] = ar;
+  }
+  rew[PGTT_R_TERMINATION] = t.done ? 1.f : 0.f;
+  {
+    float slip = 0.f, clear = 0.f, perr = 0.f, swing = 0.f, airr = 0.f, con = 0.f, center = 0.f, fh = 0.f, minfoot = INFINITY;
+    auto foot = [&](int f, float contact_f, float hmax_f, float phase_f, float air_f, float first_f, float peak_f) {
+      float vx = sh_fr[PGTT_F_FEET_VEL + 3 * f], vy = sh_fr[PGTT_F_FEET_VEL + 3 * f + 1];
+      float v2 = vx * vx + vy * vy;
+      slip += v2 * contact_f;
+      float px = sh_fr[PGTT_F_FEET_POS + 3 * f], py = sh_fr[PGTT_F_FEET_POS + 3 * f + 1], pz = sh_fr[PGTT_F_FEET_POS + 3 * f + 2];
+      const float clr = baseline ? sh_fr[PGTT_F_FOOT_SITE_Z + f] - (hmax_f - cfg->base_feet_distance + cfg->swing_height)   // joystick.py:569-572
+                                 : pz - (hmax_f + cfg->swing_height);                                                  // joystick_pgtt.py:576-578
+      clear += fabsf(clr) * sqrtf(sqrtf(v2));
+      float rz = gait_get_z(phase_f, hmax_f + cfg->swing_height, cfg->base_feet_distance);
+      perr += (pz - rz) * (pz - rz);
+      bool swing_mask = phase_f / (float)(2 * M_PI) >= 0.5f;
+      swing += ((pz - cfg->swing_height) * (pz - cfg->swing_height)) * (swing_mask ? 1.f : 0.f);
+      con += (swing_mask && contact_f != 0.f) ? 1.f : 0.f;
+      airr += (air_f - (baseline ? 0.5f : 0.1f)) * first_f;        // joystick.py:591 / joystick_pgtt.py:597
+      center += px * px + py * py;
+      float er = peak_f / cfg->swing_height - 1.0f;
+      fh += (er * er) * first_f;
+      minfoot = fminf(minfoot, sh_fr[PGTT_F_FOOT_SITE_Z + f]);
+    };
+    if constexpr (WAVE) {
+      const int f = (int)(threadIdx.x & 3);
+      foot(f, sel4(f, t.contact[0], t.contact[1], t.contact[2], t.contact[3]), sel4(f, t.hmax[0], t.hmax[1], t.hmax[2], t.hmax[3]),
+           sel4(f, t.phase[0], t.phase[1], t.phase[2], t.phase[3]), sel4(f, t.air[0], t.air[1], t.air[2], t.air[3]),
+           sel4(f, t.first_contact[0], t.first_contact[1], t.first_contact[2], t.first_contact[3]), sel4(f, t.peak[0], t.peak[1], t.peak[2], t.peak[3]));
+      slip = quad4_sum(slip); clear = quad4_sum(clear); perr = quad4_sum(perr); swing = quad4_sum(swing); airr = quad4_sum(airr);
+      con = quad4_sum(con); center = quad4_sum(center); fh = quad4_sum(fh); minfoot = quad4_min(minfoot);
+    } else {
+#pragma unroll
+      for (int f = 0; f < 4; f++) foot(f, t.contact[f], t.hmax[f], t.phase[f], t.air[f], t.first_contact[f], t.peak[f]);
+    }
+    float moving = cmd_norm > 0.01f ? 1.f : 0.f;
+    rew[PGTT_R_FEET_SLIP] = slip * moving; rew[PGTT_R_FEET_CLEARANCE] = clear;
+    const float xph = -perr / cfg->phase_sigma;
+    if constexpr (WAVE) {
+      const int ln = (int)(threadIdx.x & 63);
+      const int ex = __float_as_int(expf(ln == 0 ? xlin : (ln == 1 ? xang : xph)));
+      rew[PGTT_R_TRACKING_LIN_VEL] = __int_as_float(__builtin_amdgcn_readlane(ex, 0));
+      rew[PGTT_R_TRACKING_ANG_VEL] = __int_as_float(__builtin_amdgcn_readlane(ex, 1));
+      rew[PGTT_R_FEET_PHASE] = __int_as_float(__builtin_amdgcn_readlane(ex, 2));
+    } else {
+      rew[PGTT_R_TRACKING_LIN_VEL] = expf(xlin); rew[PGTT_R_TRACKING_ANG_VEL] = expf(xang); rew[PGTT_R_FEET_PHASE] = expf(xph);
+    }
+    rew[PGTT_R_FEET_SWING] = swing;
+    rew[PGTT_R_FEET_AIR_TIME] = airr * moving; rew[PGTT_R_CONTACT] = -con; rew[PGTT_R_CENTER] = center;
+    rew[PGTT_R_FEET_HEIGHT] = fh * moving;
+    float bh = sh_st[PGTT_S_QPOS + 2] - minfoot - 0.27f;
+    rew[PGTT_R_BODY_HEIGHT] = bh * bh;
+  }
+  float sum = 0.f;
+#pragma unroll
+  for (int k = 0; k < PGTT_NREW; k++) { t.metrics[k] = rew[k] * cfg->reward_scale[k]; sum += t.metrics[k]; }
+  t.reward = fminf(fmaxf(sum * dt, 0.f), 10000.f);
+  // bookkeeping (joystick_pgtt.py:205-227)
+  t.step_ctr += 1;
+#pragma unroll
+  for (int f = 0; f < 4; f++) t.phase[f] = fmod_once(t.phase[f] + phase_dt, (float)(2 * M_PI));
+  t.timer -= 1;
+  if constexpr (WAVE) {
+    // the waves that resample (1 - 2 % of a launch) are among the last to leave it: their four counter blocks (command y / z / w, timer)
+    // in ONE Philox pass, lanes 0..3, instead of four - same words as rng_uniform(.., stream, i) = word i of block 0 of the stream
+    if (t.done || t.timer <= 0) {
+      const int ln = (int)(threadIdx.x & 63);
+      unsigned c0 = id, c1 = ep, c2 = (unsigned)(ln == 0 ? PGTT_RS_CMD_Y : (ln == 1 ? PGTT_RS_CMD_Z : (ln == 2 ? PGTT_RS_CMD_W : PGTT_RS_TIMER))), c3 = 0u;
+      philox4x32_10((unsigned)seed, (unsigned)(seed >> 32), c0, c1, c2, c3);
+      auto uni = [&](unsigned w, int src) {
+        const float u = (float)((unsigned)__builtin_amdgcn_readlane((int)w, src) >> 8) * (1.0f / 16777216.0f);
+        return rng_fix == rng_fix ? rng_fix : u;
+      };
+      if (t.timer <= 0) {
+        const unsigned w[3] = {c0, c1, c2};
 #pragma unroll
         for (int i = 0; i < 3; i++) {
-          float y = rng_uniform(a.seed, id, ep, PGTT_RS_CMD_Y, i, rng_fix) * (cfg->cmd_u_max[i] - cfg->cmd_u_min[i]) + cfg->cmd_u_min[i];
-          float zb = rng_uniform(a.seed, id, ep, PGTT_RS_CMD_Z, i, rng_fix) < cfg->cmd_b[i] ? 1.f : 0.f;
-          float wb = rng_uniform(a.seed, id, ep, PGTT_RS_CMD_W, i, rng_fix) < 0.5f ? 1.f : 0.f;
-          cmd[i] = cmd[i] - wb * (cmd[i] - y * zb);
+          float y = uni(w[i], 0) * (cfg->cmd_u_max[i] - cfg->cmd_u_min[i]) + cfg->cmd_u_min[i];
+          float zb = uni(w[i], 1) < cfg->cmd_b[i] ? 1.f : 0.f;
+          float wb = uni(w[i], 2) < 0.5f ? 1.f : 0.f;
+          t.cmd[i] = t.cmd[i] - wb * (t.cmd[i] - y * zb);
         }
       }
-      if (done || timer <= 0) timer = exp_timer(a.seed, id, ep, PGTT_RS_TIMER, dt, rng_fix);
+      const double wait = -log1p(-(double)uni(c0, 3)) * 5.0;        // exp_timer
+      t.timer = (int)rint(wait / (double)dt);
     }
-    float sp = 0.f;
+  } else {
+    if (t.timer <= 0) {
 #pragma unroll
-    for (int f = 0; f < 4; f++) {
-      float nc = contact[f] != 0.f ? 0.f : 1.f;
-      air[f] *= nc; peak[f] *= nc; last_contact[f] = contact[f]; sp += peak[f];
+      for (int i = 0; i < 3; i++) {
+        float y = rng_uniform(seed, id, ep, PGTT_RS_CMD_Y, i, rng_fix) * (cfg->cmd_u_max[i] - cfg->cmd_u_min[i]) + cfg->cmd_u_min[i];
+        float zb = rng_uniform(seed, id, ep, PGTT_RS_CMD_Z, i, rng_fix) < cfg->cmd_b[i] ? 1.f : 0.f;
+        float wb = rng_uniform(seed, id, ep, PGTT_RS_CMD_W, i, rng_fix) < 0.5f ? 1.f : 0.f;
+        t.cmd[i] = t.cmd[i] - wb * (t.cmd[i] - y * zb);
+      }
     }
-    metrics[PGTT_NREW] = sp / 4;
+    if (t.done || t.timer <= 0) t.timer = exp_timer(seed, id, ep, PGTT_RS_TIMER, dt, rng_fix);
+  }
+  float sp = 0.f;
+#pragma unroll
+  for (int f = 0; f < 4; f++) {
+    float nc = t.contact[f] != 0.f ? 0.f : 1.f;
+    t.air[f] *= nc; t.peak[f] *= nc; t.last_contact[f] = t.contact[f]; sp += t.peak[f];
+  }
+  t.metrics[PGTT_NREW] = sp / 4;
 }
 
 // ---- observation rows as a table.  Every row of the state observation is (source value [- zmin]) [+ noise] [- offset]; which source, which
@@ -421,470 +431,490 @@ constexpr ObsRowTab make_obs_row_tab() {
 static_assert(OL_END * 4 < 2048 && (8 + (PGTT_NSCAN + 3) / 4) * 16 <= 1024 && PGTT_OBS <= kObsRowSlots && PGTT_PRIV - PGTT_OBS <= kPrivSlots, "descriptor fields");
 __device__ const ObsRowTab kObsRowTab = make_obs_row_tab();
 
-template <int OMODE, bool HAS_TERRAIN>
-// four waves per SIMD (128 VGPRs): the kernel is latency-bound, a launch lasts as long as the resident waves of a SIMD take in turn
-__global__ __launch_bounds__(64, 4) void observe_kernel(KArgs a, const float* __restrict__ action) {
-  const int e = xcd_block(blockIdx.x, gridDim.x), lane = threadIdx.x, N = a.N;
-  if (OMODE != OBS_STEP && OMODE != OBS_STEP_OBS && a.mask && !a.mask[e]) return;
-  const PgttModel* __restrict__ m = a.model;
-  const PgttConfig* __restrict__ cfg = a.cfg;
-  float* __restrict__ S = a.buf.state;
-  int* __restrict__ I = a.buf.istate;
+// What the phases of observe_kernel pass on.  ObsPrefetch: what is requested from memory ahead of its use (see load_rows); ObsScan: the scan heights of
+// this lane (cells lane and lane + 64) and the base height; ObsQuad: the quadrant statistics; ObsHist: lane < 24 holds one entry of each history.
+struct ObsPrefetch { const TerrainBox* boxes; float4 brec[2]; unsigned rdesc[3], psrc; uint2 qcell; float epm_old, ivs_old; };
+struct ObsScan { float bz, z[2]; };
+struct ObsQuad { float max[4], min[4], zmin; };
+struct ObsHist { float q, v; bool upd; };
+// One wave's view of its env: what every phase needs - the launch arguments, the env, the lane, the wave's LDS arrays - and the phases themselves,
+// in the order observe_kernel runs them.  Every phase is entered by all 64 lanes (the barriers inside count on it).
+struct ObserveWave {
+  const KArgs& a; const int e, lane, N;
+  const PgttModel* __restrict__ m; const PgttConfig* __restrict__ cfg; float* __restrict__ S; int* __restrict__ I;
+  float* sh_src; float* sh_st; float* sh_fr; float* sh_scan; float* sh_drv; float* sh_obs; float* sh_act;
+  bool baseline;                        // set by load_rows
+  int OBSD, PRIVD; unsigned id, ep; float dt;      // set by env_constants
 
-  __shared__ float sh_src[OL_END];
-  float* const sh_st = sh_src + OL_ST; float* const sh_fr = sh_src + OL_FR; float* const sh_scan = sh_src + OL_SCAN; float* const sh_drv = sh_src + OL_DRV;
-  __shared__ float sh_obs[PGTT_OBS + PGTT_PRIV + 2];
-  __shared__ float sh_act[12];
-
-  // The cull data of the env's variant do not depend on the state: lane j requests (centre x, y, world-AABB half extents x, y) of boxes j and
-  // j + 64 BEFORE the state rows are waited for, so the two round trips overlap.  They come from the compact table (16 contiguous bytes per
-  // box: 13 lines per variant) - the same four numbers out of the 80-byte records cost 160 line requests per wave, more than all its rows
-  const TerrainBox* __restrict__ boxes = nullptr;
-  float4 brec[2];
-  if (HAS_TERRAIN) {
-    const int v = a.buf.variant ? min(max(a.buf.variant[e], 0), a.T - 1) : 0;      // clamped like in physics_kernel
-    boxes = a.terrain + (long)v * a.B;
+  template <int OMODE, bool HAS_TERRAIN> PG_INL void load_rows(const float* __restrict__ action, ObsPrefetch& pf) {
+    // The cull data of the env's variant do not depend on the state: lane j requests (centre x, y, world-AABB half extents x, y) of boxes j and
+    // j + 64 BEFORE the state rows are waited for, so the two round trips overlap.  They come from the compact table (16 contiguous bytes per
+    // box: 13 lines per variant) - the same four numbers out of the 80-byte records cost 160 line requests per wave, more than all its rows
+    pf.boxes = nullptr;
+    if (HAS_TERRAIN) {
+      const int v = a.buf.variant ? min(max(a.buf.variant[e], 0), a.T - 1) : 0;      // clamped like in physics_kernel
+      pf.boxes = a.terrain + (long)v * a.B;
 #pragma unroll
-    for (int h = 0; h < 2; h++) brec[h] = a.cull[(long)v * a.B + min(lane + 64 * h, a.B - 1)];
-  }
-  if (OMODE == OBS_STEP && a.handover_r) {
-    // this step's physics launch left qpos, qvel, the motor targets and the sensor frame env-major: two coalesced loads.  Of the other rows
-    // the step reads PGTT_S_CMD .. PGTT_NSTATE - 1 without H_max / H_min (formed anew from this step's scan) and the older halves of the two
-    // histories - not the warm start either
-    const float* __restrict__ Hr = a.handover_r + (long)e * kHandover;
-#pragma unroll
-    for (int h = 0; h < 2; h++) {
-      const int j = lane + 64 * h;
-      if (j < HO_END) {
-        const float v = Hr[j];
-        if (j < HO_MOTOR) sh_st[j] = v;                     // qpos, qvel: rows 0 .. 36 in the same order
-        else if (j < HO_FRAME) sh_st[PGTT_S_MOTOR_TARGETS + j - HO_MOTOR] = v;
-        else sh_fr[j - HO_FRAME] = v;
-      }
+      for (int h = 0; h < 2; h++) pf.brec[h] = a.cull[(long)v * a.B + min(lane + 64 * h, a.B - 1)];
     }
+    if (OMODE == OBS_STEP && a.handover_r) {
+      // this step's physics launch left qpos, qvel, the motor targets and the sensor frame env-major: two coalesced loads.  Of the other rows
+      // the step reads PGTT_S_CMD .. PGTT_NSTATE - 1 without H_max / H_min (formed anew from this step's scan) and the older halves of the two
+      // histories - not the warm start either
+      const float* __restrict__ Hr = a.handover_r + (long)e * kHandover;
 #pragma unroll
-    for (int h = 0; h < 2; h++) {
-      const int r = PGTT_S_CMD + lane + 64 * h;
-      const bool need = r < PGTT_NSTATE && !(r >= PGTT_S_HMAX && r < PGTT_S_HMIN + 4) && !(r >= PGTT_S_MOTOR_TARGETS && r < PGTT_S_MOTOR_TARGETS + 12) &&
-                        !(r >= PGTT_S_QERR_HIST + 12 && r < PGTT_S_QERR_HIST + 24) && !(r >= PGTT_S_QVEL_HIST + 12 && r < PGTT_S_QVEL_HIST + 24);     // the older half of a history only ever leaves
-      if (need) sh_st[r] = S[r * (long)N + e];
+      for (int h = 0; h < 2; h++) {
+        const int j = lane + 64 * h;
+        if (j < HO_END) {
+          const float v = Hr[j];
+          if (j < HO_MOTOR) sh_st[j] = v;                     // qpos, qvel: rows 0 .. 36 in the same order
+          else if (j < HO_FRAME) sh_st[PGTT_S_MOTOR_TARGETS + j - HO_MOTOR] = v;
+          else sh_fr[j - HO_FRAME] = v;
+        }
+      }
+#pragma unroll
+      for (int h = 0; h < 2; h++) {
+        const int r = PGTT_S_CMD + lane + 64 * h;
+        const bool need = r < PGTT_NSTATE && !(r >= PGTT_S_HMAX && r < PGTT_S_HMIN + 4) && !(r >= PGTT_S_MOTOR_TARGETS && r < PGTT_S_MOTOR_TARGETS + 12) &&
+                          !(r >= PGTT_S_QERR_HIST + 12 && r < PGTT_S_QERR_HIST + 24) && !(r >= PGTT_S_QVEL_HIST + 12 && r < PGTT_S_QVEL_HIST + 24);     // the older half of a history only ever leaves
+        if (need) sh_st[r] = S[r * (long)N + e];
+      }
+    } else {
+      for (int r = lane; r < PGTT_NSTATE; r += 64) sh_st[r] = S[r * (long)N + e];
+      for (int r = lane; r < PGTT_NFRAME; r += 64) sh_fr[r] = a.buf.frame[r * (long)N + e];
     }
-  } else {
-    for (int r = lane; r < PGTT_NSTATE; r += 64) sh_st[r] = S[r * (long)N + e];
-    for (int r = lane; r < PGTT_NFRAME; r += 64) sh_fr[r] = a.buf.frame[r * (long)N + e];
-  }
-  if (OMODE == OBS_STEP && lane < 12) sh_act[lane] = action[(long)e * 12 + lane];
-  // row descriptors of the three passes over the observation and of the privileged extras (constants: requested with the state rows)
-  const bool baseline = cfg->method == PGTT_METHOD_BASELINE;
-  unsigned rdesc[3]; unsigned psrc;
+    if (OMODE == OBS_STEP && lane < 12) sh_act[lane] = action[(long)e * 12 + lane];
+    // row descriptors of the three passes over the observation and of the privileged extras (constants: requested with the state rows)
+    baseline = cfg->method == PGTT_METHOD_BASELINE;
 #pragma unroll
-  for (int it = 0; it < 3; it++) rdesc[it] = kObsRowTab.row[baseline ? 1 : 0][lane + 64 * it];
-  psrc = kObsRowTab.priv[lane];
-  const uint2 qcell = *reinterpret_cast<const uint2*>(kObsRowTab.quad[lane]);      // byte offsets of this lane's three scan cells
-  // the running sums this step adds to (rows of this env, touched by this wave only) are requested here, a launch ahead of their use:
-  // at the end of the wave nothing is left to hide a round trip behind
-  float epm_old = 0.f, ivs_old = 0.f;
-  if (OMODE == OBS_STEP && lane < PGTT_NMETRIC + 2) {
-    if (a.buf.ep_metrics) epm_old = a.buf.ep_metrics[lane * (long)N + e];
-    if (a.buf.interval_sums) ivs_old = a.buf.interval_sums[lane * (long)N + e];
-  }
-  __syncthreads();
-
-  // ---------------- height scan (heightmap.py:25-67)
-  const float bx = sh_st[PGTT_S_QPOS + 0], by = sh_st[PGTT_S_QPOS + 1], bz = sh_st[PGTT_S_QPOS + 2];
-  float yaw;
-  if (OMODE == OBS_STEP || OMODE == OBS_STEP_OBS || (OMODE == OBS_SCAN_ONLY && a.yaw_override != a.yaw_override)) {
-    float qw = sh_st[PGTT_S_QPOS + 3], qx = sh_st[PGTT_S_QPOS + 4], qy = sh_st[PGTT_S_QPOS + 5], qz = sh_st[PGTT_S_QPOS + 6];
-    float qn = sqrtf(qw * qw + qx * qx + qy * qy + qz * qz);
-    qw /= qn; qx /= qn; qy /= qn; qz /= qn;
-    yaw = atan2f(2.0f * (qw * qz + qx * qy), 1.0f - 2.0f * (qy * qy + qz * qz));
-  } else if (OMODE == OBS_SCAN_ONLY) {
-    yaw = a.yaw_override;
-  } else {
-    yaw = 0.f;
-  }
-  // ONE sincos evaluation for the yaw (lanes 8..63; every lane then takes it from lane 8) and for the eight phase rows of the observation
-  // (lanes 0..7: cos x4, sin x4 of the phases the step starts with - parked in LDS until the rows are formed): the expansion is ~80 vector
-  // instructions whatever the number of lanes that want it
-  float sy, cy;
-  if (OMODE == OBS_SCAN_ONLY || OMODE == OBS_SCAN_LIFT) sincosf(yaw, &sy, &cy);
-  else {
-    const int f = lane & 3;
-    const float ph = OMODE == OBS_RESET ? ((f == 1 || f == 2) ? (float)M_PI : 0.f) : sh_st[PGTT_S_PHASE + f];
-    float sn, cs; sincosf(lane < 8 ? ph : yaw, &sn, &cs);
-    if (lane < 8) sh_drv[OD_PHASE + lane] = lane < 4 ? cs : sn;
-    sy = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(sn), 8)); cy = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(cs), 8));
-  }
-  const float oz = bz + cfg->scan_z_offset;
-  V3 org[2]; float hit[2];
-#pragma unroll
-  for (int h = 0; h < 2; h++) {
-    int idx = lane + 64 * h;
-    int ii = idx < PGTT_NSCAN ? idx : 0;
-    int r = ii / PGTT_SCAN_W, c = ii - r * PGTT_SCAN_W;
-    float ox = ((float)(PGTT_SCAN_H - 1) * 0.5f - (float)r) * cfg->scan_dist_x;
-    float oy = ((float)(PGTT_SCAN_W - 1) * 0.5f - (float)c) * cfg->scan_dist_y;
-    float wx = ox * cy + oy * (-sy), wy = ox * sy + oy * cy;
-    org[h] = v3(bx + wx, by + wy, oz);
-    if (r == (PGTT_SCAN_H - 1) / 2 && c == (PGTT_SCAN_W - 1) / 2) org[h] = v3(bx, by, oz);
-    // plane z=0 (normal +z): x = -pnt_z / vec_z = pnt_z, valid if x >= 0
-    float x = oz;
-    hit[h] = x >= 0.f ? x : INFINITY;
-  }
-  if (HAS_TERRAIN) {
-    // cull, lane-parallel: lane j looks at boxes j and j + 64: world AABB of the box against the scan footprint, a
-    // rectangle of half-sides (hx, hy) turned by the yaw - the four separating axes of a rectangle / AABB pair in the
-    // plane, with 1 mm of slack (a vertical ray can only hit a box whose footprint contains it, so dropping the boxes
-    // that do not overlap the rectangle changes no hit).  min() over the hits does not depend on the visiting order.
-    const float hx = 0.5f * (PGTT_SCAN_H - 1) * fabsf(cfg->scan_dist_x) + 1e-3f, hy = 0.5f * (PGTT_SCAN_W - 1) * fabsf(cfg->scan_dist_y) + 1e-3f;
-    const float acy = fabsf(cy), asy = fabsf(sy);
-    // The survivors are COMPACTED into LDS (slot = number of surviving boxes before this one), prepared by the lane that owns them, and the ray
-    // loop reads them from there through wave-uniform addresses, the next one requested while the current one is tested: no scalar-memory
-    // round trip and no per-box arithmetic in the loop (a wave used to wait ~0.3 us for every 80-byte record; the slowest waves of a launch
-    // are those that stand among many boxes).  kScanSlots survivors fit; further ones (never on the shipped terrains) are read from the table.
-    constexpr int kScanSlots = 40;
-    __shared__ float4 sh_box[kScanSlots * 3];
-    unsigned long long todo[2];
-    int nsurv = 0;
-#pragma unroll
-    for (int h = 0; h < 2; h++) {
-      const int b = lane + 64 * h;
-      bool reach = false;
-      if (b < a.B) {
-        const float4 C = brec[h];            // centre x, y; world-AABB half extents x, y
-        const float dx = C.x - bx, dy = C.y - by;
-        reach = (fabsf(dx) <= C.z + hx * acy + hy * asy) & (fabsf(dy) <= C.w + hx * asy + hy * acy) &
-                (fabsf(dx * cy + dy * sy) <= hx + C.z * acy + C.w * asy) & (fabsf(dy * cy - dx * sy) <= hy + C.z * asy + C.w * acy);
-      }
-      const unsigned long long mk = __ballot(reach);
-      const int slot = nsurv + __popcll(mk & ((1ull << lane) - 1ull));
-      if (reach && slot < kScanSlots) {
-        // The lane that owns a surviving box prepares it for the ray loop - all survivors at once, one per lane.  A box turned about z only
-        // (m20 = m21 = m02 = m12 = 0 exactly; every shipped / generated terrain) has lp2 = 0 * relx + 0 * rely + m22 * relz = round(m22 * relz)
-        // with relz = oz - pz the same for every ray of the env: the parameters of its two z faces and their validity are properties of the
-        // BOX (`hz` below, the value ray_box_down's two-face form returns for a ray inside the footprint); a ray only decides "inside or not".
-        // Such a box goes to LDS as the 9 numbers that test needs; any other box as its index (the loop reads its record from the table).
-        const float4 q0 = reinterpret_cast<const float4*>(boxes + b)[0], q1 = reinterpret_cast<const float4*>(boxes + b)[1], q2 = reinterpret_cast<const float4*>(boxes + b)[2],
-                     q3 = reinterpret_cast<const float4*>(boxes + b)[3];
-        const float m22 = q3.w;
-        const bool fast = (q3.y == 0.f) & (q3.z == 0.f) & (m22 != 0.f) & (q2.y == 0.f) & (q3.x == 0.f);      // m20, m21, m22, m02, m12
-        const float il2 = __builtin_amdgcn_rcpf(-m22);
-        const float lp2 = mul_unfused(m22, oz - q0.z);       // a product on its own (the generic form adds it to two exact zeros): must not be fused into sz - lp2
-        const float xt = (q1.z - lp2) * il2, xb = (-q1.z - lp2) * il2;
-        float hz = xt >= 0.f ? xt : INFINITY;
-        hz = ((xb >= 0.f) & (xb < hz)) ? xb : hz;
-        sh_box[slot * 3 + 0] = make_float4(q0.x, q0.y, q1.w, q2.z);                    // px, py, m00, m10
-        sh_box[slot * 3 + 1] = make_float4(q2.x, q2.w, q1.x, q1.y);                    // m01, m11, sx, sy
-        sh_box[slot * 3 + 2] = make_float4(hz, fast ? 1.f : 0.f, __int_as_float(b), 0.f);
-      }
-      // boxes beyond the slots: the highest set bits of this half (slot order = bit order)
-      int over = nsurv + __popcll(mk) - kScanSlots;
-      unsigned long long rest = 0ull, t = mk;
-      while (over > 0 && t != 0ull) { const int hb = 63 - __builtin_clzll(t); rest |= 1ull << hb; t &= ~(1ull << hb); over--; }
-      todo[h] = rest;
-      nsurv += __popcll(mk);
+    for (int it = 0; it < 3; it++) pf.rdesc[it] = kObsRowTab.row[baseline ? 1 : 0][lane + 64 * it];
+    pf.psrc = kObsRowTab.priv[lane];
+    pf.qcell = *reinterpret_cast<const uint2*>(kObsRowTab.quad[lane]);      // byte offsets of this lane's three scan cells
+    // the running sums this step adds to (rows of this env, touched by this wave only) are requested here, a launch ahead of their use:
+    // at the end of the wave nothing is left to hide a round trip behind
+    pf.epm_old = 0.f; pf.ivs_old = 0.f;
+    if (OMODE == OBS_STEP && lane < PGTT_NMETRIC + 2) {
+      if (a.buf.ep_metrics) pf.epm_old = a.buf.ep_metrics[lane * (long)N + e];
+      if (a.buf.interval_sums) pf.ivs_old = a.buf.interval_sums[lane * (long)N + e];
     }
     __syncthreads();
-    const int nslot = min(nsurv, kScanSlots);
-    auto load_slot = [&](int i, float4 (&r)[3]) {
-#pragma unroll
-      for (int q = 0; q < 3; q++) r[q] = sh_box[i * 3 + q];
-    };
-    auto test_box = [&](const float4 (&r)[3]) {
-      if (__builtin_amdgcn_readfirstlane(__float_as_int(r[2].y)) != 0) {        // the record is the same in every lane: a scalar branch
-        const float hz = r[2].x;
-#pragma unroll
-        for (int k = 0; k < 2; k++) {
-          const float rx = org[k].x - r[0].x, ry = org[k].y - r[0].y;
-          const float lp0 = r[0].z * rx + r[0].w * ry, lp1 = r[1].x * rx + r[1].y * ry;      // + m20 * relz = + (+-0): only the sign of a zero, and |lp| is what is tested
-          const bool inside = (fabsf(lp0) <= r[1].z) & (fabsf(lp1) <= r[1].w);
-          hit[k] = fminf(hit[k], inside ? hz : INFINITY);
-        }
-        return;
-      }
-      const TerrainBox tb = boxes[__builtin_amdgcn_readfirstlane(__float_as_int(r[2].z))];
-      const RayBox rb = ray_box_prepare(tb);
-#pragma unroll
-      for (int k = 0; k < 2; k++) hit[k] = fminf(hit[k], ray_box_down(tb, rb, org[k]));
-    };
-    float4 cur[3], nxt[3];
-    if (nslot > 0) load_slot(0, cur);
-    for (int i = 0; i < nslot; i++) {
-      if (i + 1 < nslot) load_slot(i + 1, nxt);
-      test_box(cur);
-#pragma unroll
-      for (int q = 0; q < 3; q++) cur[q] = nxt[q];
+  }
+
+  template <int OMODE, bool HAS_TERRAIN> PG_INL void height_scan(const ObsPrefetch& pf, ObsScan& sc) {
+    // ---------------- height scan (heightmap.py:25-67)
+    const float bx = sh_st[PGTT_S_QPOS + 0], by = sh_st[PGTT_S_QPOS + 1], bz = sh_st[PGTT_S_QPOS + 2];
+    float yaw;
+    if (OMODE == OBS_STEP || OMODE == OBS_STEP_OBS || (OMODE == OBS_SCAN_ONLY && a.yaw_override != a.yaw_override)) {
+      float qw = sh_st[PGTT_S_QPOS + 3], qx = sh_st[PGTT_S_QPOS + 4], qy = sh_st[PGTT_S_QPOS + 5], qz = sh_st[PGTT_S_QPOS + 6];
+      float qn = sqrtf(qw * qw + qx * qx + qy * qy + qz * qz);
+      qw /= qn; qx /= qn; qy /= qn; qz /= qn;
+      yaw = atan2f(2.0f * (qw * qz + qx * qy), 1.0f - 2.0f * (qy * qy + qz * qz));
+    } else if (OMODE == OBS_SCAN_ONLY) {
+      yaw = a.yaw_override;
+    } else {
+      yaw = 0.f;
     }
+    // ONE sincos evaluation for the yaw (lanes 8..63; every lane then takes it from lane 8) and for the eight phase rows of the observation
+    // (lanes 0..7: cos x4, sin x4 of the phases the step starts with - parked in LDS until the rows are formed): the expansion is ~80 vector
+    // instructions whatever the number of lanes that want it
+    float sy, cy;
+    if (OMODE == OBS_SCAN_ONLY || OMODE == OBS_SCAN_LIFT) sincosf(yaw, &sy, &cy);
+    else {
+      const int f = lane & 3;
+      const float ph = OMODE == OBS_RESET ? ((f == 1 || f == 2) ? (float)M_PI : 0.f) : sh_st[PGTT_S_PHASE + f];
+      float sn, cs; sincosf(lane < 8 ? ph : yaw, &sn, &cs);
+      if (lane < 8) sh_drv[OD_PHASE + lane] = lane < 4 ? cs : sn;
+      sy = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(sn), 8)); cy = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(cs), 8));
+    }
+    const float oz = bz + cfg->scan_z_offset;
+    V3 org[2]; float hit[2];
 #pragma unroll
     for (int h = 0; h < 2; h++) {
-      unsigned long long mk = todo[h];
-      while (mk != 0ull) {
-        const int b = 64 * h + __builtin_ctzll(mk);
-        mk &= mk - 1ull;
-        TerrainBox tb = boxes[b];
+      int idx = lane + 64 * h;
+      int ii = idx < PGTT_NSCAN ? idx : 0;
+      int r = ii / PGTT_SCAN_W, c = ii - r * PGTT_SCAN_W;
+      float ox = ((float)(PGTT_SCAN_H - 1) * 0.5f - (float)r) * cfg->scan_dist_x;
+      float oy = ((float)(PGTT_SCAN_W - 1) * 0.5f - (float)c) * cfg->scan_dist_y;
+      float wx = ox * cy + oy * (-sy), wy = ox * sy + oy * cy;
+      org[h] = v3(bx + wx, by + wy, oz);
+      if (r == (PGTT_SCAN_H - 1) / 2 && c == (PGTT_SCAN_W - 1) / 2) org[h] = v3(bx, by, oz);
+      // plane z=0 (normal +z): x = -pnt_z / vec_z = pnt_z, valid if x >= 0
+      float x = oz;
+      hit[h] = x >= 0.f ? x : INFINITY;
+    }
+    if (HAS_TERRAIN) {
+      // cull, lane-parallel: lane j looks at boxes j and j + 64: world AABB of the box against the scan footprint, a
+      // rectangle of half-sides (hx, hy) turned by the yaw - the four separating axes of a rectangle / AABB pair in the
+      // plane, with 1 mm of slack (a vertical ray can only hit a box whose footprint contains it, so dropping the boxes
+      // that do not overlap the rectangle changes no hit).  min() over the hits does not depend on the visiting order.
+      const float hx = 0.5f * (PGTT_SCAN_H - 1) * fabsf(cfg->scan_dist_x) + 1e-3f, hy = 0.5f * (PGTT_SCAN_W - 1) * fabsf(cfg->scan_dist_y) + 1e-3f;
+      const float acy = fabsf(cy), asy = fabsf(sy);
+      // The survivors are COMPACTED into LDS (slot = number of surviving boxes before this one), prepared by the lane that owns them, and the ray
+      // loop reads them from there through wave-uniform addresses, the next one requested while the current one is tested: no scalar-memory
+      // round trip and no per-box arithmetic in the loop (a wave used to wait ~0.3 us for every 80-byte record; the slowest waves of a launch
+      // are those that stand among many boxes).  kScanSlots survivors fit; further ones (never on the shipped terrains) are read from the table.
+      constexpr int kScanSlots = 40;
+      __shared__ float4 sh_box[kScanSlots * 3];
+      unsigned long long todo[2];
+      int nsurv = 0;
+#pragma unroll
+      for (int h = 0; h < 2; h++) {
+        const int b = lane + 64 * h;
+        bool reach = false;
+        if (b < a.B) {
+          const float4 C = pf.brec[h];            // centre x, y; world-AABB half extents x, y
+          const float dx = C.x - bx, dy = C.y - by;
+          reach = (fabsf(dx) <= C.z + hx * acy + hy * asy) & (fabsf(dy) <= C.w + hx * asy + hy * acy) &
+                  (fabsf(dx * cy + dy * sy) <= hx + C.z * acy + C.w * asy) & (fabsf(dy * cy - dx * sy) <= hy + C.z * asy + C.w * acy);
+        }
+        const unsigned long long mk = __ballot(reach);
+        const int slot = nsurv + __popcll(mk & ((1ull << lane) - 1ull));
+        if (reach && slot < kScanSlots) {
+          // The lane that owns a surviving box prepares it for the ray loop - all survivors at once, one per lane.  A box turned about z only
+          // (m20 = m21 = m02 = m12 = 0 exactly; every shipped / generated terrain) has lp2 = 0 * relx + 0 * rely + m22 * relz = round(m22 * relz)
+          // with relz = oz - pz the same for every ray of the env: the parameters of its two z faces and their validity are properties of the
+          // BOX (`hz` below, the value ray_box_down's two-face form returns for a ray inside the footprint); a ray only decides "inside or not".
+          // Such a box goes to LDS as the 9 numbers that test needs; any other box as its index (the loop reads its record from the table).
+          const float4 q0 = reinterpret_cast<const float4*>(pf.boxes + b)[0], q1 = reinterpret_cast<const float4*>(pf.boxes + b)[1], q2 = reinterpret_cast<const float4*>(pf.boxes + b)[2],
+                       q3 = reinterpret_cast<const float4*>(pf.boxes + b)[3];
+          const float m22 = q3.w;
+          const bool fast = (q3.y == 0.f) & (q3.z == 0.f) & (m22 != 0.f) & (q2.y == 0.f) & (q3.x == 0.f);      // m20, m21, m22, m02, m12
+          const float il2 = __builtin_amdgcn_rcpf(-m22);
+          const float lp2 = mul_unfused(m22, oz - q0.z);       // a product on its own (the generic form adds it to two exact zeros): must not be fused into sz - lp2
+          const float xt = (q1.z - lp2) * il2, xb = (-q1.z - lp2) * il2;
+          float hz = xt >= 0.f ? xt : INFINITY;
+          hz = ((xb >= 0.f) & (xb < hz)) ? xb : hz;
+          sh_box[slot * 3 + 0] = make_float4(q0.x, q0.y, q1.w, q2.z);                    // px, py, m00, m10
+          sh_box[slot * 3 + 1] = make_float4(q2.x, q2.w, q1.x, q1.y);                    // m01, m11, sx, sy
+          sh_box[slot * 3 + 2] = make_float4(hz, fast ? 1.f : 0.f, __int_as_float(b), 0.f);
+        }
+        // boxes beyond the slots: the highest set bits of this half (slot order = bit order)
+        int over = nsurv + __popcll(mk) - kScanSlots;
+        unsigned long long rest = 0ull, t = mk;
+        while (over > 0 && t != 0ull) { const int hb = 63 - __builtin_clzll(t); rest |= 1ull << hb; t &= ~(1ull << hb); over--; }
+        todo[h] = rest;
+        nsurv += __popcll(mk);
+      }
+      __syncthreads();
+      const int nslot = min(nsurv, kScanSlots);
+      auto load_slot = [&](int i, float4 (&r)[3]) {
+#pragma unroll
+        for (int q = 0; q < 3; q++) r[q] = sh_box[i * 3 + q];
+      };
+      auto test_box = [&](const float4 (&r)[3]) {
+        if (__builtin_amdgcn_readfirstlane(__float_as_int(r[2].y)) != 0) {        // the record is the same in every lane: a scalar branch
+          const float hz = r[2].x;
+#pragma unroll
+          for (int k = 0; k < 2; k++) {
+            const float rx = org[k].x - r[0].x, ry = org[k].y - r[0].y;
+            const float lp0 = r[0].z * rx + r[0].w * ry, lp1 = r[1].x * rx + r[1].y * ry;      // + m20 * relz = + (+-0): only the sign of a zero, and |lp| is what is tested
+            const bool inside = (fabsf(lp0) <= r[1].z) & (fabsf(lp1) <= r[1].w);
+            hit[k] = fminf(hit[k], inside ? hz : INFINITY);
+          }
+          return;
+        }
+        const TerrainBox tb = pf.boxes[__builtin_amdgcn_readfirstlane(__float_as_int(r[2].z))];
         const RayBox rb = ray_box_prepare(tb);
 #pragma unroll
         for (int k = 0; k < 2; k++) hit[k] = fminf(hit[k], ray_box_down(tb, rb, org[k]));
+      };
+      float4 cur[3], nxt[3];
+      if (nslot > 0) load_slot(0, cur);
+      for (int i = 0; i < nslot; i++) {
+        if (i + 1 < nslot) load_slot(i + 1, nxt);
+        test_box(cur);
+#pragma unroll
+        for (int q = 0; q < 3; q++) cur[q] = nxt[q];
+      }
+#pragma unroll
+      for (int h = 0; h < 2; h++) {
+        unsigned long long mk = todo[h];
+        while (mk != 0ull) {
+          const int b = 64 * h + __builtin_ctzll(mk);
+          mk &= mk - 1ull;
+          TerrainBox tb = pf.boxes[b];
+          const RayBox rb = ray_box_prepare(tb);
+#pragma unroll
+          for (int k = 0; k < 2; k++) hit[k] = fminf(hit[k], ray_box_down(tb, rb, org[k]));
+        }
       }
     }
-  }
-  float z[2];
 #pragma unroll
-  for (int h = 0; h < 2; h++) {
-    float dist = hit[h] == INFINITY ? -1.0f : hit[h];
-    z[h] = org[h].z + (-1.0f) * dist;
-    int idx = lane + 64 * h;
-    if ((OMODE == OBS_STEP || OMODE == OBS_STEP_OBS) && a.scan_preset != 0) z[h] = a.buf.scan_z[(long)e * PGTT_NSCAN + (idx < PGTT_NSCAN ? idx : 0)];   // test hook
-    if (idx < PGTT_NSCAN) { sh_scan[idx] = z[h]; a.buf.scan_z[(long)e * PGTT_NSCAN + idx] = z[h]; }
-  }
-  if (OMODE == OBS_SCAN_ONLY) return;
-  const bool v1 = lane + 64 < PGTT_NSCAN;
-  if (OMODE == OBS_SCAN_LIFT) {
-    float zmax = wave_max(fmaxf(z[0], v1 ? z[1] : -INFINITY));
-    if (lane == 0) S[(PGTT_S_QPOS + 2) * (long)N + e] = bz + zmax;
-    return;
-  }
-  // ---------------- quadrant statistics (joystick_pgtt.py:169-190): n = 6 on both axes of the 13x9 grid
-  float qmax[4], qmin[4];
-  {
-    __syncthreads();                     // the scan is in LDS
-    const char* const srcb = reinterpret_cast<const char*>(sh_src);
-    const float c0 = *reinterpret_cast<const float*>(srcb + (qcell.x & 0xffffu)), c1 = *reinterpret_cast<const float*>(srcb + (qcell.x >> 16)),
-                c2 = *reinterpret_cast<const float*>(srcb + (qcell.y & 0xffffu));
-    float mx = fmaxf(fmaxf(c0, c1), c2), mn = fminf(fminf(c0, c1), c2);
-    mx = fmaxf(mx, dpp_f<0xB1>(mx)); mx = fmaxf(mx, dpp_f<0x4E>(mx)); mx = fmaxf(mx, dpp_f<0x124>(mx)); mx = fmaxf(mx, dpp_f<0x128>(mx));
-    mn = fminf(mn, dpp_f<0xB1>(mn)); mn = fminf(mn, dpp_f<0x4E>(mn)); mn = fminf(mn, dpp_f<0x124>(mn)); mn = fminf(mn, dpp_f<0x128>(mn));
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-      qmax[k] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mx), 16 * k));
-      qmin[k] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mn), 16 * k));
+    for (int h = 0; h < 2; h++) {
+      float dist = hit[h] == INFINITY ? -1.0f : hit[h];
+      sc.z[h] = org[h].z + (-1.0f) * dist;
+      int idx = lane + 64 * h;
+      if ((OMODE == OBS_STEP || OMODE == OBS_STEP_OBS) && a.scan_preset != 0) sc.z[h] = a.buf.scan_z[(long)e * PGTT_NSCAN + (idx < PGTT_NSCAN ? idx : 0)];   // test hook
+      if (idx < PGTT_NSCAN) { sh_scan[idx] = sc.z[h]; a.buf.scan_z[(long)e * PGTT_NSCAN + idx] = sc.z[h]; }
     }
+    sc.bz = bz;
   }
-  const float zmin = wave_min(fminf(z[0], v1 ? z[1] : INFINITY));
 
-  // ---------------- per-env scalars (computed redundantly by every lane from LDS)
-  // method 1 = the baseline task go2/joystick.py: no phase / gait_freq rows in the observation (162 / 206 instead of
-  // 171 / 215), H_max = quadrant max, world-frame clearance target, 0.5 s air-time threshold
-  const int OBSD = baseline ? PGTT_OBS_BASELINE : PGTT_OBS, PRIVD = OBSD + (PGTT_PRIV - PGTT_OBS);
-  const unsigned id = (unsigned)(a.env_off + e);
-  const unsigned ep = (unsigned)I[PGTT_I_RNG_CTR * (long)N + e];
-  int step_ctr = I[PGTT_I_STEP * (long)N + e];
-  int timer = I[PGTT_I_STEPS_UNTIL_CMD * (long)N + e];
-  int ep_steps = I[PGTT_I_EP_STEPS * (long)N + e];
-  const float dt = cfg->ctrl_dt;
-  float cmd[3], phase[4], air[4], peak[4], hmax[4], hmin[4], last_contact[4], contact[4], first_contact[4];
-  float gait_freq, phase_dt;
-  bool prev_done = false;
-  if (OMODE == OBS_RESET) {
+  // OBS_SCAN_LIFT: the base is set down on the highest scan point
+  PG_INL void lift_base(const ObsScan& sc) {
+    const bool v1 = lane + 64 < PGTT_NSCAN;
+    const float zmax = wave_max(fmaxf(sc.z[0], v1 ? sc.z[1] : -INFINITY));
+    if (lane == 0) S[(PGTT_S_QPOS + 2) * (long)N + e] = sc.bz + zmax;
+  }
+
+  PG_INL void quadrant_stats(uint2 cells, const ObsScan& sc, ObsQuad& q) {
+    // ---------------- quadrant statistics (joystick_pgtt.py:169-190): n = 6 on both axes of the 13x9 grid
+    {
+      __syncthreads();                     // the scan is in LDS
+      const char* const srcb = reinterpret_cast<const char*>(sh_src);
+      const float c0 = *reinterpret_cast<const float*>(srcb + (cells.x & 0xffffu)), c1 = *reinterpret_cast<const float*>(srcb + (cells.x >> 16)),
+                  c2 = *reinterpret_cast<const float*>(srcb + (cells.y & 0xffffu));
+      float mx = fmaxf(fmaxf(c0, c1), c2), mn = fminf(fminf(c0, c1), c2);
+      mx = row16_max(mx); mn = row16_min(mn);
+#pragma unroll
+      for (int k = 0; k < 4; k++) {
+        q.max[k] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mx), 16 * k));
+        q.min[k] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mn), 16 * k));
+      }
+    }
+    const bool v1 = lane + 64 < PGTT_NSCAN;
+    q.zmin = wave_min(fminf(sc.z[0], v1 ? sc.z[1] : INFINITY));
+  }
+
+  PG_INL void env_constants() {
+    // ---------------- per-env scalars (computed redundantly by every lane from LDS)
+    // method 1 = the baseline task go2/joystick.py: no phase / gait_freq rows in the observation (162 / 206 instead of
+    // 171 / 215), H_max = quadrant max, world-frame clearance target, 0.5 s air-time threshold
+    OBSD = baseline ? PGTT_OBS_BASELINE : PGTT_OBS; PRIVD = OBSD + (PGTT_PRIV - PGTT_OBS);
+    id = (unsigned)(a.env_off + e);
+    ep = (unsigned)I[PGTT_I_RNG_CTR * (long)N + e];
+    dt = cfg->ctrl_dt;
+  }
+
+  // the scalars of a reset env (Joystick.reset, joystick_pgtt.py:72-139) and the info arrays of its row image
+  PG_INL void reset_scalars(TaskScalars& t) {
 #pragma unroll
     for (int i = 0; i < 3; i++)
-      cmd[i] = rng_uniform(a.seed, id, ep, PGTT_RS_RESET_CMD, i, a.rng_fix) * (cfg->cmd_u_max[i] - cfg->cmd_u_min[i]) + cfg->cmd_u_min[i];
-    gait_freq = rng_uniform(a.seed, id, ep, PGTT_RS_RESET_FREQ, 0, a.rng_fix) * (cfg->gait_freq[1] - cfg->gait_freq[0]) + cfg->gait_freq[0];
-    phase_dt = (float)(2 * M_PI) * dt * gait_freq;
-    phase[0] = 0.f; phase[1] = (float)M_PI; phase[2] = (float)M_PI; phase[3] = 0.f;
+      t.cmd[i] = rng_uniform(a.seed, id, ep, PGTT_RS_RESET_CMD, i, a.rng_fix) * (cfg->cmd_u_max[i] - cfg->cmd_u_min[i]) + cfg->cmd_u_min[i];
+    t.gait_freq = rng_uniform(a.seed, id, ep, PGTT_RS_RESET_FREQ, 0, a.rng_fix) * (cfg->gait_freq[1] - cfg->gait_freq[0]) + cfg->gait_freq[0];
+    t.phase_dt = (float)(2 * M_PI) * dt * t.gait_freq;
+    t.phase[0] = 0.f; t.phase[1] = (float)M_PI; t.phase[2] = (float)M_PI; t.phase[3] = 0.f;
 #pragma unroll
-    for (int f = 0; f < 4; f++) { air[f] = 0.f; peak[f] = 0.f; hmax[f] = 0.1f; hmin[f] = 0.f; last_contact[f] = 0.f; contact[f] = 0.f; first_contact[f] = 0.f; }
-    timer = exp_timer(a.seed, id, ep, PGTT_RS_RESET_TIMER, dt, a.rng_fix);
-    step_ctr = 0; ep_steps = 0;
+    for (int f = 0; f < 4; f++) { t.air[f] = 0.f; t.peak[f] = 0.f; t.hmax[f] = 0.1f; t.hmin[f] = 0.f; t.last_contact[f] = 0.f; t.contact[f] = 0.f; t.first_contact[f] = 0.f; }
+    t.timer = exp_timer(a.seed, id, ep, PGTT_RS_RESET_TIMER, dt, a.rng_fix);
+    t.step_ctr = 0;
     __syncthreads();
     // info arrays that _get_obs reads
     if (lane < 12) { sh_st[PGTT_S_LAST_ACT + lane] = 0.f; sh_st[PGTT_S_LAST_LAST_ACT + lane] = 0.f; sh_st[PGTT_S_MOTOR_TARGETS + lane] = 0.f; }
     if (lane < 24) { sh_st[PGTT_S_QERR_HIST + lane] = 0.f; sh_st[PGTT_S_QVEL_HIST + lane] = 0.f; }
     __syncthreads();
-  } else {
-    prev_done = cfg->autoreset && a.buf.done[e] != 0.f;
-    if (prev_done) ep_steps = 0;
+  }
+
+  // the scalars a step starts with; H_max / H_min from this scan
+  PG_INL void step_scalars(const ObsQuad& q, TaskScalars& t) {
+    t.step_ctr = I[PGTT_I_STEP * (long)N + e];
+    t.timer = I[PGTT_I_STEPS_UNTIL_CMD * (long)N + e];
 #pragma unroll
-    for (int i = 0; i < 3; i++) cmd[i] = sh_st[PGTT_S_CMD + i];
-    gait_freq = sh_st[PGTT_S_GAIT_FREQ]; phase_dt = sh_st[PGTT_S_PHASE_DT];
+    for (int i = 0; i < 3; i++) t.cmd[i] = sh_st[PGTT_S_CMD + i];
+    t.gait_freq = sh_st[PGTT_S_GAIT_FREQ]; t.phase_dt = sh_st[PGTT_S_PHASE_DT];
 #pragma unroll
     for (int f = 0; f < 4; f++) {
-      phase[f] = sh_st[PGTT_S_PHASE + f];
-      last_contact[f] = sh_st[PGTT_S_LAST_CONTACT + f];
-      contact[f] = sh_fr[PGTT_F_CONTACT + f];
-      bool filt = (contact[f] != 0.f) || (last_contact[f] != 0.f);
-      first_contact[f] = (sh_st[PGTT_S_AIR_TIME + f] > 0.f ? 1.f : 0.f) * (filt ? 1.f : 0.f);
-      air[f] = sh_st[PGTT_S_AIR_TIME + f] + dt;
-      peak[f] = fmaxf(sh_st[PGTT_S_SWING_PEAK + f], sh_fr[PGTT_F_FEET_POS + 3 * f + 2]);
-      hmax[f] = baseline ? qmax[f] : qmax[f] - qmin[f]; hmin[f] = qmin[f];     // joystick.py:186 vs joystick_pgtt.py:189
+      task_foot_start(sh_st, sh_fr, dt, f, t);
+      t.hmax[f] = baseline ? q.max[f] : q.max[f] - q.min[f]; t.hmin[f] = q.min[f];     // joystick.py:186 vs joystick_pgtt.py:189
     }
   }
 
-  // ---------------- observation rows in LDS (joystick_pgtt.py:336-365)
-  const float lvl = cfg->noise_level;
-  // The noise draws of all rows in ONE Philox pass: the 147 noisy rows need 38 counter blocks (gyro 1, gravity 1, joint
-  // positions 3, joint velocities 3, scan 30; rng_uniform(.., stream, idx) is word idx & 3 of block idx >> 2), lane j forms
-  // block j and parks its four words in LDS - same draws as one rng_uniform call per row, a third of the multiplies.
-  __shared__ unsigned sh_rng[64 * 4];
-  static_assert(8 + (PGTT_NSCAN + 3) / 4 <= 64, "one lane per Philox block");
-  {
-    const int stream = lane == 0 ? PGTT_RS_GYRO : (lane == 1 ? PGTT_RS_GRAVITY : (lane < 5 ? PGTT_RS_QPOS : (lane < 8 ? PGTT_RS_QVEL : PGTT_RS_SCAN)));
-    const int blk = lane < 2 ? 0 : (lane < 5 ? lane - 2 : (lane < 8 ? lane - 5 : lane - 8));
-    unsigned c0 = id, c1 = ep, c2 = (unsigned)stream, c3 = (unsigned)blk;
-    philox4x32_10((unsigned)a.seed, (unsigned)(a.seed >> 32), c0, c1, c2, c3);
-    sh_rng[4 * lane + 0] = c0; sh_rng[4 * lane + 1] = c1; sh_rng[4 * lane + 2] = c2; sh_rng[4 * lane + 3] = c3;
-  }
-  // the per-env scalars the rows draw on, next to the rows' other sources (the phase rows are there since the yaw was formed): gait frequency, command, last contact, air time, the five noise scales and the twelve joint offsets
-  if (lane < 12) sh_drv[OD_OFFS + 1 + lane] = m->key_qpos[7 + lane];
-  if (lane == 0) {
-    sh_drv[OD_GAIT] = gait_freq; sh_drv[OD_ZERO] = 0.f; sh_drv[OD_OFFS] = 0.f;
+  template <int OMODE> PG_INL void observation_rows(const ObsPrefetch& pf, const TaskScalars& t, float zmin, ObsHist& hs) {
+    // ---------------- observation rows in LDS (joystick_pgtt.py:336-365)
+    const float lvl = cfg->noise_level;
+    // The noise draws of all rows in ONE Philox pass: the 147 noisy rows need 38 counter blocks (gyro 1, gravity 1, joint
+    // positions 3, joint velocities 3, scan 30; rng_uniform(.., stream, idx) is word idx & 3 of block idx >> 2), lane j forms
+    // block j and parks its four words in LDS - same draws as one rng_uniform call per row, a third of the multiplies.
+    __shared__ unsigned sh_rng[64 * 4];
+    static_assert(8 + (PGTT_NSCAN + 3) / 4 <= 64, "one lane per Philox block");
+    {
+      const int stream = lane == 0 ? PGTT_RS_GYRO : (lane == 1 ? PGTT_RS_GRAVITY : (lane < 5 ? PGTT_RS_QPOS : (lane < 8 ? PGTT_RS_QVEL : PGTT_RS_SCAN)));
+      const int blk = lane < 2 ? 0 : (lane < 5 ? lane - 2 : (lane < 8 ? lane - 5 : lane - 8));
+      unsigned c0 = id, c1 = ep, c2 = (unsigned)stream, c3 = (unsigned)blk;
+      philox4x32_10((unsigned)a.seed, (unsigned)(a.seed >> 32), c0, c1, c2, c3);
+      sh_rng[4 * lane + 0] = c0; sh_rng[4 * lane + 1] = c1; sh_rng[4 * lane + 2] = c2; sh_rng[4 * lane + 3] = c3;
+    }
+    // the per-env scalars the rows draw on, next to the rows' other sources (the phase rows are there since the yaw was formed): gait frequency, command, last contact, air time, the five noise scales and the twelve joint offsets
+    if (lane < 12) sh_drv[OD_OFFS + 1 + lane] = m->key_qpos[7 + lane];
+    if (lane == 0) {
+      sh_drv[OD_GAIT] = t.gait_freq; sh_drv[OD_ZERO] = 0.f; sh_drv[OD_OFFS] = 0.f;
 #pragma unroll
-    for (int k = 0; k < 3; k++) sh_drv[OD_CMD + k] = cmd[k];
+      for (int k = 0; k < 3; k++) sh_drv[OD_CMD + k] = t.cmd[k];
 #pragma unroll
-    for (int f = 0; f < 4; f++) { sh_drv[OD_LASTC + f] = last_contact[f]; sh_drv[OD_AIR + f] = air[f]; }
-    sh_drv[OD_SCALE + 0] = 0.f; sh_drv[OD_SCALE + 1] = cfg->noise_gyro; sh_drv[OD_SCALE + 2] = cfg->noise_gravity;
-    sh_drv[OD_SCALE + 3] = cfg->noise_joint_pos; sh_drv[OD_SCALE + 4] = cfg->noise_joint_vel; sh_drv[OD_SCALE + 5] = cfg->noise_heightscan;
-  }
-  __syncthreads();
-  const char* const srcb = reinterpret_cast<const char*>(sh_src);
+      for (int f = 0; f < 4; f++) { sh_drv[OD_LASTC + f] = t.last_contact[f]; sh_drv[OD_AIR + f] = t.air[f]; }
+      sh_drv[OD_SCALE + 0] = 0.f; sh_drv[OD_SCALE + 1] = cfg->noise_gyro; sh_drv[OD_SCALE + 2] = cfg->noise_gravity;
+      sh_drv[OD_SCALE + 3] = cfg->noise_joint_pos; sh_drv[OD_SCALE + 4] = cfg->noise_joint_vel; sh_drv[OD_SCALE + 5] = cfg->noise_heightscan;
+    }
+    __syncthreads();
+    const char* const srcb = reinterpret_cast<const char*>(sh_src);
 #pragma unroll
-  for (int it = 0; it < 3; it++) {
-    const int io = lane + 64 * it;
-    if (io >= OBSD) continue;
-    // every row is (base + noise) - offset with noise = (2u - 1) * level * scale (rows without noise read a word too, with scale 0; rows
-    // without an offset subtract the table's zero: x - 0 is x)
-    const unsigned d = rdesc[it], so = (d >> 21) & 0x1fu;
-    const float base0 = *reinterpret_cast<const float*>(srcb + (d & 0x7ffu));
-    const unsigned word = *reinterpret_cast<const unsigned*>(reinterpret_cast<const char*>(sh_rng) + ((d >> 11) & 0x3ffu));
-    const float scale = *reinterpret_cast<const float*>(srcb + (OL_DRV + OD_SCALE) * 4 + so);
-    const float offs = *reinterpret_cast<const float*>(srcb + (OL_DRV + OD_OFFS) * 4 + (d >> 26));
-    const float base = base0 - (so == 20u ? zmin : 0.f);              // scan rows are heights above the lowest scan point
-    const float uw = (float)(word >> 8) * (1.0f / 16777216.0f);
-    const float u = a.rng_fix == a.rng_fix ? a.rng_fix : uw;
-    const float noisy = scale != 0.f ? base + (2.f * u - 1.f) * lvl * scale : base;
-    sh_obs[io] = noisy - offs;
+    for (int it = 0; it < 3; it++) {
+      const int io = lane + 64 * it;
+      if (io >= OBSD) continue;
+      // every row is (base + noise) - offset with noise = (2u - 1) * level * scale (rows without noise read a word too, with scale 0; rows
+      // without an offset subtract the table's zero: x - 0 is x)
+      const unsigned d = pf.rdesc[it], so = (d >> 21) & 0x1fu;
+      const float base0 = *reinterpret_cast<const float*>(srcb + (d & 0x7ffu));
+      const unsigned word = *reinterpret_cast<const unsigned*>(reinterpret_cast<const char*>(sh_rng) + ((d >> 11) & 0x3ffu));
+      const float scale = *reinterpret_cast<const float*>(srcb + (OL_DRV + OD_SCALE) * 4 + so);
+      const float offs = *reinterpret_cast<const float*>(srcb + (OL_DRV + OD_OFFS) * 4 + (d >> 26));
+      const float base = base0 - (so == 20u ? zmin : 0.f);              // scan rows are heights above the lowest scan point
+      const float uw = (float)(word >> 8) * (1.0f / 16777216.0f);
+      const float u = a.rng_fix == a.rng_fix ? a.rng_fix : uw;
+      const float noisy = scale != 0.f ? base + (2.f * u - 1.f) * lvl * scale : base;
+      sh_obs[io] = noisy - offs;
+    }
+    if (lane < PGTT_PRIV - PGTT_OBS) sh_obs[OBSD + OBSD + lane] = *reinterpret_cast<const float*>(srcb + pf.psrc);
+    // privileged extras 41..43: the force on the torso during this step (xfrc_applied[torso, :3], joystick_pgtt.py:364); 0 without a wrench buffer
+    // and in the observation of a reset
+    if ((OMODE == OBS_STEP || OMODE == OBS_STEP_OBS) && a.buf.xfrc && lane >= 41 && lane < 44) sh_obs[OBSD + OBSD + lane] = a.buf.xfrc[(lane - 41) * (long)N + e];
+    // history buffers (joystick_pgtt.py:319-334): motor_targets in sh_st was written by the physics kernel
+    hs.q = 0.f; hs.v = 0.f; hs.upd = (t.step_ctr % cfg->history_update_steps) == 0;
+    if (lane < 24) {
+      if (hs.upd) {
+        hs.v = lane < 12 ? sh_st[PGTT_S_QVEL + 6 + lane] : sh_st[PGTT_S_QVEL_HIST + lane - 12];
+        hs.q = lane < 12 ? sh_st[PGTT_S_QPOS + 7 + lane] - sh_st[PGTT_S_MOTOR_TARGETS + lane] : sh_st[PGTT_S_QERR_HIST + lane - 12];
+      } else { hs.v = sh_st[PGTT_S_QVEL_HIST + lane]; hs.q = sh_st[PGTT_S_QERR_HIST + lane]; }
+    }
+    __syncthreads();
+    for (int i = lane; i < OBSD; i += 64) sh_obs[OBSD + i] = sh_obs[i];     // privileged = state || extras
+    __syncthreads();
   }
-  if (lane < PGTT_PRIV - PGTT_OBS) sh_obs[OBSD + OBSD + lane] = *reinterpret_cast<const float*>(srcb + psrc);
-  // privileged extras 41..43: the force on the torso during this step (xfrc_applied[torso, :3], joystick_pgtt.py:364); 0 without a wrench buffer
-  // and in the observation of a reset
-  if ((OMODE == OBS_STEP || OMODE == OBS_STEP_OBS) && a.buf.xfrc && lane >= 41 && lane < 44) sh_obs[OBSD + OBSD + lane] = a.buf.xfrc[(lane - 41) * (long)N + e];
-  // history buffers (joystick_pgtt.py:319-334): motor_targets in sh_st was written by the physics kernel
-  float hist_q = 0.f, hist_v = 0.f; const bool upd = (step_ctr % cfg->history_update_steps) == 0;
-  if (lane < 24) {
-    if (upd) {
-      hist_v = lane < 12 ? sh_st[PGTT_S_QVEL + 6 + lane] : sh_st[PGTT_S_QVEL_HIST + lane - 12];
-      hist_q = lane < 12 ? sh_st[PGTT_S_QPOS + 7 + lane] - sh_st[PGTT_S_MOTOR_TARGETS + lane] : sh_st[PGTT_S_QERR_HIST + lane - 12];
-    } else { hist_v = sh_st[PGTT_S_QVEL_HIST + lane]; hist_q = sh_st[PGTT_S_QERR_HIST + lane]; }
-  }
-  __syncthreads();
-  for (int i = lane; i < OBSD; i += 64) sh_obs[OBSD + i] = sh_obs[i];     // privileged = state || extras
-  __syncthreads();
-  if (OMODE == OBS_STEP_OBS) {
+
+  PG_INL void store_split(const TaskScalars& t) {
     // scan + observation half: H_max / H_min of this scan for task_kernel, the observation rows (a finished episode's
     // rows are replaced by task_kernel), nothing else
     if (lane < 4) {
-      S[(PGTT_S_HMAX + lane) * (long)N + e] = sel4(lane, hmax[0], hmax[1], hmax[2], hmax[3]);
-      S[(PGTT_S_HMIN + lane) * (long)N + e] = sel4(lane, hmin[0], hmin[1], hmin[2], hmin[3]);
+      S[(PGTT_S_HMAX + lane) * (long)N + e] = sel4(lane, t.hmax[0], t.hmax[1], t.hmax[2], t.hmax[3]);
+      S[(PGTT_S_HMIN + lane) * (long)N + e] = sel4(lane, t.hmin[0], t.hmin[1], t.hmin[2], t.hmin[3]);
     }
     for (int i = lane; i < OBSD; i += 64) a.buf.obs_state[(long)e * OBSD + i] = sh_obs[i];
     for (int i = lane; i < PRIVD; i += 64) a.buf.obs_priv[(long)e * PRIVD + i] = sh_obs[OBSD + i];
-    return;
   }
 
-  // ---------------- rewards, termination, bookkeeping
-  float reward = 0.f; bool done = false; float metrics[PGTT_NMETRIC];
-#pragma unroll
-  for (int k = 0; k < PGTT_NMETRIC; k++) metrics[k] = 0.f;
-  float act_i = 0.f;
-  if (OMODE == OBS_STEP) {
-    TaskScalars t;
-#pragma unroll
-    for (int i = 0; i < 3; i++) t.cmd[i] = cmd[i];
-#pragma unroll
-    for (int f = 0; f < 4; f++) { t.phase[f] = phase[f]; t.air[f] = air[f]; t.peak[f] = peak[f]; t.hmax[f] = hmax[f]; t.last_contact[f] = last_contact[f]; t.contact[f] = contact[f]; t.first_contact[f] = first_contact[f]; }
-    t.phase_dt = phase_dt; t.step_ctr = step_ctr; t.timer = timer;
-    task_rewards<true>(sh_st, sh_fr, sh_act, cfg, m, baseline, a.seed, id, ep, dt, a.rng_fix, t);
-#pragma unroll
-    for (int i = 0; i < 3; i++) cmd[i] = t.cmd[i];
-#pragma unroll
-    for (int f = 0; f < 4; f++) { phase[f] = t.phase[f]; air[f] = t.air[f]; peak[f] = t.peak[f]; last_contact[f] = t.last_contact[f]; }
-    step_ctr = t.step_ctr; timer = t.timer; done = t.done; reward = t.reward;
-#pragma unroll
-    for (int k = 0; k < PGTT_NMETRIC; k++) metrics[k] = t.metrics[k];
-    if (lane < 12) act_i = sh_act[lane];
-  }
-  // ---------------- Episode / AutoReset wrapper semantics (UPSTREAM-RECALL)
-  bool wdone = done;
-  if (OMODE == OBS_STEP && cfg->autoreset) {
-    ep_steps += 1;
-    if (ep_steps >= cfg->episode_length) wdone = true;
-  }
-  // Every value below is the same in all lanes (a per-env scalar in a vector register).  Lane 0 parks them in LDS - the new values of the
-  // env's state rows in their slots of the row image sh_st, the metrics with (reward, 1) behind them - and the wave then stores ROW RANGES
-  // with one address per lane; picking "my row's value" out of registers costs a compare + select per candidate (22 for a metric) and a
-  // 64-bit address per store site, in a kernel whose four waves per SIMD share the vector ALU.
-  // AutoReset of a finished episode: the first state and its observation are requested HERE, all at once (the copy loops at the end of the
-  // wave were eight dependent round trips - each store could alias the next load - and the few waves with a finished episode were the last
-  // of the launch to leave)
-  const bool restore = OMODE == OBS_STEP && cfg->autoreset && wdone && a.buf.first_state && a.buf.first_obs;
-  constexpr int kFirstObsPasses = (PGTT_OBS + PGTT_PRIV + 63) / 64;
-  float first_st = 0.f, first_ob[kFirstObsPasses];
-  if (restore) {
-    if (lane < PGTT_S_CMD) first_st = a.buf.first_state[lane * (long)N + e];
-    const float* __restrict__ fo = a.buf.first_obs + (long)e * (OBSD + PRIVD);
-#pragma unroll
-    for (int i = 0; i < kFirstObsPasses; i++) first_ob[i] = lane + 64 * i < OBSD + PRIVD ? fo[lane + 64 * i] : 0.f;
-  }
-  __shared__ float sh_met[PGTT_NMETRIC + 2];
-  __syncthreads();                       // the row image has been read for the last time (rewards, history)
-  if (lane < 12) {
-    const float prev = sh_st[PGTT_S_LAST_ACT + lane];
-    sh_st[PGTT_S_LAST_LAST_ACT + lane] = OMODE == OBS_STEP ? prev : 0.f;
-    sh_st[PGTT_S_LAST_ACT + lane] = OMODE == OBS_STEP ? act_i : 0.f;
-    if (OMODE != OBS_STEP) sh_st[PGTT_S_MOTOR_TARGETS + lane] = 0.f;
-  }
-  if (lane < 24) { sh_st[PGTT_S_QVEL_HIST + lane] = hist_v; sh_st[PGTT_S_QERR_HIST + lane] = hist_q; }
-  if (lane == 0) {
-#pragma unroll
-    for (int i = 0; i < 3; i++) sh_st[PGTT_S_CMD + i] = cmd[i];
-#pragma unroll
-    for (int f = 0; f < 4; f++) {
-      sh_st[PGTT_S_PHASE + f] = phase[f]; sh_st[PGTT_S_AIR_TIME + f] = air[f]; sh_st[PGTT_S_SWING_PEAK + f] = peak[f];
-      sh_st[PGTT_S_HMAX + f] = hmax[f]; sh_st[PGTT_S_HMIN + f] = hmin[f]; sh_st[PGTT_S_LAST_CONTACT + f] = last_contact[f];
+  template <int OMODE> PG_INL void wrap_and_store(const ObsPrefetch& pf, const TaskScalars& t, const ObsHist& hs, int ep_steps, bool prev_done) {
+    // ---------------- Episode / AutoReset wrapper semantics (UPSTREAM-RECALL)
+    float act_i = 0.f;
+    if (OMODE == OBS_STEP && lane < 12) act_i = sh_act[lane];
+    bool wdone = t.done;
+    if (OMODE == OBS_STEP && cfg->autoreset) {
+      ep_steps += 1;
+      if (ep_steps >= cfg->episode_length) wdone = true;
     }
-    sh_st[PGTT_S_PHASE_DT] = phase_dt; sh_st[PGTT_S_GAIT_FREQ] = gait_freq;
+    // Every value below is the same in all lanes (a per-env scalar in a vector register).  Lane 0 parks them in LDS - the new values of the
+    // env's state rows in their slots of the row image sh_st, the metrics with (reward, 1) behind them - and the wave then stores ROW RANGES
+    // with one address per lane; picking "my row's value" out of registers costs a compare + select per candidate (22 for a metric) and a
+    // 64-bit address per store site, in a kernel whose four waves per SIMD share the vector ALU.
+    // AutoReset of a finished episode: the first state and its observation are requested HERE, all at once (the copy loops at the end of the
+    // wave were eight dependent round trips - each store could alias the next load - and the few waves with a finished episode were the last
+    // of the launch to leave)
+    const bool restore = OMODE == OBS_STEP && cfg->autoreset && wdone && a.buf.first_state && a.buf.first_obs;
+    constexpr int kFirstObsPasses = (PGTT_OBS + PGTT_PRIV + 63) / 64;
+    float first_st = 0.f, first_ob[kFirstObsPasses];
+    if (restore) {
+      if (lane < PGTT_S_CMD) first_st = a.buf.first_state[lane * (long)N + e];
+      const float* __restrict__ fo = a.buf.first_obs + (long)e * (OBSD + PRIVD);
 #pragma unroll
-    for (int k = 0; k < PGTT_NMETRIC; k++) sh_met[k] = metrics[k];
-    sh_met[PGTT_NMETRIC] = reward; sh_met[PGTT_NMETRIC + 1] = 1.0f;
-  }
-  __syncthreads();
-  if (OMODE == OBS_STEP && cfg->autoreset && a.buf.ep_metrics && lane < PGTT_NMETRIC + 2)
-    a.buf.ep_metrics[lane * (long)N + e] = (epm_old + sh_met[lane]) * (prev_done ? 0.f : 1.f);
-
-  // ---------------- stores: rows PGTT_S_CMD .. PGTT_NSTATE - 1 of the image (the step leaves the motor targets, which are the physics kernel's, alone)
-  static_assert(PGTT_NSTATE - PGTT_S_CMD <= 128 && PGTT_NMETRIC + 2 <= 64, "two passes over the rows, one over the metrics");
+      for (int i = 0; i < kFirstObsPasses; i++) first_ob[i] = lane + 64 * i < OBSD + PRIVD ? fo[lane + 64 * i] : 0.f;
+    }
+    __shared__ float sh_met[PGTT_NMETRIC + 2];
+    __syncthreads();                       // the row image has been read for the last time (rewards, history)
+    if (lane < 12) {
+      const float prev = sh_st[PGTT_S_LAST_ACT + lane];
+      sh_st[PGTT_S_LAST_LAST_ACT + lane] = OMODE == OBS_STEP ? prev : 0.f;
+      sh_st[PGTT_S_LAST_ACT + lane] = OMODE == OBS_STEP ? act_i : 0.f;
+      if (OMODE != OBS_STEP) sh_st[PGTT_S_MOTOR_TARGETS + lane] = 0.f;
+    }
+    if (lane < 24) { sh_st[PGTT_S_QVEL_HIST + lane] = hs.v; sh_st[PGTT_S_QERR_HIST + lane] = hs.q; }
+    if (lane == 0) {
 #pragma unroll
-  for (int h = 0; h < 2; h++) {
-    const int r = PGTT_S_CMD + lane + 64 * h;
-    // the step leaves the histories alone except on the steps that shift them (1 in history_update_steps)
-    const bool mine = r < PGTT_NSTATE && (OMODE != OBS_STEP || r < PGTT_S_MOTOR_TARGETS || r >= PGTT_S_LAST_CONTACT || (upd && r >= PGTT_S_QERR_HIST));
-    if (mine) S[r * (long)N + e] = sh_st[r];
-  }
-  if (lane == 0) {
-    I[PGTT_I_STEP * (long)N + e] = step_ctr; I[PGTT_I_STEPS_UNTIL_CMD * (long)N + e] = timer;
-    I[PGTT_I_RNG_CTR * (long)N + e] = (int)(ep + 1u); I[PGTT_I_EP_STEPS * (long)N + e] = ep_steps;
-    a.buf.reward[e] = reward; a.buf.done[e] = wdone ? 1.f : 0.f;
-  }
-  if (lane < PGTT_NMETRIC) {
-    const float v = sh_met[lane];
-    a.buf.metrics[lane * (long)N + e] = v;
-  }
-  if (OMODE == OBS_STEP && a.buf.interval_sums && lane < PGTT_NMETRIC + 2)
-    a.buf.interval_sums[lane * (long)N + e] = ivs_old + (lane < PGTT_NMETRIC ? sh_met[lane] : (lane == PGTT_NMETRIC ? reward : (wdone ? 1.f : 0.f)));
-  if (restore) {                         // the first observation takes the place of this step's in LDS (same layout: state rows, then privileged rows)
-    static_assert(PGTT_S_CMD <= 64, "one lane per restored state row");
-    if (lane < PGTT_S_CMD) S[lane * (long)N + e] = first_st;
+      for (int i = 0; i < 3; i++) sh_st[PGTT_S_CMD + i] = t.cmd[i];
 #pragma unroll
-    for (int i = 0; i < kFirstObsPasses; i++) if (lane + 64 * i < OBSD + PRIVD) sh_obs[lane + 64 * i] = first_ob[i];
+      for (int f = 0; f < 4; f++) {
+        sh_st[PGTT_S_PHASE + f] = t.phase[f]; sh_st[PGTT_S_AIR_TIME + f] = t.air[f]; sh_st[PGTT_S_SWING_PEAK + f] = t.peak[f];
+        sh_st[PGTT_S_HMAX + f] = t.hmax[f]; sh_st[PGTT_S_HMIN + f] = t.hmin[f]; sh_st[PGTT_S_LAST_CONTACT + f] = t.last_contact[f];
+      }
+      sh_st[PGTT_S_PHASE_DT] = t.phase_dt; sh_st[PGTT_S_GAIT_FREQ] = t.gait_freq;
+#pragma unroll
+      for (int k = 0; k < PGTT_NMETRIC; k++) sh_met[k] = t.metrics[k];
+      sh_met[PGTT_NMETRIC] = t.reward; sh_met[PGTT_NMETRIC + 1] = 1.0f;
+    }
     __syncthreads();
+    if (OMODE == OBS_STEP && cfg->autoreset && a.buf.ep_metrics && lane < PGTT_NMETRIC + 2)
+      a.buf.ep_metrics[lane * (long)N + e] = (pf.epm_old + sh_met[lane]) * (prev_done ? 0.f : 1.f);
+
+    // ---------------- stores: rows PGTT_S_CMD .. PGTT_NSTATE - 1 of the image (the step leaves the motor targets, which are the physics kernel's, alone)
+    static_assert(PGTT_NSTATE - PGTT_S_CMD <= 128 && PGTT_NMETRIC + 2 <= 64, "two passes over the rows, one over the t.metrics");
+#pragma unroll
+    for (int h = 0; h < 2; h++) {
+      const int r = PGTT_S_CMD + lane + 64 * h;
+      // the step leaves the histories alone except on the steps that shift them (1 in history_update_steps)
+      const bool mine = r < PGTT_NSTATE && (OMODE != OBS_STEP || r < PGTT_S_MOTOR_TARGETS || r >= PGTT_S_LAST_CONTACT || (hs.upd && r >= PGTT_S_QERR_HIST));
+      if (mine) S[r * (long)N + e] = sh_st[r];
+    }
+    if (lane == 0) {
+      I[PGTT_I_STEP * (long)N + e] = t.step_ctr; I[PGTT_I_STEPS_UNTIL_CMD * (long)N + e] = t.timer;
+      I[PGTT_I_RNG_CTR * (long)N + e] = (int)(ep + 1u); I[PGTT_I_EP_STEPS * (long)N + e] = ep_steps;
+      a.buf.reward[e] = t.reward; a.buf.done[e] = wdone ? 1.f : 0.f;
+    }
+    if (lane < PGTT_NMETRIC) {
+      const float v = sh_met[lane];
+      a.buf.metrics[lane * (long)N + e] = v;
+    }
+    if (OMODE == OBS_STEP && a.buf.interval_sums && lane < PGTT_NMETRIC + 2)
+      a.buf.interval_sums[lane * (long)N + e] = pf.ivs_old + (lane < PGTT_NMETRIC ? sh_met[lane] : (lane == PGTT_NMETRIC ? t.reward : (wdone ? 1.f : 0.f)));
+    if (restore) {                         // the first observation takes the place of this step's in LDS (same layout: state rows, then privileged rows)
+      static_assert(PGTT_S_CMD <= 64, "one lane per restored state row");
+      if (lane < PGTT_S_CMD) S[lane * (long)N + e] = first_st;
+#pragma unroll
+      for (int i = 0; i < kFirstObsPasses; i++) if (lane + 64 * i < OBSD + PRIVD) sh_obs[lane + 64 * i] = first_ob[i];
+      __syncthreads();
+    }
+    for (int i = lane; i < OBSD; i += 64) a.buf.obs_state[(long)e * OBSD + i] = sh_obs[i];
+    for (int i = lane; i < PRIVD; i += 64) a.buf.obs_priv[(long)e * PRIVD + i] = sh_obs[OBSD + i];
+    if (OMODE == OBS_RESET) {
+      if (a.buf.first_state) for (int r = lane; r < PGTT_S_CMD; r += 64) a.buf.first_state[r * (long)N + e] = sh_st[r];
+      if (a.buf.first_obs) for (int i = lane; i < OBSD + PRIVD; i += 64) a.buf.first_obs[(long)e * (OBSD + PRIVD) + i] = sh_obs[i];
+      if (a.buf.ep_metrics) for (int k = lane; k < PGTT_NMETRIC + 2; k += 64) a.buf.ep_metrics[k * (long)N + e] = 0.f;
+    }
   }
-  for (int i = lane; i < OBSD; i += 64) a.buf.obs_state[(long)e * OBSD + i] = sh_obs[i];
-  for (int i = lane; i < PRIVD; i += 64) a.buf.obs_priv[(long)e * PRIVD + i] = sh_obs[OBSD + i];
-  if (OMODE == OBS_RESET) {
-    if (a.buf.first_state) for (int r = lane; r < PGTT_S_CMD; r += 64) a.buf.first_state[r * (long)N + e] = sh_st[r];
-    if (a.buf.first_obs) for (int i = lane; i < OBSD + PRIVD; i += 64) a.buf.first_obs[(long)e * (OBSD + PRIVD) + i] = sh_obs[i];
-    if (a.buf.ep_metrics) for (int k = lane; k < PGTT_NMETRIC + 2; k += 64) a.buf.ep_metrics[k * (long)N + e] = 0.f;
+};
+
+template <int OMODE, bool HAS_TERRAIN>
+// four waves per SIMD (128 VGPRs): the kernel is latency-bound, a launch lasts as long as the resident waves of a SIMD take in turn
+__global__ __launch_bounds__(64, 4) void observe_kernel(KArgs a, const float* __restrict__ action) {
+  const int e = xcd_block(blockIdx.x, gridDim.x), lane = threadIdx.x, N = a.N;
+  if (OMODE != OBS_STEP && OMODE != OBS_STEP_OBS && a.mask && !a.mask[e]) return;
+
+  __shared__ float sh_src[OL_END];
+  __shared__ float sh_obs[PGTT_OBS + PGTT_PRIV + 2];
+  __shared__ float sh_act[12];
+  ObserveWave w{a, e, lane, N, a.model, a.cfg, a.buf.state, a.buf.istate, sh_src, sh_src + OL_ST, sh_src + OL_FR, sh_src + OL_SCAN, sh_src + OL_DRV, sh_obs, sh_act};
+  ObsPrefetch pf; ObsScan sc;
+  w.template load_rows<OMODE, HAS_TERRAIN>(action, pf);              // every mode: the row image, the prefetches
+  w.template height_scan<OMODE, HAS_TERRAIN>(pf, sc);                // every mode: yaw, cull, rays; scan_z
+  if (OMODE == OBS_SCAN_ONLY) return;
+  if (OMODE == OBS_SCAN_LIFT) { w.lift_base(sc); return; }
+  // OBS_STEP, OBS_STEP_OBS, OBS_RESET: the observation
+  ObsQuad q; ObsHist hs; TaskScalars t;
+  w.quadrant_stats(pf.qcell, sc, q);
+  w.env_constants();
+  int ep_steps = 0; bool prev_done = false;       // Episode / AutoReset wrapper state
+  if (OMODE == OBS_RESET) w.reset_scalars(t);
+  else {
+    ep_steps = w.I[PGTT_I_EP_STEPS * (long)N + e];
+    prev_done = w.cfg->autoreset && a.buf.done[e] != 0.f;
+    if (prev_done) ep_steps = 0;
+    w.step_scalars(q, t);
   }
+  w.template observation_rows<OMODE>(pf, t, q.zmin, hs);
+  if (OMODE == OBS_STEP_OBS) { w.store_split(t); return; }         // the split form ends here: task_kernel does the rest
+  // OBS_STEP: rewards, termination, bookkeeping; OBS_RESET: none
+  t.reward = 0.f; t.done = false;
+#pragma unroll
+  for (int k = 0; k < PGTT_NMETRIC; k++) t.metrics[k] = 0.f;
+  if (OMODE == OBS_STEP) task_rewards<true>(w.sh_st, w.sh_fr, w.sh_act, w.cfg, w.m, w.baseline, a.seed, w.id, w.ep, w.dt, a.rng_fix, t);
+  w.template wrap_and_store<OMODE>(pf, t, hs, ep_steps, prev_done);    // OBS_STEP, OBS_RESET
 }
 
 
@@ -952,13 +982,7 @@ __global__ __launch_bounds__(64) void task_kernel(KArgs a, const float* __restri
   t.phase_dt = st[PGTT_S_PHASE_DT];
 #pragma unroll
   for (int f = 0; f < 4; f++) {
-    t.phase[f] = st[PGTT_S_PHASE + f];
-    t.last_contact[f] = st[PGTT_S_LAST_CONTACT + f];
-    t.contact[f] = fr[PGTT_F_CONTACT + f];
-    const bool filt = (t.contact[f] != 0.f) || (t.last_contact[f] != 0.f);
-    t.first_contact[f] = (st[PGTT_S_AIR_TIME + f] > 0.f ? 1.f : 0.f) * (filt ? 1.f : 0.f);
-    t.air[f] = st[PGTT_S_AIR_TIME + f] + dt;
-    t.peak[f] = fmaxf(st[PGTT_S_SWING_PEAK + f], fr[PGTT_F_FEET_POS + 3 * f + 2]);
+    task_foot_start(st, fr, dt, f, t);
     t.hmax[f] = st[PGTT_S_HMAX + f];                                                     // of the current scan
   }
   // history buffers (joystick_pgtt.py:319-334) use the step counter BEFORE it advances

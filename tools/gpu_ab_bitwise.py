@@ -2,7 +2,7 @@
 (state, counters, sensor frame, scan, both observation blocks, reward, done, metrics, episode / interval sums).
    usage: python tools/gpu_ab_bitwise.py alt_build/libpgtt_ref.so phase_guided_terrain_traversal_amd/libpgtt.so [steps]
    (each build runs in its own process: PGTT_LIB is read when the library is first loaded; PGTT_AB_OCT=1 adds the oct layout)
-Workloads: level4 and flat ground at 1024 envs per lane layout, and level13 + full DR + AutoReset at a RAGGED env count (1000: the last
+Workloads: level4 and flat ground at 1024 envs per lane layout, level4 once more in the split observe form and once with the baseline method, and level13 + full DR + AutoReset at a RAGGED env count (1000: the last
 workgroup of the tiled observe kernel is partly empty) with a short episode length so that AutoReset-to-first-state is exercised."""
 import os, subprocess, sys
 import numpy as np
@@ -33,6 +33,11 @@ if sys.argv[1] == "--child":
             terrain = None if wl == "flat" else np.load(A + "level4.npy")
             kw = {} if terrain is None else {"variant": torch.from_numpy(np.random.default_rng(0).integers(0, terrain.shape[0], n).astype(np.int32))}
             run(f"{wl}_{lay}", "flat_terrain" if wl == "flat" else "stairs", n, terrain, lay, **kw)
+    # the split form (observe_kernel<OBS_STEP_OBS> + task_kernel) and the baseline method's rows and rewards: level4, 1024 envs, hex
+    t4 = np.load(A + "level4.npy"); n = 1024
+    v4 = torch.from_numpy(np.random.default_rng(0).integers(0, t4.shape[0], n).astype(np.int32))
+    run("level4_split", "stairs", n, t4, "hex", variant=v4, observe_form="split")
+    run("level4_baseline", "stairs", n, t4, "hex", cfg=configs.with_overrides(configs.training_config(), method="baseline"), variant=v4)
     t13 = np.load(A + "level13.npy"); n = 1000
     dr = domain_randomize(mjcf.load_model("stairs"), n, seed=3, terrain=t13)
     for lay in ("hex",) + (("oct", "quad") if os.environ.get("PGTT_AB_OCT") else ()):          # the DR + terrain kernels of every layout
