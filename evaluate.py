@@ -54,6 +54,14 @@ def load_policy_from_args(args, tmp_dir):
     return PolicyMLP(os.path.join(args.checkpoint_folder, npz[-1])).to(DEVICE)
 
 
+def resize_nearest(img, height, width):
+    """[..., H, W] -> [..., height, width]: output pixel (i, j) takes the input pixel under its centre"""
+    H, W = img.shape[-2:]
+    rows = ((torch.arange(height, device=img.device) * 2 + 1) * H) // (2 * height)
+    cols = ((torch.arange(width, device=img.device) * 2 + 1) * W) // (2 * width)
+    return img[..., rows[:, None], cols[None, :]]
+
+
 class VideoRecorder:
     """--video: renders the first --video_envs evaluation envs with a tracking camera before every --video_every-th control step (frames stay
     on the device: [H, K * W, 3] per frame, the envs side by side, a progress bar of the episode along the bottom rows) and writes them at
@@ -68,6 +76,12 @@ class VideoRecorder:
         self.renderer = Renderer(env, w, h, shadows=True)
         self.camera = Camera("track", target=(0.0, 0.0, 0.0), distance=2.2, azimuth=120.0, elevation=-25.0, fovy=45.0)
         self.frames = []
+        self.depth = None
+        if getattr(args, "video_depth", False):
+            # --video_depth: each env's onboard depth image (the sensor of depth.DEFAULTS, resolution included), grey, scaled to the tile by
+            # nearest neighbour and put under its RGB tile
+            from phase_guided_terrain_traversal_amd.depth import DepthCamera, settings
+            self.depth = DepthCamera(env, **settings())
 
     def capture(self, t):
         if t % self.every:
@@ -82,6 +96,11 @@ class VideoRecorder:
         frame = rgb.permute(1, 0, 2, 3).reshape(h, v * w, 3).clone()
         bar = max(1, h // 80)
         frame[h - bar:, : int(round(v * w * (t + 1) / self.L))] = 255
+        if self.depth is not None:
+            d = self.depth.tick(force=True)[self.ids]
+            grey = (255 * (1 - (d - self.depth.near) / (self.depth.far - self.depth.near))).clamp(0, 255).to(torch.uint8)
+            grey = resize_nearest(grey, h, w)
+            frame = torch.cat([frame, grey.permute(1, 0, 2).reshape(h, v * w, 1).expand(h, v * w, 3)], 0)
         self.frames.append(frame)
 
     def write(self, verbose=True):
@@ -91,6 +110,8 @@ class VideoRecorder:
         os.makedirs(d, exist_ok=True)
         out = save_gif(self.path, frames, fps=1.0 / (self.env.dt * self.every))
         self.renderer.close()
+        if self.depth is not None:
+            self.depth.close()
         if verbose:
             print(f"video: {len(frames)} frames of {frames.shape[2]}x{frames.shape[1]} -> {out}")
         return out
@@ -177,6 +198,7 @@ def make_parser():
     ap.add_argument("--video_size", type=str, default="320x240", help="WxH of each env's tile")
     ap.add_argument("--video_every", type=int, default=2, help="one frame every n control steps")
     ap.add_argument("--video_scan", action="store_true", help="overlay the 117 height-scan hits as marker spheres")
+    ap.add_argument("--video_depth", action="store_true", help="tile each video env's onboard depth image (grey, near = white) under its RGB tile")
     configs.add_push_args(ap)
     ap.add_argument("--terrain_files", type=str, default=None, help="comma-separated level files stacked into one table (as train.py --terrain_files); evaluated on --level")
     ap.add_argument("--level", type=int, default=0, help="with --terrain_files: the level every evaluation env stands on (no curriculum at evaluation)")

@@ -1,0 +1,479 @@
+// pgtt_depth.hip — libpgtt_depth.so: the onboard depth camera (include/pgtt_depth.h), one workgroup per env.
+//
+// depth_kernel, 256 lanes per env:
+//   phase A  lanes 0..3 run the forward kinematics of one leg each (the formulas of mjcf.kinematics_np; only when the mount is not on the
+//            torso or the robot is in the scene); every lane then forms the camera basis from the mount body's pose.
+//            Lane b < B moves box b of the env's variant into the CAMERA frame (x right, y up, z along the optical axis; the ray origin is
+//            the frame's origin) and tests its bounding sphere against the cone around the view frustum and against `far`.  Survivors are
+//            compacted into LDS in box order with a ballot and prefix counts: no atomics, so the list is deterministic.  The posed robot
+//            geoms go the same way.
+//   phase B  pixels over lanes, 256 per pass.  The ray of pixel (i, j) in the camera frame is (u, v, 1) for every env; with that
+//            un-normalised direction the slab parameter of a box IS the distance along the optical axis, and a record holds all that the
+//            slab test needs (the origin in the box frame, the box's axes, the half extents).  Every lane walks the same list (LDS
+//            broadcasts, wave-uniform trip count), takes the minimum with the plane, clamps, adds the noise and stores coalesced.
+// A tick that the sensor period skips returns at once in every workgroup (the decision reads counter[0] on the device); depth_advance_kernel,
+// enqueued behind it, adds one to the counter.  Nothing is shared between envs: an env's image does not depend on the batch.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "../../include/pgtt_depth.h"
+
+#ifndef PGTT_DEPTH_SRC
+#define PGTT_DEPTH_SRC "unknown"
+#endif
+// experiment build (make -f pgtt_depth.mk EXTRA=-DPGTT_DEPTH_NOCULL ...): every box and geom is kept; the figure DESIGN.md 14 compares against
+#ifdef PGTT_DEPTH_NOCULL
+#define PGTT_DEPTH_FLAVOR "nocull"
+#else
+#define PGTT_DEPTH_FLAVOR "product"
+#endif
+
+namespace {
+
+thread_local std::string g_err;
+
+int fail(int code, const std::string& msg) { g_err = msg; return code; }
+
+#define HIP_TRY(expr)                                                                              \
+  do {                                                                                             \
+    hipError_t _e = (expr);                                                                        \
+    if (_e != hipSuccess) return fail(PGTT_E_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
+  } while (0)
+
+constexpr int kLanes = 256;             // lanes per workgroup = per env
+constexpr int kWaves = kLanes / 64;
+constexpr int kTabWords = 16;           // terrain table, world frame: centre[3], local axes r0[3] r1[3] r2[3], half extents[3], pad
+constexpr int kBoxWords = 16;           // LDS box, camera frame: ray origin in the box frame[3], axes r0 r1 r2 [9], half extents[3], pad
+constexpr int kGeomWords = 16;          // LDS geom, camera frame: centre[3], axes r0 r1 r2 [9], size[3], type
+static_assert(PGTT_MAX_BOX <= kLanes && PGTT_RENDER_MAX_GEOM <= 64, "one lane per box, the geoms in one wave");
+
+struct DepthArgs {
+  const float* state;
+  const float* params;
+  const int32_t* variant;
+  float* depth;
+  int64_t* counter;
+  const float* boxes;                   // [T][B][kTabWords]
+  const PgttModel* model;
+  const PgttRenderGeom* geoms;
+  int N, T, B, ngeom;                   // ngeom = 0 when the robot is not in the scene
+  int W, H, mount_body, every, force;
+  float tan_y, near_m, far_m;
+  float mpos[3], mquat[4];
+  float sigma, dropout;
+  unsigned long long seed;
+  long long env_off;
+};
+
+struct V3 { float x, y, z; };
+__device__ __forceinline__ V3 v3(float x, float y, float z) { return {x, y, z}; }
+__device__ __forceinline__ V3 operator+(V3 a, V3 b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
+__device__ __forceinline__ V3 operator-(V3 a, V3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
+__device__ __forceinline__ V3 operator*(float s, V3 a) { return {s * a.x, s * a.y, s * a.z}; }
+__device__ __forceinline__ float dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
+__device__ __forceinline__ V3 cross(V3 a, V3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
+__device__ __forceinline__ V3 ld3(const float* p) { return {p[0], p[1], p[2]}; }
+
+struct Q4 { float w, x, y, z; };
+__device__ __forceinline__ Q4 qmul(Q4 a, Q4 b) {
+  return {a.w * b.w - a.x * b.x - a.y * b.y - a.z * b.z, a.w * b.x + a.x * b.w + a.y * b.z - a.z * b.y,
+          a.w * b.y - a.x * b.z + a.y * b.w + a.z * b.x, a.w * b.z + a.x * b.y - a.y * b.x + a.z * b.w};
+}
+// columns of the rotation matrix of q: the frame's local axes in the parent's coordinates
+__device__ __forceinline__ void qaxes(Q4 q, V3& c0, V3& c1, V3& c2) {
+  const float w = q.w, x = q.x, y = q.y, z = q.z;
+  c0 = v3(w * w + x * x - y * y - z * z, 2.f * (x * y + w * z), 2.f * (x * z - w * y));
+  c1 = v3(2.f * (x * y - w * z), w * w - x * x + y * y - z * z, 2.f * (y * z + w * x));
+  c2 = v3(2.f * (x * z + w * y), 2.f * (y * z - w * x), w * w - x * x - y * y + z * z);
+}
+__device__ __forceinline__ V3 qrot(Q4 q, V3 v) {
+  V3 c0, c1, c2; qaxes(q, c0, c1, c2);
+  return v.x * c0 + v.y * c1 + v.z * c2;
+}
+
+// Philox4x32-10, the env's generator (pgtt.h)
+__device__ __forceinline__ void philox4x32_10(unsigned k0, unsigned k1, unsigned& c0, unsigned& c1, unsigned& c2, unsigned& c3) {
+#pragma unroll
+  for (int r = 0; r < 10; r++) {
+    const unsigned h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
+    const unsigned h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
+    const unsigned n0 = h1 ^ c1 ^ k0, n2 = h0 ^ c3 ^ k1;
+    c0 = n0; c1 = l1; c2 = n2; c3 = l0;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+}
+
+// the camera: world vector -> camera frame (x right, y up, z forward)
+struct Cam { V3 o, right, up, fwd; };
+__device__ __forceinline__ V3 to_cam(const Cam& c, V3 w) { return v3(dot(c.right, w), dot(c.up, w), dot(c.fwd, w)); }
+
+// May a ray of the frustum, out to depth far_m, touch the sphere (centre c in the camera frame, radius r)?  Conservative: the frustum lies inside
+// the cone of half angle atan(tan_c) about +z (tan_c = the corner ray's slope; sin_c, cos_c of that angle); for a centre at angle phi > the cone's
+// from the axis, |c| sin(phi - cone) = rho cos - z sin is a lower bound of its distance to the cone.  A hit deeper than far_m reads far_m like a miss.
+// The slack covers the fp32 rounding of the centre and of the test itself.
+__device__ __forceinline__ bool sphere_in_view(V3 c, float r, float sin_c, float cos_c, float far_m) {
+#ifdef PGTT_DEPTH_NOCULL
+  return true;
+#else
+  const float rho = sqrtf(c.x * c.x + c.y * c.y);
+  const float slack = 1e-3f * r + 1e-5f * (1.f + rho + fabsf(c.z));
+  return rho * cos_c - c.z * sin_c <= r + slack && c.z - r <= far_m + slack;
+#endif
+}
+
+// slab test of the ray t * (u, v, 1) against a box record (origin in the box frame, axes, half extents): t of the entry = depth along the axis
+// (a ray that starts inside the box does not see it)
+__device__ __forceinline__ float hit_box(const float* __restrict__ r, float u, float v) {
+  float tn = -INFINITY, tf = INFINITY;
+#pragma unroll
+  for (int k = 0; k < 3; k++) {
+    const float dl = r[3 + 3 * k] * u + r[4 + 3 * k] * v + r[5 + 3 * k];
+    const float inv = __builtin_amdgcn_rcpf(dl), ol = r[k], h = r[12 + k];
+    const float t1 = (-h - ol) * inv, t2 = (h - ol) * inv;
+    tn = fmaxf(tn, fminf(t1, t2));
+    tf = fminf(tf, fmaxf(t1, t2));
+  }
+  return (tn <= tf && tn > 0.f) ? tn : INFINITY;
+}
+// sphere / capsule for a ray from the origin along the UNIT direction d: t = distance along the ray
+__device__ __forceinline__ float hit_sphere(V3 oc, V3 d, float r) {
+  const float b = dot(oc, d), cc = dot(oc, oc) - r * r, disc = b * b - cc;
+  if (disc < 0.f) return INFINITY;
+  const float t = -b - sqrtf(disc);
+  return t > 0.f ? t : INFINITY;
+}
+__device__ __forceinline__ float hit_capsule(V3 d, V3 c, V3 ax, float r, float hl) {
+  const V3 pa = c - hl * ax, ba = (2.f * hl) * ax, oa = -1.f * pa;
+  const float baba = dot(ba, ba), bard = dot(ba, d), baoa = dot(ba, oa), rdoa = dot(d, oa), oaoa = dot(oa, oa);
+  const float a = baba - bard * bard, b = baba * rdoa - baoa * bard, cc = baba * oaoa - baoa * baoa - r * r * baba;
+  const float h = b * b - a * cc;
+  if (h < 0.f) return INFINITY;
+  const float t = (-b - sqrtf(h)) / a, y = baoa + t * bard;
+  if (y > 0.f && y < baba) return t > 0.f ? t : INFINITY;
+  return hit_sphere(y <= 0.f ? oa : oa - ba, d, r);
+}
+
+template <bool NOISE>
+__global__ void __launch_bounds__(kLanes) depth_kernel(DepthArgs a) {
+  __shared__ float sh_pose[PGTT_NBODY][8];                              // xpos[3], xquat[4]
+  __shared__ __attribute__((aligned(16))) float sh_box[PGTT_MAX_BOX * kBoxWords];
+  __shared__ __attribute__((aligned(16))) float sh_geom[PGTT_RENDER_MAX_GEOM * kGeomWords];
+  __shared__ int sh_nbox[kWaves], sh_ngeom;
+  const long long tick = a.counter[0];
+  if (!a.force && (unsigned long long)tick % (unsigned)a.every != 0) return;       // the same decision in every workgroup
+  const int e = blockIdx.x, tid = threadIdx.x, N = a.N;
+  const int lane = tid & 63, wave = tid >> 6;
+
+  // ---- phase A: kinematics (lanes 0..3: the base, then one leg each)
+  const bool chain = a.mount_body != 0 || a.ngeom > 0;
+  if (tid < PGTT_NLEG) {
+    auto row = [&](int r) { return a.state[(size_t)r * N + e]; };
+    const PgttModel* m = a.model;
+    V3 xp = v3(row(PGTT_S_QPOS + 0), row(PGTT_S_QPOS + 1), row(PGTT_S_QPOS + 2));
+    Q4 xq;
+    {
+      const Q4 q = {row(PGTT_S_QPOS + 3), row(PGTT_S_QPOS + 4), row(PGTT_S_QPOS + 5), row(PGTT_S_QPOS + 6)};
+      const float n = sqrtf(q.w * q.w + q.x * q.x + q.y * q.y + q.z * q.z);
+      xq = {q.w / n, q.x / n, q.y / n, q.z / n};
+    }
+    if (tid == 0) {
+      sh_pose[0][0] = xp.x; sh_pose[0][1] = xp.y; sh_pose[0][2] = xp.z;
+      sh_pose[0][3] = xq.w; sh_pose[0][4] = xq.x; sh_pose[0][5] = xq.y; sh_pose[0][6] = xq.z;
+    }
+    if (chain) {
+      for (int k = 0; k < 3; k++) {                                     // hip, thigh, calf: each the child of the one before
+        const int b = 1 + 3 * tid + k;
+        xp = xp + qrot(xq, ld3(m->body_pos[b]));
+        const Q4 quat = qmul(xq, Q4{m->body_quat[b][0], m->body_quat[b][1], m->body_quat[b][2], m->body_quat[b][3]});
+        const float q0 = a.params ? a.params[(size_t)(PGTT_P_QPOS0 + b - 1) * N + e] : m->qpos0[7 + b - 1];
+        const float ang = row(PGTT_S_QPOS + 7 + b - 1) - q0;
+        float s, c; sincosf(0.5f * ang, &s, &c);
+        xq = qmul(quat, Q4{c, m->jnt_axis[b - 1][0] * s, m->jnt_axis[b - 1][1] * s, m->jnt_axis[b - 1][2] * s});
+        sh_pose[b][0] = xp.x; sh_pose[b][1] = xp.y; sh_pose[b][2] = xp.z;
+        sh_pose[b][3] = xq.w; sh_pose[b][4] = xq.x; sh_pose[b][5] = xq.y; sh_pose[b][6] = xq.z;
+      }
+    }
+  }
+  __syncthreads();
+
+  // ---- the camera: body pose * mount pose; fwd = +x, up = +z, right = fwd x up
+  Cam cam;
+  {
+    const float* bp = sh_pose[a.mount_body];
+    const Q4 bq = {bp[3], bp[4], bp[5], bp[6]};
+    cam.o = ld3(bp) + qrot(bq, v3(a.mpos[0], a.mpos[1], a.mpos[2]));
+    V3 c1;
+    qaxes(qmul(bq, Q4{a.mquat[0], a.mquat[1], a.mquat[2], a.mquat[3]}), cam.fwd, c1, cam.up);
+    cam.right = cross(cam.fwd, cam.up);
+  }
+  const float tan_x = a.tan_y * ((float)a.W / (float)a.H);
+  const float tan_c = sqrtf(tan_x * tan_x + a.tan_y * a.tan_y);
+  const float cos_c = 1.f / sqrtf(1.f + tan_c * tan_c), sin_c = tan_c * cos_c;
+
+  // ---- boxes of the env's variant -> camera frame, culled, compacted in box order
+  int nbox = 0, ngeom = 0;
+  if (a.T > 0 || a.ngeom > 0) {                                          // the flat task without the robot: the plane alone, no list at all
+    float rec[kBoxWords];
+    bool keep = false;
+    if (a.T > 0 && tid < a.B) {
+      const int v = a.variant ? min(max(a.variant[e], 0), a.T - 1) : 0;
+      const float4* src = reinterpret_cast<const float4*>(a.boxes + ((size_t)v * a.B + tid) * kTabWords);
+      float w[kTabWords];
+#pragma unroll
+      for (int i = 0; i < kTabWords / 4; i++) { const float4 q = src[i]; w[4 * i] = q.x; w[4 * i + 1] = q.y; w[4 * i + 2] = q.z; w[4 * i + 3] = q.w; }
+      const V3 c = to_cam(cam, ld3(w) - cam.o);
+      const V3 h = ld3(w + 12);
+      keep = sphere_in_view(c, sqrtf(dot(h, h)), sin_c, cos_c, a.far_m);
+#pragma unroll
+      for (int k = 0; k < 3; k++) {
+        const V3 r = to_cam(cam, ld3(w + 3 + 3 * k));
+        rec[3 + 3 * k] = r.x; rec[4 + 3 * k] = r.y; rec[5 + 3 * k] = r.z;
+        rec[k] = -dot(r, c);                                             // the ray origin (the camera) in the box frame
+      }
+      rec[12] = h.x; rec[13] = h.y; rec[14] = h.z; rec[15] = 0.f;
+    }
+    const unsigned long long kept = __ballot(keep);
+    if (lane == 0) sh_nbox[wave] = __popcll(kept);
+
+    // ---- robot geoms (wave 0): posed, culled and compacted the same way
+    if (wave == 0 && a.ngeom > 0) {
+      float grec[kGeomWords];
+      bool gkeep = false;
+      if (tid < a.ngeom) {
+        const PgttRenderGeom G = a.geoms[tid];
+        const int b = min(max(G.body, 0), PGTT_NBODY - 1);
+        const Q4 bq = {sh_pose[b][3], sh_pose[b][4], sh_pose[b][5], sh_pose[b][6]};
+        const V3 c = to_cam(cam, ld3(sh_pose[b]) + qrot(bq, ld3(G.pos)) - cam.o);
+        V3 r[3]; qaxes(qmul(bq, Q4{G.quat[0], G.quat[1], G.quat[2], G.quat[3]}), r[0], r[1], r[2]);
+        grec[0] = c.x; grec[1] = c.y; grec[2] = c.z;
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+          const V3 rc = to_cam(cam, r[k]);
+          grec[3 + 3 * k] = rc.x; grec[4 + 3 * k] = rc.y; grec[5 + 3 * k] = rc.z;
+        }
+        grec[12] = G.size[0]; grec[13] = G.size[1]; grec[14] = G.size[2]; grec[15] = __int_as_float(G.type);
+        const float rb = G.type == PGTT_RENDER_SPHERE ? G.size[0]
+                         : (G.type == PGTT_RENDER_CAPSULE ? G.size[0] + G.size[1] : sqrtf(dot(ld3(G.size), ld3(G.size))));
+        gkeep = sphere_in_view(c, rb, sin_c, cos_c, a.far_m);
+      }
+      const unsigned long long gk = __ballot(gkeep);
+      if (lane == 0) sh_ngeom = __popcll(gk);
+      if (gkeep) {
+        float* dst = sh_geom + __popcll(gk & ((1ull << lane) - 1ull)) * kGeomWords;
+#pragma unroll
+        for (int i = 0; i < kGeomWords; i++) dst[i] = grec[i];
+      }
+    }
+    __syncthreads();
+    int first = 0;
+#pragma unroll
+    for (int w = 0; w < kWaves; w++) { first += w < wave ? sh_nbox[w] : 0; nbox += sh_nbox[w]; }
+    if (a.ngeom > 0) ngeom = sh_ngeom;
+    if (keep) {
+      float4* dst = reinterpret_cast<float4*>(sh_box + (first + __popcll(kept & ((1ull << lane) - 1ull))) * kBoxWords);
+#pragma unroll
+      for (int i = 0; i < kBoxWords / 4; i++) dst[i] = make_float4(rec[4 * i], rec[4 * i + 1], rec[4 * i + 2], rec[4 * i + 3]);
+    }
+    __syncthreads();
+  }
+
+  // ---- phase B: pixels over lanes
+  const V3 pn = v3(cam.right.z, cam.up.z, cam.fwd.z);                   // the plane's normal (world +z) in the camera frame
+  const int npix = a.W * a.H;
+  float* out = a.depth + (size_t)e * npix;
+  for (int p = tid; p < npix; p += kLanes) {
+    const int py = p / a.W, px = p - py * a.W;
+    const float u = (2.f * ((float)px + 0.5f) / (float)a.W - 1.f) * tan_x;
+    const float v = (1.f - 2.f * ((float)py + 0.5f) / (float)a.H) * a.tan_y;
+    float best = INFINITY;
+    {
+      const float den = pn.x * u + pn.y * v + pn.z;
+      if (den != 0.f) {
+        const float t = -cam.o.z / den;
+        if (t > 0.f) best = t;
+      }
+    }
+    for (int k = 0; k < nbox; k++) best = fminf(best, hit_box(sh_box + k * kBoxWords, u, v));
+    if (ngeom > 0) {
+      const float dz = 1.f / sqrtf(u * u + v * v + 1.f);
+      const V3 d = v3(u * dz, v * dz, dz);
+      for (int g = 0; g < ngeom; g++) {
+        const float* G = sh_geom + g * kGeomWords;
+        const int type = __float_as_int(G[15]);
+        const V3 c = ld3(G);
+        float t;
+        if (type == PGTT_RENDER_SPHERE) t = hit_sphere(-1.f * c, d, G[12]) * dz;
+        else if (type == PGTT_RENDER_CAPSULE) t = hit_capsule(d, c, ld3(G + 9), G[12], G[13]) * dz;
+        else {
+          float r[kBoxWords];
+#pragma unroll
+          for (int i = 3; i < 15; i++) r[i] = G[i];
+#pragma unroll
+          for (int i = 0; i < 3; i++) r[i] = -dot(ld3(G + 3 + 3 * i), c);
+          t = hit_box(r, u, v);
+        }
+        best = fminf(best, t);
+      }
+    }
+    float val = fminf(fmaxf(best, a.near_m), a.far_m);
+    if (NOISE) {
+      unsigned c0 = (unsigned)(a.env_off + e), c1 = (unsigned)tick, c2 = PGTT_RS_DEPTH, c3 = (unsigned)p;
+      philox4x32_10((unsigned)a.seed, (unsigned)(a.seed >> 32), c0, c1, c2, c3);
+      const float k24 = 1.0f / 16777216.0f;
+      const float u0 = (float)(c0 >> 8) * k24, u1 = (float)(c1 >> 8) * k24, u2 = (float)(c2 >> 8) * k24;
+      const float z = sqrtf(-2.f * logf(1.f - u1)) * cosf(6.283185307179586f * u2);
+      val = u0 < a.dropout ? a.far_m : fminf(fmaxf(val * (1.f + a.sigma * z), a.near_m), a.far_m);
+    }
+    out[p] = val;
+  }
+}
+
+__global__ void __launch_bounds__(64) depth_advance_kernel(int64_t* counter) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) counter[0] = counter[0] + 1;
+}
+
+}  // namespace
+
+struct pgtt_depth_camera {
+  int device = 0;
+  int num_envs = 0;
+  int ngeom = 0;
+  PgttDepthConfig cfg{};
+  PgttDepthBuffers buf{};
+  bool bound = false;
+  PgttModel* d_model = nullptr;
+  PgttRenderGeom* d_geoms = nullptr;
+  float* d_boxes = nullptr;      // [T][B][kTabWords]
+  int T = 0, B = 0;
+};
+
+extern "C" {
+
+const char* pgtt_depth_last_error(void) { return g_err.c_str(); }
+const char* pgtt_depth_build_info(void) { return "src=" PGTT_DEPTH_SRC ";flavor=" PGTT_DEPTH_FLAVOR; }
+int pgtt_depth_sizeof_config(void) { return (int)sizeof(PgttDepthConfig); }
+int pgtt_depth_sizeof_buffers(void) { return (int)sizeof(PgttDepthBuffers); }
+
+int pgtt_depth_create(const PgttModel* model, const PgttDepthConfig* cfg, const PgttRenderGeom* geoms, int ngeom, int device, int num_envs,
+                      pgtt_depth_handle* out) {
+  if (!model || !cfg || !out || (ngeom > 0 && !geoms)) return fail(PGTT_E_ARG, "pgtt_depth_create: null argument");
+  *out = nullptr;
+  if (num_envs < 1) return fail(PGTT_E_ARG, "pgtt_depth_create: num_envs must be >= 1");
+  if (cfg->width < 1 || cfg->width > PGTT_DEPTH_MAX_DIM || cfg->height < 1 || cfg->height > PGTT_DEPTH_MAX_DIM)
+    return fail(PGTT_E_ARG, "pgtt_depth_create: width and height must be in [1, PGTT_DEPTH_MAX_DIM]");
+  if (!(cfg->fovy_deg > 0.f) || !(cfg->fovy_deg < 180.f)) return fail(PGTT_E_ARG, "pgtt_depth_create: fovy must be in (0, 180) degrees");
+  if (!(cfg->near > 0.f) || !(cfg->near < cfg->far) || !std::isfinite(cfg->far)) return fail(PGTT_E_ARG, "pgtt_depth_create: need 0 < near < far, finite");
+  if (cfg->mount_body < 0 || cfg->mount_body >= PGTT_NBODY) return fail(PGTT_E_ARG, "pgtt_depth_create: mount_body outside [0, PGTT_NBODY)");
+  if (cfg->every < 1) return fail(PGTT_E_ARG, "pgtt_depth_create: every must be >= 1");
+  if (cfg->see_robot != 0 && cfg->see_robot != 1) return fail(PGTT_E_ARG, "pgtt_depth_create: see_robot must be 0 or 1");
+  if (!(cfg->noise_sigma >= 0.f) || !std::isfinite(cfg->noise_sigma)) return fail(PGTT_E_ARG, "pgtt_depth_create: noise_sigma must be >= 0");
+  if (!(cfg->dropout >= 0.f) || !(cfg->dropout < 1.f)) return fail(PGTT_E_ARG, "pgtt_depth_create: dropout must be in [0, 1)");
+  double qn = 0.0;
+  for (int i = 0; i < 4; i++) qn += (double)cfg->mount_quat[i] * cfg->mount_quat[i];
+  qn = std::sqrt(qn);
+  if (!(qn > 0.0) || !std::isfinite(qn)) return fail(PGTT_E_ARG, "pgtt_depth_create: mount_quat must be a non-zero quaternion");
+  for (int i = 0; i < 3; i++)
+    if (!std::isfinite(cfg->mount_pos[i])) return fail(PGTT_E_ARG, "pgtt_depth_create: mount_pos must be finite");
+  if (ngeom < 0 || ngeom > PGTT_RENDER_MAX_GEOM) return fail(PGTT_E_ARG, "pgtt_depth_create: ngeom must be in [0, PGTT_RENDER_MAX_GEOM]");
+  for (int g = 0; g < ngeom; g++) {
+    if (geoms[g].body < 0 || geoms[g].body >= PGTT_NBODY) return fail(PGTT_E_ARG, "pgtt_depth_create: geom body outside [0, PGTT_NBODY)");
+    if (geoms[g].type < PGTT_RENDER_SPHERE || geoms[g].type > PGTT_RENDER_BOX) return fail(PGTT_E_ARG, "pgtt_depth_create: unknown geom type");
+    if (!(geoms[g].size[0] > 0.f) || (geoms[g].type != PGTT_RENDER_SPHERE && !(geoms[g].size[1] > 0.f)) ||
+        (geoms[g].type == PGTT_RENDER_BOX && !(geoms[g].size[2] > 0.f)))
+      return fail(PGTT_E_ARG, "pgtt_depth_create: geom sizes must be positive");
+  }
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(PGTT_E_NODEVICE, "pgtt_depth_create: no HIP device (this library has no CPU path)");
+  if (device < 0 || device >= ndev) return fail(PGTT_E_ARG, "pgtt_depth_create: device index out of range");
+  HIP_TRY(hipSetDevice(device));
+  pgtt_depth_camera* h = new pgtt_depth_camera();
+  h->device = device; h->num_envs = num_envs; h->ngeom = ngeom; h->cfg = *cfg;
+  for (int i = 0; i < 4; i++) h->cfg.mount_quat[i] = (float)(cfg->mount_quat[i] / qn);
+  auto built = [&]() -> int {
+    HIP_TRY(hipMalloc(&h->d_model, sizeof(PgttModel)));
+    HIP_TRY(hipMalloc(&h->d_geoms, PGTT_RENDER_MAX_GEOM * sizeof(PgttRenderGeom)));
+    HIP_TRY(hipMemcpy(h->d_model, model, sizeof(PgttModel), hipMemcpyHostToDevice));
+    if (ngeom > 0) HIP_TRY(hipMemcpy(h->d_geoms, geoms, ngeom * sizeof(PgttRenderGeom), hipMemcpyHostToDevice));
+    return PGTT_OK;
+  };
+  if (int rc = built()) { pgtt_depth_destroy(h); return rc; }
+  *out = h;
+  return PGTT_OK;
+}
+
+int pgtt_depth_destroy(pgtt_depth_handle h) {
+  if (!h) return PGTT_OK;
+  hipSetDevice(h->device);
+  if (h->d_model) hipFree(h->d_model);
+  if (h->d_geoms) hipFree(h->d_geoms);
+  if (h->d_boxes) hipFree(h->d_boxes);
+  delete h;
+  return PGTT_OK;
+}
+
+int pgtt_depth_set_terrain(pgtt_depth_handle h, const float* boxes, int T, int B) {
+  if (!h) return fail(PGTT_E_ARG, "null handle");
+  if (T < 0 || B < 0 || B > PGTT_MAX_BOX) return fail(PGTT_E_ARG, "pgtt_depth_set_terrain: need 0 <= B <= PGTT_MAX_BOX, T >= 0");
+  if (T > 0 && (!boxes || B == 0)) return fail(PGTT_E_ARG, "pgtt_depth_set_terrain: null table");
+  // world-frame table: centre, the box's local axes in world coordinates (columns of the rotation of the NORMALISED quaternion, in double), half extents
+  std::vector<float> tab((size_t)T * B * kTabWords, 0.f);
+  for (size_t i = 0; i < (size_t)T * B; i++) {
+    const float* r = boxes + 10 * i;
+    float* t = tab.data() + kTabWords * i;
+    double w = r[3], x = r[4], y = r[5], z = r[6];
+    const double qn = std::sqrt(w * w + x * x + y * y + z * z);
+    if (!(qn > 0.0)) return fail(PGTT_E_ARG, "pgtt_depth_set_terrain: zero quaternion");
+    w /= qn; x /= qn; y /= qn; z /= qn;
+    const double ax[9] = {w * w + x * x - y * y - z * z, 2 * (x * y + w * z), 2 * (x * z - w * y),
+                          2 * (x * y - w * z), w * w - x * x + y * y - z * z, 2 * (y * z + w * x),
+                          2 * (x * z + w * y), 2 * (y * z - w * x), w * w - x * x - y * y + z * z};
+    t[0] = r[0]; t[1] = r[1]; t[2] = r[2];
+    for (int k = 0; k < 9; k++) t[3 + k] = (float)ax[k];
+    t[12] = r[7]; t[13] = r[8]; t[14] = r[9];
+  }
+  HIP_TRY(hipSetDevice(h->device));
+  if (h->d_boxes) { HIP_TRY(hipFree(h->d_boxes)); h->d_boxes = nullptr; }
+  h->T = 0; h->B = 0;
+  if (T == 0) return PGTT_OK;
+  HIP_TRY(hipMalloc(&h->d_boxes, tab.size() * sizeof(float)));
+  HIP_TRY(hipMemcpy(h->d_boxes, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice));
+  h->T = T; h->B = B;
+  return PGTT_OK;
+}
+
+int pgtt_depth_bind(pgtt_depth_handle h, const PgttDepthBuffers* bufs) {
+  if (!h || !bufs) return fail(PGTT_E_ARG, "pgtt_depth_bind: null argument");
+  if (!bufs->state || !bufs->depth || !bufs->counter) return fail(PGTT_E_ARG, "pgtt_depth_bind: state, depth and counter are required");
+  h->buf = *bufs;
+  h->bound = true;
+  return PGTT_OK;
+}
+
+int pgtt_depth(pgtt_depth_handle h, int force, void* stream) {
+  if (!h) return fail(PGTT_E_ARG, "pgtt_depth: null handle");
+  if (!h->bound) return fail(PGTT_E_STATE, "pgtt_depth: no buffers bound (pgtt_depth_bind first)");
+  HIP_TRY(hipSetDevice(h->device));
+  const PgttDepthConfig& c = h->cfg;
+  DepthArgs a{};
+  a.state = h->buf.state; a.params = h->buf.params; a.variant = h->buf.variant; a.depth = h->buf.depth; a.counter = h->buf.counter;
+  a.boxes = h->d_boxes; a.model = h->d_model; a.geoms = h->d_geoms;
+  a.N = h->num_envs; a.T = h->T; a.B = h->B; a.ngeom = c.see_robot ? h->ngeom : 0;
+  a.W = c.width; a.H = c.height; a.mount_body = c.mount_body; a.every = c.every; a.force = force ? 1 : 0;
+  a.tan_y = (float)std::tan(0.5 * (double)c.fovy_deg * 3.14159265358979323846 / 180.0);
+  a.near_m = c.near; a.far_m = c.far;
+  for (int i = 0; i < 3; i++) a.mpos[i] = c.mount_pos[i];
+  for (int i = 0; i < 4; i++) a.mquat[i] = c.mount_quat[i];
+  a.sigma = c.noise_sigma; a.dropout = c.dropout; a.seed = c.seed; a.env_off = c.env_id_offset;
+  hipStream_t st = (hipStream_t)stream;
+  if (c.noise_sigma > 0.f || c.dropout > 0.f) hipLaunchKernelGGL(depth_kernel<true>, dim3(h->num_envs), dim3(kLanes), 0, st, a);
+  else hipLaunchKernelGGL(depth_kernel<false>, dim3(h->num_envs), dim3(kLanes), 0, st, a);
+  hipLaunchKernelGGL(depth_advance_kernel, dim3(1), dim3(64), 0, st, h->buf.counter);
+  HIP_TRY(hipGetLastError());
+  return PGTT_OK;
+}
+
+}  // extern "C"

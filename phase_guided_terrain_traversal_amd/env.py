@@ -28,7 +28,7 @@ class Joystick:
                  autoreset: bool = False, debug_contacts: bool = False, env_id_offset: int = 0,
                  model: Optional[Dict[str, Any]] = None, layout: Optional[str] = None, observe_form: Optional[str] = None,
                  test_hooks: bool = False, interval_sums: bool = False, push: Optional[Dict[str, Any]] = None, xfrc: bool = False,
-                 curriculum: Optional[Dict[str, Any]] = None, level: Optional[torch.Tensor] = None):
+                 curriculum: Optional[Dict[str, Any]] = None, level: Optional[torch.Tensor] = None, depth: Optional[Dict[str, Any]] = None):
         """layout: "auto" | "quad" | "oct" | "hex" lane layout of physics_kernel (PgttConfig.lane_layout; results are bit-identical
         across batch sizes and shards within one layout); observe_form: "fused" | "split"; test_hooks: allow set_test_overrides
         (fixture replay only); interval_sums: keep per-env running sums of the step outputs for a logging trainer (PgttBuffers.interval_sums);
@@ -39,7 +39,12 @@ class Joystick:
         (pgtt_curriculum; needs autoreset): each finished episode moves its env up / down the levels and restarts it on a fresh variant.  With ONE
         stacked table as `terrain`, `level_start` (from curriculum.stack_levels) is required.  level / variant: the initial labels ([N] each), e.g.
         the "level" / "variant" of randomize.domain_randomize(seed=s, level_start=...); default: curriculum.initial_labels(curriculum["seed"], ...),
-        the same draws for seed = s.  None: nothing of it is allocated, bound or launched."""
+        the same draws for seed = s.  None: nothing of it is allocated, bound or launched.
+        depth: an onboard depth camera (depth.DepthCamera's arguments over depth.DEFAULTS, e.g. dict(width=64, height=48, fovy=58, near=0.1, far=3.0,
+        mount_pos=(0.30, 0.0, 0.05), pitch_deg=30, every=1, see_robot=True, noise=dict(sigma=0.0, dropout=0.0)); the mount defaults are placeholders
+        for a Go2 head camera - settings, not facts): `env.depth` is the [N, H, W] image, step() ticks the sensor after the step on the same stream,
+        reset() ticks it with force.  A side output: the observations and every other buffer are what they are without it.  None: nothing of it
+        is allocated, loaded, bound or launched."""
         self.level_start = None
         if isinstance(terrain, (list, tuple)):
             terrain, self.level_start = _curriculum.stack_levels(terrain)
@@ -137,6 +142,10 @@ class Joystick:
         if self.curriculum is not None:
             self._set_curriculum()
         self._seed = 0
+        self.depth_camera = None
+        if depth is not None:
+            from . import depth as _depth                     # libpgtt_depth.so is opened only here
+            self.depth_camera = _depth.DepthCamera(self, **_depth.settings(depth))
 
     # ---- reference-compatible properties
     @property
@@ -209,6 +218,11 @@ class Joystick:
         x[3:6, ids] = t.T if t.ndim == 2 else t[:, None]
         return x
 
+    @property
+    def depth(self) -> Optional[torch.Tensor]:
+        """[N, H, W] float32 image of the onboard depth camera (metres along the optical axis, `far` on a miss), or None without one"""
+        return None if self.depth_camera is None else self.depth_camera.image
+
     def push_step(self) -> None:
         """the push scheduler alone (pgtt_push): what step() runs first when pushes are on; for callers of physics() / observe()"""
         native.check(self._lib.pgtt_push(self._h, self._stream()))
@@ -235,10 +249,14 @@ class Joystick:
                 "mean_level": float(self.buffers["level"].float().mean())}
 
     def set_terrain(self, terrain: np.ndarray) -> None:
+        """replace the resident terrain table (the depth camera's too).  The tables are reallocated: a graph captured before this call still
+        points at the old ones and must be captured again, not replayed"""
         t = np.ascontiguousarray(terrain, dtype=np.float32)
         assert t.ndim == 3 and t.shape[2] == 10 and t.shape[1] <= abi.MAX_BOX
         native.check(self._lib.pgtt_set_terrain(self._h, t.ctypes.data, t.shape[0], t.shape[1]))
         self.terrain = t
+        if getattr(self, "depth_camera", None) is not None:
+            self.depth_camera.set_terrain(t)
 
     def _stream(self) -> int:
         return torch.cuda.current_stream(self.device).cuda_stream
@@ -253,6 +271,8 @@ class Joystick:
             mask = mask.to(self.device, torch.uint8).contiguous()
             mp = mask.data_ptr()
         native.check(self._lib.pgtt_reset(self._h, self._seed, self.env_id_offset, mp, self._stream()))
+        if self.depth_camera is not None:
+            self.depth_camera.tick(force=True)
         return self._obs()
 
     def step(self, action: torch.Tensor, curriculum: bool = True):
@@ -264,6 +284,8 @@ class Joystick:
             native.check(self._lib.pgtt_set_curriculum_deferred(self._h, int(not curriculum)))
             self._cur_deferred = not curriculum
         native.check(self._lib.pgtt_step(self._h, a.data_ptr(), self._stream()))
+        if self.depth_camera is not None:
+            self.depth_camera.tick()
         info = {"metrics": self.buffers["metrics"], "episode_metrics": self.buffers["ep_metrics"]}
         return self._obs(), self.buffers["reward"], self.buffers["done"], info
 
@@ -308,6 +330,9 @@ class Joystick:
         return p.value, o.value, k.value
 
     def close(self) -> None:
+        if getattr(self, "depth_camera", None) is not None:
+            self.depth_camera.close()
+            self.depth_camera = None
         if getattr(self, "_h", None):
             self._lib.pgtt_destroy(self._h)
             self._h = C.c_void_p()
