@@ -42,7 +42,13 @@ int pgtt_ppo_linear_backward(const float* x_KxM, const float* dy_KxN, int K, int
  * Weights are PACKED by the caller (phase_guided_terrain_traversal_amd/ppo.py::pack_linear) for the fp32 MFMA tiles: a layer [out][in] is
  * zero-padded to multiples of 16 and stored as [out / 16][in / 16][g = 0..3][i = 0..15][s = 0..3] = W[16 tile + i][16 kb + 4 g + s]
  * (pgtt_policy_packed_floats(in, out) floats), its bias zero-padded to a multiple of 16.  All pointers are device pointers (float32
- * unless said otherwise), kernels are enqueued on `stream`, nothing synchronises; 0 / negative PGTT_E_* codes as in pgtt.h. */
+ * unless said otherwise), kernels are enqueued on `stream`, nothing synchronises; 0 / negative PGTT_E_* codes as in pgtt.h.
+ *
+ * The in-kernel draw (eps == NULL): actuators 2k and 2k + 1 of env e share ONE Philox4x32-10 block, key (seed & 0xffffffff, seed >> 32),
+ * counter ((uint32)(env_id_offset + e), draw & 0xffffffff, (draw >> 32) ^ 0x50475454, k) with draw = counters[1], words w0 .. w3 (w2, w3 unused).
+ * u1 = ((float)(w0 >> 8) + 0.5f) * 2^-24 in (0, 1]: never 0; for w0 >> 8 >= 2^23 the + 0.5f is a tie that rounds to even, so u1 == 1 for
+ * w0 >> 8 == 2^24 - 1 (r = 0, both draws 0).  u2 = (float)(w1 >> 8) * 2^-24 in [0, 1): exact.
+ * r = sqrtf(-2 logf(u1)), theta = 6.28318530717958648f * u2 (one fp32 product): eps[2k] = r cosf(theta), eps[2k + 1] = r sinf(theta). */
 typedef struct PgttPolicyActArgs {
   const float* obs;            /* [N][obs_dim] the env's observation rows (PgttBuffers.obs_state) */
   const float* priv;           /* [N][priv_dim] or NULL: only copied into store_priv */
