@@ -17,15 +17,15 @@
 
 #include <cmath>
 #include <cstdint>
-#include <string>
-#include <vector>
 
 #include "../../include/pgtt_depth.h"
+#include "pgtt_raycast.hip.h"
+#include "pgtt_raycast_host.h"
 
 #ifndef PGTT_DEPTH_SRC
 #define PGTT_DEPTH_SRC "unknown"
 #endif
-// experiment build (make -f pgtt_depth.mk EXTRA=-DPGTT_DEPTH_NOCULL ...): every box and geom is kept; the figure DESIGN.md 14 compares against
+// experiment build (pgtt_raycast.mk, EXTRA=-DPGTT_DEPTH_NOCULL): every box and geom is kept; the figure DESIGN.md 14 compares against
 #ifdef PGTT_DEPTH_NOCULL
 #define PGTT_DEPTH_FLAVOR "nocull"
 #else
@@ -34,19 +34,8 @@
 
 namespace {
 
-thread_local std::string g_err;
-
-int fail(int code, const std::string& msg) { g_err = msg; return code; }
-
-#define HIP_TRY(expr)                                                                              \
-  do {                                                                                             \
-    hipError_t _e = (expr);                                                                        \
-    if (_e != hipSuccess) return fail(PGTT_E_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-  } while (0)
-
 constexpr int kLanes = 256;             // lanes per workgroup = per env
 constexpr int kWaves = kLanes / 64;
-constexpr int kTabWords = 16;           // terrain table, world frame: centre[3], local axes r0[3] r1[3] r2[3], half extents[3], pad
 constexpr int kBoxWords = 16;           // LDS box, camera frame: ray origin in the box frame[3], axes r0 r1 r2 [9], half extents[3], pad
 constexpr int kGeomWords = 16;          // LDS geom, camera frame: centre[3], axes r0 r1 r2 [9], size[3], type
 static_assert(PGTT_MAX_BOX <= kLanes && PGTT_RENDER_MAX_GEOM <= 64, "one lane per box, the geoms in one wave");
@@ -68,32 +57,6 @@ struct DepthArgs {
   unsigned long long seed;
   long long env_off;
 };
-
-struct V3 { float x, y, z; };
-__device__ __forceinline__ V3 v3(float x, float y, float z) { return {x, y, z}; }
-__device__ __forceinline__ V3 operator+(V3 a, V3 b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
-__device__ __forceinline__ V3 operator-(V3 a, V3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ V3 operator*(float s, V3 a) { return {s * a.x, s * a.y, s * a.z}; }
-__device__ __forceinline__ float dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-__device__ __forceinline__ V3 cross(V3 a, V3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
-__device__ __forceinline__ V3 ld3(const float* p) { return {p[0], p[1], p[2]}; }
-
-struct Q4 { float w, x, y, z; };
-__device__ __forceinline__ Q4 qmul(Q4 a, Q4 b) {
-  return {a.w * b.w - a.x * b.x - a.y * b.y - a.z * b.z, a.w * b.x + a.x * b.w + a.y * b.z - a.z * b.y,
-          a.w * b.y - a.x * b.z + a.y * b.w + a.z * b.x, a.w * b.z + a.x * b.y - a.y * b.x + a.z * b.w};
-}
-// columns of the rotation matrix of q: the frame's local axes in the parent's coordinates
-__device__ __forceinline__ void qaxes(Q4 q, V3& c0, V3& c1, V3& c2) {
-  const float w = q.w, x = q.x, y = q.y, z = q.z;
-  c0 = v3(w * w + x * x - y * y - z * z, 2.f * (x * y + w * z), 2.f * (x * z - w * y));
-  c1 = v3(2.f * (x * y - w * z), w * w - x * x + y * y - z * z, 2.f * (y * z + w * x));
-  c2 = v3(2.f * (x * z + w * y), 2.f * (y * z - w * x), w * w - x * x - y * y + z * z);
-}
-__device__ __forceinline__ V3 qrot(Q4 q, V3 v) {
-  V3 c0, c1, c2; qaxes(q, c0, c1, c2);
-  return v.x * c0 + v.y * c1 + v.z * c2;
-}
 
 // Philox4x32-10, the env's generator (pgtt.h)
 __device__ __forceinline__ void philox4x32_10(unsigned k0, unsigned k1, unsigned& c0, unsigned& c1, unsigned& c2, unsigned& c3) {
@@ -173,6 +136,7 @@ __global__ void __launch_bounds__(kLanes) depth_kernel(DepthArgs a) {
   if (tid < PGTT_NLEG) {
     auto row = [&](int r) { return a.state[(size_t)r * N + e]; };
     const PgttModel* m = a.model;
+    // this kernel's own statement of the chain, like the placement and the hit tests: see pgtt_raycast.hip.h
     V3 xp = v3(row(PGTT_S_QPOS + 0), row(PGTT_S_QPOS + 1), row(PGTT_S_QPOS + 2));
     Q4 xq;
     {
@@ -339,16 +303,12 @@ __global__ void __launch_bounds__(64) depth_advance_kernel(int64_t* counter) {
 }  // namespace
 
 struct pgtt_depth_camera {
-  int device = 0;
   int num_envs = 0;
   int ngeom = 0;
   PgttDepthConfig cfg{};
   PgttDepthBuffers buf{};
   bool bound = false;
-  PgttModel* d_model = nullptr;
-  PgttRenderGeom* d_geoms = nullptr;
-  float* d_boxes = nullptr;      // [T][B][kTabWords]
-  int T = 0, B = 0;
+  SceneTables scene;
 };
 
 extern "C" {
@@ -378,71 +338,26 @@ int pgtt_depth_create(const PgttModel* model, const PgttDepthConfig* cfg, const 
   if (!(qn > 0.0) || !std::isfinite(qn)) return fail(PGTT_E_ARG, "pgtt_depth_create: mount_quat must be a non-zero quaternion");
   for (int i = 0; i < 3; i++)
     if (!std::isfinite(cfg->mount_pos[i])) return fail(PGTT_E_ARG, "pgtt_depth_create: mount_pos must be finite");
-  if (ngeom < 0 || ngeom > PGTT_RENDER_MAX_GEOM) return fail(PGTT_E_ARG, "pgtt_depth_create: ngeom must be in [0, PGTT_RENDER_MAX_GEOM]");
-  for (int g = 0; g < ngeom; g++) {
-    if (geoms[g].body < 0 || geoms[g].body >= PGTT_NBODY) return fail(PGTT_E_ARG, "pgtt_depth_create: geom body outside [0, PGTT_NBODY)");
-    if (geoms[g].type < PGTT_RENDER_SPHERE || geoms[g].type > PGTT_RENDER_BOX) return fail(PGTT_E_ARG, "pgtt_depth_create: unknown geom type");
-    if (!(geoms[g].size[0] > 0.f) || (geoms[g].type != PGTT_RENDER_SPHERE && !(geoms[g].size[1] > 0.f)) ||
-        (geoms[g].type == PGTT_RENDER_BOX && !(geoms[g].size[2] > 0.f)))
-      return fail(PGTT_E_ARG, "pgtt_depth_create: geom sizes must be positive");
-  }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(PGTT_E_NODEVICE, "pgtt_depth_create: no HIP device (this library has no CPU path)");
-  if (device < 0 || device >= ndev) return fail(PGTT_E_ARG, "pgtt_depth_create: device index out of range");
-  HIP_TRY(hipSetDevice(device));
+  if (int rc = check_geoms(geoms, ngeom, "pgtt_depth_create")) return rc;
+  if (int rc = check_device(device, "pgtt_depth_create")) return rc;
   pgtt_depth_camera* h = new pgtt_depth_camera();
-  h->device = device; h->num_envs = num_envs; h->ngeom = ngeom; h->cfg = *cfg;
+  h->num_envs = num_envs; h->ngeom = ngeom; h->cfg = *cfg; h->scene.device = device;
   for (int i = 0; i < 4; i++) h->cfg.mount_quat[i] = (float)(cfg->mount_quat[i] / qn);
-  auto built = [&]() -> int {
-    HIP_TRY(hipMalloc(&h->d_model, sizeof(PgttModel)));
-    HIP_TRY(hipMalloc(&h->d_geoms, PGTT_RENDER_MAX_GEOM * sizeof(PgttRenderGeom)));
-    HIP_TRY(hipMemcpy(h->d_model, model, sizeof(PgttModel), hipMemcpyHostToDevice));
-    if (ngeom > 0) HIP_TRY(hipMemcpy(h->d_geoms, geoms, ngeom * sizeof(PgttRenderGeom), hipMemcpyHostToDevice));
-    return PGTT_OK;
-  };
-  if (int rc = built()) { pgtt_depth_destroy(h); return rc; }
+  if (int rc = h->scene.upload(model, geoms, ngeom)) { pgtt_depth_destroy(h); return rc; }
   *out = h;
   return PGTT_OK;
 }
 
 int pgtt_depth_destroy(pgtt_depth_handle h) {
   if (!h) return PGTT_OK;
-  hipSetDevice(h->device);
-  if (h->d_model) hipFree(h->d_model);
-  if (h->d_geoms) hipFree(h->d_geoms);
-  if (h->d_boxes) hipFree(h->d_boxes);
+  h->scene.release();
   delete h;
   return PGTT_OK;
 }
 
 int pgtt_depth_set_terrain(pgtt_depth_handle h, const float* boxes, int T, int B) {
   if (!h) return fail(PGTT_E_ARG, "null handle");
-  if (T < 0 || B < 0 || B > PGTT_MAX_BOX) return fail(PGTT_E_ARG, "pgtt_depth_set_terrain: need 0 <= B <= PGTT_MAX_BOX, T >= 0");
-  if (T > 0 && (!boxes || B == 0)) return fail(PGTT_E_ARG, "pgtt_depth_set_terrain: null table");
-  // world-frame table: centre, the box's local axes in world coordinates (columns of the rotation of the NORMALISED quaternion, in double), half extents
-  std::vector<float> tab((size_t)T * B * kTabWords, 0.f);
-  for (size_t i = 0; i < (size_t)T * B; i++) {
-    const float* r = boxes + 10 * i;
-    float* t = tab.data() + kTabWords * i;
-    double w = r[3], x = r[4], y = r[5], z = r[6];
-    const double qn = std::sqrt(w * w + x * x + y * y + z * z);
-    if (!(qn > 0.0)) return fail(PGTT_E_ARG, "pgtt_depth_set_terrain: zero quaternion");
-    w /= qn; x /= qn; y /= qn; z /= qn;
-    const double ax[9] = {w * w + x * x - y * y - z * z, 2 * (x * y + w * z), 2 * (x * z - w * y),
-                          2 * (x * y - w * z), w * w - x * x + y * y - z * z, 2 * (y * z + w * x),
-                          2 * (x * z + w * y), 2 * (y * z - w * x), w * w - x * x - y * y + z * z};
-    t[0] = r[0]; t[1] = r[1]; t[2] = r[2];
-    for (int k = 0; k < 9; k++) t[3 + k] = (float)ax[k];
-    t[12] = r[7]; t[13] = r[8]; t[14] = r[9];
-  }
-  HIP_TRY(hipSetDevice(h->device));
-  if (h->d_boxes) { HIP_TRY(hipFree(h->d_boxes)); h->d_boxes = nullptr; }
-  h->T = 0; h->B = 0;
-  if (T == 0) return PGTT_OK;
-  HIP_TRY(hipMalloc(&h->d_boxes, tab.size() * sizeof(float)));
-  HIP_TRY(hipMemcpy(h->d_boxes, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice));
-  h->T = T; h->B = B;
-  return PGTT_OK;
+  return h->scene.set_terrain(boxes, T, B, "pgtt_depth_set_terrain");
 }
 
 int pgtt_depth_bind(pgtt_depth_handle h, const PgttDepthBuffers* bufs) {
@@ -456,12 +371,12 @@ int pgtt_depth_bind(pgtt_depth_handle h, const PgttDepthBuffers* bufs) {
 int pgtt_depth(pgtt_depth_handle h, int force, void* stream) {
   if (!h) return fail(PGTT_E_ARG, "pgtt_depth: null handle");
   if (!h->bound) return fail(PGTT_E_STATE, "pgtt_depth: no buffers bound (pgtt_depth_bind first)");
-  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipSetDevice(h->scene.device));
   const PgttDepthConfig& c = h->cfg;
   DepthArgs a{};
   a.state = h->buf.state; a.params = h->buf.params; a.variant = h->buf.variant; a.depth = h->buf.depth; a.counter = h->buf.counter;
-  a.boxes = h->d_boxes; a.model = h->d_model; a.geoms = h->d_geoms;
-  a.N = h->num_envs; a.T = h->T; a.B = h->B; a.ngeom = c.see_robot ? h->ngeom : 0;
+  a.boxes = h->scene.d_boxes; a.model = h->scene.d_model; a.geoms = h->scene.d_geoms;
+  a.N = h->num_envs; a.T = h->scene.T; a.B = h->scene.B; a.ngeom = c.see_robot ? h->ngeom : 0;
   a.W = c.width; a.H = c.height; a.mount_body = c.mount_body; a.every = c.every; a.force = force ? 1 : 0;
   a.tan_y = (float)std::tan(0.5 * (double)c.fovy_deg * 3.14159265358979323846 / 180.0);
   a.near_m = c.near; a.far_m = c.far;

@@ -1,0 +1,46 @@
+// pgtt_raycast.hip.h — the device-side algebra that libpgtt_render.so (pgtt_render.hip) and libpgtt_depth.so (pgtt_depth.hip) share: V3 / Q4,
+// qmul, qaxes, qrot(q, v).  The host side of the same two libraries is pgtt_raycast_host.h.
+// NOT here, although both kernels state them: the forward kinematics of the body chain (the formulas of mjcf.kinematics_np), the placement of
+// a PgttRenderGeom on its body, and the sphere / capsule tests.  Moved into shared helpers with their expressions unchanged, they make the
+// compiler pair and contract the fp32 products of the kernels differently.  Measured on an MI355X against the build before: a shared chain
+// moved body poses by one ulp (6e-8) and with them 0.2 % of the renderer's and 10 % of a thigh-mounted depth camera's pixels
+// (profiles/r10_ab_raycast_chain.txt); a shared placement and shared hit tests, the depth camera calling the renderer's forms with the ray
+// origin at zero, moved 1.5 % of the pixels of a thigh-mounted camera that sees the robot by up to 7e-6 m (profiles/r10_ab_raycast_hits.txt).
+// So each kernel keeps its own statement of these, and tests/test_gpu_render.py and tests/test_gpu_depth.py hold both against fp64 references.
+// Included by those two translation units only.  It does not include pgtt_common.hip.h (whose qrot(v, q) is the physics kernels' form): that
+// file is inside the physics source hash (srchash.py), and this one is inside the two side hashes only.  For the same reason the Philox copies
+// of pgtt_depth.hip and pgtt_policy.hip stay where they are.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "../../include/pgtt_render.h"
+
+namespace {
+
+struct V3 { float x, y, z; };
+__device__ __forceinline__ V3 v3(float x, float y, float z) { return {x, y, z}; }
+__device__ __forceinline__ V3 operator+(V3 a, V3 b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
+__device__ __forceinline__ V3 operator-(V3 a, V3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
+__device__ __forceinline__ V3 operator*(float s, V3 a) { return {s * a.x, s * a.y, s * a.z}; }
+__device__ __forceinline__ float dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
+__device__ __forceinline__ V3 cross(V3 a, V3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
+__device__ __forceinline__ V3 ld3(const float* p) { return {p[0], p[1], p[2]}; }
+
+struct Q4 { float w, x, y, z; };
+__device__ __forceinline__ Q4 qmul(Q4 a, Q4 b) {
+  return {a.w * b.w - a.x * b.x - a.y * b.y - a.z * b.z, a.w * b.x + a.x * b.w + a.y * b.z - a.z * b.y,
+          a.w * b.y - a.x * b.z + a.y * b.w + a.z * b.x, a.w * b.z + a.x * b.y - a.y * b.x + a.z * b.w};
+}
+// columns of the rotation matrix of q: the frame's local axes in the parent's coordinates
+__device__ __forceinline__ void qaxes(Q4 q, V3& c0, V3& c1, V3& c2) {
+  const float w = q.w, x = q.x, y = q.y, z = q.z;
+  c0 = v3(w * w + x * x - y * y - z * z, 2.f * (x * y + w * z), 2.f * (x * z - w * y));
+  c1 = v3(2.f * (x * y - w * z), w * w - x * x + y * y - z * z, 2.f * (y * z + w * x));
+  c2 = v3(2.f * (x * z + w * y), 2.f * (y * z - w * x), w * w - x * x - y * y + z * z);
+}
+__device__ __forceinline__ V3 qrot(Q4 q, V3 v) {
+  V3 c0, c1, c2; qaxes(q, c0, c1, c2);
+  return v.x * c0 + v.y * c1 + v.z * c2;
+}
+
+}  // namespace

@@ -13,10 +13,10 @@
 #include <cmath>
 #include <cstdint>
 #include <cstring>
-#include <string>
-#include <vector>
 
 #include "../../include/pgtt_render.h"
+#include "pgtt_raycast.hip.h"
+#include "pgtt_raycast_host.h"
 
 #ifndef PGTT_RENDER_SRC
 #define PGTT_RENDER_SRC "unknown"
@@ -24,19 +24,9 @@
 
 namespace {
 
-thread_local std::string g_err;
-
-int fail(int code, const std::string& msg) { g_err = msg; return code; }
-
-#define HIP_TRY(expr)                                                                              \
-  do {                                                                                             \
-    hipError_t _e = (expr);                                                                        \
-    if (_e != hipSuccess) return fail(PGTT_E_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-  } while (0)
-
 constexpr int kTile = 16;               // pixel tile edge: 256 lanes per workgroup
 constexpr int kChunk = 64;              // views per setup launch (their cameras travel as launch arguments)
-constexpr int kBoxWords = 16;           // ray-ready box: centre[3], local axes in world coordinates r0[3] r1[3] r2[3], half extents[3], pad
+constexpr int kBoxWords = kTabWords;    // ray-ready box (pgtt_raycast_host.h): centre[3], local axes in world coordinates r0[3] r1[3] r2[3], half extents[3], pad
 constexpr int kGeomWords = 20;          // placed geom: centre[3], local axes r0 r1 r2 [9], size[3], rgb[3], type, pad
 constexpr int kHeadWords = 16;          // camera pos[3] fwd[3] right[3] up[3], tan(fovy / 2), env, variant, pad
 constexpr int kViewWords = kHeadWords + PGTT_RENDER_MAX_GEOM * kGeomWords;
@@ -48,32 +38,6 @@ struct ViewArg {
 struct SetupChunk {
   ViewArg v[kChunk];
 };
-
-struct V3 { float x, y, z; };
-__device__ __forceinline__ V3 v3(float x, float y, float z) { return {x, y, z}; }
-__device__ __forceinline__ V3 operator+(V3 a, V3 b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
-__device__ __forceinline__ V3 operator-(V3 a, V3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ V3 operator*(float s, V3 a) { return {s * a.x, s * a.y, s * a.z}; }
-__device__ __forceinline__ float dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-__device__ __forceinline__ V3 cross(V3 a, V3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
-__device__ __forceinline__ V3 ld3(const float* p) { return {p[0], p[1], p[2]}; }
-
-struct Q4 { float w, x, y, z; };
-__device__ __forceinline__ Q4 qmul(Q4 a, Q4 b) {
-  return {a.w * b.w - a.x * b.x - a.y * b.y - a.z * b.z, a.w * b.x + a.x * b.w + a.y * b.z - a.z * b.y,
-          a.w * b.y - a.x * b.z + a.y * b.w + a.z * b.x, a.w * b.z + a.x * b.y - a.y * b.x + a.z * b.w};
-}
-// columns of the rotation matrix of q: the body's local axes in world coordinates
-__device__ __forceinline__ void qaxes(Q4 q, V3& c0, V3& c1, V3& c2) {
-  const float w = q.w, x = q.x, y = q.y, z = q.z;
-  c0 = v3(w * w + x * x - y * y - z * z, 2.f * (x * y + w * z), 2.f * (x * z - w * y));
-  c1 = v3(2.f * (x * y - w * z), w * w - x * x + y * y - z * z, 2.f * (y * z + w * x));
-  c2 = v3(2.f * (x * z + w * y), 2.f * (y * z - w * x), w * w - x * x - y * y + z * z);
-}
-__device__ __forceinline__ V3 qrot(Q4 q, V3 v) {
-  V3 c0, c1, c2; qaxes(q, c0, c1, c2);
-  return v.x * c0 + v.y * c1 + v.z * c2;
-}
 
 // ---------------------------------------------------------------- setup: kinematics, camera, placed geoms
 __global__ void __launch_bounds__(64) render_setup_kernel(SetupChunk chunk, int first_view, const float* __restrict__ state, const float* __restrict__ params,
@@ -87,6 +51,7 @@ __global__ void __launch_bounds__(64) render_setup_kernel(SetupChunk chunk, int 
     const int e = chunk.v[lv].env;
     const PgttRenderCamera cam = chunk.v[lv].cam;
     auto row = [&](int r) { return state[(size_t)r * N + e]; };
+    // the body chain, serially on this lane (this kernel's own statement, like the placement and the hit tests below: see pgtt_raycast.hip.h)
     V3 xpos[PGTT_NBODY]; Q4 xq[PGTT_NBODY];
     xpos[0] = v3(row(PGTT_S_QPOS + 0), row(PGTT_S_QPOS + 1), row(PGTT_S_QPOS + 2));
     {
@@ -320,12 +285,8 @@ __global__ void __launch_bounds__(kTile * kTile) render_pixel_kernel(const float
 }  // namespace
 
 struct pgtt_renderer {
-  int device = 0;
   int ngeom = 0;
-  PgttModel* d_model = nullptr;
-  PgttRenderGeom* d_geoms = nullptr;
-  float* d_boxes = nullptr;      // [T][B][kBoxWords]
-  int T = 0, B = 0;
+  SceneTables scene;
 };
 
 extern "C" {
@@ -344,71 +305,25 @@ int64_t pgtt_render_workspace_bytes(int num_views) {
 int pgtt_render_create(const PgttModel* model, const PgttRenderGeom* geoms, int ngeom, int device, pgtt_render_handle* out) {
   if (!model || !out || (ngeom > 0 && !geoms)) return fail(PGTT_E_ARG, "pgtt_render_create: null argument");
   *out = nullptr;
-  if (ngeom < 0 || ngeom > PGTT_RENDER_MAX_GEOM) return fail(PGTT_E_ARG, "pgtt_render_create: ngeom must be in [0, PGTT_RENDER_MAX_GEOM]");
-  for (int g = 0; g < ngeom; g++) {
-    if (geoms[g].body < 0 || geoms[g].body >= PGTT_NBODY) return fail(PGTT_E_ARG, "pgtt_render_create: geom body outside [0, PGTT_NBODY)");
-    if (geoms[g].type < PGTT_RENDER_SPHERE || geoms[g].type > PGTT_RENDER_BOX) return fail(PGTT_E_ARG, "pgtt_render_create: unknown geom type");
-    if (!(geoms[g].size[0] > 0.f) || (geoms[g].type != PGTT_RENDER_SPHERE && !(geoms[g].size[1] > 0.f)) ||
-        (geoms[g].type == PGTT_RENDER_BOX && !(geoms[g].size[2] > 0.f)))
-      return fail(PGTT_E_ARG, "pgtt_render_create: geom sizes must be positive");
-  }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(PGTT_E_NODEVICE, "pgtt_render_create: no HIP device (this library has no CPU path)");
-  if (device < 0 || device >= ndev) return fail(PGTT_E_ARG, "pgtt_render_create: device index out of range");
-  HIP_TRY(hipSetDevice(device));
+  if (int rc = check_geoms(geoms, ngeom, "pgtt_render_create")) return rc;
+  if (int rc = check_device(device, "pgtt_render_create")) return rc;
   pgtt_renderer* h = new pgtt_renderer();
-  h->device = device; h->ngeom = ngeom;
-  auto built = [&]() -> int {
-    HIP_TRY(hipMalloc(&h->d_model, sizeof(PgttModel)));
-    HIP_TRY(hipMalloc(&h->d_geoms, PGTT_RENDER_MAX_GEOM * sizeof(PgttRenderGeom)));
-    HIP_TRY(hipMemcpy(h->d_model, model, sizeof(PgttModel), hipMemcpyHostToDevice));
-    if (ngeom > 0) HIP_TRY(hipMemcpy(h->d_geoms, geoms, ngeom * sizeof(PgttRenderGeom), hipMemcpyHostToDevice));
-    return PGTT_OK;
-  };
-  if (int rc = built()) { pgtt_render_destroy(h); return rc; }
+  h->ngeom = ngeom; h->scene.device = device;
+  if (int rc = h->scene.upload(model, geoms, ngeom)) { pgtt_render_destroy(h); return rc; }
   *out = h;
   return PGTT_OK;
 }
 
 int pgtt_render_destroy(pgtt_render_handle h) {
   if (!h) return PGTT_OK;
-  hipSetDevice(h->device);
-  if (h->d_model) hipFree(h->d_model);
-  if (h->d_geoms) hipFree(h->d_geoms);
-  if (h->d_boxes) hipFree(h->d_boxes);
+  h->scene.release();
   delete h;
   return PGTT_OK;
 }
 
 int pgtt_render_set_terrain(pgtt_render_handle h, const float* boxes, int T, int B) {
   if (!h) return fail(PGTT_E_ARG, "null handle");
-  if (T < 0 || B < 0 || B > PGTT_MAX_BOX) return fail(PGTT_E_ARG, "pgtt_render_set_terrain: need 0 <= B <= PGTT_MAX_BOX, T >= 0");
-  if (T > 0 && (!boxes || B == 0)) return fail(PGTT_E_ARG, "pgtt_render_set_terrain: null table");
-  HIP_TRY(hipSetDevice(h->device));
-  if (h->d_boxes) { HIP_TRY(hipFree(h->d_boxes)); h->d_boxes = nullptr; }
-  h->T = 0; h->B = 0;
-  if (T == 0) return PGTT_OK;
-  // ray-ready form: centre, the box's local axes in world coordinates (columns of the rotation of the NORMALISED quaternion, in double),
-  // half extents
-  std::vector<float> tab((size_t)T * B * kBoxWords, 0.f);
-  for (size_t i = 0; i < (size_t)T * B; i++) {
-    const float* r = boxes + 10 * i;
-    float* t = tab.data() + kBoxWords * i;
-    double w = r[3], x = r[4], y = r[5], z = r[6];
-    const double qn = std::sqrt(w * w + x * x + y * y + z * z);
-    if (!(qn > 0.0)) return fail(PGTT_E_ARG, "pgtt_render_set_terrain: zero quaternion");
-    w /= qn; x /= qn; y /= qn; z /= qn;
-    const double ax[9] = {w * w + x * x - y * y - z * z, 2 * (x * y + w * z), 2 * (x * z - w * y),
-                          2 * (x * y - w * z), w * w - x * x + y * y - z * z, 2 * (y * z + w * x),
-                          2 * (x * z + w * y), 2 * (y * z - w * x), w * w - x * x - y * y + z * z};
-    t[0] = r[0]; t[1] = r[1]; t[2] = r[2];
-    for (int k = 0; k < 9; k++) t[3 + k] = (float)ax[k];
-    t[12] = r[7]; t[13] = r[8]; t[14] = r[9];
-  }
-  HIP_TRY(hipMalloc(&h->d_boxes, tab.size() * sizeof(float)));
-  HIP_TRY(hipMemcpy(h->d_boxes, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice));
-  h->T = T; h->B = B;
-  return PGTT_OK;
+  return h->scene.set_terrain(boxes, T, B, "pgtt_render_set_terrain");
 }
 
 int pgtt_render(pgtt_render_handle h, const PgttRenderViews* v, void* stream) {
@@ -430,7 +345,7 @@ int pgtt_render(pgtt_render_handle h, const PgttRenderViews* v, void* stream) {
     if (!std::isfinite(c.azimuth_deg) || !std::isfinite(c.elevation_deg) || !std::isfinite(c.target[0]) || !std::isfinite(c.target[1]) || !std::isfinite(c.target[2]))
       return fail(PGTT_E_ARG, "pgtt_render: camera angles and target must be finite");
   }
-  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipSetDevice(h->scene.device));
   hipStream_t st = (hipStream_t)stream;
   float* ws = (float*)v->workspace;
   for (int first = 0; first < v->num_views; first += kChunk) {
@@ -438,11 +353,11 @@ int pgtt_render(pgtt_render_handle h, const PgttRenderViews* v, void* stream) {
     SetupChunk chunk;
     std::memset(&chunk, 0, sizeof(chunk));
     for (int i = 0; i < nv; i++) { chunk.v[i].env = v->env_ids[first + i]; chunk.v[i].cam = v->cameras[first + i]; }
-    hipLaunchKernelGGL(render_setup_kernel, dim3(nv), dim3(64), 0, st, chunk, first, v->state, v->params, v->variant, v->num_envs, h->T,
-                       h->d_model, h->d_geoms, h->ngeom, ws, v->body_pose);
+    hipLaunchKernelGGL(render_setup_kernel, dim3(nv), dim3(64), 0, st, chunk, first, v->state, v->params, v->variant, v->num_envs, h->scene.T,
+                       h->scene.d_model, h->scene.d_geoms, h->ngeom, ws, v->body_pose);
   }
   const int tiles_x = (v->width + kTile - 1) / kTile, tiles_y = (v->height + kTile - 1) / kTile;
-  hipLaunchKernelGGL(render_pixel_kernel, dim3(tiles_x * tiles_y, v->num_views), dim3(kTile * kTile), 0, st, ws, h->d_boxes, h->B, v->markers,
+  hipLaunchKernelGGL(render_pixel_kernel, dim3(tiles_x * tiles_y, v->num_views), dim3(kTile * kTile), 0, st, ws, h->scene.d_boxes, h->scene.B, v->markers,
                      v->num_markers, h->ngeom, v->width, v->height, tiles_x, (v->flags & PGTT_RENDER_SHADOWS) ? 1 : 0, v->rgba, v->depth,
                      v->segmentation);
   HIP_TRY(hipGetLastError());

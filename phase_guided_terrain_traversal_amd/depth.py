@@ -17,7 +17,7 @@ from typing import Dict, Optional, Sequence
 
 import numpy as np
 
-from . import abi
+from . import _sidelib, abi
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libpgtt_depth.so")
@@ -63,37 +63,30 @@ class DepthError(RuntimeError):
 
 
 def lib() -> C.CDLL:
+    """libpgtt_depth.so at LIB_PATH, as it is when the library is first asked for"""
     global _LIB
     if _LIB is None:
-        if not os.path.exists(LIB_PATH):
-            raise DepthError(f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-                             "(hipcc --offload-arch=gfx950); there is no CPU fallback")
-        # torch's own HIP runtime first, as native.lib() does for libpgtt.so
-        import torch  # noqa: F401
         from .render import PgttRenderGeom
-        L = C.CDLL(LIB_PATH)
-        L.pgtt_depth_last_error.restype = C.c_char_p
-        L.pgtt_depth_build_info.restype = C.c_char_p
-        L.pgtt_depth_create.argtypes = [C.POINTER(abi.PgttModel), C.POINTER(PgttDepthConfig), C.POINTER(PgttRenderGeom), C.c_int, C.c_int, C.c_int,
-                                        C.POINTER(C.c_void_p)]
-        L.pgtt_depth_destroy.argtypes = [C.c_void_p]
-        L.pgtt_depth_set_terrain.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
-        L.pgtt_depth_bind.argtypes = [C.c_void_p, C.POINTER(PgttDepthBuffers)]
-        L.pgtt_depth.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-        assert L.pgtt_depth_sizeof_config() == C.sizeof(PgttDepthConfig)
-        assert L.pgtt_depth_sizeof_buffers() == C.sizeof(PgttDepthBuffers)
-        _LIB = L
+        vp = C.c_void_p
+        _LIB = _sidelib.load(LIB_PATH, DepthError, {
+            "pgtt_depth_last_error": (C.c_char_p, None), "pgtt_depth_build_info": (C.c_char_p, None),
+            "pgtt_depth_create": (None, [C.POINTER(abi.PgttModel), C.POINTER(PgttDepthConfig), C.POINTER(PgttRenderGeom), C.c_int, C.c_int, C.c_int,
+                                         C.POINTER(vp)]),
+            "pgtt_depth_destroy": (None, [vp]), "pgtt_depth_set_terrain": (None, [vp, vp, C.c_int, C.c_int]),
+            "pgtt_depth_bind": (None, [vp, C.POINTER(PgttDepthBuffers)]), "pgtt_depth": (None, [vp, C.c_int, vp]),
+        }, {"pgtt_depth_sizeof_config": PgttDepthConfig, "pgtt_depth_sizeof_buffers": PgttDepthBuffers})
     return _LIB
 
 
 def check(rc: int) -> None:
-    if rc != 0:
-        raise DepthError(f"libpgtt_depth error {rc}: {lib().pgtt_depth_last_error().decode()}")
+    _sidelib.check(rc, lib(), "pgtt_depth", DepthError)
 
 
 def build_info() -> dict:
-    """{"src": <SHA-256 of pgtt_depth.hip + pgtt_depth.h at build time>, "flavor": "product"}"""
-    return dict(kv.split("=", 1) for kv in lib().pgtt_depth_build_info().decode().split(";"))
+    """{"src": srchash.side_sha256("depth") at build time - SHA-256 over everything the library is built from, pgtt_depth.hip and the files
+    it includes (pgtt_raycast.hip.h, pgtt_raycast_host.h, pgtt_depth.h, pgtt_render.h, pgtt.h), comments and white space removed -,
+    "flavor": "product" or "nocull"}"""
+    return _sidelib.build_info(lib(), "pgtt_depth")
 
 
 def pitch_quat(pitch_deg: float) -> np.ndarray:
@@ -113,7 +106,7 @@ def config_struct(width, height, fovy, near, far, mount_body=0, mount_pos=(0.0, 
     return c
 
 
-class DepthCamera:
+class DepthCamera(_sidelib.Handle):
     """A depth camera rigidly mounted on body `mount_body` (0 = the torso) of every env of a Joystick, pose (mount_pos, mount_quat wxyz) in that
     body's frame: optical axis = the mount frame's +x, up = its +z.  `pitch_deg` instead of mount_quat pitches the camera down by that angle.
     every: the sensor period in ticks; see_robot: the robot's own primitives (`geoms`, default render.default_robot_geoms(model)) are in the
@@ -121,6 +114,7 @@ class DepthCamera:
     (seed, env.env_id_offset + env, tick counter, pixel) as the env's own streams are.
     The defaults of Joystick(depth=...) (depth.DEFAULTS) are placeholders for a Go2 head camera: settings, not facts.
     Runs on the env's device and current stream; writes nothing but `image` and `counter`."""
+    _prefix, _check = "pgtt_depth", staticmethod(check)
 
     def __init__(self, env, width: int, height: int, fovy: float, near: float, far: float, mount_body: int = 0,
                  mount_pos: Sequence[float] = (0.0, 0.0, 0.0), mount_quat: Optional[Sequence[float]] = None, pitch_deg: Optional[float] = None,
@@ -148,34 +142,13 @@ class DepthCamera:
 
     def bind(self) -> None:
         """(re)bind the env's buffers (after the env replaced one of state / params / variant)"""
-        b, env = PgttDepthBuffers(), self.env
-        b.state = env.buffers["state"].data_ptr()
-        b.params = env.buffers["params"].data_ptr() if "params" in env.buffers else None
-        b.variant = env.buffers["variant"].data_ptr() if "variant" in env.buffers else None
+        b = PgttDepthBuffers()
+        b.state, b.params, b.variant = _sidelib.env_pointers(self.env)
         b.depth, b.counter = self.image.data_ptr(), self.counter.data_ptr()
         check(self._lib.pgtt_depth_bind(self._h, C.byref(b)))
-
-    def set_terrain(self, terrain) -> None:
-        if terrain is None:
-            check(self._lib.pgtt_depth_set_terrain(self._h, None, 0, 0))
-            return
-        t = np.ascontiguousarray(terrain, dtype=np.float32)
-        assert t.ndim == 3 and t.shape[2] == 10 and t.shape[1] <= abi.MAX_BOX
-        check(self._lib.pgtt_depth_set_terrain(self._h, t.ctypes.data, t.shape[0], t.shape[1]))
 
     def tick(self, force: bool = False):
         """one sensor tick: the image is recomputed when `force` or the counter is 0 modulo `every` (decided on the device), the counter advances"""
         import torch
         check(self._lib.pgtt_depth(self._h, int(bool(force)), torch.cuda.current_stream(self.env.device).cuda_stream))
         return self.image
-
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            self._lib.pgtt_depth_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

@@ -19,7 +19,7 @@ from typing import Dict, List, Optional, Sequence, Union
 
 import numpy as np
 
-from . import abi
+from . import _sidelib, abi
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libpgtt_render.so")
@@ -61,37 +61,27 @@ class RenderError(RuntimeError):
 
 
 def lib() -> C.CDLL:
+    """libpgtt_render.so at LIB_PATH, as it is when the library is first asked for"""
     global _LIB
     if _LIB is None:
-        if not os.path.exists(LIB_PATH):
-            raise RenderError(f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-                              "(hipcc --offload-arch=gfx950); there is no CPU fallback")
-        # torch's own HIP runtime first, as native.lib() does for libpgtt.so
-        import torch  # noqa: F401
-        L = C.CDLL(LIB_PATH)
-        L.pgtt_render_last_error.restype = C.c_char_p
-        L.pgtt_render_build_info.restype = C.c_char_p
-        L.pgtt_render_create.argtypes = [C.POINTER(abi.PgttModel), C.POINTER(PgttRenderGeom), C.c_int, C.c_int, C.POINTER(C.c_void_p)]
-        L.pgtt_render_destroy.argtypes = [C.c_void_p]
-        L.pgtt_render_set_terrain.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
-        L.pgtt_render_workspace_bytes.argtypes = [C.c_int]
-        L.pgtt_render_workspace_bytes.restype = C.c_int64
-        L.pgtt_render.argtypes = [C.c_void_p, C.POINTER(PgttRenderViews), C.c_void_p]
-        assert L.pgtt_render_sizeof_geom() == C.sizeof(PgttRenderGeom)
-        assert L.pgtt_render_sizeof_camera() == C.sizeof(PgttRenderCamera)
-        assert L.pgtt_render_sizeof_views() == C.sizeof(PgttRenderViews)
-        _LIB = L
+        vp = C.c_void_p
+        _LIB = _sidelib.load(LIB_PATH, RenderError, {
+            "pgtt_render_last_error": (C.c_char_p, None), "pgtt_render_build_info": (C.c_char_p, None),
+            "pgtt_render_create": (None, [C.POINTER(abi.PgttModel), C.POINTER(PgttRenderGeom), C.c_int, C.c_int, C.POINTER(vp)]),
+            "pgtt_render_destroy": (None, [vp]), "pgtt_render_set_terrain": (None, [vp, vp, C.c_int, C.c_int]),
+            "pgtt_render_workspace_bytes": (C.c_int64, [C.c_int]), "pgtt_render": (None, [vp, C.POINTER(PgttRenderViews), vp]),
+        }, {"pgtt_render_sizeof_geom": PgttRenderGeom, "pgtt_render_sizeof_camera": PgttRenderCamera, "pgtt_render_sizeof_views": PgttRenderViews})
     return _LIB
 
 
 def check(rc: int) -> None:
-    if rc != 0:
-        raise RenderError(f"libpgtt_render error {rc}: {lib().pgtt_render_last_error().decode()}")
+    _sidelib.check(rc, lib(), "pgtt_render", RenderError)
 
 
 def build_info() -> dict:
-    """{"src": <SHA-256 of pgtt_render.hip + pgtt_render.h at build time>, "flavor": "product"}"""
-    return dict(kv.split("=", 1) for kv in lib().pgtt_render_build_info().decode().split(";"))
+    """{"src": srchash.side_sha256("render") at build time - SHA-256 over everything the library is built from, pgtt_render.hip and the files
+    it includes (pgtt_raycast.hip.h, pgtt_raycast_host.h, pgtt_render.h, pgtt.h), comments and white space removed -, "flavor": "product"}"""
+    return _sidelib.build_info(lib(), "pgtt_render")
 
 
 # ---------------------------------------------------------------- robot primitives
@@ -240,9 +230,10 @@ def scan_points(env, env_ids=None):
 
 
 # ---------------------------------------------------------------- renderer
-class Renderer:
+class Renderer(_sidelib.Handle):
     """Renders views of a Joystick's envs (state, params, variant and terrain table taken from the env) on the env's device and current
     stream.  Never writes an env buffer."""
+    _prefix, _check = "pgtt_render", staticmethod(check)
 
     def __init__(self, env, width: int, height: int, shadows: bool = True, geoms: Optional[Sequence[Dict]] = None):
         import torch
@@ -255,14 +246,6 @@ class Renderer:
         check(self._lib.pgtt_render_create(C.byref(self._ms), ga, len(self.geoms), env.device.index or 0, C.byref(self._h)))
         self.set_terrain(env.terrain)
         self._ws: Dict[int, "torch.Tensor"] = {}
-
-    def set_terrain(self, terrain) -> None:
-        if terrain is None:
-            check(self._lib.pgtt_render_set_terrain(self._h, None, 0, 0))
-            return
-        t = np.ascontiguousarray(terrain, dtype=np.float32)
-        assert t.ndim == 3 and t.shape[2] == 10 and t.shape[1] <= abi.MAX_BOX
-        check(self._lib.pgtt_render_set_terrain(self._h, t.ctypes.data, t.shape[0], t.shape[1]))
 
     def _workspace(self, nv: int):
         import torch
@@ -296,9 +279,7 @@ class Renderer:
         if body_pose and "body_pose" not in out:
             out["body_pose"] = torch.empty((V, abi.NBODY, 7), dtype=torch.float32, device=dev)
         v = PgttRenderViews()
-        v.state = env.buffers["state"].data_ptr()
-        v.params = env.buffers["params"].data_ptr() if "params" in env.buffers else None
-        v.variant = env.buffers["variant"].data_ptr() if "variant" in env.buffers else None
+        v.state, v.params, v.variant = _sidelib.env_pointers(env)
         v.num_envs, v.num_views = env.num_envs, V
         id_arr = (i32 * max(1, V))(*ids)
         cam_arr = (PgttRenderCamera * max(1, V))(*[c.struct() for c in cams])
@@ -317,17 +298,6 @@ class Renderer:
         check(self._lib.pgtt_render(self._h, C.byref(v), torch.cuda.current_stream(dev).cuda_stream))
         out["rgb"] = out["rgba"][..., :3]
         return out
-
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            self._lib.pgtt_render_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 # ---------------------------------------------------------------- writers

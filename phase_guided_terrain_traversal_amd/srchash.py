@@ -2,7 +2,10 @@
 it): the include closure of the translation unit csrc/pgtt_physics_inst.hip - itself, the two physics headers, the common header, include/pgtt.h -
 and csrc/flags.mk, the make fragment that holds the compile flags of that unit.  Comments and white space are removed (a comment edit does not
 change the kernel).  The task-side kernels, the host code and the other rules of the Makefile are not covered: a change there leaves the hash,
-and with it the counters recorded under profiles/, valid.  EXTRA flags and the 1-ulp division are what the build's flavor says."""
+and with it the counters recorded under profiles/, valid.  EXTRA flags and the 1-ulp division are what the build's flavor says.
+
+The two side libraries (csrc/pgtt_raycast.mk) embed a hash of their own, side_sha256("render" | "depth"): the include closure of their one
+translation unit (SIDE_SOURCES), normalised the same way.  `python3 srchash.py` prints the physics hash, `python3 srchash.py render` a side hash."""
 import hashlib
 import os
 import re
@@ -10,6 +13,10 @@ import re
 _HERE = os.path.dirname(os.path.abspath(__file__))
 PHYSICS_SOURCES = ("pgtt_physics_inst.hip", "pgtt_physics.hip.h", "pgtt_physics_quad.hip.h", "pgtt_common.hip.h")
 FLAGS_FRAGMENT = "flags.mk"
+# per side library: the unit and the shared headers in csrc/, then the public headers in include/ (every project file the unit includes)
+_RAYCAST = ("pgtt_raycast.hip.h", "pgtt_raycast_host.h")
+SIDE_SOURCES = {"render": (("pgtt_render.hip",) + _RAYCAST, ("pgtt_render.h", "pgtt.h")),
+                "depth": (("pgtt_depth.hip",) + _RAYCAST, ("pgtt_depth.h", "pgtt_render.h", "pgtt.h"))}
 
 
 def hashed_files(pkg: str = _HERE):
@@ -17,9 +24,23 @@ def hashed_files(pkg: str = _HERE):
     return sorted([os.path.join(pkg, "csrc", f) for f in PHYSICS_SOURCES + (FLAGS_FRAGMENT,)] + [os.path.join(os.path.dirname(pkg), "include", "pgtt.h")])
 
 
+def side_files(name: str, pkg: str = _HERE):
+    """the files side_sha256(name) covers"""
+    csrc, include = SIDE_SOURCES[name]
+    return sorted([os.path.join(pkg, "csrc", f) for f in csrc] + [os.path.join(os.path.dirname(pkg), "include", f) for f in include])
+
+
 def source_sha256(pkg: str = _HERE) -> str:
+    return _sha256(hashed_files(pkg))
+
+
+def side_sha256(name: str, pkg: str = _HERE) -> str:
+    return _sha256(side_files(name, pkg))
+
+
+def _sha256(files) -> str:
     h = hashlib.sha256()
-    for f in hashed_files(pkg):
+    for f in files:
         with open(f, "r") as fh:
             text = fh.read()
         if f.endswith(".mk"):
@@ -32,4 +53,5 @@ def source_sha256(pkg: str = _HERE) -> str:
 
 
 if __name__ == "__main__":
-    print(source_sha256())
+    import sys
+    print(side_sha256(sys.argv[1]) if len(sys.argv) > 1 else source_sha256())

@@ -204,3 +204,92 @@ def test_source_hash_files_are_the_include_closure_of_the_physics_translation_un
     deps = {os.path.realpath(os.path.join(csrc, t)) for t in mm.replace("\\\n", " ").split()[1:]}
     local = {d for d in deps if d.startswith(os.path.realpath(ROOT) + os.sep)}
     assert local | {os.path.realpath(os.path.join(csrc, "flags.mk"))} == hashed
+
+
+# ---------------------------------------------------------------- the two ray-casting side libraries (csrc/pgtt_raycast.mk)
+SIDE = ("render", "depth")
+
+
+def _side_module(name):
+    from phase_guided_terrain_traversal_amd import depth, render
+    return {"render": render, "depth": depth}[name]
+
+
+@pytest.mark.parametrize("name", SIDE)
+def test_side_hash_matches_the_built_library(name):
+    """pgtt_<name>_build_info() carries srchash.side_sha256(name) of the sources as they are now"""
+    from phase_guided_terrain_traversal_amd import srchash
+    mod = _side_module(name)
+    if not os.path.exists(mod.LIB_PATH):
+        pytest.skip(f"libpgtt_{name}.so not built (run __graft_entry__.build())")
+    assert mod.build_info()["src"] == srchash.side_sha256(name)
+
+
+@pytest.mark.parametrize("name", SIDE)
+def test_side_hash_files_are_the_include_closure_of_the_unit(name):
+    """SIDE_SOURCES[name] is exactly the set of project files csrc/pgtt_<name>.hip includes, transitively (quoted includes, followed by hand)"""
+    from phase_guided_terrain_traversal_amd import srchash
+    csrc = os.path.join(ROOT, "phase_guided_terrain_traversal_amd", "csrc")
+    seen, todo = set(), [os.path.join(csrc, f"pgtt_{name}.hip")]
+    while todo:
+        f = os.path.realpath(todo.pop())
+        if f in seen:
+            continue
+        seen.add(f)
+        for inc in re.findall(r'^\s*#\s*include\s+"([^"]+)"', open(f).read(), re.M):
+            todo.append(os.path.join(os.path.dirname(f), inc))
+    assert all(f.startswith(os.path.realpath(ROOT) + os.sep) for f in seen)
+    assert seen == {os.path.realpath(f) for f in srchash.side_files(name)}
+    in_csrc, in_include = srchash.SIDE_SOURCES[name]
+    assert {os.path.basename(f) for f in seen} == set(in_csrc) | set(in_include)
+    assert "pgtt_common.hip.h" not in in_csrc                  # the physics hash and the side hashes share include/pgtt.h only
+
+
+def test_side_hashes_react_to_the_right_edits(tmp_path):
+    """on a copied tree: a statement in the shared core moves both side hashes and not the physics hash, a comment moves nothing, an edit of
+    pgtt_depth.hip moves the depth hash alone"""
+    import shutil
+    from phase_guided_terrain_traversal_amd import srchash
+    csrc = os.path.join(ROOT, "phase_guided_terrain_traversal_amd", "csrc")
+    cp = tmp_path / "phase_guided_terrain_traversal_amd"
+    (cp / "csrc").mkdir(parents=True)
+    (tmp_path / "include").mkdir()
+    for f in os.listdir(csrc):
+        if f.endswith((".hip", ".h", ".mk")) or f == "Makefile":
+            shutil.copy(os.path.join(csrc, f), cp / "csrc" / f)
+    for f in os.listdir(os.path.join(ROOT, "include")):
+        shutil.copy(os.path.join(ROOT, "include", f), tmp_path / "include" / f)
+
+    def hashes():
+        return srchash.side_sha256("render", str(cp)), srchash.side_sha256("depth", str(cp)), srchash.source_sha256(str(cp))
+    r0, d0, p0 = hashes()
+    assert (r0, d0, p0) == (srchash.side_sha256("render"), srchash.side_sha256("depth"), srchash.source_sha256()) and len({r0, d0, p0}) == 3
+
+    def appended(name, text):
+        p = cp / "csrc" / name
+        old = p.read_text()
+        p.write_text(old + text)
+        h = hashes()
+        p.write_text(old)
+        return h
+    for core in ("pgtt_raycast.hip.h", "pgtt_raycast_host.h"):
+        r, d, p = appended(core, "\nint pgtt_extra_statement;\n")
+        assert r != r0 and d != d0 and p == p0, core
+        assert appended(core, "\n// a comment\n") == (r0, d0, p0), core
+    r, d, p = appended("pgtt_depth.hip", "\nint pgtt_extra_statement;\n")
+    assert r == r0 and d != d0 and p == p0
+    r, d, p = appended("pgtt_render.hip", "\nint pgtt_extra_statement;\n")
+    assert r != r0 and d == d0 and p == p0
+    r, d, p = appended("pgtt_common.hip.h", "\nint pgtt_extra_statement;\n")            # the physics kernels' header is no part of either side library
+    assert r == r0 and d == d0 and p != p0
+
+
+def test_side_libraries_raise_their_own_error_class():
+    from phase_guided_terrain_traversal_amd import depth, render
+    for mod, err, libname in ((render, render.RenderError, "libpgtt_render"), (depth, depth.DepthError, "libpgtt_depth")):
+        if not os.path.exists(mod.LIB_PATH):
+            pytest.skip(f"{libname}.so not built (run __graft_entry__.build())")
+        mod.check(0)
+        with pytest.raises(err, match=libname + " error 1"):
+            mod.check(1)
+    assert not issubclass(render.RenderError, depth.DepthError) and not issubclass(depth.DepthError, render.RenderError)
