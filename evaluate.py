@@ -10,7 +10,8 @@ one episode of `episode_length` control steps under the DETERMINISTIC policy (th
 env's FIRST episode [UPSTREAM-RECALL: brax.training.acting.Evaluator + envs.training.EvalWrapper] - and returns the number of envs whose
 final `termination` reward term is zero (:221-223), i.e. the robots that did not fall.  Here the same rollout runs directly: no learner
 is built.  The policy comes from `--checkpoint_folder` (the newest `<env_steps>.pt` of `train.py`, or its `policy<index>.npz`) or from
-`--policy` (an .npz path or the name of a shipped policy); the remaining flags of the reference's CLI are accepted and ignored.
+`--policy` (an .npz path or the name of a shipped policy); with `--student student.npz` (train_student.py) the policy acts on the observation
+whose scan rows the student perception module estimated from the onboard depth image; the remaining flags of the reference's CLI are accepted and ignored.
 """
 import argparse
 import os
@@ -138,7 +139,12 @@ def run_evaluation(args, num_eval_envs=NUM_EVAL_ENVS, seed=0, verbose=True):
     push = configs.push_from_args(args)                           # --push_*: random kicks of the torso (off unless one is given)
     if push is not None:
         kw["push"] = push
+    if getattr(args, "student", None):
+        # --student: the policy acts on env.student_obs - the observation whose scan rows a perceive.ScanEstimator estimated from the onboard
+        # depth image (the camera of depth.DEFAULTS) - instead of the privileged scan
+        kw.update(depth={}, student=args.student)
     env = Joystick(args.task_name, cfg, num_envs=n, terrain=terrain, device=DEVICE, autoreset=True, **kw)
+    acts_on = env.buffers["obs_state"] if env.student is None else env.student_obs
     tmp = os.path.join(ROOT, "plots"); os.makedirs(tmp, exist_ok=True)
     pi = load_policy_from_args(args, tmp)
     if pi.mean.shape[0] != env.observation_size["state"]:
@@ -153,7 +159,7 @@ def run_evaluation(args, num_eval_envs=NUM_EVAL_ENVS, seed=0, verbose=True):
     for t in range(L):
         if video is not None:
             video.capture(t)
-        _, reward, done, info = env.step(pi(env.buffers["obs_state"]))
+        _, reward, done, info = env.step(pi(acts_on))
         w = first.float()
         ret += reward * w; length += w; terms += info["metrics"] * w
         d = done > 0
@@ -199,6 +205,7 @@ def make_parser():
     ap.add_argument("--video_every", type=int, default=2, help="one frame every n control steps")
     ap.add_argument("--video_scan", action="store_true", help="overlay the 117 height-scan hits as marker spheres")
     ap.add_argument("--video_depth", action="store_true", help="tile each video env's onboard depth image (grey, near = white) under its RGB tile")
+    ap.add_argument("--student", type=str, default=None, help="a student.npz of train_student.py: the policy acts on the depth camera's estimate of the scan rows")
     configs.add_push_args(ap)
     ap.add_argument("--terrain_files", type=str, default=None, help="comma-separated level files stacked into one table (as train.py --terrain_files); evaluated on --level")
     ap.add_argument("--level", type=int, default=0, help="with --terrain_files: the level every evaluation env stands on (no curriculum at evaluation)")

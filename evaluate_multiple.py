@@ -19,9 +19,11 @@ import evaluate
 HERE = os.path.dirname(os.path.abspath(__file__))
 
 
-def survivors_per_level(method, policy, levels):
-    """[number of the 1000 evaluation envs that did not fall, for every terrain file]"""
+def survivors_per_level(method, policy, levels, student=None):
+    """[number of the 1000 evaluation envs that did not fall, for every terrain file]; student: a student.npz, the policy then acts on its estimate"""
     source = ["--checkpoint_folder", policy] if os.path.isdir(policy) else ["--policy", policy]
+    if student:
+        source += ["--student", student]
     counts = []
     for level in levels:
         args = evaluate.make_parser().parse_args(["--method", method, "--task_name", "stairs", "--terrain_file", level] + source)
@@ -37,8 +39,11 @@ if __name__ == "__main__":
     ap.add_argument("--pgtt", default="policy177")
     ap.add_argument("--baseline", default="policy175")
     ap.add_argument("--levels", nargs="*", default=["level4", "level7", "level10", "level13"])
+    ap.add_argument("--student", default=None, help="a student.npz of train_student.py for the pgtt policy (evaluate.py --student)")
+    ap.add_argument("--baseline_student", default=None, help="the same for the baseline policy (its observation has 162 rows)")
     opt = ap.parse_args()
-    table = {"pgtt": survivors_per_level("pgtt", opt.pgtt, opt.levels), "baseline": survivors_per_level("baseline", opt.baseline, opt.levels)}
+    table = {"pgtt": survivors_per_level("pgtt", opt.pgtt, opt.levels, opt.student),
+             "baseline": survivors_per_level("baseline", opt.baseline, opt.levels, opt.baseline_student)}
     out = os.path.join(HERE, "plots")
     os.makedirs(out, exist_ok=True)
     for name, counts in table.items():

@@ -1,6 +1,6 @@
-"""What render.py (libpgtt_render.so) and depth.py (libpgtt_depth.so) share: loading a side library through ctypes, turning its return codes
-into the module's exception, parsing its build info, the terrain / close methods of a handle's owner, and the three env pointers both read.
-Imported by those two modules only: env.py does not reach it unless a depth camera is asked for."""
+"""What render.py (libpgtt_render.so), depth.py (libpgtt_depth.so) and perceive.py (libpgtt_perceive.so) share: loading a side library through
+ctypes, turning its return codes into the module's exception, parsing its build info, the terrain / close methods of a handle's owner, and the three
+env pointers the two ray casters read.  Imported by those modules only: env.py does not reach it unless a depth camera or a student is asked for."""
 from __future__ import annotations
 
 import ctypes as C

@@ -63,7 +63,10 @@ def pack_linear(w: torch.Tensor, b: torch.Tensor) -> Tuple[torch.Tensor, torch.T
 class FusedActor:
     """Roll-out storage + the two acting kernels for one `Joystick` (autoreset=True)."""
 
-    def __init__(self, env, T: int, seed: int = 0, reward_scaling: float = 1.0, episode_sums: Optional[torch.Tensor] = None):
+    def __init__(self, env, T: int, seed: int = 0, reward_scaling: float = 1.0, episode_sums: Optional[torch.Tensor] = None,
+                 obs: Optional[torch.Tensor] = None):
+        """obs: the [N, obs_dim] tensor the policy reads instead of env.buffers["obs_state"] (e.g. env.student_obs); the storage's "obs" rows record
+        what the policy saw"""
         if env.device.type != "cuda":
             raise native.PgttError("FusedActor needs a Joystick on a ROCm device; there is no CPU path")
         self.env, self.T = env, int(T)
@@ -84,7 +87,10 @@ class FusedActor:
         self._b = [z(-(-dims[l + 1] // 16) * 16) for l in range(4)]
         self._dims = dims
         a = PgttPolicyActArgs()
-        a.obs, a.priv = env.buffers["obs_state"].data_ptr(), env.buffers["obs_priv"].data_ptr()
+        self.obs = env.buffers["obs_state"] if obs is None else obs
+        if not (self.obs.dtype == torch.float32 and self.obs.is_contiguous() and tuple(self.obs.shape) == (n, od) and self.obs.device == env.buffers["obs_state"].device):
+            raise ValueError(f"FusedActor: `obs` must be {n} x {od} contiguous float32 values on {dev}")
+        a.obs, a.priv = self.obs.data_ptr(), env.buffers["obs_priv"].data_ptr()
         a.mean, a.std = self.mean.data_ptr(), self.std.data_ptr()
         for l in range(4):
             a.w[l], a.b[l] = self._w[l].data_ptr(), self._b[l].data_ptr()

@@ -11,6 +11,7 @@ kernels of libpgtt.so on the current torch stream.  PyTorch is only the allocato
 from __future__ import annotations
 
 import ctypes as C
+import os
 from typing import Any, Dict, Optional
 
 import numpy as np
@@ -28,7 +29,7 @@ class Joystick:
                  autoreset: bool = False, debug_contacts: bool = False, env_id_offset: int = 0,
                  model: Optional[Dict[str, Any]] = None, layout: Optional[str] = None, observe_form: Optional[str] = None,
                  test_hooks: bool = False, interval_sums: bool = False, push: Optional[Dict[str, Any]] = None, xfrc: bool = False,
-                 curriculum: Optional[Dict[str, Any]] = None, level: Optional[torch.Tensor] = None, depth: Optional[Dict[str, Any]] = None):
+                 curriculum: Optional[Dict[str, Any]] = None, level: Optional[torch.Tensor] = None, depth: Optional[Dict[str, Any]] = None, student=None):
         """layout: "auto" | "quad" | "oct" | "hex" lane layout of physics_kernel (PgttConfig.lane_layout; results are bit-identical
         across batch sizes and shards within one layout); observe_form: "fused" | "split"; test_hooks: allow set_test_overrides
         (fixture replay only); interval_sums: keep per-env running sums of the step outputs for a logging trainer (PgttBuffers.interval_sums);
@@ -44,7 +45,12 @@ class Joystick:
         mount_pos=(0.30, 0.0, 0.05), pitch_deg=30, every=1, see_robot=True, noise=dict(sigma=0.0, dropout=0.0)); the mount defaults are placeholders
         for a Go2 head camera - settings, not facts): `env.depth` is the [N, H, W] image, step() ticks the sensor after the step on the same stream,
         reset() ticks it with force.  A side output: the observations and every other buffer are what they are without it.  None: nothing of it
-        is allocated, loaded, bound or launched."""
+        is allocated, loaded, bound or launched.
+        student: a perceive.ScanEstimator or the path of a saved one (needs depth): the student perception module (libpgtt_perceive.so) runs behind
+        the camera after every step and reset; `env.student_obs` is the [N, obs_dim] observation with the 117 scan rows replaced by its estimate.  A
+        side output like the image.  None: the library is not opened."""
+        if student is not None and depth is None:
+            raise ValueError("Joystick(student=...) needs depth=dict(...): the student reads the onboard depth image")
         self.level_start = None
         if isinstance(terrain, (list, tuple)):
             terrain, self.level_start = _curriculum.stack_levels(terrain)
@@ -146,6 +152,11 @@ class Joystick:
         if depth is not None:
             from . import depth as _depth                     # libpgtt_depth.so is opened only here
             self.depth_camera = _depth.DepthCamera(self, **_depth.settings(depth))
+        self.student = None
+        if student is not None:
+            from . import perceive as _perceive               # libpgtt_perceive.so is opened only here
+            est = _perceive.ScanEstimator.load(student) if isinstance(student, (str, os.PathLike)) else student
+            self.student = _perceive.StudentPerception(self, est)
 
     # ---- reference-compatible properties
     @property
@@ -223,6 +234,11 @@ class Joystick:
         """[N, H, W] float32 image of the onboard depth camera (metres along the optical axis, `far` on a miss), or None without one"""
         return None if self.depth_camera is None else self.depth_camera.image
 
+    @property
+    def student_obs(self) -> Optional[torch.Tensor]:
+        """[N, obs_dim] float32: the observation with its scan rows replaced by the student's estimate from the depth image, or None without one"""
+        return None if self.student is None else self.student.obs
+
     def push_step(self) -> None:
         """the push scheduler alone (pgtt_push): what step() runs first when pushes are on; for callers of physics() / observe()"""
         native.check(self._lib.pgtt_push(self._h, self._stream()))
@@ -273,6 +289,8 @@ class Joystick:
         native.check(self._lib.pgtt_reset(self._h, self._seed, self.env_id_offset, mp, self._stream()))
         if self.depth_camera is not None:
             self.depth_camera.tick(force=True)
+        if self.student is not None:
+            self.student.tick()
         return self._obs()
 
     def step(self, action: torch.Tensor, curriculum: bool = True):
@@ -286,6 +304,8 @@ class Joystick:
         native.check(self._lib.pgtt_step(self._h, a.data_ptr(), self._stream()))
         if self.depth_camera is not None:
             self.depth_camera.tick()
+        if self.student is not None:
+            self.student.tick()
         info = {"metrics": self.buffers["metrics"], "episode_metrics": self.buffers["ep_metrics"]}
         return self._obs(), self.buffers["reward"], self.buffers["done"], info
 
@@ -330,6 +350,9 @@ class Joystick:
         return p.value, o.value, k.value
 
     def close(self) -> None:
+        if getattr(self, "student", None) is not None:
+            self.student.close()
+            self.student = None
         if getattr(self, "depth_camera", None) is not None:
             self.depth_camera.close()
             self.depth_camera = None

@@ -4,8 +4,8 @@ and csrc/flags.mk, the make fragment that holds the compile flags of that unit. 
 change the kernel).  The task-side kernels, the host code and the other rules of the Makefile are not covered: a change there leaves the hash,
 and with it the counters recorded under profiles/, valid.  EXTRA flags and the 1-ulp division are what the build's flavor says.
 
-The two side libraries (csrc/pgtt_raycast.mk) embed a hash of their own, side_sha256("render" | "depth"): the include closure of their one
-translation unit (SIDE_SOURCES), normalised the same way.  `python3 srchash.py` prints the physics hash, `python3 srchash.py render` a side hash."""
+The side libraries (csrc/pgtt_raycast.mk, csrc/pgtt_perceive.mk) embed a hash of their own, side_sha256("render" | "depth" | "perceive"): the
+include closure of their one translation unit (SIDE_SOURCES), normalised the same way.  `python3 srchash.py` prints the physics hash, `python3 srchash.py render` a side hash."""
 import hashlib
 import os
 import re
@@ -16,7 +16,8 @@ FLAGS_FRAGMENT = "flags.mk"
 # per side library: the unit and the shared headers in csrc/, then the public headers in include/ (every project file the unit includes)
 _RAYCAST = ("pgtt_raycast.hip.h", "pgtt_raycast_host.h")
 SIDE_SOURCES = {"render": (("pgtt_render.hip",) + _RAYCAST, ("pgtt_render.h", "pgtt.h")),
-                "depth": (("pgtt_depth.hip",) + _RAYCAST, ("pgtt_depth.h", "pgtt_render.h", "pgtt.h"))}
+                "depth": (("pgtt_depth.hip",) + _RAYCAST, ("pgtt_depth.h", "pgtt_render.h", "pgtt.h")),
+                "perceive": (("pgtt_perceive.hip", "pgtt_raycast_host.h"), ("pgtt_perceive.h", "pgtt_render.h", "pgtt.h"))}
 
 
 def hashed_files(pkg: str = _HERE):
