@@ -18,6 +18,7 @@ from phase_guided_terrain_traversal_amd.env import Joystick
 from phase_guided_terrain_traversal_amd.randomize import domain_randomize
 
 import parity_explain as px
+from wrench_reference import _hold_action, _minimiser, _model_for
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TERRAIN = np.load(os.path.join(ROOT, "phase_guided_terrain_traversal_amd", "assets", "terrains", "level4.npy"))
@@ -70,29 +71,6 @@ def test_zero_wrench_is_the_default_path(layout):
     assert float(b.xfrc.abs().sum()) == 0.0                 # with pushes off the library never writes the wrench
 
 
-def _model_for(model, prm):
-    """the env's DR'd model dict (body masses, torso COM, hinge zero offsets, armature) for the fp64 helpers of mjcf"""
-    m = dict(model)
-    m["body_mass"] = prm[abi.P_BODY_MASS:abi.P_BODY_MASS + 13].astype(np.float64)
-    ipos = np.array(model["body_ipos"], np.float64).copy(); ipos[0] = prm[abi.P_BASE_IPOS:abi.P_BASE_IPOS + 3]
-    m["body_ipos"] = ipos
-    q0 = np.array(model["qpos0"], np.float64).copy(); q0[7:] = prm[abi.P_QPOS0:abi.P_QPOS0 + 12]
-    m["qpos0"] = q0
-    arm = np.array(model["dof_armature"], np.float64).copy(); arm[6:] = prm[abi.P_ARMATURE:abi.P_ARMATURE + 12]
-    m["dof_armature"] = arm
-    return m
-
-
-def _hold_action(model, qpos, cfg):
-    """actions whose motor targets equal the current hinge angles (no actuator force at zero hinge velocity)"""
-    key = np.asarray(model["key_qpos"], np.float32)
-    act = np.zeros((qpos.shape[1], 12), np.float32)
-    for ac in range(12):
-        j = 3 * ((ac // 3) ^ 1) + ac % 3
-        act[:, ac] = (qpos[7 + j].astype(np.float32) - key[7 + ac]) / np.float32(cfg["action_scale"])
-    return act
-
-
 @pytest.mark.parametrize("layout", ["quad", "oct", "hex"])
 def test_contact_free_wrench_is_minv_jt_w(layout):
     """twin envs 1 m above the floor, hinges mid-range, one mjx.step per call (ctrl_dt = sim_dt): the twins' last-substep qacc differ by
@@ -140,37 +118,6 @@ def test_contact_free_wrench_is_minv_jt_w(layout):
         worst = max(worst, err)
         assert np.abs(want[6:]).max() > 0                         # the hinges feel the push through M^-1, not through J^T w
     assert worst < 1e-5, worst
-
-
-def _minimiser(D, qfrc_smooth):
-    """fp64 minimiser of 1/2 (a - qs)^T M (a - qs) + 1/2 sum_active D_r min(0, J_r a - aref_r)^2 with qs = M^-1 qfrc_smooth (Newton on the active set,
-    backtracking on the cost)"""
-    M, J, Dd, aref = D["qM"], D["efc_J"], D["efc_D"], D["efc_aref"]
-    on = np.asarray(D["efc_active"]) != 0
-    qs = np.linalg.solve(M, qfrc_smooth)
-
-    def cost(a):
-        r = J @ a - aref
-        act = on & (r < 0)
-        d = a - qs
-        return 0.5 * d @ M @ d + 0.5 * (Dd * r * r * act).sum(), act, r
-
-    a = qs.copy()
-    c, act, r = cost(a)
-    for _ in range(200):
-        H = M + (J[act].T * Dd[act]) @ J[act]
-        g = M @ (a - qs) + J[act].T @ (Dd[act] * r[act])
-        step = -np.linalg.solve(H, g)
-        s = 1.0
-        while True:
-            c2, act2, r2 = cost(a + s * step)
-            if c2 <= c + 1e-14 * abs(c) or s < 1e-10:
-                break
-            s *= 0.5
-        a, c, act, r = a + s * step, c2, act2, r2
-        if np.abs(s * step).max() < 1e-13 * (1 + np.abs(a).max()):
-            break
-    return a
 
 
 @pytest.mark.parametrize("task", ["stairs", "flat_terrain"])
@@ -279,16 +226,24 @@ def _replay(cfg_s, seed, ids, ep, done_prev, P, mass):
     return P, F
 
 
-def test_scheduler_replays_on_the_host():
+@pytest.mark.parametrize("dr", [True, False], ids=["dr", "nodr"])
+def test_scheduler_replays_on_the_host(dr):
     """kick parameters from oracle.uniform with the PGTT_RS_PUSH_* streams (exact), the force profile (fp32 rounding), horizontal forces, zero
-    between kicks, restarts after done and after a masked reset"""
-    n, seed = 192, 9
-    env = _env("stairs", n, autoreset=True, push=PUSH)
+    between kicks, restarts after done and after a masked reset; with the DR rows (the env's torso mass, 192 envs) and without a params buffer
+    (push_kernel's params == NULL arm: the model's body_mass[0]; 50 envs, a ragged last block)"""
+    seed = 9
+    if dr:
+        n = 192
+        env = _env("stairs", n, autoreset=True, push=PUSH)
+    else:
+        n = 50
+        env = Joystick("stairs", configs.training_config(), num_envs=n, device="cuda:0", autoreset=True, terrain=TERRAIN, push=PUSH)
+        assert "params" not in env.buffers
     env.reset(seed)
     P = env.buffers["push_state"]
     assert float(env.xfrc.abs().sum()) == 0.0 and bool((P[abi.PU_WAIT] == -1).all())
     ids = np.arange(n)
-    mass = env.buffers["params"][abi.P_BODY_MASS].cpu().numpy()
+    mass = env.buffers["params"][abi.P_BODY_MASS].cpu().numpy() if dr else np.full(n, np.float32(env.model["body_mass"][0]), np.float32)
     rng = np.random.default_rng(0)
     kicks, restarts = 0, 0
     for t in range(120):
