@@ -11,7 +11,8 @@ env's FIRST episode [UPSTREAM-RECALL: brax.training.acting.Evaluator + envs.trai
 final `termination` reward term is zero (:221-223), i.e. the robots that did not fall.  Here the same rollout runs directly: no learner
 is built.  The policy comes from `--checkpoint_folder` (the newest `<env_steps>.pt` of `train.py`, or its `policy<index>.npz`) or from
 `--policy` (an .npz path or the name of a shipped policy); with `--student student.npz` (train_student.py) the policy acts on the observation
-whose scan rows the student perception module estimated from the onboard depth image; the remaining flags of the reference's CLI are accepted and ignored.
+whose scan rows the student perception module estimated from the onboard depth image, with `--elevation [grid,res,alpha]` on the observation whose
+scan rows are sampled from the depth-fused elevation map (elevation.py; nothing to train); the remaining flags of the reference's CLI are accepted and ignored.
 """
 import argparse
 import os
@@ -143,8 +144,27 @@ def run_evaluation(args, num_eval_envs=NUM_EVAL_ENVS, seed=0, verbose=True):
         # --student: the policy acts on env.student_obs - the observation whose scan rows a perceive.ScanEstimator estimated from the onboard
         # depth image (the camera of depth.DEFAULTS) - instead of the privileged scan
         kw.update(depth={}, student=args.student)
+    elev = getattr(args, "elevation", None)
+    if elev is not None:
+        # --elevation [grid,res,alpha]: the policy acts on env.elevation_obs - the observation whose scan rows are sampled from the elevation map
+        # fused from the onboard depth image (the camera of depth.DEFAULTS; elevation.DEFAULTS where a value is not given)
+        if getattr(args, "student", None):
+            raise SystemExit("--student and --elevation both say what the policy acts on: give one")
+        vals = [v for v in elev.split(",") if v]
+        if len(vals) > 3:
+            raise SystemExit("--elevation takes at most grid,res,alpha")
+        try:
+            given = dict(zip(("grid", "res", "alpha"), (int(vals[0]),) + tuple(float(v) for v in vals[1:]))) if vals else True
+        except ValueError:
+            raise SystemExit(f"--elevation {elev}: grid must be an integer, res and alpha numbers")
+        kw.update(depth={}, elevation=given)
     env = Joystick(args.task_name, cfg, num_envs=n, terrain=terrain, device=DEVICE, autoreset=True, **kw)
-    acts_on = env.buffers["obs_state"] if env.student is None else env.student_obs
+    if env.elevation_map is not None:
+        acts_on = env.elevation_obs
+    elif env.student is not None:
+        acts_on = env.student_obs
+    else:
+        acts_on = env.buffers["obs_state"]
     tmp = os.path.join(ROOT, "plots"); os.makedirs(tmp, exist_ok=True)
     pi = load_policy_from_args(args, tmp)
     if pi.mean.shape[0] != env.observation_size["state"]:
@@ -206,6 +226,8 @@ def make_parser():
     ap.add_argument("--video_scan", action="store_true", help="overlay the 117 height-scan hits as marker spheres")
     ap.add_argument("--video_depth", action="store_true", help="tile each video env's onboard depth image (grey, near = white) under its RGB tile")
     ap.add_argument("--student", type=str, default=None, help="a student.npz of train_student.py: the policy acts on the depth camera's estimate of the scan rows")
+    ap.add_argument("--elevation", type=str, nargs="?", const="", default=None, metavar="GRID,RES,ALPHA",
+                    help="the policy acts on the scan rows sampled from the depth-fused elevation map (elevation.py); optional grid[,res[,alpha]]")
     configs.add_push_args(ap)
     ap.add_argument("--terrain_files", type=str, default=None, help="comma-separated level files stacked into one table (as train.py --terrain_files); evaluated on --level")
     ap.add_argument("--level", type=int, default=0, help="with --terrain_files: the level every evaluation env stands on (no curriculum at evaluation)")

@@ -1,0 +1,128 @@
+/*
+ * pgtt_elevation.h — C ABI of libpgtt_elevation.so: a depth-fused elevation map per env, and the 13 x 9 height scan sampled from it.
+ *
+ * The geometric counterpart of the student (pgtt_perceive.h): the onboard depth image (pgtt_depth.h) is unprojected with the camera pose, fused
+ * into a rolling robot-centred map of world heights, and the observation's 117 scan rows are read from the map.  Nothing is learned.
+ * A separate library from libpgtt.so and the other side libraries: it only READS the env's `state`, `obs` and `done` and the camera's image, and
+ * writes the caller's `map`, `origin`, `est`, `known` and `obs_out`.
+ *
+ * Conventions (those of pgtt.h)
+ *   - plain C; `stream` is a hipStream_t passed as void*.
+ *   - every function returns 0 or a negative PGTT_E_* code (pgtt.h); the message is available from pgtt_elevation_last_error().
+ *   - device buffers are CALLER-OWNED; pgtt_elevation() enqueues ONE kernel on the caller's stream and neither allocates, synchronises nor
+ *     reads anything back, so it can be captured in a HIP graph.  The library reads no environment variable.
+ *   - everything is fp32 on the device, and the order of the steps below is fixed.
+ *
+ * Camera.  The camera model of pgtt_depth.h: width, height, fovy_deg, near, far, mount_pos, mount_quat; optical axis fwd = the camera frame's +x,
+ * up = its +z, right = fwd x up; pixel (i, j) (row i from the top, column j) is sampled at its centre,
+ *     u = (2 (j + 0.5) / W - 1) * tan(fovy / 2) * W / H,   v = (1 - 2 (i + 0.5) / H) * tan(fovy / 2).
+ * Only a camera on the torso is supported (mount_body == 0, anything else is PGTT_E_ARG), so no forward kinematics is needed:
+ *     camera pose = base pose * mount pose,   base pose = rows PGTT_S_QPOS + 0..6 of `state`, the quaternion normalised first.
+ * mount_quat is normalised by pgtt_elevation_create.  The image is taken as the pose's own: a caller whose sensor period is above 1 would
+ * unproject a stale image under a moved pose, and must not use this library.
+ *
+ * Map.  Per env, map[G][G] (G = cfg.grid) holds world-z heights in metres; NaN = unknown.  The window is world-aligned and toroidal, with
+ * square cells of side `res`:
+ *     world cell (ix, iy) = (floor(x / res), floor(y / res)) lives at slot map[ix mod G][iy mod G]    (floor-mod: negative coordinates work)
+ *     origin[e] = (floor(bx / res), floor(by / res)), the cell of the base position (bx, by), is the window's centre cell
+ *     the window holds the cells [origin - G/2, origin - G/2 + G) per axis (G/2 rounded down)
+ * Limits: 8 <= G <= 96 (PGTT_ELEVATION_MIN_GRID / MAX_GRID; 4 G G <= 36864 bytes of LDS), res > 0.
+ * Before the first call the caller fills `map` with NaN, or passes clear_all to the first call; `origin` may hold anything then.
+ *
+ * One pgtt_elevation() call does, per env, in this order:
+ *  1. Clear.  Every cell becomes NaN when clear_all != 0, or clear_mask[e] != 0, or use_done != 0 and done[e] != 0.  A cleared env takes the new
+ *     origin directly.
+ *  2. Recentre.  The new origin is computed from the current base position.  Every slot whose world cell under the new window differs from its
+ *     world cell under the old window (origin[e] as the last call left it) becomes NaN; a jump of G cells or more clears everything.
+ *     origin[e] is written.
+ *  3. Tick maximum.  For every pixel with near < d < far (a NaN, a miss that reads `far` and a dropout pixel are all skipped):
+ *         p = cam_pos + R_cam (d, d u, d v) in (fwd, right, up): the depth is the distance along the optical axis
+ *         skipped when p, expressed in the base frame, lies in the box |x| <= self_half[0], |y| <= self_half[1], |z| <= self_half[2] - the self
+ *           filter of a camera that sees the robot (see_robot); self_half = (0, 0, 0) disables it
+ *         skipped when p's cell is outside the window
+ *         otherwise m[cell] = max(m[cell], p.z)
+ *     m lives in LDS and is updated with an LDS atomic maximum (on an order-preserving integer key of the fp32 value): the result does not
+ *     depend on the order of the lanes, so the map is deterministic.
+ *  4. Fuse.  For the cells step 3 touched: h = isnan(h) ? m : h + alpha (m - h), alpha in (0, 1]; alpha = 1 replaces the old value (by m itself,
+ *     bit for bit).
+ *  5. Sample.  The scan grid of the observe kernel, point i = 9 r + c: ox = (6 - r) scan_dist_x, oy = (4 - c) scan_dist_y, rotated by
+ *         yaw = atan2(2 (qw qz + qx qy), 1 - 2 (qy^2 + qz^2))      of the normalised base quaternion
+ *     and offset from the base xy.  z[i] = the value of the cell that contains the point; known[i] = 1 when that cell is inside the window and
+ *     not NaN, else 0.  An unknown point takes the minimum over the known points; when no point is known every z is 0.  Then
+ *         est[i] = z[i] - min z:    the observation's noise-free scan rows (heights above the lowest scan point), 0 at an unknown point.
+ *  6. Assemble.  When obs_out is bound: obs_out = obs with rows [scan_row0, scan_row0 + 117) replaced by est, every other row copied bit for
+ *     bit (scan_row0 = 38 for the PGTT task, 30 for the baseline).
+ *
+ * An env's outputs are functions of its own rows only: the same bits at any batch position and at any N.
+ *
+ * use_done and auto-reset.  With PgttConfig.autoreset = 1 the step that finishes an episode leaves done[e] = 1 AND has already restored the
+ * env's qpos rows to the new episode's first state, so a call with use_done after the step clears the map and integrates the first image of the
+ * new episode under its own pose.  With autoreset = 0 the state rows stay the finished episode's and done[e] stays as the step's termination
+ * test gives it: use_done then clears the map at every call while done[e] != 0, so it holds that call's image alone, until the caller resets the
+ * env (pgtt_reset with a mask) and passes the same mask as clear_mask.
+ */
+#ifndef PGTT_ELEVATION_H_
+#define PGTT_ELEVATION_H_
+
+#include <stdint.h>
+
+#include "pgtt.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define PGTT_ELEVATION_MAX_DIM 256       /* width and height of the image */
+#define PGTT_ELEVATION_MIN_GRID 8
+#define PGTT_ELEVATION_MAX_GRID 96       /* 4 * 96 * 96 = 36864 bytes of LDS */
+
+typedef struct PgttElevationConfig {
+  int32_t width, height;                 /* 1 .. PGTT_ELEVATION_MAX_DIM each */
+  float fovy_deg;                        /* vertical field of view, in (0, 180) */
+  float near, far;                       /* 0 < near < far, metres along the optical axis */
+  int32_t mount_body;                    /* must be 0 (the torso) */
+  float mount_pos[3];                    /* camera pose in the torso frame */
+  float mount_quat[4];                   /* wxyz, non-zero; normalised by pgtt_elevation_create */
+  int32_t grid;                          /* G: cells per side of the window */
+  float res;                             /* cell size in metres, > 0 */
+  float alpha;                           /* fusion gain, in (0, 1] */
+  float self_half[3];                    /* >= 0: half extents of the self-filter box in the base frame; all 0 = no filter */
+  float scan_dist_x, scan_dist_y;        /* PgttConfig.scan_dist_x / _y */
+  int32_t obs_dim;                       /* rows of the observation (PGTT_OBS or the baseline's) */
+  int32_t scan_row0;                     /* first scan row of the observation; scan_row0 + PGTT_NSCAN <= obs_dim */
+} PgttElevationConfig;
+
+/* device pointers, all caller-owned, sized for N = num_envs given to pgtt_elevation_create */
+typedef struct PgttElevationBuffers {
+  const float* state;                    /* [PGTT_NSTATE][N] (PgttBuffers.state), required */
+  const float* depth;                    /* [N][H][W] (PgttDepthBuffers.depth), required */
+  const float* obs;                      /* [N][obs_dim] (PgttBuffers.obs_state); required with obs_out, else may be NULL */
+  const float* done;                     /* [N] 0 / 1 (PgttBuffers.done) or NULL: use_done then clears nothing */
+  float* map;                            /* [N][G][G], required; NaN = unknown */
+  int32_t* origin;                       /* [N][2], required */
+  float* est;                            /* [N][PGTT_NSCAN], required */
+  uint8_t* known;                        /* [N][PGTT_NSCAN], required */
+  float* obs_out;                        /* [N][obs_dim] or NULL */
+} PgttElevationBuffers;
+
+typedef struct pgtt_elevation_map* pgtt_elevation_handle;
+
+/* the config's checks alone: host only, needs no GPU.  PGTT_E_ARG for a config outside the ranges above. */
+int pgtt_elevation_check(const PgttElevationConfig* cfg);
+int pgtt_elevation_create(const PgttElevationConfig* cfg, int device, int num_envs, pgtt_elevation_handle* out);
+int pgtt_elevation_destroy(pgtt_elevation_handle h);
+/* PGTT_E_ARG when a required pointer is NULL.  A pgtt_elevation() captured in a HIP graph keeps the pointers bound at capture. */
+int pgtt_elevation_bind(pgtt_elevation_handle h, const PgttElevationBuffers* bufs);
+/* one tick for all N envs: one launch, one workgroup of 256 lanes per env.  clear_mask: device uint8 [N] or NULL.
+ * PGTT_E_STATE before pgtt_elevation_bind. */
+int pgtt_elevation(pgtt_elevation_handle h, const uint8_t* clear_mask, int clear_all, int use_done, void* stream);
+int pgtt_elevation_sizeof_config(void);
+int pgtt_elevation_sizeof_buffers(void);
+/* "src=<SHA-256 of pgtt_elevation.hip and the files it includes>;flavor=product" */
+const char* pgtt_elevation_build_info(void);
+const char* pgtt_elevation_last_error(void);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* PGTT_ELEVATION_H_ */

@@ -1,0 +1,348 @@
+// pgtt_elevation.hip — libpgtt_elevation.so: the depth-fused elevation map (include/pgtt_elevation.h), one launch per call.
+//
+// elevation_kernel, one workgroup of four waves per env.  LDS holds one word per map slot, `sh_m`: first the tick maximum as an
+// order-preserving integer key (0 = no pixel fell into the slot), then, after the fuse, the slot's fused height, which the scan is sampled from.
+//   phase A  lane 0 forms the base pose, the camera pose, the yaw's sine and cosine, the new origin and writes it; the other lanes zero sh_m.
+//   phase B  lanes 0 .. 2G - 1 mark, per axis, the slot rows / columns whose world cell differs between the old and the new window.
+//   phase C  every lane unprojects pixels (16-byte runs of the image when the pixel count allows) and raises sh_m[slot] with an LDS atomic maximum.
+//   phase D  the persistent map streams through: 16-byte runs from HBM, stale slots to NaN, touched slots fused, the run written back only when
+//            one of its slots changed; the fused value replaces the key in sh_m.
+//   phase E  lanes 0 .. 116 sample the scan, the minimum over the known points is a wave reduction and one LDS exchange; est, known.
+//   phase F  obs_out = obs with the scan rows replaced.
+// The phases are separated by workgroup barriers.  No global atomics, no scratch; nothing is shared between envs.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+
+#include "../../include/pgtt_elevation.h"
+#include "pgtt_raycast_host.h"
+
+#ifndef PGTT_ELEVATION_SRC
+#define PGTT_ELEVATION_SRC "unknown"
+#endif
+// an experiment build names itself: make -f pgtt_elevation.mk EXTRA=-DPGTT_ELEVATION_FLAVOR=\"name\" ...
+#ifndef PGTT_ELEVATION_FLAVOR
+#define PGTT_ELEVATION_FLAVOR "product"
+#endif
+
+namespace {
+
+constexpr int kLanes = 256;                       // four waves per env
+constexpr int kMaxG = PGTT_ELEVATION_MAX_GRID;
+constexpr float kCellClamp = 1.0e9f;              // |cell index| stays below 2^30: a far-away or NaN coordinate cannot overflow the integer window test
+static_assert(PGTT_NSCAN <= 128 && 2 * kMaxG <= kLanes && 4 * kMaxG * kMaxG <= 36864, "two waves sample the scan; one lane per slot row and column");
+
+struct ElevArgs {
+  const float* state; const float* depth; const float* obs; const float* done; const uint8_t* clear_mask;
+  float* map; int32_t* origin; float* est; uint8_t* known; float* obs_out;
+  int N, W, H, G, obs_dim, scan_row0, clear_all, use_done, self_on, vec_map, vec_img;
+  float near_m, far_m, res, alpha, tu, tv, sdx, sdy;         // tu = tan(fovy / 2) W / H, tv = tan(fovy / 2)
+  float mpos[3], mquat[4], self_half[3];
+};
+
+// what lane 0 stages for the workgroup
+enum { P_CAM = 0, P_FWD = 3, P_RIGHT = 6, P_UP = 9, P_BASE = 12, P_RB = 15, P_SY = 24, P_CY = 25, P_N = 26 };
+enum { I_LOX = 0, I_LOY = 1, I_LMX = 2, I_LMY = 3, I_OLDX = 4, I_OLDY = 5, I_CLEAR = 6, I_N = 8 };
+
+__device__ __forceinline__ int cell_of(float x, float res) { return (int)fminf(fmaxf(floorf(x / res), -kCellClamp), kCellClamp); }
+// a value every lane holds alike, moved to a scalar register
+__device__ __forceinline__ float uni(float x) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(x))); }
+__device__ __forceinline__ int floor_mod(int a, int g) { const int r = a % g; return r < 0 ? r + g : r; }
+// fp32 -> a key whose unsigned order is the order of the floats; no finite value maps to 0
+__device__ __forceinline__ unsigned key_of(float z) { const unsigned b = __float_as_uint(z); return b ^ ((unsigned)((int)b >> 31) | 0x80000000u); }
+__device__ __forceinline__ float value_of(unsigned k) { return __uint_as_float(k ^ (((k >> 31) - 1u) | 0x80000000u)); }
+
+__global__ void __launch_bounds__(kLanes) elevation_kernel(ElevArgs a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned sh_m[];      // [G * G]
+  __shared__ float sh_p[P_N];
+  __shared__ int sh_i[I_N];
+  __shared__ unsigned char sh_stale[2 * kMaxG];                        // [0, G): slot rows (x), [G, 2G): slot columns (y)
+  __shared__ float sh_est[PGTT_NSCAN];
+  __shared__ float sh_red[2];
+  const int e = blockIdx.x, tid = threadIdx.x, G = a.G, GG = G * G;
+  const long N = a.N;
+
+  // ---- phase A: the poses (lane 0); the tick maximum starts empty
+  if (tid == 0) {
+    const float* S = a.state + e;
+    const float bx = S[(PGTT_S_QPOS + 0) * N], by = S[(PGTT_S_QPOS + 1) * N], bz = S[(PGTT_S_QPOS + 2) * N];
+    float qw = S[(PGTT_S_QPOS + 3) * N], qx = S[(PGTT_S_QPOS + 4) * N], qy = S[(PGTT_S_QPOS + 5) * N], qz = S[(PGTT_S_QPOS + 6) * N];
+    const float qn = sqrtf(qw * qw + qx * qx + qy * qy + qz * qz);
+    qw /= qn; qx /= qn; qy /= qn; qz /= qn;
+    // rows of the base rotation
+    const float r00 = qw * qw + qx * qx - qy * qy - qz * qz, r01 = 2.f * (qx * qy - qw * qz), r02 = 2.f * (qx * qz + qw * qy);
+    const float r10 = 2.f * (qx * qy + qw * qz), r11 = qw * qw - qx * qx + qy * qy - qz * qz, r12 = 2.f * (qy * qz - qw * qx);
+    const float r20 = 2.f * (qx * qz - qw * qy), r21 = 2.f * (qy * qz + qw * qx), r22 = qw * qw - qx * qx - qy * qy + qz * qz;
+    sh_p[P_BASE + 0] = bx; sh_p[P_BASE + 1] = by; sh_p[P_BASE + 2] = bz;
+    sh_p[P_RB + 0] = r00; sh_p[P_RB + 1] = r01; sh_p[P_RB + 2] = r02; sh_p[P_RB + 3] = r10; sh_p[P_RB + 4] = r11; sh_p[P_RB + 5] = r12;
+    sh_p[P_RB + 6] = r20; sh_p[P_RB + 7] = r21; sh_p[P_RB + 8] = r22;
+    sh_p[P_CAM + 0] = bx + r00 * a.mpos[0] + r01 * a.mpos[1] + r02 * a.mpos[2];
+    sh_p[P_CAM + 1] = by + r10 * a.mpos[0] + r11 * a.mpos[1] + r12 * a.mpos[2];
+    sh_p[P_CAM + 2] = bz + r20 * a.mpos[0] + r21 * a.mpos[1] + r22 * a.mpos[2];
+    // camera = base * mount; fwd = its +x, up = its +z, right = fwd x up
+    const float mw = a.mquat[0], mx = a.mquat[1], my = a.mquat[2], mz = a.mquat[3];
+    const float cw = qw * mw - qx * mx - qy * my - qz * mz, cx = qw * mx + qx * mw + qy * mz - qz * my;
+    const float cyq = qw * my - qx * mz + qy * mw + qz * mx, cz = qw * mz + qx * my - qy * mx + qz * mw;
+    const float fx = cw * cw + cx * cx - cyq * cyq - cz * cz, fy = 2.f * (cx * cyq + cw * cz), fz = 2.f * (cx * cz - cw * cyq);
+    const float ux = 2.f * (cx * cz + cw * cyq), uy = 2.f * (cyq * cz - cw * cx), uz = cw * cw - cx * cx - cyq * cyq + cz * cz;
+    sh_p[P_FWD + 0] = fx; sh_p[P_FWD + 1] = fy; sh_p[P_FWD + 2] = fz;
+    sh_p[P_UP + 0] = ux; sh_p[P_UP + 1] = uy; sh_p[P_UP + 2] = uz;
+    sh_p[P_RIGHT + 0] = fy * uz - fz * uy; sh_p[P_RIGHT + 1] = fz * ux - fx * uz; sh_p[P_RIGHT + 2] = fx * uy - fy * ux;
+    const float yaw = atan2f(2.0f * (qw * qz + qx * qy), 1.0f - 2.0f * (qy * qy + qz * qz));
+    float sy, cy; sincosf(yaw, &sy, &cy);
+    sh_p[P_SY] = sy; sh_p[P_CY] = cy;
+    // clear, the old and the new window
+    const bool clear = a.clear_all || (a.clear_mask && a.clear_mask[e]) || (a.use_done && a.done && a.done[e] != 0.f);
+    const int ox = cell_of(bx, a.res), oy = cell_of(by, a.res);
+    const int lox = ox - G / 2, loy = oy - G / 2;
+    sh_i[I_LOX] = lox; sh_i[I_LOY] = loy; sh_i[I_LMX] = floor_mod(lox, G); sh_i[I_LMY] = floor_mod(loy, G);
+    // an old origin outside the clamp (a map never ticked, garbage in the buffer) is as far away as the clamp: everything is stale
+    const int px = a.origin[2 * (long)e], py = a.origin[2 * (long)e + 1];
+    const bool sane = px >= -(1 << 30) && px <= (1 << 30) && py >= -(1 << 30) && py <= (1 << 30);
+    sh_i[I_OLDX] = px - G / 2; sh_i[I_OLDY] = py - G / 2; sh_i[I_CLEAR] = (clear || !sane) ? 1 : 0;
+    a.origin[2 * (long)e] = ox; a.origin[2 * (long)e + 1] = oy;
+  }
+  for (int s = tid; s < GG; s += kLanes) sh_m[s] = 0u;
+  __syncthreads();
+
+  // ---- phase B: per axis, the slots whose world cell moved.  Slot s holds world cell lo + ((s - lo) mod G) under the window that starts at lo.
+  if (tid < 2 * G) {
+    const int ax = tid >= G, s = tid - ax * G;
+    const int lo_new = sh_i[I_LOX + ax], lo_old = sh_i[I_OLDX + ax];
+    unsigned char st = 1;
+    if (!sh_i[I_CLEAR]) st = (lo_new + floor_mod(s - lo_new, G)) != (lo_old + floor_mod(s - lo_old, G));
+    sh_stale[tid] = st;
+  }
+
+  // ---- phase C: the tick maximum
+  {
+    const float cpx = sh_p[P_CAM + 0], cpy = sh_p[P_CAM + 1], cpz = sh_p[P_CAM + 2];
+    const float fx = sh_p[P_FWD + 0], fy = sh_p[P_FWD + 1], fz = sh_p[P_FWD + 2];
+    const float rx = sh_p[P_RIGHT + 0], ry = sh_p[P_RIGHT + 1], rz = sh_p[P_RIGHT + 2];
+    const float ux = sh_p[P_UP + 0], uy = sh_p[P_UP + 1], uz = sh_p[P_UP + 2];
+    // the self filter's base position and rotation are read once, like the camera basis (the compiler cannot hoist LDS reads over the LDS atomics),
+    // and kept in scalar registers: twelve more vector registers would cost the eighth wave per SIMD
+    const float bpx = uni(sh_p[P_BASE + 0]), bpy = uni(sh_p[P_BASE + 1]), bpz = uni(sh_p[P_BASE + 2]);
+    const float b00 = uni(sh_p[P_RB + 0]), b01 = uni(sh_p[P_RB + 1]), b02 = uni(sh_p[P_RB + 2]), b10 = uni(sh_p[P_RB + 3]), b11 = uni(sh_p[P_RB + 4]);
+    const float b12 = uni(sh_p[P_RB + 5]), b20 = uni(sh_p[P_RB + 6]), b21 = uni(sh_p[P_RB + 7]), b22 = uni(sh_p[P_RB + 8]);
+    const int lox = sh_i[I_LOX], loy = sh_i[I_LOY], lmx = sh_i[I_LMX], lmy = sh_i[I_LMY];
+    const int W = a.W, npix = a.W * a.H;
+    const float* img = a.depth + (long)e * npix;
+    auto pixel = [&](float d, int i, int j) {
+      if (!(d > a.near_m && d < a.far_m)) return;                     // NaN, a miss, a dropout, below near
+      const float u = (2.f * ((float)j + 0.5f) / (float)W - 1.f) * a.tu, v = (1.f - 2.f * ((float)i + 0.5f) / (float)a.H) * a.tv;
+      const float px = cpx + d * (fx + u * rx + v * ux), py = cpy + d * (fy + u * ry + v * uy), pz = cpz + d * (fz + u * rz + v * uz);
+      if (a.self_on) {
+        const float dx = px - bpx, dy = py - bpy, dz = pz - bpz;             // R^T (p - base)
+        const float lx = b00 * dx + b10 * dy + b20 * dz, ly = b01 * dx + b11 * dy + b21 * dz, lz = b02 * dx + b12 * dy + b22 * dz;
+        if (fabsf(lx) <= a.self_half[0] && fabsf(ly) <= a.self_half[1] && fabsf(lz) <= a.self_half[2]) return;
+      }
+      const int relx = cell_of(px, a.res) - lox, rely = cell_of(py, a.res) - loy;
+      if ((unsigned)relx >= (unsigned)G || (unsigned)rely >= (unsigned)G || !(pz == pz)) return;
+      int sx = relx + lmx, sy = rely + lmy;                            // (lo + rel) mod G
+      sx -= sx >= G ? G : 0; sy -= sy >= G ? G : 0;
+      atomicMax(&sh_m[sx * G + sy], key_of(pz));
+    };
+    if (a.vec_img) {
+      for (int p = 4 * tid; p < npix; p += 4 * kLanes) {
+        const float4 d = *reinterpret_cast<const float4*>(img + p);
+        int i = p / W, j = p - i * W;
+        const float dv[4] = {d.x, d.y, d.z, d.w};
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+          pixel(dv[k], i, j);
+          j++;
+          if (j == W) { j = 0; i++; }
+        }
+      }
+    } else {
+      for (int p = tid; p < npix; p += kLanes) { const int i = p / W; pixel(img[p], i, p - i * W); }
+    }
+  }
+  __syncthreads();
+
+  // ---- phase D: the map streams through; sh_m takes the fused heights
+  {
+    float* mp = a.map + (long)e * GG;
+    const float alpha = a.alpha;
+    const float nanv = __uint_as_float(0x7fc00000u);
+    // one slot: -> the new height; `changed` when the stored value has to be written
+    auto slot = [&](float h, unsigned key, int sx, int sy, bool& changed) {
+      if (sh_stale[sx] | sh_stale[G + sy]) { h = nanv; changed = true; }
+      if (key) {
+        const float m = value_of(key);
+        h = (h != h || alpha == 1.f) ? m : h + alpha * (m - h);       // alpha = 1 stores m itself: h + (m - h) would round
+        changed = true;
+      }
+      return h;
+    };
+    if (a.vec_map) {
+      for (int s = 4 * tid; s < GG; s += 4 * kLanes) {
+        const float4 hv = *reinterpret_cast<const float4*>(mp + s);
+        const uint4 kv = *reinterpret_cast<const uint4*>(sh_m + s);
+        int sx = s / G, sy = s - sx * G;
+        float h[4] = {hv.x, hv.y, hv.z, hv.w};
+        const unsigned k4[4] = {kv.x, kv.y, kv.z, kv.w};
+        bool changed = false;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+          h[k] = slot(h[k], k4[k], sx, sy, changed);
+          sy++;
+          if (sy == G) { sy = 0; sx++; }
+        }
+        const float4 out = make_float4(h[0], h[1], h[2], h[3]);
+        if (changed) *reinterpret_cast<float4*>(mp + s) = out;
+        *reinterpret_cast<float4*>(sh_m + s) = out;
+      }
+    } else {
+      for (int s = tid; s < GG; s += kLanes) {
+        const int sx = s / G;
+        bool changed = false;
+        const float h = slot(mp[s], sh_m[s], sx, s - sx * G, changed);
+        if (changed) mp[s] = h;
+        sh_m[s] = __float_as_uint(h);
+      }
+    }
+  }
+  __syncthreads();
+
+  // ---- phase E: the scan
+  float z = 0.f;
+  bool kn = false;
+  if (tid < PGTT_NSCAN) {
+    const int r = tid / PGTT_SCAN_W, c = tid - r * PGTT_SCAN_W;
+    const float ox = ((float)(PGTT_SCAN_H - 1) * 0.5f - (float)r) * a.sdx, oy = ((float)(PGTT_SCAN_W - 1) * 0.5f - (float)c) * a.sdy;
+    const float sy = sh_p[P_SY], cy = sh_p[P_CY];
+    const float wx = sh_p[P_BASE + 0] + (ox * cy + oy * (-sy)), wy = sh_p[P_BASE + 1] + (ox * sy + oy * cy);
+    const int relx = cell_of(wx, a.res) - sh_i[I_LOX], rely = cell_of(wy, a.res) - sh_i[I_LOY];
+    if ((unsigned)relx < (unsigned)G && (unsigned)rely < (unsigned)G) {
+      int sx = relx + sh_i[I_LMX], sy2 = rely + sh_i[I_LMY];
+      sx -= sx >= G ? G : 0; sy2 -= sy2 >= G ? G : 0;
+      z = __uint_as_float(sh_m[sx * G + sy2]);
+      kn = z == z;
+    }
+  }
+  float zmin = kn ? z : INFINITY;
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) zmin = fminf(zmin, __shfl_xor(zmin, off, 64));
+  if (tid < 128 && (tid & 63) == 0) sh_red[tid >> 6] = zmin;
+  __syncthreads();
+  zmin = fminf(sh_red[0], sh_red[1]);
+  if (tid < PGTT_NSCAN) {
+    const float es = (kn && zmin < INFINITY) ? z - zmin : 0.f;
+    sh_est[tid] = es;
+    a.est[(long)e * PGTT_NSCAN + tid] = es;
+    a.known[(long)e * PGTT_NSCAN + tid] = kn ? 1 : 0;
+  }
+
+  // ---- phase F: obs_out = obs with the scan rows replaced
+  if (a.obs_out) {
+    __syncthreads();
+    const int od = a.obs_dim;
+    for (int k = tid; k < od; k += kLanes) {
+      const int j = k - a.scan_row0;
+      a.obs_out[(long)e * od + k] = (j >= 0 && j < PGTT_NSCAN) ? sh_est[j] : a.obs[(long)e * od + k];
+    }
+  }
+}
+
+// the config's checks; `who` prefixes the message
+int resolve(const PgttElevationConfig* c, const char* who) {
+  const std::string p = std::string(who) + ": ";
+  if (!c) return fail(PGTT_E_ARG, p + "null config");
+  if (c->width < 1 || c->width > PGTT_ELEVATION_MAX_DIM || c->height < 1 || c->height > PGTT_ELEVATION_MAX_DIM)
+    return fail(PGTT_E_ARG, p + "width and height must be in [1, PGTT_ELEVATION_MAX_DIM]");
+  if (!(c->fovy_deg > 0.f && c->fovy_deg < 180.f)) return fail(PGTT_E_ARG, p + "fovy_deg must be in (0, 180)");
+  if (!(c->near > 0.f) || !(c->near < c->far) || !std::isfinite(c->far)) return fail(PGTT_E_ARG, p + "need 0 < near < far, finite");
+  if (c->mount_body != 0) return fail(PGTT_E_ARG, p + "only a camera on the torso is supported (mount_body == 0)");
+  double qn = 0.0;
+  for (int i = 0; i < 4; i++) qn += (double)c->mount_quat[i] * c->mount_quat[i];
+  if (!(qn > 0.0) || !std::isfinite(qn)) return fail(PGTT_E_ARG, p + "mount_quat must be a non-zero quaternion");
+  for (int i = 0; i < 3; i++)
+    if (!std::isfinite(c->mount_pos[i])) return fail(PGTT_E_ARG, p + "mount_pos must be finite");
+  if (c->grid < PGTT_ELEVATION_MIN_GRID || c->grid > PGTT_ELEVATION_MAX_GRID) return fail(PGTT_E_ARG, p + "grid must be in [8, 96]");
+  if (!(c->res > 0.f) || !std::isfinite(c->res)) return fail(PGTT_E_ARG, p + "res must be positive and finite");
+  if (!(c->alpha > 0.f && c->alpha <= 1.f)) return fail(PGTT_E_ARG, p + "alpha must be in (0, 1]");
+  for (int i = 0; i < 3; i++)
+    if (!(c->self_half[i] >= 0.f) || !std::isfinite(c->self_half[i])) return fail(PGTT_E_ARG, p + "self_half must be >= 0 and finite");
+  if (!std::isfinite(c->scan_dist_x) || !std::isfinite(c->scan_dist_y)) return fail(PGTT_E_ARG, p + "scan_dist_x and scan_dist_y must be finite");
+  if (c->obs_dim < 1 || c->scan_row0 < 0 || (long)c->scan_row0 + PGTT_NSCAN > c->obs_dim) return fail(PGTT_E_ARG, p + "need 0 <= scan_row0 and scan_row0 + 117 <= obs_dim");
+  return PGTT_OK;
+}
+
+}  // namespace
+
+struct pgtt_elevation_map {
+  int device = 0, num_envs = 0;
+  PgttElevationConfig cfg{};
+  PgttElevationBuffers buf{};
+  bool bound = false;
+};
+
+extern "C" {
+
+const char* pgtt_elevation_last_error(void) { return g_err.c_str(); }
+const char* pgtt_elevation_build_info(void) { return "src=" PGTT_ELEVATION_SRC ";flavor=" PGTT_ELEVATION_FLAVOR; }
+int pgtt_elevation_sizeof_config(void) { return (int)sizeof(PgttElevationConfig); }
+int pgtt_elevation_sizeof_buffers(void) { return (int)sizeof(PgttElevationBuffers); }
+
+int pgtt_elevation_check(const PgttElevationConfig* cfg) { return resolve(cfg, "pgtt_elevation_check"); }
+
+int pgtt_elevation_create(const PgttElevationConfig* cfg, int device, int num_envs, pgtt_elevation_handle* out) {
+  if (!cfg || !out) return fail(PGTT_E_ARG, "pgtt_elevation_create: null argument");
+  *out = nullptr;
+  if (num_envs < 1) return fail(PGTT_E_ARG, "pgtt_elevation_create: num_envs must be >= 1");
+  if (int rc = resolve(cfg, "pgtt_elevation_create")) return rc;
+  if (int rc = check_device(device, "pgtt_elevation_create")) return rc;
+  pgtt_elevation_map* h = new pgtt_elevation_map();
+  h->device = device; h->num_envs = num_envs; h->cfg = *cfg;
+  double qn = 0.0;
+  for (int i = 0; i < 4; i++) qn += (double)cfg->mount_quat[i] * cfg->mount_quat[i];
+  qn = std::sqrt(qn);
+  for (int i = 0; i < 4; i++) h->cfg.mount_quat[i] = (float)(cfg->mount_quat[i] / qn);
+  *out = h;
+  return PGTT_OK;
+}
+
+int pgtt_elevation_destroy(pgtt_elevation_handle h) {
+  delete h;
+  return PGTT_OK;
+}
+
+int pgtt_elevation_bind(pgtt_elevation_handle h, const PgttElevationBuffers* bufs) {
+  if (!h || !bufs) return fail(PGTT_E_ARG, "pgtt_elevation_bind: null argument");
+  if (!bufs->state || !bufs->depth || !bufs->map || !bufs->origin || !bufs->est || !bufs->known)
+    return fail(PGTT_E_ARG, "pgtt_elevation_bind: state, depth, map, origin, est and known are required");
+  if (bufs->obs_out && !bufs->obs) return fail(PGTT_E_ARG, "pgtt_elevation_bind: obs is required with obs_out");
+  h->buf = *bufs;
+  h->bound = true;
+  return PGTT_OK;
+}
+
+int pgtt_elevation(pgtt_elevation_handle h, const uint8_t* clear_mask, int clear_all, int use_done, void* stream) {
+  if (!h) return fail(PGTT_E_ARG, "pgtt_elevation: null handle");
+  if (!h->bound) return fail(PGTT_E_STATE, "pgtt_elevation: no buffers bound (pgtt_elevation_bind first)");
+  HIP_TRY(hipSetDevice(h->device));
+  const PgttElevationConfig& c = h->cfg;
+  const PgttElevationBuffers& b = h->buf;
+  ElevArgs a{};
+  a.state = b.state; a.depth = b.depth; a.obs = b.obs; a.done = b.done; a.clear_mask = clear_mask;
+  a.map = b.map; a.origin = b.origin; a.est = b.est; a.known = b.known; a.obs_out = b.obs_out;
+  a.N = h->num_envs; a.W = c.width; a.H = c.height; a.G = c.grid; a.obs_dim = c.obs_dim; a.scan_row0 = c.scan_row0;
+  a.clear_all = clear_all ? 1 : 0; a.use_done = use_done ? 1 : 0;
+  a.self_on = (c.self_half[0] != 0.f || c.self_half[1] != 0.f || c.self_half[2] != 0.f) ? 1 : 0;
+  // 16-byte runs need every env's block to start on a 16-byte boundary
+  a.vec_map = ((c.grid * c.grid) % 4 == 0 && ((uintptr_t)b.map & 15) == 0) ? 1 : 0;
+  a.vec_img = ((c.width * c.height) % 4 == 0 && ((uintptr_t)b.depth & 15) == 0) ? 1 : 0;
+  const double th = std::tan(0.5 * (double)c.fovy_deg * 3.14159265358979323846 / 180.0);
+  a.near_m = c.near; a.far_m = c.far; a.res = c.res; a.alpha = c.alpha; a.tu = (float)(th * c.width / c.height); a.tv = (float)th;
+  a.sdx = c.scan_dist_x; a.sdy = c.scan_dist_y;
+  for (int i = 0; i < 3; i++) { a.mpos[i] = c.mount_pos[i]; a.self_half[i] = c.self_half[i]; }
+  for (int i = 0; i < 4; i++) a.mquat[i] = c.mount_quat[i];
+  hipLaunchKernelGGL(elevation_kernel, dim3(h->num_envs), dim3(kLanes), (size_t)c.grid * c.grid * sizeof(unsigned), (hipStream_t)stream, a);
+  HIP_TRY(hipGetLastError());
+  return PGTT_OK;
+}
+
+}  // extern "C"

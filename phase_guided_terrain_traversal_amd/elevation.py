@@ -1,0 +1,164 @@
+"""Depth-fused elevation map: a geometric height scan per env (libpgtt_elevation.so, include/pgtt_elevation.h).  The onboard depth image is
+unprojected with the camera pose, fused into a rolling robot-centred map of world heights, and the observation's 117 scan rows are sampled from
+the map: what a deployed robot's elevation-mapping stack provides, with nothing to train.
+
+    em = ElevationMap(env, grid=64, res=0.04, alpha=1.0)     # env: a Joystick with a torso depth camera of period 1
+    em.tick(clear_all=True)                                  # one launch on the env's current stream, no synchronisation
+    em.map, em.origin, em.est, em.known, em.obs              # [N, G, G] heights (NaN = unknown), [N, 2], [N, 117], [N, 117] uint8, [N, obs_dim]
+
+`Joystick(..., depth=dict(...), elevation=dict(...) | True)` owns one and ticks it behind the camera (env.elevation_obs).  The module is not imported
+by env.py unless an elevation map is asked for.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import os
+from typing import Dict, Optional, Sequence
+
+import torch
+
+from . import _sidelib, abi
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+LIB_PATH = os.path.join(_HERE, "libpgtt_elevation.so")
+_LIB: Optional[C.CDLL] = None
+
+# include/pgtt_elevation.h
+MAX_DIM, MIN_GRID, MAX_GRID = 256, 8, 96
+NSCAN = abi.NSCAN
+SCAN_ROW0 = {"pgtt": 38, "baseline": 30}           # perceive.SCAN_ROW0: the scan rows sit between phase / joint_vel and gait_freq / last_act
+EXPORTS = ["pgtt_elevation_check", "pgtt_elevation_create", "pgtt_elevation_destroy", "pgtt_elevation_bind", "pgtt_elevation",
+           "pgtt_elevation_sizeof_config", "pgtt_elevation_sizeof_buffers", "pgtt_elevation_build_info", "pgtt_elevation_last_error"]
+# Joystick(elevation=True) / evaluate.py --elevation: a 2.56 m window of 4 cm cells, the newest view replaces the old one, and a box around the
+# torso that drops the robot's own legs from a camera that sees them - settings, not measured facts about a robot
+DEFAULTS = dict(grid=64, res=0.04, alpha=1.0, self_half=(0.45, 0.25, 0.45))
+
+f, i32 = C.c_float, C.c_int32
+
+
+class PgttElevationConfig(C.Structure):
+    _fields_ = [("width", i32), ("height", i32), ("fovy_deg", f), ("near", f), ("far", f), ("mount_body", i32), ("mount_pos", f * 3),
+                ("mount_quat", f * 4), ("grid", i32), ("res", f), ("alpha", f), ("self_half", f * 3), ("scan_dist_x", f), ("scan_dist_y", f),
+                ("obs_dim", i32), ("scan_row0", i32)]
+
+
+class PgttElevationBuffers(C.Structure):
+    _fields_ = [("state", C.c_void_p), ("depth", C.c_void_p), ("obs", C.c_void_p), ("done", C.c_void_p), ("map", C.c_void_p),
+                ("origin", C.c_void_p), ("est", C.c_void_p), ("known", C.c_void_p), ("obs_out", C.c_void_p)]
+
+
+assert C.sizeof(PgttElevationConfig) == 92 and C.sizeof(PgttElevationBuffers) == 72
+
+
+class ElevationError(RuntimeError):
+    pass
+
+
+def lib() -> C.CDLL:
+    """libpgtt_elevation.so at LIB_PATH, as it is when the library is first asked for"""
+    global _LIB
+    if _LIB is None:
+        vp, cp = C.c_void_p, C.POINTER(PgttElevationConfig)
+        _LIB = _sidelib.load(LIB_PATH, ElevationError, {
+            "pgtt_elevation_last_error": (C.c_char_p, None), "pgtt_elevation_build_info": (C.c_char_p, None),
+            "pgtt_elevation_check": (None, [cp]), "pgtt_elevation_create": (None, [cp, C.c_int, C.c_int, C.POINTER(vp)]),
+            "pgtt_elevation_destroy": (None, [vp]), "pgtt_elevation_bind": (None, [vp, C.POINTER(PgttElevationBuffers)]),
+            "pgtt_elevation": (None, [vp, vp, C.c_int, C.c_int, vp]),
+        }, {"pgtt_elevation_sizeof_config": PgttElevationConfig, "pgtt_elevation_sizeof_buffers": PgttElevationBuffers})
+    return _LIB
+
+
+def check(rc: int) -> None:
+    _sidelib.check(rc, lib(), "pgtt_elevation", ElevationError)
+
+
+def build_info() -> dict:
+    """{"src": srchash.side_sha256("elevation") at build time, "flavor": "product" or an experiment's name}"""
+    return _sidelib.build_info(lib(), "pgtt_elevation")
+
+
+def settings(overrides=None) -> Dict:
+    """ElevationMap's keyword arguments: DEFAULTS with `overrides` on top (True or None = the defaults)"""
+    return {**DEFAULTS, **({} if overrides is None or overrides is True else dict(overrides))}
+
+
+def config_struct(width, height, fovy, near, far, mount_pos=(0.0, 0.0, 0.0), mount_quat=(1.0, 0.0, 0.0, 0.0), mount_body=0, grid=64, res=0.04,
+                  alpha=1.0, self_half=(0.0, 0.0, 0.0), scan_dist_x=0.1, scan_dist_y=0.1, obs_dim=abi.OBS, scan_row0=38) -> PgttElevationConfig:
+    """no checks: the library makes its own"""
+    c = PgttElevationConfig()
+    c.width, c.height, c.fovy_deg, c.near, c.far, c.mount_body = int(width), int(height), float(fovy), float(near), float(far), int(mount_body)
+    c.mount_pos[:] = [float(x) for x in mount_pos]
+    c.mount_quat[:] = [float(x) for x in mount_quat]
+    c.grid, c.res, c.alpha = int(grid), float(res), float(alpha)
+    c.self_half[:] = [float(x) for x in self_half]
+    c.scan_dist_x, c.scan_dist_y, c.obs_dim, c.scan_row0 = float(scan_dist_x), float(scan_dist_y), int(obs_dim), int(scan_row0)
+    return c
+
+
+class ElevationMap(_sidelib.Handle):
+    """The elevation map of one Joystick with a depth camera: owns the handle and the tensors `map` [N, G, G] (world heights, NaN = unknown; world
+    cell (ix, iy) at map[ix mod G, iy mod G]), `origin` [N, 2] int32 (the base's cell), `est` [N, 117], `known` [N, 117] uint8 and `obs`
+    [N, obs_dim] (the obs_out buffer: the env's observation with the scan rows replaced by est).  The camera's intrinsics and mount are those of
+    env.depth_camera.  grid / res: the window is grid x grid cells of res metres; alpha: fusion gain in (0, 1], 1 = the newest view replaces the
+    old; self_half: half extents of a box in the base frame whose points are dropped (the robot's own body in a see_robot camera), zeros = none.
+    The defaults are settings, not facts.
+    Runs on the env's device and current stream; reads env.depth, env.buffers["state" | "obs_state" | "done"] and writes nothing but its own tensors."""
+    _prefix, _check = "pgtt_elevation", staticmethod(check)
+
+    def __init__(self, env, grid: int = 64, res: float = 0.04, alpha: float = 1.0, self_half: Sequence[float] = (0.45, 0.25, 0.45)):
+        cam = getattr(env, "depth_camera", None)
+        if cam is None:
+            raise ValueError("ElevationMap needs an env with a depth camera: Joystick(..., depth=dict(...))")
+        cc = cam.config
+        if cc.mount_body != 0:
+            raise ValueError(f"ElevationMap supports a camera on the torso only (mount_body == 0), not on body {cc.mount_body}")
+        if cc.every != 1:
+            raise ValueError(f"ElevationMap needs a camera of period 1 (every={cc.every}): a stale image under a moved pose would be unprojected wrongly")
+        self.env, self.grid, self.res, self.alpha = env, int(grid), float(res), float(alpha)
+        od = env.observation_size["state"]
+        self.config = config_struct(cc.width, cc.height, cc.fovy_deg, cc.near, cc.far, list(cc.mount_pos), list(cc.mount_quat), cc.mount_body, grid, res,
+                                    alpha, self_half, env.config["scan_dist_x"], env.config["scan_dist_y"], od, SCAN_ROW0[env.method])
+        self._lib = lib()
+        self._h = C.c_void_p()
+        check(self._lib.pgtt_elevation_create(C.byref(self.config), env.device.index or 0, env.num_envs, C.byref(self._h)))
+        dev, n = env.device, env.num_envs
+        self.map = torch.full((n, self.grid, self.grid), float("nan"), dtype=torch.float32, device=dev)
+        self.origin = torch.zeros((n, 2), dtype=torch.int32, device=dev)
+        self.est = torch.zeros((n, NSCAN), dtype=torch.float32, device=dev)
+        self.known = torch.zeros((n, NSCAN), dtype=torch.uint8, device=dev)
+        self.obs = torch.zeros((n, od), dtype=torch.float32, device=dev)
+        self._mask = None
+        self.bind()
+
+    def bind(self) -> None:
+        """(re)bind: the env's state, image, observation and done flags, this object's outputs"""
+        b = PgttElevationBuffers()
+        eb = self.env.buffers
+        b.state, b.depth, b.obs = eb["state"].data_ptr(), self.env.depth.data_ptr(), eb["obs_state"].data_ptr()
+        b.done = eb["done"].data_ptr() if eb.get("done") is not None else None
+        b.map, b.origin, b.est, b.known, b.obs_out = (t.data_ptr() for t in (self.map, self.origin, self.est, self.known, self.obs))
+        check(self._lib.pgtt_elevation_bind(self._h, C.byref(b)))
+
+    def tick(self, clear_mask: Optional[torch.Tensor] = None, clear_all: bool = False, use_done: bool = False) -> torch.Tensor:
+        """integrate the env's current image under its current pose and sample the scan: one launch on the env's current stream, no
+        synchronisation.  Before integrating, the maps of the envs with clear_mask[e] != 0 ([N] uint8 / bool), of every env (clear_all) or of the
+        envs whose done flag is set (use_done) are cleared."""
+        mp = None
+        if clear_mask is not None:
+            self._mask = clear_mask.to(self.env.device, torch.uint8).contiguous()      # kept alive until the next tick: the launch is asynchronous
+            assert self._mask.shape == (self.env.num_envs,)
+            mp = self._mask.data_ptr()
+        check(self._lib.pgtt_elevation(self._h, mp, int(bool(clear_all)), int(bool(use_done)), torch.cuda.current_stream(self.env.device).cuda_stream))
+        return self.obs
+
+    def world_cells(self) -> torch.Tensor:
+        """[N, G, G, 2] int64: the world cell (ix, iy) each slot of `map` holds under the current window"""
+        g = self.grid
+        s = torch.arange(g, device=self.map.device)
+        lo = self.origin.long() - g // 2                                                # [N, 2]
+        wx = lo[:, 0, None] + (s[None] - lo[:, 0, None]) % g
+        wy = lo[:, 1, None] + (s[None] - lo[:, 1, None]) % g
+        return torch.stack([wx[:, :, None].expand(-1, g, g), wy[:, None, :].expand(-1, g, g)], dim=-1)
+
+    def set_terrain(self, terrain) -> None:
+        raise AttributeError("ElevationMap has no terrain")

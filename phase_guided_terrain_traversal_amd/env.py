@@ -29,7 +29,8 @@ class Joystick:
                  autoreset: bool = False, debug_contacts: bool = False, env_id_offset: int = 0,
                  model: Optional[Dict[str, Any]] = None, layout: Optional[str] = None, observe_form: Optional[str] = None,
                  test_hooks: bool = False, interval_sums: bool = False, push: Optional[Dict[str, Any]] = None, xfrc: bool = False,
-                 curriculum: Optional[Dict[str, Any]] = None, level: Optional[torch.Tensor] = None, depth: Optional[Dict[str, Any]] = None, student=None):
+                 curriculum: Optional[Dict[str, Any]] = None, level: Optional[torch.Tensor] = None, depth: Optional[Dict[str, Any]] = None, student=None,
+                 elevation=None):
         """layout: "auto" | "quad" | "oct" | "hex" lane layout of physics_kernel (PgttConfig.lane_layout; results are bit-identical
         across batch sizes and shards within one layout); observe_form: "fused" | "split"; test_hooks: allow set_test_overrides
         (fixture replay only); interval_sums: keep per-env running sums of the step outputs for a logging trainer (PgttBuffers.interval_sums);
@@ -48,9 +49,22 @@ class Joystick:
         is allocated, loaded, bound or launched.
         student: a perceive.ScanEstimator or the path of a saved one (needs depth): the student perception module (libpgtt_perceive.so) runs behind
         the camera after every step and reset; `env.student_obs` is the [N, obs_dim] observation with the 117 scan rows replaced by its estimate.  A
-        side output like the image.  None: the library is not opened."""
+        side output like the image.  None: the library is not opened.
+        elevation: True or elevation.ElevationMap's arguments over elevation.DEFAULTS, e.g. dict(grid=64, res=0.04, alpha=1.0) (needs depth, with the
+        camera on the torso and every=1): a depth-fused elevation map per env (libpgtt_elevation.so) is ticked behind the camera - after reset() with
+        the reset envs' maps cleared, after step() with the maps of the envs whose episode just ended cleared; `env.elevation_obs` is the
+        [N, obs_dim] observation with the 117 scan rows sampled from the map, `env.elevation_known` [N, 117] says which of them the map knew,
+        `env.elevation_map` is the ElevationMap.  A side output like the image; may be combined with student.  None: the library is not opened.
+        The map has memory, so what moves an env must clear it: reset() and step() do, set_terrain() forgets every map, but with a deferred
+        curriculum (step(action, curriculum=False), then curriculum_step()) the envs are restarted AFTER the step's tick, as they are after the
+        camera's - such a caller ticks the camera and then `env.elevation_map.tick(use_done=True)` once more after curriculum_step()."""
         if student is not None and depth is None:
             raise ValueError("Joystick(student=...) needs depth=dict(...): the student reads the onboard depth image")
+        if elevation is not None and elevation is not False and depth is None:
+            raise ValueError("Joystick(elevation=...) needs depth=dict(...): the elevation map is fused from the onboard depth image")
+        if elevation is not None and elevation is not False and (int(dict(depth).get("every", 1)) != 1 or int(dict(depth).get("mount_body", 0)) != 0):
+            raise ValueError("Joystick(elevation=...) needs a camera on the torso (mount_body=0) with every=1: a stale image under a moved pose "
+                             "would be unprojected wrongly")
         self.level_start = None
         if isinstance(terrain, (list, tuple)):
             terrain, self.level_start = _curriculum.stack_levels(terrain)
@@ -157,6 +171,10 @@ class Joystick:
             from . import perceive as _perceive               # libpgtt_perceive.so is opened only here
             est = _perceive.ScanEstimator.load(student) if isinstance(student, (str, os.PathLike)) else student
             self.student = _perceive.StudentPerception(self, est)
+        self.elevation_map = None
+        if elevation is not None and elevation is not False:
+            from . import elevation as _elevation             # libpgtt_elevation.so is opened only here
+            self.elevation_map = _elevation.ElevationMap(self, **_elevation.settings(elevation))
 
     # ---- reference-compatible properties
     @property
@@ -239,6 +257,16 @@ class Joystick:
         """[N, obs_dim] float32: the observation with its scan rows replaced by the student's estimate from the depth image, or None without one"""
         return None if self.student is None else self.student.obs
 
+    @property
+    def elevation_obs(self) -> Optional[torch.Tensor]:
+        """[N, obs_dim] float32: the observation with its scan rows sampled from the depth-fused elevation map, or None without one"""
+        return None if self.elevation_map is None else self.elevation_map.obs
+
+    @property
+    def elevation_known(self) -> Optional[torch.Tensor]:
+        """[N, 117] uint8: 1 where the elevation map knew the scan point's cell, or None without a map"""
+        return None if self.elevation_map is None else self.elevation_map.known
+
     def push_step(self) -> None:
         """the push scheduler alone (pgtt_push): what step() runs first when pushes are on; for callers of physics() / observe()"""
         native.check(self._lib.pgtt_push(self._h, self._stream()))
@@ -250,7 +278,8 @@ class Joystick:
 
     def curriculum_step(self) -> None:
         """the curriculum alone (pgtt_curriculum): what step() runs last when the curriculum is on; for callers of physics() / observe() and of
-        step(action, curriculum=False)"""
+        step(action, curriculum=False).  The camera, the student and the elevation map were ticked by that step, before this restart: their
+        outputs for a restarted env are the old pose's until the next step, and its map keeps that one image of the old place (see `elevation`)"""
         native.check(self._lib.pgtt_curriculum(self._h, self._stream()))
 
     def curriculum_stats(self) -> Dict[str, Any]:
@@ -265,14 +294,16 @@ class Joystick:
                 "mean_level": float(self.buffers["level"].float().mean())}
 
     def set_terrain(self, terrain: np.ndarray) -> None:
-        """replace the resident terrain table (the depth camera's too).  The tables are reallocated: a graph captured before this call still
-        points at the old ones and must be captured again, not replayed"""
+        """replace the resident terrain table (the depth camera's too; an elevation map forgets what it saw of the old one).  The tables are
+        reallocated: a graph captured before this call still points at the old ones and must be captured again, not replayed"""
         t = np.ascontiguousarray(terrain, dtype=np.float32)
         assert t.ndim == 3 and t.shape[2] == 10 and t.shape[1] <= abi.MAX_BOX
         native.check(self._lib.pgtt_set_terrain(self._h, t.ctypes.data, t.shape[0], t.shape[1]))
         self.terrain = t
         if getattr(self, "depth_camera", None) is not None:
             self.depth_camera.set_terrain(t)
+        if getattr(self, "elevation_map", None) is not None:
+            self.elevation_map.map.fill_(float("nan"))                # heights of the old terrain: the next tick starts from an empty map
 
     def _stream(self) -> int:
         return torch.cuda.current_stream(self.device).cuda_stream
@@ -291,6 +322,8 @@ class Joystick:
             self.depth_camera.tick(force=True)
         if self.student is not None:
             self.student.tick()
+        if self.elevation_map is not None:
+            self.elevation_map.tick(clear_mask=mask, clear_all=mask is None)
         return self._obs()
 
     def step(self, action: torch.Tensor, curriculum: bool = True):
@@ -306,6 +339,8 @@ class Joystick:
             self.depth_camera.tick()
         if self.student is not None:
             self.student.tick()
+        if self.elevation_map is not None:
+            self.elevation_map.tick(use_done=True)
         info = {"metrics": self.buffers["metrics"], "episode_metrics": self.buffers["ep_metrics"]}
         return self._obs(), self.buffers["reward"], self.buffers["done"], info
 
@@ -350,6 +385,9 @@ class Joystick:
         return p.value, o.value, k.value
 
     def close(self) -> None:
+        if getattr(self, "elevation_map", None) is not None:
+            self.elevation_map.close()
+            self.elevation_map = None
         if getattr(self, "student", None) is not None:
             self.student.close()
             self.student = None

@@ -1,0 +1,225 @@
+"""Time and accuracy of the depth-fused elevation map, with the protocol of DESIGN.md 14 / 15: 4096 envs, level4 with per-env variants
+from domain_randomize(seed=0), 64x48 images of the default camera, G = 64, poses after 40 control steps of small random actions; device events
+around 20 back-to-back calls after 5 warm-up calls, median [min, max] of 11 such windows.
+
+    python tools/gpu_elevation_time.py [--out profiles/NAME.txt] [--accuracy]
+
+(i) pgtt_elevation (one launch); (ii) the same six steps as torch ops (scatter_reduce_ with amax) - what (i) replaces, the yardstick; (iii) the
+camera tick; (iv) the student's two launches; (v) the env step (no camera).
+--accuracy: policy177 acting on the true observation, 1000 envs, full domain randomisation, auto-reset; after 50 steps, 200 steps of RMSE of the map's
+est against perceive.scan_target over the known points, per band, and the known share per band."""
+import argparse
+import math
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from phase_guided_terrain_traversal_amd import abi, configs, elevation, mjcf, perceive  # noqa: E402
+from phase_guided_terrain_traversal_amd.env import Joystick  # noqa: E402
+from phase_guided_terrain_traversal_amd.policy import load_policy  # noqa: E402
+from phase_guided_terrain_traversal_amd.randomize import domain_randomize  # noqa: E402
+
+
+def window_us(fn, calls=20, warm=5, windows=11):
+    for _ in range(warm):
+        fn()
+    out = []
+    for _ in range(windows):
+        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        s.record()
+        for _ in range(calls):
+            fn()
+        e.record()
+        e.synchronize()
+        out.append(1e3 * s.elapsed_time(e) / calls)
+    return float(np.median(out)), min(out), max(out)
+
+
+def qmat(q):
+    w, x, y, z = q.unbind(-1)
+    return torch.stack([w * w + x * x - y * y - z * z, 2 * (x * y - w * z), 2 * (x * z + w * y),
+                        2 * (x * y + w * z), w * w - x * x + y * y - z * z, 2 * (y * z - w * x),
+                        2 * (x * z - w * y), 2 * (y * z + w * x), w * w - x * x - y * y + z * z], -1).view(-1, 3, 3)
+
+
+def qmul(a, b):
+    aw, ax, ay, az = a.unbind(-1)
+    bw, bx, by, bz = b.unbind(-1)
+    return torch.stack([aw * bw - ax * bx - ay * by - az * bz, aw * bx + ax * bw + ay * bz - az * by,
+                        aw * by - ax * bz + ay * bw + az * bx, aw * bz + ax * by - ay * bx + az * bw], -1)
+
+
+class TorchElevation:
+    """the six steps of include/pgtt_elevation.h as batched torch ops on the same buffers' shapes (its own map and origin)"""
+
+    def __init__(self, em: elevation.ElevationMap):
+        c, env = em.config, em.env
+        self.em, self.env, self.G, self.res, self.alpha = em, env, c.grid, c.res, c.alpha
+        dev = env.device
+        th = math.tan(math.radians(c.fovy_deg) / 2)
+        j, i = torch.arange(c.width, device=dev) + 0.5, torch.arange(c.height, device=dev) + 0.5
+        u, v = (2 * j / c.width - 1) * th * c.width / c.height, (1 - 2 * i / c.height) * th
+        self.u, self.v = u[None, :].expand(c.height, -1).reshape(-1), v[:, None].expand(-1, c.width).reshape(-1)
+        self.mpos = torch.tensor(list(c.mount_pos), device=dev)
+        mq = torch.tensor(list(c.mount_quat), device=dev)
+        self.mq = mq / mq.norm()
+        self.half = torch.tensor(list(c.self_half), device=dev)
+        self.near, self.far, self.r0 = c.near, c.far, c.scan_row0
+        r, cc = torch.arange(abi.NSCAN, device=dev) // abi.SCAN_W, torch.arange(abi.NSCAN, device=dev) % abi.SCAN_W
+        self.ox, self.oy = ((abi.SCAN_H - 1) * 0.5 - r) * c.scan_dist_x, ((abi.SCAN_W - 1) * 0.5 - cc) * c.scan_dist_y
+        n = env.num_envs
+        self.map = torch.full((n, self.G, self.G), float("nan"), device=dev)
+        self.origin = torch.zeros((n, 2), dtype=torch.long, device=dev)
+        self.s = torch.arange(self.G, device=dev)
+        self.env_index = torch.arange(n, device=dev)[:, None]
+
+    @torch.no_grad()
+    def tick(self, clear=None):
+        S, G, res = self.env.buffers["state"], self.G, self.res
+        n = S.shape[1]
+        b, q = S[0:3].T, S[3:7].T
+        q = q / q.norm(dim=1, keepdim=True)
+        R = qmat(q)
+        cam = b + (R @ self.mpos)
+        Rc = qmat(qmul(q, self.mq.expand(n, 4)))
+        fwd, up = Rc[:, :, 0], Rc[:, :, 2]
+        right = torch.linalg.cross(fwd, up)
+        d = self.env.depth.reshape(n, -1)
+        valid = (d > self.near) & (d < self.far)
+        dirs = fwd[:, None] + self.u[None, :, None] * right[:, None] + self.v[None, :, None] * up[:, None]
+        p = cam[:, None] + torch.where(valid, d, torch.ones_like(d))[..., None] * dirs
+        local = torch.einsum("npi,nij->npj", p - b[:, None], R)
+        if bool(self.half.any()):
+            valid &= ~(local.abs() <= self.half).all(-1)
+        # 1, 2
+        new = torch.floor(b[:, :2] / res).long()
+        lo_new, lo_old = new - G // 2, self.origin - G // 2
+        for ax in (0, 1):
+            stale = (lo_new[:, ax, None] + (self.s - lo_new[:, ax, None]) % G) != (lo_old[:, ax, None] + (self.s - lo_old[:, ax, None]) % G)
+            if clear is not None:
+                stale |= clear[:, None]
+            self.map.masked_fill_(stale[:, :, None] if ax == 0 else stale[:, None, :], float("nan"))
+        self.origin = new
+        # 3
+        cell = torch.floor(p[..., :2] / res).long()
+        rel = cell - lo_new[:, None]
+        use = valid & ((rel >= 0) & (rel < G)).all(-1)
+        slot = cell % G
+        flat = (self.env_index * G + slot[..., 0]) * G + slot[..., 1]
+        m = torch.full((n * G * G,), float("-inf"), device=S.device)
+        m.scatter_reduce_(0, flat[use], p[..., 2][use], "amax")
+        m = m.view(n, G, G)
+        # 4
+        t = m > float("-inf")
+        h = self.map
+        self.map = torch.where(t, torch.where(h.isnan(), m, h + self.alpha * (m - h)), h)
+        # 5
+        yaw = torch.atan2(2 * (q[:, 0] * q[:, 3] + q[:, 1] * q[:, 2]), 1 - 2 * (q[:, 2] ** 2 + q[:, 3] ** 2))
+        cy, sy = yaw.cos()[:, None], yaw.sin()[:, None]
+        xy = torch.stack([b[:, 0, None] + self.ox * cy - self.oy * sy, b[:, 1, None] + self.ox * sy + self.oy * cy], -1)
+        c = torch.floor(xy / res).long()
+        rel = c - lo_new[:, None]
+        inside = ((rel >= 0) & (rel < G)).all(-1)
+        z = self.map[self.env_index, c[..., 0] % G, c[..., 1] % G]
+        known = inside & ~z.isnan()
+        zk = torch.where(known, z, torch.full_like(z, float("inf")))
+        zmin = zk.min(dim=1, keepdim=True).values
+        est = torch.where(known, z - zmin, torch.zeros_like(z))
+        # 6
+        obs = self.env.buffers["obs_state"]
+        return torch.cat([obs[:, :self.r0], est, obs[:, self.r0 + abi.NSCAN:]], 1), est, known
+
+
+def accuracy(terrain, steps_warm=50, steps=200, n=1000):
+    dr = domain_randomize(mjcf.load_model("stairs"), n, seed=0, terrain=terrain)
+    kw = dict(params=torch.from_numpy(dr["params"]), variant=torch.from_numpy(dr["variant"]), box_friction=torch.from_numpy(dr["box_friction"]))
+    env = Joystick("stairs", configs.evaluation_config("pgtt"), num_envs=n, terrain=terrain, device="cuda:0", autoreset=True, depth={}, elevation=True, **kw)
+    pi = load_policy("policy177", "cuda:0")
+    env.reset(0)
+    se = {k: 0.0 for k in perceive.BANDS}
+    cnt = {k: 0.0 for k in perceive.BANDS}
+    tot = {k: 0.0 for k in perceive.BANDS}
+    fresh_se = fresh_cnt = 0.0
+    age = torch.zeros(n, device="cuda:0")
+    with torch.no_grad():
+        for t in range(steps_warm + steps):
+            _, _, done, _ = env.step(pi(env.buffers["obs_state"]))
+            age = torch.where(done > 0, torch.zeros_like(age), age + 1)
+            if t < steps_warm:
+                continue
+            # the env's scan_z is the step's; a done env's state rows are the new episode's, so its target is not this pose's: leave it out
+            live = (done == 0)[:, None]
+            err, known = env.elevation_map.est - perceive.scan_target(env), (env.elevation_known > 0) & live
+            for k, sl in perceive.BANDS.items():
+                se[k] += float((err[:, sl] ** 2 * known[:, sl]).sum()); cnt[k] += float(known[:, sl].sum()); tot[k] += float(live.sum()) * (sl.stop - sl.start)
+            young = known & (age < 50)[:, None]
+            fresh_se += float((err ** 2 * young).sum()); fresh_cnt += float(young.sum())
+    env.close()
+    lines = [f"accuracy: policy177 on the true observation, {n} envs, level4, full DR, steps {steps_warm}..{steps_warm + steps}; est against perceive.scan_target over the known points"]
+    for k in perceive.BANDS:
+        lines.append(f"  {k:7s} rmse {math.sqrt(se[k] / max(cnt[k], 1)):.4f} m, known share {cnt[k] / max(tot[k], 1):.3f}")
+    allse, allcnt = sum(se.values()), sum(cnt.values())
+    lines.append(f"  all     rmse {math.sqrt(allse / max(allcnt, 1)):.4f} m; within 50 steps of a reset: rmse {math.sqrt(fresh_se / max(fresh_cnt, 1)):.4f} m on {fresh_cnt / max(allcnt, 1):.3f} of the known points; "
+                 f"older: rmse {math.sqrt((allse - fresh_se) / max(allcnt - fresh_cnt, 1)):.4f} m")
+    return lines
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--num_envs", type=int, default=4096)
+    ap.add_argument("--out", type=str, default=None)
+    ap.add_argument("--accuracy", action="store_true")
+    args = ap.parse_args()
+    n = args.num_envs
+    terrain = np.load(os.path.join(ROOT, "phase_guided_terrain_traversal_amd", "assets", "terrains", "level4.npy"))
+    dr = domain_randomize(mjcf.load_model("stairs"), n, seed=0, terrain=terrain)
+    kw = dict(params=torch.from_numpy(dr["params"]), variant=torch.from_numpy(dr["variant"]), box_friction=torch.from_numpy(dr["box_friction"]))
+    torch.manual_seed(0)
+    env = Joystick("stairs", configs.training_config(), num_envs=n, terrain=terrain, device="cuda:0", depth={}, student=perceive.ScanEstimator(), elevation=True, **kw)
+    plain = Joystick("stairs", configs.training_config(), num_envs=n, terrain=terrain, device="cuda:0", **kw)
+    g = torch.Generator().manual_seed(1)
+    for e in (env, plain):
+        e.reset(0)
+    em = env.elevation_map
+    te = TorchElevation(em)
+    te.tick()
+    for _ in range(40):
+        act = (0.2 * torch.randn(n, 12, generator=g)).clamp(-1, 1).cuda()
+        env.step(act); plain.step(act)
+        te.tick()
+    torch.cuda.synchronize()
+    _, est_t, known_t = te.tick()
+    em.tick()
+    both = known_t & (em.known > 0)
+    agree = float(((est_t - em.est).abs() * both).max())
+    same_known = float((known_t == (em.known > 0)).float().mean())
+    rows = [("(i)   pgtt_elevation, one launch", window_us(em.tick)),
+            ("(ii)  the six steps as torch ops (scatter_reduce_ amax)", window_us(te.tick)),
+            ("(iii) camera tick (force)", window_us(lambda: env.depth_camera.tick(force=True))),
+            ("(iv)  pgtt_perceive, two launches", window_us(env.student.tick)),
+            ("(v)   env step, no camera", window_us(lambda: plain.step(act)))]
+    c = em.config
+    traffic = n * (2 * 4 * c.grid ** 2 + 4 * c.width * c.height + 2 * 4 * c.obs_dim + 5 * abi.NSCAN)
+    lines = [f"{n} envs, level4, {c.width}x{c.height}, G = {c.grid}, res = {c.res:.3f}, alpha = {c.alpha}; us per call, median [min, max] of 11 windows of 20 calls",
+             f"libpgtt_elevation build: {elevation.build_info()}"]
+    lines += [f"{name:60s} {m:9.1f} [{lo:.1f}, {hi:.1f}]" for name, (m, lo, hi) in rows]
+    lines.append(f"(ii) / (i) = {rows[1][1][0] / rows[0][1][0]:.2f};  upper bound of (i)'s HBM traffic (whole map read and written) {traffic / 1e6:.1f} MB -> "
+                 f"{traffic / rows[0][1][0] / 1e6:.2f} TB/s at the median")
+    lines.append(f"torch statement against the kernel after 41 ticks: known flags equal on {same_known:.5f} of the points, max |est difference| where both know = {agree:.2e}")
+    env.close(); plain.close()
+    if args.accuracy:
+        lines += accuracy(terrain)
+    text = "\n".join(lines)
+    print(text)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        open(args.out, "w").write(text + "\n")
+
+
+if __name__ == "__main__":
+    main()
