@@ -1,0 +1,102 @@
+/*
+ * pgtt_learn.h - libpgtt_learn.so: the pieces of one PPO minibatch update that pgtt_train.h does not have, so that the whole update of
+ * phase_guided_terrain_traversal_amd/learn.py::NativeLearner is hand-written HIP (gfx950) on ONE stream: the minibatch gather with the
+ * observation and advantage normalisation, the Linear layers forward (bias, SiLU) and their data gradient on fp32 MFMA, the value loss,
+ * the global-norm clip with Adam over one flat parameter buffer, and generalised advantage estimation.  The policy loss and the weight /
+ * bias gradients stay pgtt_ppo_policy_loss / pgtt_ppo_linear_backward of libpgtt.so (pgtt_train.h).  Like pgtt_train.h these replace no
+ * entry point of the reference (its PPO is Brax's, configured at training/train.py:135-161); the arithmetic they restate is that of
+ * phase_guided_terrain_traversal_amd/ppo.py, held to the fp64 statement in tests/ppo_reference.py.
+ *
+ * Conventions as in pgtt_train.h: plain C, device pointers (float32 unless said otherwise), every kernel enqueued on the caller's stream,
+ * nothing synchronises and nothing allocates (every call can be captured in a HIP graph), 0 or a negative PGTT_E_* code with the message
+ * in pgtt_learn_last_error().  Every entry refuses a NULL pointer (where NULL is not named as allowed) or a non-positive size with
+ * PGTT_E_ARG and writes nothing.  Weights are torch's [out][in] layout as they are; nothing is packed.  Sums have a fixed order: two calls
+ * on equal inputs give equal bits.
+ */
+#ifndef PGTT_LEARN_H_
+#define PGTT_LEARN_H_
+#include "pgtt.h"
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* One minibatch out of the flat [rows] batch: for i < B, r = idx[i] (clamped into [0, rows): an index outside reads no foreign memory),
+ *   x_s[i][:] = (obs[r][:] - mean_s) / std_s,   x_p[i][:] = (priv[r][:] - mean_p) / std_p   (one subtraction, one correctly rounded division),
+ *   u_out[i][:] = u[r][:],  logp_out[i] = logp[r],  ret_out[i] = ret[r]   (copies, equal bits),
+ *   adv_out[i] = (a_i - mean a) / (sqrt(mean (a - mean a)^2) + 1e-8),  a_i = adv[r]   (population standard deviation, two passes).
+ * Two launches: one workgroup per row, then a single workgroup that forms the two sums over B in a fixed order and normalises adv_out in place. */
+typedef struct PgttLearnGatherArgs {
+  const int64_t* idx;          /* [B] rows of the batch */
+  const float* obs;            /* [rows][obs_dim] */
+  const float* priv;           /* [rows][priv_dim] */
+  const float* u;              /* [rows][act_dim] */
+  const float* logp;           /* [rows] */
+  const float* adv;            /* [rows] raw advantages */
+  const float* ret;            /* [rows] value targets */
+  const float* mean_s;         /* [obs_dim] */
+  const float* std_s;          /* [obs_dim] */
+  const float* mean_p;         /* [priv_dim] */
+  const float* std_p;          /* [priv_dim] */
+  float* x_s;                  /* [B][obs_dim] */
+  float* x_p;                  /* [B][priv_dim] */
+  float* u_out;                /* [B][act_dim] */
+  float* logp_out;             /* [B] */
+  float* adv_out;              /* [B] normalised */
+  float* ret_out;              /* [B] */
+  int32_t B, rows, obs_dim, priv_dim, act_dim;
+} PgttLearnGatherArgs;
+int pgtt_learn_gather(const PgttLearnGatherArgs* args, void* stream);
+
+/* Z = X W^T + b,  Y = act ? silu(Z) : Z   with X [K][M], W [N][M], b [N], Y and Z [K][N]; silu(z) = z / (1 + expf(-z)).
+ * fp32 MFMA (v_mfma_f32_16x16x4_f32: exact fp32 products, fp32 sums), the contraction runs over m in ascending blocks of 16.  Any K, M, N >= 1:
+ * the tails are masked in the kernel.  z_KxN receives the pre-activation for the backward pass; NULL is allowed when act == 0 (refused when act != 0).
+ * One launch. */
+int pgtt_learn_linear_forward(const float* x_KxM, const float* w_NxM, const float* b_N, int K, int M, int N, int act,
+                              float* y_KxN, float* z_KxN, void* stream);
+
+/* dX = (dY W) * silu'(Zprev)  with dY [K][N], W [N][M], Zprev and dX [K][M]; Zprev is the pre-activation that produced this layer's input,
+ * NULL = no factor.  silu'(z) = s (1 + z (1 - s)), s = 1 / (1 + exp(-z)), is evaluated in fp64 and rounded once: it has a root at z = -1.278
+ * where an fp32 evaluation loses every digit to cancellation.  fp32 MFMA as above, any K, M, N >= 1.  One launch. */
+int pgtt_learn_linear_backward_data(const float* dy_KxN, const float* w_NxM, const float* zprev_KxM, int K, int M, int N,
+                                    float* dx_KxM, void* stream);
+
+/* loss_1[0] = 0.25 mean((ret - v)^2),  dv[i] = 0.5 (v[i] - ret[i]) / B: one launch of a single workgroup, fixed order. */
+int pgtt_learn_value_loss(const float* v_B, const float* ret_B, int B, float* loss_1, float* dv_B, void* stream);
+
+/* Global-norm clip and Adam over ONE flat buffer of P floats, two launches:
+ *   1. g <- grad_scale g (when grad_scale != 1), per-workgroup partial sums of g^2 into `partial`, *t <- *t + 1;
+ *   2. every workgroup adds the partials in the same fixed order: norm = sqrt(sum), coef = min(1, max_norm / (norm + 1e-6)), then with c = coef g
+ *      m <- beta1 m + (1 - beta1) c,  v <- beta2 v + (1 - beta2) c^2,  p <- p - lr (m / (1 - beta1^t)) / (sqrt(v / (1 - beta2^t)) + eps);
+ *      the two bias corrections are formed in fp64 from the fp64 betas and rounded once.  *norm_1 receives the UNCLIPPED norm (of grad_scale g).
+ * g keeps grad_scale g (not coef g).  partial holds pgtt_learn_adam_partials(P) floats of scratch (at most 1024). */
+typedef struct PgttLearnAdamArgs {
+  float* p;                    /* [P] parameters */
+  float* g;                    /* [P] gradients */
+  float* m;                    /* [P] first moments */
+  float* v;                    /* [P] second moments */
+  int64_t* t;                  /* device int64[1]: the step counter, advanced by one per call */
+  float* partial;              /* [pgtt_learn_adam_partials(P)] scratch */
+  float* norm_1;               /* device float[1]: the unclipped gradient norm */
+  int64_t P;
+  double lr, beta1, beta2, eps;
+  float max_norm, grad_scale;
+} PgttLearnAdamArgs;
+int pgtt_learn_clip_adam(const PgttLearnAdamArgs* args, void* stream);
+int pgtt_learn_adam_partials(int64_t P);
+
+/* Generalised advantage estimation as Brax's compute_gae (phase_guided_terrain_traversal_amd/ppo.py::compute_gae), rows [T][N], boot [N]:
+ *   term = done (1 - trunc);  delta_t = (r_t + gamma (1 - term_t) V_{t+1} - V_t)(1 - trunc_t),  V_T = boot;
+ *   acc_t = delta_t + gamma lambda (1 - term_t)(1 - trunc_t) acc_{t+1},  acc_T = 0;   vs_t = acc_t + V_t;
+ *   adv_t = (r_t + gamma (1 - term_t) vs_{t+1} - V_t)(1 - trunc_t),  vs_T = boot.
+ * One lane per env, one backward loop over T, one launch. */
+int pgtt_learn_gae(const float* trunc_TxN, const float* done_TxN, const float* rew_TxN, const float* val_TxN, const float* boot_N,
+                   int T, int N, float lambda, float gamma, float* adv_TxN, float* vs_TxN, void* stream);
+
+int pgtt_learn_sizeof_gather_args(void);
+int pgtt_learn_sizeof_adam_args(void);
+const char* pgtt_learn_build_info(void);      /* "src=<srchash.side_sha256("learn")>;flavor=product" */
+const char* pgtt_learn_last_error(void);
+#ifdef __cplusplus
+}
+#endif
+#endif /* PGTT_LEARN_H_ */

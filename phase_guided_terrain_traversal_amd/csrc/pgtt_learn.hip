@@ -1,0 +1,424 @@
+// pgtt_learn.hip — libpgtt_learn.so (include/pgtt_learn.h, gfx950): what one PPO minibatch update needs next to the two kernels of
+// pgtt_ppo.hip, so that learn.py::NativeLearner runs the whole update as ~40 hand-written launches on one stream.
+//
+//   gather_kernel / adv_normalise_kernel     one workgroup per minibatch row (normalised observations, copies, the raw advantage), then ONE
+//                                            workgroup: mean and population std of the advantages in a fixed order, normalised in place
+//   linear_forward_kernel                    Z = X W^T + b, Y = silu(Z): fp32 MFMA 16x16x4 with blocked summation, four waves per workgroup, a 32x32 (or 32x16)
+//                                            block of the output per wave, both operands straight from global memory as 16-byte runs along the
+//                                            contraction index (lane (i, g) holds m = m0 + 4 g + s for the s-th of four MFMAs), next run prefetched
+//   linear_backward_data_kernel              dX = (dY W) silu'(Zprev): the same blocking; W is walked by rows here (four dwords per lane)
+//   value_loss_kernel                        one workgroup
+//   adam_norm_kernel / adam_apply_kernel     partial sums of g^2 (and t + 1), then clip coefficient + Adam in every workgroup alike
+//   gae_kernel                               one lane per env, one backward loop over T
+// No atomics, no scratch, no LDS beyond the reductions' 16 words; nothing allocates or synchronises.
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <string>
+
+#include "../../include/pgtt_learn.h"
+
+#ifndef PGTT_LEARN_SRC
+#define PGTT_LEARN_SRC "unknown"
+#endif
+// an experiment build names itself: make -f pgtt_learn.mk EXTRA=-DPGTT_LEARN_FLAVOR=\"name\" ...
+#ifndef PGTT_LEARN_FLAVOR
+#define PGTT_LEARN_FLAVOR "product"
+#endif
+
+namespace {
+
+thread_local std::string g_err;
+int fail(int code, const std::string& msg) { g_err = msg; return code; }
+int launched(const char* who) {
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? PGTT_OK : fail(PGTT_E_HIP, std::string(who) + ": " + hipGetErrorString(e));
+}
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+// four consecutive floats behind a pointer that is only 4-byte aligned (rows of 171 or 215 floats): one global_load_dwordx4
+struct __attribute__((packed, aligned(4))) F4 { float x, y, z, w; };
+__device__ __forceinline__ F4 ld4(const float* p) { return *reinterpret_cast<const F4*>(p); }
+
+constexpr int kRed = 1024;          // lanes of the single-workgroup reductions
+
+// sum over the workgroup, the same bits in every lane: xor butterfly inside a wave, then the waves' sums in wave order
+__device__ __forceinline__ float block_sum(float v, float* sh) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  __syncthreads();                                            // sh may still be read from the previous sum
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+  __syncthreads();
+  float s = 0.f;
+  const int nw = blockDim.x >> 6;
+  for (int w = 0; w < nw; w++) s += sh[w];
+  return s;
+}
+
+// ------------------------------------------------------------------ gather
+__global__ __launch_bounds__(256) void gather_kernel(PgttLearnGatherArgs a) {
+  const int i = blockIdx.x, tid = threadIdx.x;
+  long r = a.idx[i];
+  r = r < 0 ? 0 : (r >= a.rows ? (long)a.rows - 1 : r);
+  for (int k = tid; k < a.obs_dim; k += 256) a.x_s[(long)i * a.obs_dim + k] = (a.obs[r * a.obs_dim + k] - a.mean_s[k]) / a.std_s[k];
+  for (int k = tid; k < a.priv_dim; k += 256) a.x_p[(long)i * a.priv_dim + k] = (a.priv[r * a.priv_dim + k] - a.mean_p[k]) / a.std_p[k];
+  for (int k = tid; k < a.act_dim; k += 256) a.u_out[(long)i * a.act_dim + k] = a.u[r * a.act_dim + k];
+  if (tid == 64) a.logp_out[i] = a.logp[r];
+  if (tid == 128) a.ret_out[i] = a.ret[r];
+  if (tid == 192) a.adv_out[i] = a.adv[r];
+}
+
+__global__ __launch_bounds__(kRed) void adv_normalise_kernel(float* __restrict__ adv, int B) {
+  __shared__ float sh[kRed / 64];
+  float s = 0.f;
+  for (int i = threadIdx.x; i < B; i += kRed) s += adv[i];
+  const float mean = block_sum(s, sh) / (float)B;
+  float q = 0.f;
+  for (int i = threadIdx.x; i < B; i += kRed) { const float d = adv[i] - mean; q += d * d; }
+  const float sd = sqrtf(block_sum(q, sh) / (float)B);
+  for (int i = threadIdx.x; i < B; i += kRed) adv[i] = (adv[i] - mean) / (sd + 1e-8f);
+}
+
+// ------------------------------------------------------------------ the two GEMMs
+// A workgroup is four waves, WR x WC of them over the output; a wave owns 32 rows x (16 NCT) columns: 2 x NCT accumulators of the 16x16x4 form.
+// C/D map of that form: register r of lane l is row 4 (l >> 4) + r, column l & 15.
+// One round = 16 terms of the contraction.  The round's products are summed in accumulators of their own that start at zero, and only the round's
+// sum is added to the running total (blocked summation): the long chain has one link per 16 terms instead of four, which halves the rounding error
+// of a 512-term row against one accumulator chained through every MFMA - at the price of 8 NCT vector adds per 8 NCT MFMAs.
+template <int NCT>
+__device__ __forceinline__ void mfma_round(const F4 (&a)[2], const F4 (&b)[NCT], f32x4 (&acc)[2][NCT]) {
+  f32x4 blk[2][NCT];
+#pragma unroll
+  for (int t = 0; t < 2; t++)
+#pragma unroll
+    for (int c = 0; c < NCT; c++) blk[t][c] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[t].x, b[c].x, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+#pragma unroll
+  for (int t = 0; t < 2; t++)
+#pragma unroll
+    for (int c = 0; c < NCT; c++) blk[t][c] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[t].y, b[c].y, blk[t][c], 0, 0, 0);
+#pragma unroll
+  for (int t = 0; t < 2; t++)
+#pragma unroll
+    for (int c = 0; c < NCT; c++) blk[t][c] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[t].z, b[c].z, blk[t][c], 0, 0, 0);
+#pragma unroll
+  for (int t = 0; t < 2; t++)
+#pragma unroll
+    for (int c = 0; c < NCT; c++) blk[t][c] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[t].w, b[c].w, blk[t][c], 0, 0, 0);
+#pragma unroll
+  for (int t = 0; t < 2; t++)
+#pragma unroll
+    for (int c = 0; c < NCT; c++) acc[t][c] += blk[t][c];
+}
+
+__device__ __forceinline__ float silu_f(float z) { return z / (1.0f + expf(-z)); }
+// fp64, rounded once: silu' passes through 0 at z = -1.2785, where s and s z (1 - s) cancel
+__device__ __forceinline__ float dsilu_f(float zf) {
+  const double z = (double)zf, s = 1.0 / (1.0 + exp(-z));
+  return (float)(s * (1.0 + z * (1.0 - s)));
+}
+
+template <int WC, int NCT>
+__global__ __launch_bounds__(256) void linear_forward_kernel(const float* __restrict__ X, const float* __restrict__ W, const float* __restrict__ bias,
+                                                             int K, int M, int N, int act, float* __restrict__ Y, float* __restrict__ Z) {
+  constexpr int WR = 4 / WC;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, li = lane & 15, g = lane >> 4;
+  const long r0 = (long)blockIdx.x * (WR * 32) + (wave / WC) * 32;
+  const int c0 = blockIdx.y * (WC * NCT * 16) + (wave % WC) * (NCT * 16);
+  if (r0 >= K || c0 >= N) return;                        // wave-uniform; the kernel has no barrier
+  // operand rows of this lane, clamped: a row or column past the edge repeats the last one and is not stored
+  const float* xa[2];
+  const float* wb[NCT];
+#pragma unroll
+  for (int t = 0; t < 2; t++) { const long r = r0 + 16 * t + li; xa[t] = X + (r < K ? r : (long)K - 1) * M + 4 * g; }
+#pragma unroll
+  for (int c = 0; c < NCT; c++) { const int n = c0 + 16 * c + li; wb[c] = W + (long)(n < N ? n : N - 1) * M + 4 * g; }
+  f32x4 acc[2][NCT];
+#pragma unroll
+  for (int t = 0; t < 2; t++)
+#pragma unroll
+    for (int c = 0; c < NCT; c++) acc[t][c] = f32x4{0.f, 0.f, 0.f, 0.f};
+  F4 a[2], b[NCT];
+  const int nfull = M / 16;
+  if (nfull > 0) {
+#pragma unroll
+    for (int t = 0; t < 2; t++) a[t] = ld4(xa[t]);
+#pragma unroll
+    for (int c = 0; c < NCT; c++) b[c] = ld4(wb[c]);
+    for (int i = 0; i < nfull; i++) {
+      const int nx = (i + 1 < nfull ? i + 1 : i) * 16;   // the last trip loads its own run again instead of branching
+      F4 an[2], bn[NCT];
+#pragma unroll
+      for (int t = 0; t < 2; t++) an[t] = ld4(xa[t] + nx);
+#pragma unroll
+      for (int c = 0; c < NCT; c++) bn[c] = ld4(wb[c] + nx);
+      mfma_round<NCT>(a, b, acc);
+#pragma unroll
+      for (int t = 0; t < 2; t++) a[t] = an[t];
+#pragma unroll
+      for (int c = 0; c < NCT; c++) b[c] = bn[c];
+    }
+  }
+  const int m0 = nfull * 16;
+  if (m0 < M) {                                          // the last 1 .. 15 terms: element by element, zeros past the end (nothing is read there)
+    const int mq = m0 + 4 * g;
+    const bool o0 = mq < M, o1 = mq + 1 < M, o2 = mq + 2 < M, o3 = mq + 3 < M;
+#pragma unroll
+    for (int t = 0; t < 2; t++) { const float* p = xa[t] + m0; a[t] = F4{o0 ? p[0] : 0.f, o1 ? p[1] : 0.f, o2 ? p[2] : 0.f, o3 ? p[3] : 0.f}; }
+#pragma unroll
+    for (int c = 0; c < NCT; c++) { const float* p = wb[c] + m0; b[c] = F4{o0 ? p[0] : 0.f, o1 ? p[1] : 0.f, o2 ? p[2] : 0.f, o3 ? p[3] : 0.f}; }
+    mfma_round<NCT>(a, b, acc);
+  }
+#pragma unroll
+  for (int c = 0; c < NCT; c++) {
+    const int n = c0 + 16 * c + li;
+    if (n >= N) continue;
+    const float bn = bias[n];
+#pragma unroll
+    for (int t = 0; t < 2; t++)
+#pragma unroll
+      for (int r = 0; r < 4; r++) {
+        const long row = r0 + 16 * t + 4 * g + r;
+        if (row >= K) continue;
+        const float z = acc[t][c][r] + bn;
+        if (Z) Z[row * N + n] = z;
+        Y[row * N + n] = act ? silu_f(z) : z;
+      }
+  }
+}
+
+template <int WC, int NCT>
+__global__ __launch_bounds__(256) void linear_backward_data_kernel(const float* __restrict__ dY, const float* __restrict__ W, const float* __restrict__ Zp,
+                                                                   int K, int M, int N, float* __restrict__ dX) {
+  constexpr int WR = 4 / WC;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, li = lane & 15, g = lane >> 4;
+  const long r0 = (long)blockIdx.x * (WR * 32) + (wave / WC) * 32;
+  const int c0 = blockIdx.y * (WC * NCT * 16) + (wave % WC) * (NCT * 16);
+  if (r0 >= K || c0 >= M) return;
+  const float* ya[2];
+  const float* wb[NCT];                                  // column m of W, at row 4 g: the lane's four rows are M floats apart
+#pragma unroll
+  for (int t = 0; t < 2; t++) { const long r = r0 + 16 * t + li; ya[t] = dY + (r < K ? r : (long)K - 1) * N + 4 * g; }
+#pragma unroll
+  for (int c = 0; c < NCT; c++) { const int m = c0 + 16 * c + li; wb[c] = W + (long)(4 * g) * M + (m < M ? m : M - 1); }
+  f32x4 acc[2][NCT];
+#pragma unroll
+  for (int t = 0; t < 2; t++)
+#pragma unroll
+    for (int c = 0; c < NCT; c++) acc[t][c] = f32x4{0.f, 0.f, 0.f, 0.f};
+  F4 a[2], b[NCT];
+  const int nfull = N / 16;
+  const long M1 = M, M2 = 2L * M, M3 = 3L * M;
+  if (nfull > 0) {
+#pragma unroll
+    for (int t = 0; t < 2; t++) a[t] = ld4(ya[t]);
+#pragma unroll
+    for (int c = 0; c < NCT; c++) b[c] = F4{wb[c][0], wb[c][M1], wb[c][M2], wb[c][M3]};
+    for (int i = 0; i < nfull; i++) {
+      const int nx = (i + 1 < nfull ? i + 1 : i) * 16;
+      F4 an[2], bn[NCT];
+#pragma unroll
+      for (int t = 0; t < 2; t++) an[t] = ld4(ya[t] + nx);
+#pragma unroll
+      for (int c = 0; c < NCT; c++) { const float* p = wb[c] + (long)nx * M; bn[c] = F4{p[0], p[M1], p[M2], p[M3]}; }
+      mfma_round<NCT>(a, b, acc);
+#pragma unroll
+      for (int t = 0; t < 2; t++) a[t] = an[t];
+#pragma unroll
+      for (int c = 0; c < NCT; c++) b[c] = bn[c];
+    }
+  }
+  const int n0 = nfull * 16;
+  if (n0 < N) {
+    const int nq = n0 + 4 * g;
+    const bool o0 = nq < N, o1 = nq + 1 < N, o2 = nq + 2 < N, o3 = nq + 3 < N;
+#pragma unroll
+    for (int t = 0; t < 2; t++) { const float* p = ya[t] + n0; a[t] = F4{o0 ? p[0] : 0.f, o1 ? p[1] : 0.f, o2 ? p[2] : 0.f, o3 ? p[3] : 0.f}; }
+#pragma unroll
+    for (int c = 0; c < NCT; c++) { const float* p = wb[c] + (long)n0 * M; b[c] = F4{o0 ? p[0] : 0.f, o1 ? p[M1] : 0.f, o2 ? p[M2] : 0.f, o3 ? p[M3] : 0.f}; }
+    mfma_round<NCT>(a, b, acc);
+  }
+#pragma unroll
+  for (int c = 0; c < NCT; c++) {
+    const int m = c0 + 16 * c + li;
+    if (m >= M) continue;
+#pragma unroll
+    for (int t = 0; t < 2; t++)
+#pragma unroll
+      for (int r = 0; r < 4; r++) {
+        const long row = r0 + 16 * t + 4 * g + r;
+        if (row >= K) continue;
+        const float d = acc[t][c][r];
+        dX[row * M + m] = Zp ? d * dsilu_f(Zp[row * M + m]) : d;
+      }
+  }
+}
+
+// cols: the width of the output.  Wide outputs take 64 x 64 per workgroup, narrow ones (the heads: 24, 1) stack the four waves over the rows
+template <typename F>
+int launch_gemm(int K, int cols, const char* who, F&& go) {
+  const int wc = cols > 32 ? 2 : 1, nct = cols > 16 ? 2 : 1;
+  const long gx = ((long)K + (4 / wc) * 32 - 1) / ((4 / wc) * 32), gy = ((long)cols + wc * nct * 16 - 1) / (wc * nct * 16);
+  if (gy > 65535) return fail(PGTT_E_ARG, std::string(who) + ": more than 65535 column blocks");
+  go(wc, nct, dim3((unsigned)gx, (unsigned)gy));
+  return launched(who);
+}
+
+// ------------------------------------------------------------------ value loss
+__global__ __launch_bounds__(kRed) void value_loss_kernel(const float* __restrict__ v, const float* __restrict__ ret, int B, float* __restrict__ loss,
+                                                          float* __restrict__ dv) {
+  __shared__ float sh[kRed / 64];
+  const float fB = (float)B;
+  float q = 0.f;
+  for (int i = threadIdx.x; i < B; i += kRed) {
+    const float d = v[i] - ret[i];
+    q += d * d;
+    dv[i] = 0.5f * d / fB;
+  }
+  q = block_sum(q, sh);
+  if (threadIdx.x == 0) loss[0] = 0.25f * (q / fB);
+}
+
+// ------------------------------------------------------------------ clip + Adam
+__global__ __launch_bounds__(256) void adam_norm_kernel(float* __restrict__ g, long P, float grad_scale, float* __restrict__ partial, int64_t* __restrict__ t) {
+  __shared__ float sh[4];
+  float q = 0.f;
+  const long stride = (long)gridDim.x * 256;
+  if (grad_scale != 1.0f) {
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < P; i += stride) { const float x = g[i] * grad_scale; g[i] = x; q += x * x; }
+  } else {
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < P; i += stride) { const float x = g[i]; q += x * x; }
+  }
+  q = block_sum(q, sh);
+  if (threadIdx.x == 0) {
+    partial[blockIdx.x] = q;
+    if (blockIdx.x == 0) t[0] = t[0] + 1;
+  }
+}
+
+struct AdamK {
+  float* p; const float* g; float* m; float* v; const int64_t* t; const float* partial; float* norm;
+  long P; int nb; double lr, b1, b2, eps; float max_norm;
+};
+
+__global__ __launch_bounds__(256) void adam_apply_kernel(AdamK a) {
+  __shared__ float sh[4];
+  __shared__ float bc[2];
+  float q = 0.f;
+  for (int i = threadIdx.x; i < a.nb; i += 256) q += a.partial[i];
+  q = block_sum(q, sh);                                   // every workgroup: the same partials in the same order
+  if (threadIdx.x == 0) {
+    const double t = (double)a.t[0];
+    bc[0] = (float)(1.0 - pow(a.b1, t));
+    bc[1] = (float)(1.0 - pow(a.b2, t));
+  }
+  __syncthreads();
+  const float norm = sqrtf(q), coef = fminf(1.0f, a.max_norm / (norm + 1e-6f));
+  if (blockIdx.x == 0 && threadIdx.x == 0) a.norm[0] = norm;
+  const float b1 = (float)a.b1, b2 = (float)a.b2, c1 = (float)(1.0 - a.b1), c2 = (float)(1.0 - a.b2), lr = (float)a.lr, eps = (float)a.eps;
+  const float bc1 = bc[0], bc2 = bc[1];
+  const long stride = (long)gridDim.x * 256;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < a.P; i += stride) {
+    const float c = coef * a.g[i];
+    const float m = b1 * a.m[i] + c1 * c, v = b2 * a.v[i] + c2 * (c * c);
+    a.m[i] = m; a.v[i] = v;
+    a.p[i] = a.p[i] - lr * (m / bc1) / (sqrtf(v / bc2) + eps);
+  }
+}
+
+// workgroups of the first pass = partial sums (2048 elements each, at most 1024), and of the second pass (1024 elements each, at most 2048)
+int adam_blocks(long P) { const long nb = (P + 2047) / 2048; return (int)(nb < 1 ? 1 : (nb > 1024 ? 1024 : nb)); }
+int adam_apply_blocks(long P) { const long nb = (P + 1023) / 1024; return (int)(nb < 1 ? 1 : (nb > 2048 ? 2048 : nb)); }
+
+// ------------------------------------------------------------------ GAE
+__global__ __launch_bounds__(256) void gae_kernel(const float* __restrict__ trunc, const float* __restrict__ done, const float* __restrict__ rew,
+                                                  const float* __restrict__ val, const float* __restrict__ boot, int T, int N, float lam, float gamma,
+                                                  float* __restrict__ adv, float* __restrict__ vs) {
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= N) return;
+  const float gl = gamma * lam;
+  float acc = 0.f, v_next = boot[e], vs_next = v_next;
+  for (int t = T - 1; t >= 0; t--) {
+    const long k = (long)t * N + e;
+    const float tr = trunc[k], mask = 1.0f - tr, nonterm = 1.0f - done[k] * mask, r = rew[k], v = val[k];
+    const float delta = (r + gamma * nonterm * v_next - v) * mask;
+    acc = delta + gl * nonterm * mask * acc;
+    adv[k] = (r + gamma * nonterm * vs_next - v) * mask;
+    vs_next = acc + v;
+    vs[k] = vs_next;
+    v_next = v;
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+const char* pgtt_learn_last_error(void) { return g_err.c_str(); }
+const char* pgtt_learn_build_info(void) { return "src=" PGTT_LEARN_SRC ";flavor=" PGTT_LEARN_FLAVOR; }
+int pgtt_learn_sizeof_gather_args(void) { return (int)sizeof(PgttLearnGatherArgs); }
+int pgtt_learn_sizeof_adam_args(void) { return (int)sizeof(PgttLearnAdamArgs); }
+int pgtt_learn_adam_partials(int64_t P) { return P > 0 ? adam_blocks((long)P) : 0; }
+
+int pgtt_learn_gather(const PgttLearnGatherArgs* a, void* stream) {
+  if (!a) return fail(PGTT_E_ARG, "pgtt_learn_gather: null args");
+  if (!a->idx || !a->obs || !a->priv || !a->u || !a->logp || !a->adv || !a->ret || !a->mean_s || !a->std_s || !a->mean_p || !a->std_p || !a->x_s ||
+      !a->x_p || !a->u_out || !a->logp_out || !a->adv_out || !a->ret_out)
+    return fail(PGTT_E_ARG, "pgtt_learn_gather: null pointer");
+  if (a->B <= 0 || a->rows <= 0 || a->obs_dim <= 0 || a->priv_dim <= 0 || a->act_dim <= 0) return fail(PGTT_E_ARG, "pgtt_learn_gather: B, rows, obs_dim, priv_dim and act_dim must be positive");
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(gather_kernel, dim3(a->B), dim3(256), 0, st, *a);
+  hipLaunchKernelGGL(adv_normalise_kernel, dim3(1), dim3(kRed), 0, st, a->adv_out, a->B);
+  return launched("pgtt_learn_gather");
+}
+
+int pgtt_learn_linear_forward(const float* x, const float* w, const float* b, int K, int M, int N, int act, float* y, float* z, void* stream) {
+  if (!x || !w || !b || !y) return fail(PGTT_E_ARG, "pgtt_learn_linear_forward: null pointer");
+  if (act && !z) return fail(PGTT_E_ARG, "pgtt_learn_linear_forward: act != 0 needs z (the backward pass reads the pre-activation)");
+  if (K <= 0 || M <= 0 || N <= 0) return fail(PGTT_E_ARG, "pgtt_learn_linear_forward: K, M and N must be positive");
+  hipStream_t st = (hipStream_t)stream;
+  return launch_gemm(K, N, "pgtt_learn_linear_forward", [&](int wc, int nct, dim3 grid) {
+    if (wc == 2) hipLaunchKernelGGL((linear_forward_kernel<2, 2>), grid, dim3(256), 0, st, x, w, b, K, M, N, act, y, z);
+    else if (nct == 2) hipLaunchKernelGGL((linear_forward_kernel<1, 2>), grid, dim3(256), 0, st, x, w, b, K, M, N, act, y, z);
+    else hipLaunchKernelGGL((linear_forward_kernel<1, 1>), grid, dim3(256), 0, st, x, w, b, K, M, N, act, y, z);
+  });
+}
+
+int pgtt_learn_linear_backward_data(const float* dy, const float* w, const float* zprev, int K, int M, int N, float* dx, void* stream) {
+  if (!dy || !w || !dx) return fail(PGTT_E_ARG, "pgtt_learn_linear_backward_data: null pointer");
+  if (K <= 0 || M <= 0 || N <= 0) return fail(PGTT_E_ARG, "pgtt_learn_linear_backward_data: K, M and N must be positive");
+  hipStream_t st = (hipStream_t)stream;
+  return launch_gemm(K, M, "pgtt_learn_linear_backward_data", [&](int wc, int nct, dim3 grid) {
+    if (wc == 2) hipLaunchKernelGGL((linear_backward_data_kernel<2, 2>), grid, dim3(256), 0, st, dy, w, zprev, K, M, N, dx);
+    else if (nct == 2) hipLaunchKernelGGL((linear_backward_data_kernel<1, 2>), grid, dim3(256), 0, st, dy, w, zprev, K, M, N, dx);
+    else hipLaunchKernelGGL((linear_backward_data_kernel<1, 1>), grid, dim3(256), 0, st, dy, w, zprev, K, M, N, dx);
+  });
+}
+
+int pgtt_learn_value_loss(const float* v, const float* ret, int B, float* loss, float* dv, void* stream) {
+  if (!v || !ret || !loss || !dv) return fail(PGTT_E_ARG, "pgtt_learn_value_loss: null pointer");
+  if (B <= 0) return fail(PGTT_E_ARG, "pgtt_learn_value_loss: B must be positive");
+  hipLaunchKernelGGL(value_loss_kernel, dim3(1), dim3(kRed), 0, (hipStream_t)stream, v, ret, B, loss, dv);
+  return launched("pgtt_learn_value_loss");
+}
+
+int pgtt_learn_clip_adam(const PgttLearnAdamArgs* a, void* stream) {
+  if (!a) return fail(PGTT_E_ARG, "pgtt_learn_clip_adam: null args");
+  if (!a->p || !a->g || !a->m || !a->v || !a->t || !a->partial || !a->norm_1) return fail(PGTT_E_ARG, "pgtt_learn_clip_adam: null pointer");
+  if (a->P <= 0) return fail(PGTT_E_ARG, "pgtt_learn_clip_adam: P must be positive");
+  const int nb = adam_blocks((long)a->P);
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(adam_norm_kernel, dim3(nb), dim3(256), 0, st, a->g, (long)a->P, a->grad_scale, a->partial, a->t);
+  AdamK k{a->p, a->g, a->m, a->v, a->t, a->partial, a->norm_1, (long)a->P, nb, a->lr, a->beta1, a->beta2, a->eps, a->max_norm};
+  hipLaunchKernelGGL(adam_apply_kernel, dim3(adam_apply_blocks((long)a->P)), dim3(256), 0, st, k);
+  return launched("pgtt_learn_clip_adam");
+}
+
+int pgtt_learn_gae(const float* trunc, const float* done, const float* rew, const float* val, const float* boot, int T, int N, float lambda, float gamma,
+                   float* adv, float* vs, void* stream) {
+  if (!trunc || !done || !rew || !val || !boot || !adv || !vs) return fail(PGTT_E_ARG, "pgtt_learn_gae: null pointer");
+  if (T <= 0 || N <= 0) return fail(PGTT_E_ARG, "pgtt_learn_gae: T and N must be positive");
+  hipLaunchKernelGGL(gae_kernel, dim3((N + 255) / 256), dim3(256), 0, (hipStream_t)stream, trunc, done, rew, val, boot, T, N, lambda, gamma, adv, vs);
+  return launched("pgtt_learn_gae");
+}
+
+}  // extern "C"

@@ -209,6 +209,7 @@ class PPOConfig:
     max_grad_norm: float = 1.0
     reward_scaling: float = 1.0
     seed: int = 0
+    learner: str = "torch"           # "native": the minibatch update and GAE as hand-written HIP on one stream (learn.py, GPU only)
 
 
 class _Actor:
@@ -428,6 +429,13 @@ def train(env, cfg: PPOConfig, progress_fn: Optional[Callable[[int, Dict[str, fl
     every rank on identical numbers (its early-stop decision must not differ between ranks), `policy_params_fn` in rank 0."""
     dev = torch.device(env.device)
     on_gpu = dev.type == "cuda"
+    if cfg.learner not in ("torch", "native"):
+        raise ValueError(f"PPOConfig.learner must be 'torch' or 'native', not {cfg.learner!r}")
+    native_learner = cfg.learner == "native"
+    if native_learner and not on_gpu:
+        raise ValueError("PPOConfig.learner='native' needs an env on a GPU (it is hand-written HIP with no CPU form); use learner='torch' on " + str(dev))
+    if native_learner:
+        from . import learn
     use_graph = use_graph and on_gpu
     sync = (lambda: torch.cuda.synchronize(dev)) if on_gpu else (lambda: None)
     (world, rank), dp = _world(), _dp()
@@ -445,10 +453,13 @@ def train(env, cfg: PPOConfig, progress_fn: Optional[Callable[[int, Dict[str, fl
             dist.broadcast(t.data, src=0)                         # one set of initial weights whatever the ranks' generators did
         if rank > 0:                                              # ... and independent exploration / minibatch noise per rank
             torch.manual_seed(cfg.seed + 1_000_003 * rank)        # (rank 0 keeps the stream a single-process run has)
-    try:        # one fused multi-tensor Adam launch instead of ~10 foreach launches per update
-        opt = torch.optim.Adam(model.parameters(), lr=cfg.learning_rate, capturable=use_graph, fused=on_gpu)
-    except (RuntimeError, TypeError):
-        opt = torch.optim.Adam(model.parameters(), lr=cfg.learning_rate, capturable=use_graph)
+    if native_learner:      # the parameters become views of one flat buffer (state_dict, checkpoint and the actor's repack see no difference)
+        opt = learn.FlatParams(model)
+    else:
+        try:        # one fused multi-tensor Adam launch instead of ~10 foreach launches per update
+            opt = torch.optim.Adam(model.parameters(), lr=cfg.learning_rate, capturable=use_graph, fused=on_gpu)
+        except (RuntimeError, TypeError):
+            opt = torch.optim.Adam(model.parameters(), lr=cfg.learning_rate, capturable=use_graph)
     assert (cfg.batch_size * cfg.num_minibatches) % (n * world) == 0, \
         "batch_size * num_minibatches must be a multiple of the total number of envs (num_envs per rank x world size)"
     unrolls = cfg.batch_size * cfg.num_minibatches // (n * world)
@@ -477,14 +488,19 @@ def train(env, cfg: PPOConfig, progress_fn: Optional[Callable[[int, Dict[str, fl
             # step contributes no temporal-difference error and stops the backward recursion (the next observation belongs
             # to the next episode after AutoReset, its value is not a bootstrap for this one), a terminated step bootstraps with
             # 0; value targets vs = acc + V, advantages = (r + gamma (1 - term) vs[t+1] - V) (1 - trunc) with vs[T] = V(last obs)
-            adv, ret = compute_gae(batch["trunc"], batch["done"] * (1.0 - batch["trunc"]), batch["rew"], values[:-1], values[-1],
-                                   cfg.gae_lambda, cfg.discounting)
+            if native_learner:      # one launch; the kernel forms termination from done and truncation itself
+                adv, ret = learn.gae(batch["trunc"], batch["done"], batch["rew"], values[:-1], values[-1], cfg.gae_lambda, cfg.discounting)
+            else:
+                adv, ret = compute_gae(batch["trunc"], batch["done"] * (1.0 - batch["trunc"]), batch["rew"], values[:-1], values[-1],
+                                       cfg.gae_lambda, cfg.discounting)
         sync(); t1 = time.perf_counter(); t_env += t1 - t0
         flat = lambda x: x.reshape(T * n, *x.shape[2:])
         if learner is None:
             B = {k: flat(batch[k]) for k in ("obs", "priv", "u", "logp")}          # views of the actor's static storage
             B["adv"], B["ret"] = torch.zeros(T * n, device=dev), torch.zeros(T * n, device=dev)
-            learner = _Learner(model, opt, norm_s, norm_p, B, T * n // cfg.num_minibatches, cfg, use_graph=use_graph)
+            learner = (learn.NativeLearner if native_learner else _Learner)(model, opt, norm_s, norm_p, B, T * n // cfg.num_minibatches, cfg, use_graph=use_graph)
+        if native_learner:
+            learner.refresh_stats()             # this iteration's statistics, once: they stand still during its updates
         learner.B["adv"].copy_(flat(adv)); learner.B["ret"].copy_(flat(ret))
         mb = T * n // cfg.num_minibatches
         for _ in range(cfg.num_updates_per_batch):

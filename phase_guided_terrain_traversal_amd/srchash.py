@@ -4,8 +4,8 @@ and csrc/flags.mk, the make fragment that holds the compile flags of that unit. 
 change the kernel).  The task-side kernels, the host code and the other rules of the Makefile are not covered: a change there leaves the hash,
 and with it the counters recorded under profiles/, valid.  EXTRA flags and the 1-ulp division are what the build's flavor says.
 
-The side libraries (csrc/pgtt_raycast.mk, csrc/pgtt_perceive.mk, csrc/pgtt_elevation.mk) embed a hash of their own, side_sha256("render" | "depth" |
-"perceive" | "elevation"): the
+The side libraries (csrc/pgtt_raycast.mk, csrc/pgtt_perceive.mk, csrc/pgtt_elevation.mk, csrc/pgtt_learn.mk) embed a hash of their own,
+side_sha256("render" | "depth" | "perceive" | "elevation" | "learn"): the
 include closure of their one translation unit (SIDE_SOURCES), normalised the same way.  `python3 srchash.py` prints the physics hash, `python3 srchash.py render` a side hash."""
 import hashlib
 import os
@@ -19,7 +19,8 @@ _RAYCAST = ("pgtt_raycast.hip.h", "pgtt_raycast_host.h")
 SIDE_SOURCES = {"render": (("pgtt_render.hip",) + _RAYCAST, ("pgtt_render.h", "pgtt.h")),
                 "depth": (("pgtt_depth.hip",) + _RAYCAST, ("pgtt_depth.h", "pgtt_render.h", "pgtt.h")),
                 "perceive": (("pgtt_perceive.hip", "pgtt_raycast_host.h"), ("pgtt_perceive.h", "pgtt_render.h", "pgtt.h")),
-                "elevation": (("pgtt_elevation.hip", "pgtt_raycast_host.h"), ("pgtt_elevation.h", "pgtt_render.h", "pgtt.h"))}
+                "elevation": (("pgtt_elevation.hip", "pgtt_raycast_host.h"), ("pgtt_elevation.h", "pgtt_render.h", "pgtt.h")),
+                "learn": (("pgtt_learn.hip",), ("pgtt_learn.h", "pgtt.h"))}
 
 
 def hashed_files(pkg: str = _HERE):

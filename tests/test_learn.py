@@ -1,0 +1,128 @@
+"""The native learner's plumbing that needs no GPU: FlatParams (every parameter a view of one flat buffer, the state_dict unchanged, a checkpoint
+round trip), the `learner` switch of PPOConfig / train.py, the refusal on a CPU device, the side library's source hash."""
+import os
+import sys
+
+import pytest
+
+torch = pytest.importorskip("torch")
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from phase_guided_terrain_traversal_amd import abi, learn, ppo, srchash  # noqa: E402
+
+
+def test_flat_params_are_views_and_the_state_dict_is_unchanged():
+    torch.manual_seed(3)
+    model = ppo.ActorCritic()
+    before = {k: v.detach().clone() for k, v in model.state_dict().items()}
+    flat = learn.FlatParams(model)
+    params = list(model.parameters())
+    assert len(params) == 16 and flat.numel == sum(p.numel() for p in params) and flat.flat.dtype == torch.float32
+    assert flat.grad.shape == flat.m.shape == flat.v.shape == flat.flat.shape and flat.t.dtype == torch.int64 and flat.t.tolist() == [0]
+    lo, size = flat.flat.data_ptr(), flat.flat.numel() * 4
+    off = 0
+    for p in params:                                    # consecutive views, in the order of model.parameters()
+        assert p.data_ptr() == lo + 4 * off and p.is_contiguous() and p.requires_grad
+        assert p.grad is not None and p.grad.data_ptr() == flat.grad.data_ptr() + 4 * off and p.grad.shape == p.shape
+        assert flat.grad_of(p).data_ptr() == p.grad.data_ptr()
+        off += p.numel()
+    assert 4 * off == size
+    after = model.state_dict()
+    assert list(after.keys()) == list(before.keys())
+    for k in before:
+        assert after[k].shape == before[k].shape and torch.equal(after[k], before[k]), k
+    # both directions of the aliasing: the buffer through the module, the module through the buffer
+    with torch.no_grad():
+        model.policy[2].weight.mul_(2.0)
+        flat.flat[-1] = 7.5
+    o = flat.offset_of[id(model.policy[2].weight)]
+    assert torch.equal(flat.flat[o:o + before["policy.2.weight"].numel()].view(256, 512), before["policy.2.weight"] * 2.0)
+    assert float(model.value[6].bias.detach()[0]) == 7.5
+    # load_state_dict copies in place: the views survive
+    model.load_state_dict(before)
+    assert all(p.data_ptr() >= lo and p.data_ptr() < lo + size for p in model.parameters())
+    assert torch.equal(flat.flat[-1:], before["value.6.bias"])
+
+
+def test_checkpoint_restore_round_trip_gives_equal_bits(tmp_path):
+    torch.manual_seed(4)
+    model = ppo.ActorCritic()
+    learn.FlatParams(model)
+    ns, np_ = ppo.RunningNorm(abi.OBS, "cpu"), ppo.RunningNorm(abi.PRIV, "cpu")
+    ns.update(torch.randn(50, abi.OBS) * 2 + 1); np_.update(torch.randn(50, abi.PRIV))
+    ck = ppo.checkpoint(model, ns, np_)
+    with torch.no_grad():
+        for p in model.parameters():
+            p.add_(1.0)                                 # the checkpoint holds copies, not views
+    assert not torch.equal(ck["model"]["policy.0.weight"], model.policy[0].weight)
+    torch.save(ck, tmp_path / "c.pt")
+    back = torch.load(tmp_path / "c.pt")
+    fresh = ppo.ActorCritic()
+    flat = learn.FlatParams(fresh)
+    fresh.load_state_dict(back["model"])                # what train(restore=...) does, here onto flat parameters
+    for k, v in fresh.state_dict().items():
+        assert torch.equal(v, ck["model"][k]), k
+    assert torch.equal(flat.flat, torch.cat([ck["model"][k].reshape(-1) for k in ck["model"]]))
+    ppo.export_policy_npz(ppo.checkpoint(fresh, ns, np_), str(tmp_path / "p.npz"))
+    import numpy as np
+    z = np.load(tmp_path / "p.npz")
+    assert np.array_equal(z["w0"], ck["model"]["policy.0.weight"].numpy().T) and np.array_equal(z["b3"], ck["model"]["policy.6.bias"].numpy())
+
+
+def test_the_default_learner_is_torch():
+    assert ppo.PPOConfig().learner == "torch"
+
+
+def test_train_parser_knows_the_two_learners(capsys):
+    import train
+    ap = train.build_parser()
+    assert ap.parse_args([]).learner == "torch"
+    assert ap.parse_args(["--learner", "torch"]).learner == "torch"
+    assert ap.parse_args(["--learner", "native"]).learner == "native"
+    with pytest.raises(SystemExit):
+        ap.parse_args(["--learner", "jax"])
+    assert "--learner" in capsys.readouterr().err
+
+
+class _CpuEnv:
+    """what ppo.train reads before it decides about the learner"""
+    num_envs, device = 8, torch.device("cpu")
+    observation_size = {"state": abi.OBS, "privileged_state": abi.PRIV}
+    config = {"episode_length": 12}
+
+
+def test_native_learner_on_a_cpu_env_is_refused():
+    with pytest.raises(ValueError, match="native.*GPU"):
+        ppo.train(_CpuEnv(), ppo.PPOConfig(learner="native", num_timesteps=1))
+    with pytest.raises(ValueError, match="learner"):
+        ppo.train(_CpuEnv(), ppo.PPOConfig(learner="fast", num_timesteps=1))
+    with pytest.raises(learn.LearnError, match="GPU"):
+        B = {"obs": torch.zeros(8, abi.OBS), "priv": torch.zeros(8, abi.PRIV), "u": torch.zeros(8, abi.NU)}
+        learn.NativeLearner(ppo.ActorCritic(), None, None, None, B, 4, ppo.PPOConfig())
+
+
+def test_srchash_knows_the_learn_library():
+    files = [os.path.basename(f) for f in srchash.side_files("learn")]
+    assert sorted(files) == ["pgtt.h", "pgtt_learn.h", "pgtt_learn.hip"]
+    h = srchash.side_sha256("learn")
+    assert len(h) == 64 and h != srchash.side_sha256("elevation") and h != srchash.source_sha256()
+    assert "learn" in open(os.path.join(ROOT, "phase_guided_terrain_traversal_amd", "csrc", "pgtt_learn.mk")).read()
+
+
+def test_the_c_mirrors_have_the_headers_fields():
+    """field names and order of the two argument structs against include/pgtt_learn.h (the sizes are checked against the library when it loads)"""
+    import re
+    text = open(os.path.join(ROOT, "include", "pgtt_learn.h")).read()
+    for name, mirror in (("PgttLearnGatherArgs", learn.PgttLearnGatherArgs), ("PgttLearnAdamArgs", learn.PgttLearnAdamArgs)):
+        body = re.search(r"typedef struct " + name + r" \{(.*?)\} " + name, text, re.S).group(1)
+        body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+        fields = []
+        for decl in body.split(";"):
+            decl = decl.strip()
+            if decl:
+                fields += [f.strip().lstrip("*") for f in decl.split(None, 1 + decl.startswith("const"))[-1].split(",")]
+        assert fields == [f for f, _ in mirror._fields_], (name, fields)
+    for fn in learn.EXPORTS:
+        assert re.search(r"\b" + fn + r"\(", text), fn

@@ -102,7 +102,8 @@ def run_training(args):
         ppo.export_policy_npz(params, os.path.join(ckpt, f"policy{args.index}.npz"))
 
     pcfg = ppo.PPOConfig(num_timesteps=args.num_timesteps, num_evals=args.num_evals, num_minibatches=args.num_minibatches,
-                         batch_size=args.batch_size, discounting=args.discount, learning_rate=args.learning_rate, seed=args.index)
+                         batch_size=args.batch_size, discounting=args.discount, learning_rate=args.learning_rate, seed=args.index,
+                         learner=getattr(args, "learner", "torch"))
     model_, norms, hist = ppo.train(env, pcfg, progress_fn=progress,
                                     policy_params_fn=save_params, restore=restore)
     if rank != 0:
@@ -115,7 +116,7 @@ def run_training(args):
     return hist
 
 
-if __name__ == "__main__":
+def build_parser():
     ap = argparse.ArgumentParser(description="Train PPO on the MI355X-native PGTT env")
     ap.add_argument("--method", type=str, default="pgtt")
     ap.add_argument("--task_name", type=str, default="stairs")
@@ -129,8 +130,15 @@ if __name__ == "__main__":
     ap.add_argument("--num_timesteps", type=int, default=1)
     ap.add_argument("--num_evals", type=int, default=31)
     ap.add_argument("--index", type=int, default=32)
+    # the minibatch update and GAE: PyTorch ops with two HIP kernels (torch, the default) or all hand-written HIP on one stream (native)
+    ap.add_argument("--learner", type=str, default="torch", choices=("torch", "native"))
     configs.add_push_args(ap)
     configs.add_curriculum_args(ap)
+    return ap
+
+
+if __name__ == "__main__":
+    ap = build_parser()
     args = ap.parse_args()
     configs.curriculum_from_args(args, ap)                        # --curriculum without --terrain_files: a usage error
     run_training(args)
