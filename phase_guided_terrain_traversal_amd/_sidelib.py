@@ -1,44 +1,60 @@
-"""What render.py (libpgtt_render.so), depth.py (libpgtt_depth.so) and perceive.py (libpgtt_perceive.so) share: loading a side library through
-ctypes, turning its return codes into the module's exception, parsing its build info, the terrain / close methods of a handle's owner, and the three
-env pointers the two ray casters read.  Imported by those modules only: env.py does not reach it unless a depth camera or a student is asked for."""
+"""What the modules of the five side libraries share - render.py (libpgtt_render.so), depth.py (libpgtt_depth.so), perceive.py
+(libpgtt_perceive.so), elevation.py (libpgtt_elevation.so) and learn.py (libpgtt_learn.so): SideLib, which loads a side library through ctypes,
+turns its return codes into the module's exception and parses its build info; the terrain / close methods of a handle's owner; and the three env
+pointers the two ray casters read.  Imported by those modules only: env.py does not reach it unless a depth camera, a student or an elevation map
+is asked for."""
 from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import Dict, Sequence, Tuple, Type
+from typing import Dict, Optional, Sequence, Tuple, Type
 
 import numpy as np
 
 from . import abi
 
 
-def load(path: str, error: Type[Exception], prototypes: Dict[str, Tuple[object, Sequence]], sizeofs: Dict[str, type]) -> C.CDLL:
-    """open the library at `path`: prototypes = {function: (restype or None to keep int, argtypes or None)}, sizeofs = {function: ctypes mirror}"""
-    if not os.path.exists(path):
-        raise error(f"{path} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-                    "(hipcc --offload-arch=gfx950); there is no CPU fallback")
-    # torch's own HIP runtime first, as native.lib() does for libpgtt.so
-    import torch  # noqa: F401
-    L = C.CDLL(path)
-    for name, (restype, argtypes) in prototypes.items():
-        fn = getattr(L, name)
-        if restype is not None:
-            fn.restype = restype
-        if argtypes is not None:
-            fn.argtypes = list(argtypes)
-    for name, mirror in sizeofs.items():
-        assert getattr(L, name)() == C.sizeof(mirror), name
-    return L
+class SideLib:
+    """libpgtt_<name>.so next to the package, opened when first asked for.  prototypes = {function: (restype or None to keep int, argtypes or
+    None)}, sizeofs = {pgtt_<name>_sizeof_* function: the ctypes mirror it must agree with}; the two uniform exports pgtt_<name>_last_error and
+    pgtt_<name>_build_info are added here.  `exports` is every function named: the module's EXPORTS.  `path` may be set before the first lib()
+    (tools/gpu_ab_raycast.py loads two builds that way); `error` is the module's exception class."""
 
+    def __init__(self, name: str, error: Type[Exception], prototypes: Dict[str, Tuple[object, Optional[Sequence]]], sizeofs: Dict[str, type]):
+        self.prefix = "pgtt_" + name
+        self.path = os.path.join(os.path.dirname(os.path.abspath(__file__)), f"lib{self.prefix}.so")
+        self.error, self.sizeofs = error, sizeofs
+        self.prototypes = {**prototypes, self.prefix + "_last_error": (C.c_char_p, None), self.prefix + "_build_info": (C.c_char_p, None)}
+        self.exports = list(self.prototypes) + list(sizeofs)
+        self._lib: Optional[C.CDLL] = None
 
-def check(rc: int, L: C.CDLL, prefix: str, error: Type[Exception]) -> None:
-    """prefix: "pgtt_render" / "pgtt_depth", the functions' common beginning; the library is lib<prefix>.so"""
-    if rc != 0:
-        raise error(f"lib{prefix} error {rc}: {getattr(L, prefix + '_last_error')().decode()}")
+    def lib(self) -> C.CDLL:
+        """the library at `path`, as it is when it is first asked for"""
+        if self._lib is None:
+            if not os.path.exists(self.path):
+                raise self.error(f"{self.path} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
+                                 "(hipcc --offload-arch=gfx950); there is no CPU fallback")
+            # torch's own HIP runtime first, as native.lib() does for libpgtt.so
+            import torch  # noqa: F401
+            L = C.CDLL(self.path)
+            for name, (restype, argtypes) in self.prototypes.items():
+                fn = getattr(L, name)
+                if restype is not None:
+                    fn.restype = restype
+                if argtypes is not None:
+                    fn.argtypes = list(argtypes)
+            for name, mirror in self.sizeofs.items():
+                assert getattr(L, name)() == C.sizeof(mirror), name
+            self._lib = L
+        return self._lib
 
+    def check(self, rc: int) -> None:
+        if rc != 0:
+            raise self.error(f"lib{self.prefix} error {rc}: {getattr(self.lib(), self.prefix + '_last_error')().decode()}")
 
-def build_info(L: C.CDLL, prefix: str) -> dict:
-    return dict(kv.split("=", 1) for kv in getattr(L, prefix + "_build_info")().decode().split(";"))
+    def build_info(self) -> dict:
+        """{"src": srchash.side_sha256(name) when the library was built, "flavor": "product" or an experiment's name}"""
+        return dict(kv.split("=", 1) for kv in getattr(self.lib(), self.prefix + "_build_info")().decode().split(";"))
 
 
 def env_pointers(env):

@@ -22,14 +22,9 @@
 #include "pgtt_raycast.hip.h"
 #include "pgtt_raycast_host.h"
 
-#ifndef PGTT_DEPTH_SRC
-#define PGTT_DEPTH_SRC "unknown"
-#endif
-// experiment build (pgtt_raycast.mk, EXTRA=-DPGTT_DEPTH_NOCULL): every box and geom is kept; the figure DESIGN.md 14 compares against
+// experiment build (pgtt_side.mk, EXTRA=-DPGTT_DEPTH_NOCULL): every box and geom is kept; the figure DESIGN.md 14 compares against
 #ifdef PGTT_DEPTH_NOCULL
 #define PGTT_DEPTH_FLAVOR "nocull"
-#else
-#define PGTT_DEPTH_FLAVOR "product"
 #endif
 
 namespace {
@@ -313,8 +308,7 @@ struct pgtt_depth_camera {
 
 extern "C" {
 
-const char* pgtt_depth_last_error(void) { return g_err.c_str(); }
-const char* pgtt_depth_build_info(void) { return "src=" PGTT_DEPTH_SRC ";flavor=" PGTT_DEPTH_FLAVOR; }
+PGTT_SIDE_EXPORTS(depth, DEPTH)
 int pgtt_depth_sizeof_config(void) { return (int)sizeof(PgttDepthConfig); }
 int pgtt_depth_sizeof_buffers(void) { return (int)sizeof(PgttDepthBuffers); }
 

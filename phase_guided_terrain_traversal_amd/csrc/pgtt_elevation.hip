@@ -16,15 +16,7 @@
 #include <cstdint>
 
 #include "../../include/pgtt_elevation.h"
-#include "pgtt_raycast_host.h"
-
-#ifndef PGTT_ELEVATION_SRC
-#define PGTT_ELEVATION_SRC "unknown"
-#endif
-// an experiment build names itself: make -f pgtt_elevation.mk EXTRA=-DPGTT_ELEVATION_FLAVOR=\"name\" ...
-#ifndef PGTT_ELEVATION_FLAVOR
-#define PGTT_ELEVATION_FLAVOR "product"
-#endif
+#include "pgtt_side_host.h"
 
 namespace {
 
@@ -282,8 +274,7 @@ struct pgtt_elevation_map {
 
 extern "C" {
 
-const char* pgtt_elevation_last_error(void) { return g_err.c_str(); }
-const char* pgtt_elevation_build_info(void) { return "src=" PGTT_ELEVATION_SRC ";flavor=" PGTT_ELEVATION_FLAVOR; }
+PGTT_SIDE_EXPORTS(elevation, ELEVATION)
 int pgtt_elevation_sizeof_config(void) { return (int)sizeof(PgttElevationConfig); }
 int pgtt_elevation_sizeof_buffers(void) { return (int)sizeof(PgttElevationBuffers); }
 

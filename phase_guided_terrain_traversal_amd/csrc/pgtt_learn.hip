@@ -14,22 +14,12 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
-#include <string>
 
 #include "../../include/pgtt_learn.h"
-
-#ifndef PGTT_LEARN_SRC
-#define PGTT_LEARN_SRC "unknown"
-#endif
-// an experiment build names itself: make -f pgtt_learn.mk EXTRA=-DPGTT_LEARN_FLAVOR=\"name\" ...
-#ifndef PGTT_LEARN_FLAVOR
-#define PGTT_LEARN_FLAVOR "product"
-#endif
+#include "pgtt_side_host.h"
 
 namespace {
 
-thread_local std::string g_err;
-int fail(int code, const std::string& msg) { g_err = msg; return code; }
 int launched(const char* who) {
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? PGTT_OK : fail(PGTT_E_HIP, std::string(who) + ": " + hipGetErrorString(e));
@@ -353,8 +343,7 @@ __global__ __launch_bounds__(256) void gae_kernel(const float* __restrict__ trun
 
 extern "C" {
 
-const char* pgtt_learn_last_error(void) { return g_err.c_str(); }
-const char* pgtt_learn_build_info(void) { return "src=" PGTT_LEARN_SRC ";flavor=" PGTT_LEARN_FLAVOR; }
+PGTT_SIDE_EXPORTS(learn, LEARN)
 int pgtt_learn_sizeof_gather_args(void) { return (int)sizeof(PgttLearnGatherArgs); }
 int pgtt_learn_sizeof_adam_args(void) { return (int)sizeof(PgttLearnAdamArgs); }
 int pgtt_learn_adam_partials(int64_t P) { return P > 0 ? adam_blocks((long)P) : 0; }

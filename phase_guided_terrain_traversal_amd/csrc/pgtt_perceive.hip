@@ -17,15 +17,7 @@
 #include <cstdint>
 
 #include "../../include/pgtt_perceive.h"
-#include "pgtt_raycast_host.h"
-
-#ifndef PGTT_PERCEIVE_SRC
-#define PGTT_PERCEIVE_SRC "unknown"
-#endif
-// an experiment build names itself: make -f pgtt_perceive.mk EXTRA=-DPGTT_PERCEIVE_FLAVOR=\"name\" ...
-#ifndef PGTT_PERCEIVE_FLAVOR
-#define PGTT_PERCEIVE_FLAVOR "product"
-#endif
+#include "pgtt_side_host.h"
 
 namespace {
 
@@ -280,8 +272,7 @@ struct pgtt_perceive_net {
 
 extern "C" {
 
-const char* pgtt_perceive_last_error(void) { return g_err.c_str(); }
-const char* pgtt_perceive_build_info(void) { return "src=" PGTT_PERCEIVE_SRC ";flavor=" PGTT_PERCEIVE_FLAVOR; }
+PGTT_SIDE_EXPORTS(perceive, PERCEIVE)
 int pgtt_perceive_sizeof_config(void) { return (int)sizeof(PgttPerceiveConfig); }
 int pgtt_perceive_sizeof_buffers(void) { return (int)sizeof(PgttPerceiveBuffers); }
 

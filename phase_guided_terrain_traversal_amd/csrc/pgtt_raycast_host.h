@@ -1,27 +1,15 @@
-// pgtt_raycast_host.h — the host side that libpgtt_render.so and libpgtt_depth.so share: the error string, the checks of the robot primitives
-// and of the device index, and the device copies of the scene (model, primitives, the ray-ready terrain table).  Everything is in an anonymous
-// namespace: each library keeps its own thread-local error string and exports nothing of this.  `who` is the entry point's name, the prefix of
-// its messages.
+// pgtt_raycast_host.h — the host side that libpgtt_render.so and libpgtt_depth.so share on top of the side libraries' prelude
+// (pgtt_side_host.h: error string, HIP_TRY, check_device): the check of the robot primitives and the device copies of the scene (model,
+// primitives, the ray-ready terrain table).  Everything is in an anonymous namespace and nothing of it is exported.  `who` is the entry
+// point's name, the prefix of its messages.
 #pragma once
-#include <hip/hip_runtime.h>
-
 #include <cmath>
-#include <string>
 #include <vector>
 
 #include "../../include/pgtt_render.h"
+#include "pgtt_side_host.h"
 
 namespace {
-
-thread_local std::string g_err;
-
-int fail(int code, const std::string& msg) { g_err = msg; return code; }
-
-#define HIP_TRY(expr)                                                                              \
-  do {                                                                                             \
-    hipError_t _e = (expr);                                                                        \
-    if (_e != hipSuccess) return fail(PGTT_E_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-  } while (0)
 
 constexpr int kTabWords = 16;           // ray-ready box, world frame: centre[3], local axes in world coordinates r0[3] r1[3] r2[3], half extents[3], pad
 
@@ -35,13 +23,6 @@ int check_geoms(const PgttRenderGeom* geoms, int ngeom, const char* who) {
         (geoms[g].type == PGTT_RENDER_BOX && !(geoms[g].size[2] > 0.f)))
       return fail(PGTT_E_ARG, p + "geom sizes must be positive");
   }
-  return PGTT_OK;
-}
-
-int check_device(int device, const char* who) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(PGTT_E_NODEVICE, std::string(who) + ": no HIP device (this library has no CPU path)");
-  if (device < 0 || device >= ndev) return fail(PGTT_E_ARG, std::string(who) + ": device index out of range");
   return PGTT_OK;
 }
 

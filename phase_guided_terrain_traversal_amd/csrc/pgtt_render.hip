@@ -18,10 +18,6 @@
 #include "pgtt_raycast.hip.h"
 #include "pgtt_raycast_host.h"
 
-#ifndef PGTT_RENDER_SRC
-#define PGTT_RENDER_SRC "unknown"
-#endif
-
 namespace {
 
 constexpr int kTile = 16;               // pixel tile edge: 256 lanes per workgroup
@@ -291,8 +287,7 @@ struct pgtt_renderer {
 
 extern "C" {
 
-const char* pgtt_render_last_error(void) { return g_err.c_str(); }
-const char* pgtt_render_build_info(void) { return "src=" PGTT_RENDER_SRC ";flavor=product"; }
+PGTT_SIDE_EXPORTS(render, RENDER)
 int pgtt_render_sizeof_geom(void) { return (int)sizeof(PgttRenderGeom); }
 int pgtt_render_sizeof_camera(void) { return (int)sizeof(PgttRenderCamera); }
 int pgtt_render_sizeof_views(void) { return (int)sizeof(PgttRenderViews); }

@@ -12,22 +12,16 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-import os
 from typing import Dict, Optional, Sequence
 
 import numpy as np
 
 from . import _sidelib, abi
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(_HERE, "libpgtt_depth.so")
-_LIB: Optional[C.CDLL] = None
+from .render import PgttRenderGeom
 
 # include/pgtt_depth.h
 MAX_DIM = 256
 RS_DEPTH = 32
-EXPORTS = ["pgtt_depth_create", "pgtt_depth_destroy", "pgtt_depth_set_terrain", "pgtt_depth_bind", "pgtt_depth", "pgtt_depth_sizeof_config",
-           "pgtt_depth_sizeof_buffers", "pgtt_depth_build_info", "pgtt_depth_last_error"]
 # Joystick(depth=...) / evaluate.py --video_depth: placeholders for a Go2 head camera - settings, not measured facts about a robot
 DEFAULTS = dict(width=64, height=48, fovy=58.0, near=0.1, far=3.0, mount_body=0, mount_pos=(0.30, 0.0, 0.05), pitch_deg=30.0, every=1,
                 see_robot=True, noise=None)
@@ -42,7 +36,7 @@ def settings(overrides: Optional[Dict] = None) -> Dict:
     return kw
 
 
-f, i32 = C.c_float, C.c_int32
+f, i32, vp = C.c_float, C.c_int32, C.c_void_p
 
 
 class PgttDepthConfig(C.Structure):
@@ -62,31 +56,13 @@ class DepthError(RuntimeError):
     pass
 
 
-def lib() -> C.CDLL:
-    """libpgtt_depth.so at LIB_PATH, as it is when the library is first asked for"""
-    global _LIB
-    if _LIB is None:
-        from .render import PgttRenderGeom
-        vp = C.c_void_p
-        _LIB = _sidelib.load(LIB_PATH, DepthError, {
-            "pgtt_depth_last_error": (C.c_char_p, None), "pgtt_depth_build_info": (C.c_char_p, None),
-            "pgtt_depth_create": (None, [C.POINTER(abi.PgttModel), C.POINTER(PgttDepthConfig), C.POINTER(PgttRenderGeom), C.c_int, C.c_int, C.c_int,
-                                         C.POINTER(vp)]),
-            "pgtt_depth_destroy": (None, [vp]), "pgtt_depth_set_terrain": (None, [vp, vp, C.c_int, C.c_int]),
-            "pgtt_depth_bind": (None, [vp, C.POINTER(PgttDepthBuffers)]), "pgtt_depth": (None, [vp, C.c_int, vp]),
-        }, {"pgtt_depth_sizeof_config": PgttDepthConfig, "pgtt_depth_sizeof_buffers": PgttDepthBuffers})
-    return _LIB
-
-
-def check(rc: int) -> None:
-    _sidelib.check(rc, lib(), "pgtt_depth", DepthError)
-
-
-def build_info() -> dict:
-    """{"src": srchash.side_sha256("depth") at build time - SHA-256 over everything the library is built from, pgtt_depth.hip and the files
-    it includes (pgtt_raycast.hip.h, pgtt_raycast_host.h, pgtt_depth.h, pgtt_render.h, pgtt.h), comments and white space removed -,
-    "flavor": "product" or "nocull"}"""
-    return _sidelib.build_info(lib(), "pgtt_depth")
+SIDE = _sidelib.SideLib("depth", DepthError, {
+    "pgtt_depth_create": (None, [C.POINTER(abi.PgttModel), C.POINTER(PgttDepthConfig), C.POINTER(PgttRenderGeom), C.c_int, C.c_int, C.c_int,
+                                 C.POINTER(vp)]),
+    "pgtt_depth_destroy": (None, [vp]), "pgtt_depth_set_terrain": (None, [vp, vp, C.c_int, C.c_int]),
+    "pgtt_depth_bind": (None, [vp, C.POINTER(PgttDepthBuffers)]), "pgtt_depth": (None, [vp, C.c_int, vp]),
+}, {"pgtt_depth_sizeof_config": PgttDepthConfig, "pgtt_depth_sizeof_buffers": PgttDepthBuffers})
+LIB_PATH, EXPORTS, lib, check, build_info = SIDE.path, SIDE.exports, SIDE.lib, SIDE.check, SIDE.build_info
 
 
 def pitch_quat(pitch_deg: float) -> np.ndarray:

@@ -12,23 +12,16 @@ by env.py unless an elevation map is asked for.
 from __future__ import annotations
 
 import ctypes as C
-import os
 from typing import Dict, Optional, Sequence
 
 import torch
 
 from . import _sidelib, abi
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(_HERE, "libpgtt_elevation.so")
-_LIB: Optional[C.CDLL] = None
-
 # include/pgtt_elevation.h
 MAX_DIM, MIN_GRID, MAX_GRID = 256, 8, 96
 NSCAN = abi.NSCAN
 SCAN_ROW0 = {"pgtt": 38, "baseline": 30}           # perceive.SCAN_ROW0: the scan rows sit between phase / joint_vel and gait_freq / last_act
-EXPORTS = ["pgtt_elevation_check", "pgtt_elevation_create", "pgtt_elevation_destroy", "pgtt_elevation_bind", "pgtt_elevation",
-           "pgtt_elevation_sizeof_config", "pgtt_elevation_sizeof_buffers", "pgtt_elevation_build_info", "pgtt_elevation_last_error"]
 # Joystick(elevation=True) / evaluate.py --elevation: a 2.56 m window of 4 cm cells, the newest view replaces the old one, and a box around the
 # torso that drops the robot's own legs from a camera that sees them - settings, not measured facts about a robot
 DEFAULTS = dict(grid=64, res=0.04, alpha=1.0, self_half=(0.45, 0.25, 0.45))
@@ -54,27 +47,13 @@ class ElevationError(RuntimeError):
     pass
 
 
-def lib() -> C.CDLL:
-    """libpgtt_elevation.so at LIB_PATH, as it is when the library is first asked for"""
-    global _LIB
-    if _LIB is None:
-        vp, cp = C.c_void_p, C.POINTER(PgttElevationConfig)
-        _LIB = _sidelib.load(LIB_PATH, ElevationError, {
-            "pgtt_elevation_last_error": (C.c_char_p, None), "pgtt_elevation_build_info": (C.c_char_p, None),
-            "pgtt_elevation_check": (None, [cp]), "pgtt_elevation_create": (None, [cp, C.c_int, C.c_int, C.POINTER(vp)]),
-            "pgtt_elevation_destroy": (None, [vp]), "pgtt_elevation_bind": (None, [vp, C.POINTER(PgttElevationBuffers)]),
-            "pgtt_elevation": (None, [vp, vp, C.c_int, C.c_int, vp]),
-        }, {"pgtt_elevation_sizeof_config": PgttElevationConfig, "pgtt_elevation_sizeof_buffers": PgttElevationBuffers})
-    return _LIB
-
-
-def check(rc: int) -> None:
-    _sidelib.check(rc, lib(), "pgtt_elevation", ElevationError)
-
-
-def build_info() -> dict:
-    """{"src": srchash.side_sha256("elevation") at build time, "flavor": "product" or an experiment's name}"""
-    return _sidelib.build_info(lib(), "pgtt_elevation")
+vp, cp = C.c_void_p, C.POINTER(PgttElevationConfig)
+SIDE = _sidelib.SideLib("elevation", ElevationError, {
+    "pgtt_elevation_check": (None, [cp]), "pgtt_elevation_create": (None, [cp, C.c_int, C.c_int, C.POINTER(vp)]),
+    "pgtt_elevation_destroy": (None, [vp]), "pgtt_elevation_bind": (None, [vp, C.POINTER(PgttElevationBuffers)]),
+    "pgtt_elevation": (None, [vp, vp, C.c_int, C.c_int, vp]),
+}, {"pgtt_elevation_sizeof_config": PgttElevationConfig, "pgtt_elevation_sizeof_buffers": PgttElevationBuffers})
+LIB_PATH, EXPORTS, lib, check, build_info = SIDE.path, SIDE.exports, SIDE.lib, SIDE.check, SIDE.build_info
 
 
 def settings(overrides=None) -> Dict:

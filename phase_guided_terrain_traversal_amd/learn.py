@@ -13,21 +13,12 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import Optional
 
 import torch
 import torch.distributed as dist
 import torch.nn as nn
 
 from . import _sidelib, native
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(_HERE, "libpgtt_learn.so")
-_LIB: Optional[C.CDLL] = None
-
-EXPORTS = ["pgtt_learn_gather", "pgtt_learn_linear_forward", "pgtt_learn_linear_backward_data", "pgtt_learn_value_loss", "pgtt_learn_clip_adam",
-           "pgtt_learn_adam_partials", "pgtt_learn_gae", "pgtt_learn_sizeof_gather_args", "pgtt_learn_sizeof_adam_args", "pgtt_learn_build_info",
-           "pgtt_learn_last_error"]
 
 vp, i32 = C.c_void_p, C.c_int32
 
@@ -50,31 +41,17 @@ class LearnError(RuntimeError):
     pass
 
 
-def lib() -> C.CDLL:
-    """libpgtt_learn.so at LIB_PATH, as it is when the library is first asked for"""
-    global _LIB
-    if _LIB is None:
-        ci, cf = C.c_int, C.c_float
-        _LIB = _sidelib.load(LIB_PATH, LearnError, {
-            "pgtt_learn_last_error": (C.c_char_p, None), "pgtt_learn_build_info": (C.c_char_p, None),
-            "pgtt_learn_gather": (None, [C.POINTER(PgttLearnGatherArgs), vp]),
-            "pgtt_learn_linear_forward": (None, [vp, vp, vp, ci, ci, ci, ci, vp, vp, vp]),
-            "pgtt_learn_linear_backward_data": (None, [vp, vp, vp, ci, ci, ci, vp, vp]),
-            "pgtt_learn_value_loss": (None, [vp, vp, ci, vp, vp, vp]),
-            "pgtt_learn_clip_adam": (None, [C.POINTER(PgttLearnAdamArgs), vp]),
-            "pgtt_learn_adam_partials": (None, [C.c_int64]),
-            "pgtt_learn_gae": (None, [vp, vp, vp, vp, vp, ci, ci, cf, cf, vp, vp, vp]),
-        }, {"pgtt_learn_sizeof_gather_args": PgttLearnGatherArgs, "pgtt_learn_sizeof_adam_args": PgttLearnAdamArgs})
-    return _LIB
-
-
-def check(rc: int) -> None:
-    _sidelib.check(rc, lib(), "pgtt_learn", LearnError)
-
-
-def build_info() -> dict:
-    """{"src": srchash.side_sha256("learn") at build time, "flavor": "product" or an experiment's name}"""
-    return _sidelib.build_info(lib(), "pgtt_learn")
+ci, cf = C.c_int, C.c_float
+SIDE = _sidelib.SideLib("learn", LearnError, {
+    "pgtt_learn_gather": (None, [C.POINTER(PgttLearnGatherArgs), vp]),
+    "pgtt_learn_linear_forward": (None, [vp, vp, vp, ci, ci, ci, ci, vp, vp, vp]),
+    "pgtt_learn_linear_backward_data": (None, [vp, vp, vp, ci, ci, ci, vp, vp]),
+    "pgtt_learn_value_loss": (None, [vp, vp, ci, vp, vp, vp]),
+    "pgtt_learn_clip_adam": (None, [C.POINTER(PgttLearnAdamArgs), vp]),
+    "pgtt_learn_adam_partials": (None, [C.c_int64]),
+    "pgtt_learn_gae": (None, [vp, vp, vp, vp, vp, ci, ci, cf, cf, vp, vp, vp]),
+}, {"pgtt_learn_sizeof_gather_args": PgttLearnGatherArgs, "pgtt_learn_sizeof_adam_args": PgttLearnAdamArgs})
+LIB_PATH, EXPORTS, lib, check, build_info = SIDE.path, SIDE.exports, SIDE.lib, SIDE.check, SIDE.build_info
 
 
 def _stream(dev) -> C.c_void_p:

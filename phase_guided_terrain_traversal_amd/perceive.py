@@ -13,7 +13,6 @@ from __future__ import annotations
 
 import ctypes as C
 import json
-import os
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -21,17 +20,10 @@ import torch
 
 from . import _sidelib, abi, acting, depth as _depth
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(_HERE, "libpgtt_perceive.so")
-_LIB: Optional[C.CDLL] = None
-
 # include/pgtt_perceive.h
 MAX_CONV, MAX_CH, MAX_PROP, MAX_HIDDEN, MAX_DIM, LDS_BYTES, NLAYER, OUT_PAD = 3, 64, 64, 512, 256, 61440, 5, 128
 NSCAN = abi.NSCAN
 SCAN_ROW0 = {"pgtt": 38, "baseline": 30}           # the scan rows sit between phase / joint_vel and gait_freq / last_act
-EXPORTS = ["pgtt_perceive_check", "pgtt_perceive_latent_dim", "pgtt_perceive_packed_floats", "pgtt_perceive_create", "pgtt_perceive_destroy",
-           "pgtt_perceive_bind", "pgtt_perceive", "pgtt_perceive_sizeof_config", "pgtt_perceive_sizeof_buffers", "pgtt_perceive_build_info",
-           "pgtt_perceive_last_error"]
 # the scan grid is 13 rows (x, ahead first) by 9 columns: the bands train_student.py reports
 BANDS = {"ahead": slice(0, 6 * abi.SCAN_W), "under": slice(6 * abi.SCAN_W, 7 * abi.SCAN_W), "behind": slice(7 * abi.SCAN_W, NSCAN)}
 
@@ -69,27 +61,13 @@ class PerceiveError(RuntimeError):
     pass
 
 
-def lib() -> C.CDLL:
-    """libpgtt_perceive.so at LIB_PATH, as it is when the library is first asked for"""
-    global _LIB
-    if _LIB is None:
-        vp, cp = C.c_void_p, C.POINTER(PgttPerceiveConfig)
-        _LIB = _sidelib.load(LIB_PATH, PerceiveError, {
-            "pgtt_perceive_last_error": (C.c_char_p, None), "pgtt_perceive_build_info": (C.c_char_p, None),
-            "pgtt_perceive_check": (None, [cp]), "pgtt_perceive_latent_dim": (None, [cp]), "pgtt_perceive_packed_floats": (None, [cp, C.c_int]),
-            "pgtt_perceive_create": (None, [cp, C.c_int, C.c_int, C.POINTER(vp)]), "pgtt_perceive_destroy": (None, [vp]),
-            "pgtt_perceive_bind": (None, [vp, C.POINTER(PgttPerceiveBuffers)]), "pgtt_perceive": (None, [vp, vp]),
-        }, {"pgtt_perceive_sizeof_config": PgttPerceiveConfig, "pgtt_perceive_sizeof_buffers": PgttPerceiveBuffers})
-    return _LIB
-
-
-def check(rc: int) -> None:
-    _sidelib.check(rc, lib(), "pgtt_perceive", PerceiveError)
-
-
-def build_info() -> dict:
-    """{"src": srchash.side_sha256("perceive") at build time, "flavor": "product" or an experiment's name}"""
-    return _sidelib.build_info(lib(), "pgtt_perceive")
+vp, cp = C.c_void_p, C.POINTER(PgttPerceiveConfig)
+SIDE = _sidelib.SideLib("perceive", PerceiveError, {
+    "pgtt_perceive_check": (None, [cp]), "pgtt_perceive_latent_dim": (None, [cp]), "pgtt_perceive_packed_floats": (None, [cp, C.c_int]),
+    "pgtt_perceive_create": (None, [cp, C.c_int, C.c_int, C.POINTER(vp)]), "pgtt_perceive_destroy": (None, [vp]),
+    "pgtt_perceive_bind": (None, [vp, C.POINTER(PgttPerceiveBuffers)]), "pgtt_perceive": (None, [vp, vp]),
+}, {"pgtt_perceive_sizeof_config": PgttPerceiveConfig, "pgtt_perceive_sizeof_buffers": PgttPerceiveBuffers})
+LIB_PATH, EXPORTS, lib, check, build_info = SIDE.path, SIDE.exports, SIDE.lib, SIDE.check, SIDE.build_info
 
 
 def conv_shapes(cfg: Dict) -> List[Tuple[int, int, int]]:

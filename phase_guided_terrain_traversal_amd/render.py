@@ -21,19 +21,12 @@ import numpy as np
 
 from . import _sidelib, abi
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(_HERE, "libpgtt_render.so")
-_LIB: Optional[C.CDLL] = None
-
 # include/pgtt_render.h
 MAX_GEOM, MAX_MARKER, MAX_DIM, MAX_VIEWS = 32, 128, 4096, 16384
 SPHERE, CAPSULE, BOX = 0, 1, 2
 CAM_MODES = {"fixed": 0, "track": 1, "track_yaw": 2}
 SHADOWS = 1
 SEG_SKY, SEG_PLANE, SEG_BOX, SEG_GEOM, SEG_MARKER = -1, 0, 1, 1000, 2000
-EXPORTS = ["pgtt_render_create", "pgtt_render_destroy", "pgtt_render_set_terrain", "pgtt_render_workspace_bytes", "pgtt_render",
-           "pgtt_render_sizeof_geom", "pgtt_render_sizeof_camera", "pgtt_render_sizeof_views", "pgtt_render_build_info",
-           "pgtt_render_last_error"]
 
 f, i32 = C.c_float, C.c_int32
 
@@ -60,28 +53,13 @@ class RenderError(RuntimeError):
     pass
 
 
-def lib() -> C.CDLL:
-    """libpgtt_render.so at LIB_PATH, as it is when the library is first asked for"""
-    global _LIB
-    if _LIB is None:
-        vp = C.c_void_p
-        _LIB = _sidelib.load(LIB_PATH, RenderError, {
-            "pgtt_render_last_error": (C.c_char_p, None), "pgtt_render_build_info": (C.c_char_p, None),
-            "pgtt_render_create": (None, [C.POINTER(abi.PgttModel), C.POINTER(PgttRenderGeom), C.c_int, C.c_int, C.POINTER(vp)]),
-            "pgtt_render_destroy": (None, [vp]), "pgtt_render_set_terrain": (None, [vp, vp, C.c_int, C.c_int]),
-            "pgtt_render_workspace_bytes": (C.c_int64, [C.c_int]), "pgtt_render": (None, [vp, C.POINTER(PgttRenderViews), vp]),
-        }, {"pgtt_render_sizeof_geom": PgttRenderGeom, "pgtt_render_sizeof_camera": PgttRenderCamera, "pgtt_render_sizeof_views": PgttRenderViews})
-    return _LIB
-
-
-def check(rc: int) -> None:
-    _sidelib.check(rc, lib(), "pgtt_render", RenderError)
-
-
-def build_info() -> dict:
-    """{"src": srchash.side_sha256("render") at build time - SHA-256 over everything the library is built from, pgtt_render.hip and the files
-    it includes (pgtt_raycast.hip.h, pgtt_raycast_host.h, pgtt_render.h, pgtt.h), comments and white space removed -, "flavor": "product"}"""
-    return _sidelib.build_info(lib(), "pgtt_render")
+vp = C.c_void_p
+SIDE = _sidelib.SideLib("render", RenderError, {
+    "pgtt_render_create": (None, [C.POINTER(abi.PgttModel), C.POINTER(PgttRenderGeom), C.c_int, C.c_int, C.POINTER(vp)]),
+    "pgtt_render_destroy": (None, [vp]), "pgtt_render_set_terrain": (None, [vp, vp, C.c_int, C.c_int]),
+    "pgtt_render_workspace_bytes": (C.c_int64, [C.c_int]), "pgtt_render": (None, [vp, C.POINTER(PgttRenderViews), vp]),
+}, {"pgtt_render_sizeof_geom": PgttRenderGeom, "pgtt_render_sizeof_camera": PgttRenderCamera, "pgtt_render_sizeof_views": PgttRenderViews})
+LIB_PATH, EXPORTS, lib, check, build_info = SIDE.path, SIDE.exports, SIDE.lib, SIDE.check, SIDE.build_info
 
 
 # ---------------------------------------------------------------- robot primitives

@@ -4,9 +4,10 @@ and csrc/flags.mk, the make fragment that holds the compile flags of that unit. 
 change the kernel).  The task-side kernels, the host code and the other rules of the Makefile are not covered: a change there leaves the hash,
 and with it the counters recorded under profiles/, valid.  EXTRA flags and the 1-ulp division are what the build's flavor says.
 
-The side libraries (csrc/pgtt_raycast.mk, csrc/pgtt_perceive.mk, csrc/pgtt_elevation.mk, csrc/pgtt_learn.mk) embed a hash of their own,
-side_sha256("render" | "depth" | "perceive" | "elevation" | "learn"): the
-include closure of their one translation unit (SIDE_SOURCES), normalised the same way.  `python3 srchash.py` prints the physics hash, `python3 srchash.py render` a side hash."""
+The side libraries (csrc/pgtt_side.mk) embed a hash of their own, side_sha256("render" | "depth" | "perceive" | "elevation" | "learn"): the
+include closure of their one translation unit, normalised the same way.  SIDE_SOURCES is the one statement of what a side library is built from:
+the hash, the make file's prerequisites and the closure test of tests/test_abi.py read it.  `python3 srchash.py` prints the physics hash,
+`python3 srchash.py render` a side hash, `python3 srchash.py --files render` the files that hash covers, one per line."""
 import hashlib
 import os
 import re
@@ -15,12 +16,13 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 PHYSICS_SOURCES = ("pgtt_physics_inst.hip", "pgtt_physics.hip.h", "pgtt_physics_quad.hip.h", "pgtt_common.hip.h")
 FLAGS_FRAGMENT = "flags.mk"
 # per side library: the unit and the shared headers in csrc/, then the public headers in include/ (every project file the unit includes)
-_RAYCAST = ("pgtt_raycast.hip.h", "pgtt_raycast_host.h")
+_PRELUDE = ("pgtt_side_host.h",)
+_RAYCAST = ("pgtt_raycast.hip.h", "pgtt_raycast_host.h") + _PRELUDE
 SIDE_SOURCES = {"render": (("pgtt_render.hip",) + _RAYCAST, ("pgtt_render.h", "pgtt.h")),
                 "depth": (("pgtt_depth.hip",) + _RAYCAST, ("pgtt_depth.h", "pgtt_render.h", "pgtt.h")),
-                "perceive": (("pgtt_perceive.hip", "pgtt_raycast_host.h"), ("pgtt_perceive.h", "pgtt_render.h", "pgtt.h")),
-                "elevation": (("pgtt_elevation.hip", "pgtt_raycast_host.h"), ("pgtt_elevation.h", "pgtt_render.h", "pgtt.h")),
-                "learn": (("pgtt_learn.hip",), ("pgtt_learn.h", "pgtt.h"))}
+                "perceive": (("pgtt_perceive.hip",) + _PRELUDE, ("pgtt_perceive.h", "pgtt.h")),
+                "elevation": (("pgtt_elevation.hip",) + _PRELUDE, ("pgtt_elevation.h", "pgtt.h")),
+                "learn": (("pgtt_learn.hip",) + _PRELUDE, ("pgtt_learn.h", "pgtt.h"))}
 
 
 def hashed_files(pkg: str = _HERE):
@@ -58,4 +60,8 @@ def _sha256(files) -> str:
 
 if __name__ == "__main__":
     import sys
-    print(side_sha256(sys.argv[1]) if len(sys.argv) > 1 else source_sha256())
+    args = sys.argv[1:]
+    if args[:1] == ["--files"]:
+        print("\n".join(side_files(args[1])))
+    else:
+        print(side_sha256(args[0]) if args else source_sha256())

@@ -206,23 +206,30 @@ def test_source_hash_files_are_the_include_closure_of_the_physics_translation_un
     assert local | {os.path.realpath(os.path.join(csrc, "flags.mk"))} == hashed
 
 
-# ---------------------------------------------------------------- the two ray-casting side libraries (csrc/pgtt_raycast.mk)
-SIDE = ("render", "depth")
+# ---------------------------------------------------------------- the five side libraries (csrc/pgtt_side.mk)
+SIDE = ("render", "depth", "perceive", "elevation", "learn")
+RAYCAST = ("render", "depth")                              # the two over the shared ray-casting core
 
 
 def _side_module(name):
-    from phase_guided_terrain_traversal_amd import depth, render
-    return {"render": render, "depth": depth}[name]
+    import importlib
+    return importlib.import_module("phase_guided_terrain_traversal_amd." + name)
+
+
+def _needs_side_lib(name):
+    mod = _side_module(name)
+    if not os.path.exists(mod.LIB_PATH):
+        pytest.skip(f"libpgtt_{name}.so not built (run __graft_entry__.build())")
+    return mod
 
 
 @pytest.mark.parametrize("name", SIDE)
 def test_side_hash_matches_the_built_library(name):
-    """pgtt_<name>_build_info() carries srchash.side_sha256(name) of the sources as they are now"""
+    """pgtt_<name>_build_info() carries srchash.side_sha256(name) of the sources as they are now, and the flavor of the shipped build"""
     from phase_guided_terrain_traversal_amd import srchash
-    mod = _side_module(name)
-    if not os.path.exists(mod.LIB_PATH):
-        pytest.skip(f"libpgtt_{name}.so not built (run __graft_entry__.build())")
-    assert mod.build_info()["src"] == srchash.side_sha256(name)
+    info = _needs_side_lib(name).build_info()
+    assert info["src"] == srchash.side_sha256(name) and re.fullmatch(r"[0-9a-f]{64}", info["src"])
+    assert info["flavor"] == "product"
 
 
 @pytest.mark.parametrize("name", SIDE)
@@ -243,11 +250,58 @@ def test_side_hash_files_are_the_include_closure_of_the_unit(name):
     in_csrc, in_include = srchash.SIDE_SOURCES[name]
     assert {os.path.basename(f) for f in seen} == set(in_csrc) | set(in_include)
     assert "pgtt_common.hip.h" not in in_csrc                  # the physics hash and the side hashes share include/pgtt.h only
+    assert "pgtt_side_host.h" in in_csrc                       # every side library stands on the one host prelude
+    # the ray-casting core - device algebra, scene tables, the renderer's public header - belongs to the two ray casters alone
+    for f in ("pgtt_raycast.hip.h", "pgtt_raycast_host.h", "pgtt_render.h"):
+        assert (f in in_csrc + in_include) == (name in RAYCAST), f
+
+
+@pytest.mark.parametrize("name", SIDE)
+def test_side_make_prerequisites_are_the_hashed_files(name):
+    """csrc/pgtt_side.mk takes a unit's prerequisites from `srchash.py --files <name>`, which prints side_files(name); it names no header itself"""
+    import subprocess
+    import sys
+    from phase_guided_terrain_traversal_amd import srchash
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "phase_guided_terrain_traversal_amd", "srchash.py"), "--files", name],
+                         check=True, capture_output=True, text=True).stdout
+    assert out.split("\n") == srchash.side_files(name) + [""]
+    mk = open(os.path.join(ROOT, "phase_guided_terrain_traversal_amd", "csrc", "pgtt_side.mk")).read()
+    rules = "\n".join(ln.split("#", 1)[0] for ln in mk.splitlines())
+    assert "srchash.py --files" in rules and not re.search(r"\.h\b", rules)
+
+
+@pytest.mark.parametrize("name", SIDE)
+def test_side_header_functions_are_the_modules_exports(name):
+    """every function include/pgtt_<name>.h declares is in the module's EXPORTS and the other way round; no name is the env ABI's or another
+    side library's"""
+    mod = _side_module(name)
+    text = open(os.path.join(ROOT, "include", f"pgtt_{name}.h")).read()
+    assert sorted(set(re.findall(rf"\b(pgtt_{name}[a-z_0-9]*)\s*\(", text))) == sorted(mod.EXPORTS)
+    assert len(set(mod.EXPORTS)) == len(mod.EXPORTS) and all(fn == f"pgtt_{name}" or fn.startswith(f"pgtt_{name}_") for fn in mod.EXPORTS)
+    assert not set(mod.EXPORTS) & set(native.EXPORTS + native.TRAIN_EXPORTS)
+    for other in SIDE:
+        assert other == name or not set(mod.EXPORTS) & set(_side_module(other).EXPORTS), other
+
+
+@pytest.mark.parametrize("name", SIDE)
+def test_side_library_exports_exactly_the_modules_exports(name):
+    """nm -D: the library defines the module's EXPORTS and no other pgtt name (nothing of libpgtt.so, nothing of another side library)"""
+    import subprocess
+    mod = _needs_side_lib(name)
+    out = subprocess.run(["nm", "-D", "--defined-only", mod.LIB_PATH], capture_output=True, text=True)
+    if out.returncode != 0:
+        pytest.skip("nm not available")
+    names = {ln.split()[-1] for ln in out.stdout.splitlines() if " T " in ln and ln.split()[-1].startswith("pgtt")}
+    assert names == set(mod.EXPORTS)
+    L = mod.lib()
+    for fn in mod.EXPORTS:
+        assert hasattr(L, fn), fn
 
 
 def test_side_hashes_react_to_the_right_edits(tmp_path):
-    """on a copied tree: a statement in the shared core moves both side hashes and not the physics hash, a comment moves nothing, an edit of
-    pgtt_depth.hip moves the depth hash alone"""
+    """on a copied tree: a statement in the host prelude moves all five side hashes and not the physics hash, one in the ray-casting core moves
+    render and depth only, one in a unit or in its public header moves that library's hash alone (pgtt_render.h: depth's too), one in the physics
+    kernels' header moves the physics hash only, a comment moves nothing"""
     import shutil
     from phase_guided_terrain_traversal_amd import srchash
     csrc = os.path.join(ROOT, "phase_guided_terrain_traversal_amd", "csrc")
@@ -261,35 +315,36 @@ def test_side_hashes_react_to_the_right_edits(tmp_path):
         shutil.copy(os.path.join(ROOT, "include", f), tmp_path / "include" / f)
 
     def hashes():
-        return srchash.side_sha256("render", str(cp)), srchash.side_sha256("depth", str(cp)), srchash.source_sha256(str(cp))
-    r0, d0, p0 = hashes()
-    assert (r0, d0, p0) == (srchash.side_sha256("render"), srchash.side_sha256("depth"), srchash.source_sha256()) and len({r0, d0, p0}) == 3
+        return {**{n: srchash.side_sha256(n, str(cp)) for n in SIDE}, "physics": srchash.source_sha256(str(cp))}
+    h0 = hashes()
+    assert h0 == {**{n: srchash.side_sha256(n) for n in SIDE}, "physics": srchash.source_sha256()} and len(set(h0.values())) == len(SIDE) + 1
 
-    def appended(name, text):
-        p = cp / "csrc" / name
-        old = p.read_text()
-        p.write_text(old + text)
+    def moved(path, text="\nint pgtt_extra_statement;\n"):
+        """the hashes that differ from h0 with `text` appended to `path`"""
+        old = path.read_text()
+        path.write_text(old + text)
         h = hashes()
-        p.write_text(old)
-        return h
+        path.write_text(old)
+        return {k for k in h if h[k] != h0[k]}
+    assert moved(cp / "csrc" / "pgtt_side_host.h") == set(SIDE)
     for core in ("pgtt_raycast.hip.h", "pgtt_raycast_host.h"):
-        r, d, p = appended(core, "\nint pgtt_extra_statement;\n")
-        assert r != r0 and d != d0 and p == p0, core
-        assert appended(core, "\n// a comment\n") == (r0, d0, p0), core
-    r, d, p = appended("pgtt_depth.hip", "\nint pgtt_extra_statement;\n")
-    assert r == r0 and d != d0 and p == p0
-    r, d, p = appended("pgtt_render.hip", "\nint pgtt_extra_statement;\n")
-    assert r != r0 and d == d0 and p == p0
-    r, d, p = appended("pgtt_common.hip.h", "\nint pgtt_extra_statement;\n")            # the physics kernels' header is no part of either side library
-    assert r == r0 and d == d0 and p != p0
+        assert moved(cp / "csrc" / core) == set(RAYCAST), core
+    for name in SIDE:
+        assert moved(cp / "csrc" / f"pgtt_{name}.hip") == {name}, name
+        assert moved(tmp_path / "include" / f"pgtt_{name}.h") == ({name} if name != "render" else set(RAYCAST)), name
+    assert moved(cp / "csrc" / "pgtt_common.hip.h") == {"physics"}    # the physics kernels' header is no part of a side library
+    for f in ("pgtt_side_host.h", "pgtt_raycast.hip.h", "pgtt_raycast_host.h", "pgtt_common.hip.h") + tuple(f"pgtt_{n}.hip" for n in SIDE):
+        assert moved(cp / "csrc" / f, "\n// a comment\n") == set(), f
 
 
 def test_side_libraries_raise_their_own_error_class():
-    from phase_guided_terrain_traversal_amd import depth, render
-    for mod, err, libname in ((render, render.RenderError, "libpgtt_render"), (depth, depth.DepthError, "libpgtt_depth")):
-        if not os.path.exists(mod.LIB_PATH):
-            pytest.skip(f"{libname}.so not built (run __graft_entry__.build())")
+    errors = {}
+    for name in SIDE:
+        mod = _needs_side_lib(name)
+        errors[name] = getattr(mod, name.capitalize() + "Error")
         mod.check(0)
-        with pytest.raises(err, match=libname + " error 1"):
+        with pytest.raises(errors[name], match=f"libpgtt_{name} error 1"):
             mod.check(1)
-    assert not issubclass(render.RenderError, depth.DepthError) and not issubclass(depth.DepthError, render.RenderError)
+    for a in SIDE:
+        for b in SIDE:
+            assert a == b or not issubclass(errors[a], errors[b]), (a, b)

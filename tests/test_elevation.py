@@ -1,9 +1,8 @@
 """The depth-fused elevation map without a GPU: facts that hold tests/elevation_reference.py (the fp64 statement of include/pgtt_elevation.h that
 the GPU tests compare the kernel with) on its own, and the host side of libpgtt_elevation.so - the config's refusals, the struct sizes, the source
-hash and its file list, and the refusals of Joystick(elevation=...) that come before anything touches a device."""
+hash (its file list: tests/test_abi.py), and the refusals of Joystick(elevation=...) that come before anything touches a device."""
 import ctypes as C
 import os
-import re
 import sys
 
 import numpy as np
@@ -15,7 +14,6 @@ import elevation_reference as ref  # noqa: E402
 
 from phase_guided_terrain_traversal_amd import configs, elevation, srchash  # noqa: E402
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CAM = dict(fovy=58.0, near=0.1, far=3.0, mount_pos=(0.0, 0.0, 0.0), mount_quat=dref.pitch_quat(30.0).astype(np.float32).astype(float), res=0.04, alpha=1.0, self_half=(0.0, 0.0, 0.0))
 W, H = 64, 48                                  # CAM's numbers are what a device would see (fp32 values): the image and the map use ONE camera
 
@@ -197,28 +195,3 @@ def test_sizeof_exports_and_build_info():
     for name in elevation.EXPORTS:
         getattr(L, name)
 
-
-def test_side_hash_files_are_the_include_closure_of_the_unit():
-    """SIDE_SOURCES["elevation"] is exactly the set of project files csrc/pgtt_elevation.hip includes, transitively (the walk of tests/test_abi.py)"""
-    csrc = os.path.join(ROOT, "phase_guided_terrain_traversal_amd", "csrc")
-    seen, todo = set(), [os.path.join(csrc, "pgtt_elevation.hip")]
-    while todo:
-        f = os.path.realpath(todo.pop())
-        if f in seen:
-            continue
-        seen.add(f)
-        for inc in re.findall(r'^\s*#\s*include\s+"([^"]+)"', open(f).read(), re.M):
-            todo.append(os.path.join(os.path.dirname(f), inc))
-    assert all(f.startswith(os.path.realpath(ROOT) + os.sep) for f in seen)
-    assert seen == {os.path.realpath(f) for f in srchash.side_files("elevation")}
-    in_csrc, in_include = srchash.SIDE_SOURCES["elevation"]
-    assert {os.path.basename(f) for f in seen} == set(in_csrc) | set(in_include)
-    assert "pgtt_common.hip.h" not in in_csrc and "pgtt_raycast.hip.h" not in in_csrc
-
-
-def test_the_other_hashes_did_not_move():
-    """the elevation library's files are its own: no other side library's file list, and not the physics hash's, names them"""
-    for name in ("render", "depth", "perceive"):
-        csrc, inc = srchash.SIDE_SOURCES[name]
-        assert "pgtt_elevation.hip" not in csrc and "pgtt_elevation.h" not in inc
-    assert not any("elevation" in f for f in srchash.hashed_files())

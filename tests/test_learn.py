@@ -1,5 +1,6 @@
 """The native learner's plumbing that needs no GPU: FlatParams (every parameter a view of one flat buffer, the state_dict unchanged, a checkpoint
-round trip), the `learner` switch of PPOConfig / train.py, the refusal on a CPU device, the side library's source hash."""
+round trip), the `learner` switch of PPOConfig / train.py, the refusal on a CPU device, the argument structs against the header (the side
+library's source hash, file list and exports: tests/test_abi.py)."""
 import os
 import sys
 
@@ -10,7 +11,7 @@ torch = pytest.importorskip("torch")
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-from phase_guided_terrain_traversal_amd import abi, learn, ppo, srchash  # noqa: E402
+from phase_guided_terrain_traversal_amd import abi, learn, ppo  # noqa: E402
 
 
 def test_flat_params_are_views_and_the_state_dict_is_unchanged():
@@ -101,14 +102,6 @@ def test_native_learner_on_a_cpu_env_is_refused():
     with pytest.raises(learn.LearnError, match="GPU"):
         B = {"obs": torch.zeros(8, abi.OBS), "priv": torch.zeros(8, abi.PRIV), "u": torch.zeros(8, abi.NU)}
         learn.NativeLearner(ppo.ActorCritic(), None, None, None, B, 4, ppo.PPOConfig())
-
-
-def test_srchash_knows_the_learn_library():
-    files = [os.path.basename(f) for f in srchash.side_files("learn")]
-    assert sorted(files) == ["pgtt.h", "pgtt_learn.h", "pgtt_learn.hip"]
-    h = srchash.side_sha256("learn")
-    assert len(h) == 64 and h != srchash.side_sha256("elevation") and h != srchash.source_sha256()
-    assert "learn" in open(os.path.join(ROOT, "phase_guided_terrain_traversal_amd", "csrc", "pgtt_learn.mk")).read()
 
 
 def test_the_c_mirrors_have_the_headers_fields():

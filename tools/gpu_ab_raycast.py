@@ -1,7 +1,7 @@
 """A/B check of two builds of the side libraries libpgtt_render.so and libpgtt_depth.so: the same seeded scenes, EVERY buffer the two
 libraries write compared bit for bit (renderer: rgba, depth, segmentation, body_pose; depth camera: the image).
    usage: python tools/gpu_ab_raycast.py OLD_DIR NEW_DIR [--out profiles/NAME.txt]
-   (OLD_DIR / NEW_DIR hold the two .so files; each build runs in its own process, render.LIB_PATH / depth.LIB_PATH set before first use;
+   (OLD_DIR / NEW_DIR hold the two .so files; each build runs in its own process, render.SIDE.path / depth.SIDE.path set before first use;
    libpgtt.so is the checkout's in both)
 Workloads, the smallest at which these kernels can go wrong: 8 envs on level4 with domain-randomised params (the qpos0 rows) and per-env
 variants, one label out of range, after 5 control steps of seeded small actions; 8 envs on flat ground without params.
@@ -23,8 +23,8 @@ def child(lib_dir, out):
     from phase_guided_terrain_traversal_amd import abi, configs, depth, mjcf, render
     from phase_guided_terrain_traversal_amd.env import Joystick
     from phase_guided_terrain_traversal_amd.randomize import domain_randomize
-    render.LIB_PATH = os.path.join(lib_dir, "libpgtt_render.so")
-    depth.LIB_PATH = os.path.join(lib_dir, "libpgtt_depth.so")
+    render.SIDE.path = os.path.join(lib_dir, "libpgtt_render.so")
+    depth.SIDE.path = os.path.join(lib_dir, "libpgtt_depth.so")
     res = {"info/render": np.frombuffer(render.build_info()["src"].encode(), np.uint8), "info/depth": np.frombuffer(depth.build_info()["src"].encode(), np.uint8)}
     n = 8
     for wl in ("level4", "flat"):
