@@ -10,6 +10,10 @@
 // perceive_head_kernel, one workgroup of eight waves per 16 envs (pgtt_policy.hip's shape: the env is the MFMA's column):
 //   z = [latent | obs[prop_rows]] is staged into LDS 256 k at a time, every wave keeps up to four 16-neuron tiles of the hidden layer in accumulators, so
 //   the (F + n_prop) x hidden matrix is read once per 16 envs; then hidden -> 117 (eight tiles, one per wave), `est`, and the obs_out assembly.
+// perceive_recurrent_head_kernel, the same shape (pgtt_perceive_recurrent): z -> hidden as above; the 16 envs' memory m0 is staged into sh_x (zeros for a
+//   cleared env); wave w owns the 16-neuron tiles w and w + 8 of the memory and keeps four accumulator groups per tile - gi_r + gh_r and gi_u + gh_u
+//   (one chain over hidden + R each), gi_n, gh_n - so with D[neuron = 16 tile + 4 g + r][env = i] the gates and the blend with m0 are lane-local;
+//   m1 goes to `mem` and back into sh_x, then R -> 117 in eight tiles and the same assembly.  One fused launch: h and m1 never leave LDS.
 // Nothing is shared between envs but the weights: a column of an MFMA does not see the other columns, so an env's rows do not depend on the batch.
 #include <hip/hip_runtime.h>
 
@@ -36,8 +40,13 @@ constexpr int kOutPad = 128;                      // 117 scan rows in eight tile
 constexpr int kES = kOutPad + 4;
 static_assert(kHeadWaves * 4 * 16 >= PGTT_PERCEIVE_MAX_HIDDEN && kHeadWaves * 16 == kOutPad && kOutPad >= PGTT_NSCAN, "tiles per wave");
 static_assert(kEnvs * kES <= kEnvs * kXS, "the estimate reuses the staging buffer");
+static_assert(PGTT_PERCEIVE_MAX_MEMORY + 4 <= kXS && 2 * kHeadWaves * 16 >= PGTT_PERCEIVE_MAX_MEMORY, "the memory reuses the staging buffer; two tiles per wave");
+static_assert(kES <= kHS, "the recurrent estimate reuses the hidden buffer");
 
 __device__ __forceinline__ float silu(float x) { return x / (1.0f + expf(-x)); }
+// t = exp(-|x|) <= 1: no overflow at any x
+__device__ __forceinline__ float sigmoidf(float x) { const float t = expf(-fabsf(x)), s = 1.0f / (1.0f + t); return x >= 0.f ? s : t * s; }
+__device__ __forceinline__ float tanh_of(float x) { const float t = expf(-2.0f * fabsf(x)); return copysignf((1.0f - t) / (1.0f + t), x); }
 
 struct ConvLayer { int cin, hin, win, cout, hout, wout, k, s, K, Kp; };
 
@@ -65,6 +74,15 @@ struct HeadArgs {
   float* est;
   float* obs_out;
   int N, F, Kin, KB, hidden, obs_dim, scan_row0;
+};
+
+struct CellArgs {                                 // the recurrent head's own: PgttPerceiveMemory and the clear flags
+  const float4* w_ih; const float4* w_hh; const float4* w_out;
+  const float* b_ih; const float* b_hh; const float* b_out;
+  const float* done;
+  const uint8_t* clear_mask;
+  float* mem;
+  int R, clear_all, use_done;
 };
 
 __global__ void __launch_bounds__(kTrunkLanes) perceive_trunk_kernel(TrunkArgs a) {
@@ -129,6 +147,7 @@ __global__ void __launch_bounds__(kTrunkLanes) perceive_trunk_kernel(TrunkArgs a
   }
 }
 
+// Its z -> hidden phase and its est / obs_out phase have twins below, hidden_layer() and emit() of the recurrent head: a fix to one is a fix to both.
 __global__ void __launch_bounds__(kHeadLanes) perceive_head_kernel(HeadArgs a) {
   __shared__ __attribute__((aligned(16))) float sh_x[kEnvs * kXS];        // the staged chunk of z; later the estimate [env][kES]
   __shared__ __attribute__((aligned(16))) float sh_h[kEnvs * kHS];        // the hidden layer
@@ -217,6 +236,228 @@ __global__ void __launch_bounds__(kHeadLanes) perceive_head_kernel(HeadArgs a) {
   }
 }
 
+// The recurrent head.  Its first and last phases are perceive_head_kernel's, statement for statement; that kernel stays as it is so that pgtt_perceive()
+// keeps its code object.
+// z -> hidden of the 16 envs from e0 on, into sh_h[env][neuron]; sh_x is the staging buffer.  Ends before the barrier that completes sh_h.
+__device__ __forceinline__ void hidden_layer(const HeadArgs& a, float* sh_x, float* sh_h, const long e0) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, i = lane & 15, g = lane >> 4;
+  const int N = a.N, F = a.F, od = a.obs_dim, nt = a.hidden >> 4;
+  // ---- z -> hidden: tiles wave, wave + 8, wave + 16, wave + 24
+  f32x4 acc[4];
+#pragma unroll
+  for (int t = 0; t < 4; t++) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int kc = 0; kc < a.KB; kc += kChunk / 16) {
+    const int nkb = min(kChunk / 16, a.KB - kc);
+    __syncthreads();                               // the chunk before this one has been consumed
+    {
+      const int env = tid >> 5, k0 = tid & 31;      // 32 lanes walk the k of one env
+      const long e = e0 + env;
+#pragma unroll
+      for (int j = 0; j < kChunk / 32; j++) {
+        const int k = k0 + 32 * j, gk = 16 * kc + k;
+        float v = 0.f;
+        if (e < N && k < 16 * nkb) {
+          if (gk < F) v = a.latent[e * F + gk];
+          else if (gk < a.Kin) v = a.obs[e * od + a.prop[gk - F]];
+        }
+        sh_x[env * kXS + k] = v;
+      }
+    }
+    __syncthreads();
+    const float* xrow = sh_x + i * kXS + 4 * g;
+    for (int kb = 0; kb < nkb; kb++) {
+      const float4 b = *reinterpret_cast<const float4*>(xrow + 16 * kb);
+      float4 w[4];
+#pragma unroll
+      for (int t = 0; t < 4; t++) {
+        const int tile = wave + kHeadWaves * t;
+        w[t] = tile < nt ? a.w1[((long)tile * a.KB + kc + kb) * 64 + lane] : make_float4(0.f, 0.f, 0.f, 0.f);
+      }
+      // consecutive MFMAs go to different accumulators
+#pragma unroll
+      for (int t = 0; t < 4; t++) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[t].x, b.x, acc[t], 0, 0, 0);
+#pragma unroll
+      for (int t = 0; t < 4; t++) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[t].y, b.y, acc[t], 0, 0, 0);
+#pragma unroll
+      for (int t = 0; t < 4; t++) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[t].z, b.z, acc[t], 0, 0, 0);
+#pragma unroll
+      for (int t = 0; t < 4; t++) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[t].w, b.w, acc[t], 0, 0, 0);
+    }
+  }
+  // bias + SiLU, D[neuron = 16 tile + 4 g + r][env = i] -> sh_h[env][neuron]
+#pragma unroll
+  for (int t = 0; t < 4; t++) {
+    const int tile = wave + kHeadWaves * t;
+    if (tile < nt) {
+      const int n = 16 * tile + 4 * g;
+      const float4 bv = *reinterpret_cast<const float4*>(a.b1 + n);
+      *reinterpret_cast<float4*>(sh_h + i * kHS + n) = make_float4(silu(acc[t][0] + bv.x), silu(acc[t][1] + bv.y), silu(acc[t][2] + bv.z), silu(acc[t][3] + bv.w));
+    }
+  }
+}
+
+// est and obs_out of the 16 envs from e0 on, from the estimate sh_e[env][kES]
+__device__ __forceinline__ void emit(const HeadArgs& a, const float* sh_e, const long e0) {
+  const int tid = threadIdx.x, N = a.N, od = a.obs_dim;
+  // ---- est, and obs_out = obs with the scan rows replaced
+  for (int idx = tid; idx < kEnvs * PGTT_NSCAN; idx += kHeadLanes) {
+    const int env = idx / PGTT_NSCAN, j = idx - env * PGTT_NSCAN;
+    if (e0 + env < N) a.est[(e0 + env) * PGTT_NSCAN + j] = sh_e[env * kES + j];
+  }
+  if (a.obs_out) {
+    for (int idx = tid; idx < kEnvs * od; idx += kHeadLanes) {
+      const int env = idx / od, k = idx - env * od, j = k - a.scan_row0;
+      if (e0 + env < N) a.obs_out[(e0 + env) * od + k] = (j >= 0 && j < PGTT_NSCAN) ? sh_e[env * kES + j] : a.obs[(e0 + env) * od + k];
+    }
+  }
+}
+
+// the GRU cell of NT neuron tiles per wave (tiles wave, wave + 8): m0 in sh_x[env][kXS], h in sh_h; m1 to `mem` and to sh_x.  Two barriers inside.
+template <int NT>
+__device__ __forceinline__ void gru_cell(const HeadArgs& a, const CellArgs& c, float* sh_x, const float* sh_h, const long e0) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, i = lane & 15, g = lane >> 4;
+  const int R = c.R, nrt = R >> 4, nht = a.hidden >> 4;
+  f32x4 acc[NT][4];                                // per tile: gi_r + gh_r, gi_u + gh_u, gi_n, gh_n
+#pragma unroll
+  for (int t = 0; t < NT; t++)
+#pragma unroll
+    for (int q = 0; q < 4; q++) acc[t][q] = f32x4{0.f, 0.f, 0.f, 0.f};
+  // W_ih h: the chains of r, u and gi_n.  Row tile of gate q and neuron tile `tile` is q * nrt + tile.
+  {
+    const float* hrow = sh_h + i * kHS + 4 * g;
+    for (int kb = 0; kb < nht; kb++) {
+      const float4 b = *reinterpret_cast<const float4*>(hrow + 16 * kb);
+      float4 w[NT][3];
+#pragma unroll
+      for (int t = 0; t < NT; t++) {
+        const int tile = wave + kHeadWaves * t;
+#pragma unroll
+        for (int q = 0; q < 3; q++) w[t][q] = tile < nrt ? c.w_ih[((long)(q * nrt + tile) * nht + kb) * 64 + lane] : make_float4(0.f, 0.f, 0.f, 0.f);
+      }
+#pragma unroll
+      for (int t = 0; t < NT; t++)
+#pragma unroll
+        for (int q = 0; q < 3; q++) acc[t][q] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[t][q].x, b.x, acc[t][q], 0, 0, 0);
+#pragma unroll
+      for (int t = 0; t < NT; t++)
+#pragma unroll
+        for (int q = 0; q < 3; q++) acc[t][q] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[t][q].y, b.y, acc[t][q], 0, 0, 0);
+#pragma unroll
+      for (int t = 0; t < NT; t++)
+#pragma unroll
+        for (int q = 0; q < 3; q++) acc[t][q] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[t][q].z, b.z, acc[t][q], 0, 0, 0);
+#pragma unroll
+      for (int t = 0; t < NT; t++)
+#pragma unroll
+        for (int q = 0; q < 3; q++) acc[t][q] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[t][q].w, b.w, acc[t][q], 0, 0, 0);
+    }
+  }
+  // W_hh m0: r and u go on in their chains, gh_n is a chain of its own (accumulator 3)
+  {
+    const float* mrow = sh_x + i * kXS + 4 * g;
+    for (int kb = 0; kb < nrt; kb++) {
+      const float4 b = *reinterpret_cast<const float4*>(mrow + 16 * kb);
+      float4 w[NT][3];
+#pragma unroll
+      for (int t = 0; t < NT; t++) {
+        const int tile = wave + kHeadWaves * t;
+#pragma unroll
+        for (int q = 0; q < 3; q++) w[t][q] = tile < nrt ? c.w_hh[((long)(q * nrt + tile) * nrt + kb) * 64 + lane] : make_float4(0.f, 0.f, 0.f, 0.f);
+      }
+#pragma unroll
+      for (int t = 0; t < NT; t++)
+#pragma unroll
+        for (int q = 0; q < 3; q++) { const int d = q == 2 ? 3 : q; acc[t][d] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[t][q].x, b.x, acc[t][d], 0, 0, 0); }
+#pragma unroll
+      for (int t = 0; t < NT; t++)
+#pragma unroll
+        for (int q = 0; q < 3; q++) { const int d = q == 2 ? 3 : q; acc[t][d] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[t][q].y, b.y, acc[t][d], 0, 0, 0); }
+#pragma unroll
+      for (int t = 0; t < NT; t++)
+#pragma unroll
+        for (int q = 0; q < 3; q++) { const int d = q == 2 ? 3 : q; acc[t][d] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[t][q].z, b.z, acc[t][d], 0, 0, 0); }
+#pragma unroll
+      for (int t = 0; t < NT; t++)
+#pragma unroll
+        for (int q = 0; q < 3; q++) { const int d = q == 2 ? 3 : q; acc[t][d] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[t][q].w, b.w, acc[t][d], 0, 0, 0); }
+    }
+  }
+  // gates and blend, lane-local: this lane holds neurons 16 tile + 4 g + 0..3 of env i
+  float4 m1[NT];
+#pragma unroll
+  for (int t = 0; t < NT; t++) {
+    const int tile = wave + kHeadWaves * t;
+    m1[t] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (tile < nrt) {
+      const int n = 16 * tile + 4 * g;
+      const float4 m0 = *reinterpret_cast<const float4*>(sh_x + i * kXS + n);
+      const float m0v[4] = {m0.x, m0.y, m0.z, m0.w};
+      float out[4];
+#pragma unroll
+      for (int r = 0; r < 4; r++) {
+        const float gr = sigmoidf(acc[t][0][r] + c.b_ih[n + r] + c.b_hh[n + r]);
+        const float gu = sigmoidf(acc[t][1][r] + c.b_ih[R + n + r] + c.b_hh[R + n + r]);
+        const float gn = tanh_of((acc[t][2][r] + c.b_ih[2 * R + n + r]) + gr * (acc[t][3][r] + c.b_hh[2 * R + n + r]));
+        out[r] = (1.0f - gu) * gn + gu * m0v[r];
+      }
+      m1[t] = make_float4(out[0], out[1], out[2], out[3]);
+    }
+  }
+  __syncthreads();                                 // every wave has read m0 and h
+#pragma unroll
+  for (int t = 0; t < NT; t++) {
+    const int tile = wave + kHeadWaves * t;
+    if (tile < nrt) {
+      const int n = 16 * tile + 4 * g;
+      *reinterpret_cast<float4*>(sh_x + i * kXS + n) = m1[t];
+      if (e0 + i < a.N) {
+        float* dst = c.mem + (e0 + i) * R + n;      // dwords: `mem` need not be 16-byte aligned
+        dst[0] = m1[t].x; dst[1] = m1[t].y; dst[2] = m1[t].z; dst[3] = m1[t].w;
+      }
+    }
+  }
+  __syncthreads();                                 // m1 is complete in sh_x
+}
+
+__global__ void __launch_bounds__(kHeadLanes) perceive_recurrent_head_kernel(HeadArgs a, CellArgs c) {
+  __shared__ __attribute__((aligned(16))) float sh_x[kEnvs * kXS];        // the staged chunk of z; then m0, then m1 [env][kXS]
+  __shared__ __attribute__((aligned(16))) float sh_h[kEnvs * kHS];        // the hidden layer; later the estimate [env][kES]
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, i = lane & 15, g = lane >> 4;
+  const int R = c.R, nrt = R >> 4;
+  const long e0 = (long)blockIdx.x * kEnvs;
+  hidden_layer(a, sh_x, sh_h, e0);
+  __syncthreads();                                 // the hidden layer is complete; sh_x is free
+  // ---- m0: zeros for a cleared env and for an env past N
+  {
+    const int env = tid >> 5, k0 = tid & 31;
+    const long e = e0 + env;
+    bool live = e < a.N && !c.clear_all;
+    if (live && c.clear_mask) live = c.clear_mask[e] == 0;
+    if (live && c.use_done && c.done) live = c.done[e] == 0.f;
+    for (int k = k0; k < R; k += 32) sh_x[env * kXS + k] = live ? c.mem[e * R + k] : 0.f;
+  }
+  __syncthreads();
+  if (nrt > kHeadWaves) gru_cell<2>(a, c, sh_x, sh_h, e0);
+  else gru_cell<1>(a, c, sh_x, sh_h, e0);
+  // ---- memory -> 117 (128): tile = wave; the estimate goes where the hidden layer was (gru_cell's first barrier freed it)
+  {
+    f32x4 o = {0.f, 0.f, 0.f, 0.f};
+    const float* mrow = sh_x + i * kXS + 4 * g;
+    const float4* wl = c.w_out + (long)wave * nrt * 64 + lane;
+    for (int kb = 0; kb < nrt; kb++) {
+      const float4 b = *reinterpret_cast<const float4*>(mrow + 16 * kb);
+      const float4 w = wl[kb * 64];
+      o = __builtin_amdgcn_mfma_f32_16x16x4f32(w.x, b.x, o, 0, 0, 0); o = __builtin_amdgcn_mfma_f32_16x16x4f32(w.y, b.y, o, 0, 0, 0);
+      o = __builtin_amdgcn_mfma_f32_16x16x4f32(w.z, b.z, o, 0, 0, 0); o = __builtin_amdgcn_mfma_f32_16x16x4f32(w.w, b.w, o, 0, 0, 0);
+    }
+    const int n = 16 * wave + 4 * g;
+    const float4 bv = *reinterpret_cast<const float4*>(c.b_out + n);
+    *reinterpret_cast<float4*>(sh_h + i * kES + n) = make_float4(o[0] + bv.x, o[1] + bv.y, o[2] + bv.z, o[3] + bv.w);
+  }
+  __syncthreads();
+  emit(a, sh_h, e0);
+}
+
 // the config's checks and what it comes to; `who` prefixes the message
 int resolve(const PgttPerceiveConfig* c, Net* net, const char* who) {
   const std::string p = std::string(who) + ": ";
@@ -259,6 +500,11 @@ int resolve(const PgttPerceiveConfig* c, Net* net, const char* who) {
   return PGTT_OK;
 }
 
+int check_memory(int memory, const char* who) {
+  if (memory < 16 || memory > PGTT_PERCEIVE_MAX_MEMORY || memory % 16) return fail(PGTT_E_ARG, std::string(who) + ": memory must be a multiple of 16 in [16, 256]");
+  return PGTT_OK;
+}
+
 }  // namespace
 
 struct pgtt_perceive_net {
@@ -268,6 +514,8 @@ struct pgtt_perceive_net {
   PgttPerceiveBuffers buf{};
   bool bound = false;
   int32_t* d_prop = nullptr;
+  PgttPerceiveMemory mem{};                        // the recurrent form; has_mem after pgtt_perceive_set_memory
+  bool has_mem = false;
 };
 
 extern "C" {
@@ -275,6 +523,7 @@ extern "C" {
 PGTT_SIDE_EXPORTS(perceive, PERCEIVE)
 int pgtt_perceive_sizeof_config(void) { return (int)sizeof(PgttPerceiveConfig); }
 int pgtt_perceive_sizeof_buffers(void) { return (int)sizeof(PgttPerceiveBuffers); }
+int pgtt_perceive_sizeof_memory(void) { return (int)sizeof(PgttPerceiveMemory); }
 
 int pgtt_perceive_check(const PgttPerceiveConfig* cfg) { return resolve(cfg, nullptr, "pgtt_perceive_check"); }
 
@@ -331,10 +580,8 @@ int pgtt_perceive_bind(pgtt_perceive_handle h, const PgttPerceiveBuffers* bufs) 
   return PGTT_OK;
 }
 
-int pgtt_perceive(pgtt_perceive_handle h, void* stream) {
-  if (!h) return fail(PGTT_E_ARG, "pgtt_perceive: null handle");
-  if (!h->bound) return fail(PGTT_E_STATE, "pgtt_perceive: no buffers bound (pgtt_perceive_bind first)");
-  HIP_TRY(hipSetDevice(h->device));
+// the arguments of the two launches from what is bound
+static void launch_args(const pgtt_perceive_net* h, TrunkArgs* tp, HeadArgs* ap) {
   const PgttPerceiveConfig& c = h->cfg;
   const Net& n = h->net;
   TrunkArgs t{};
@@ -347,9 +594,65 @@ int pgtt_perceive(pgtt_perceive_handle h, void* stream) {
   a.w2 = reinterpret_cast<const float4*>(h->buf.w[4]); a.b2 = h->buf.b[4];
   a.est = h->buf.est; a.obs_out = h->buf.obs_out;
   a.N = h->num_envs; a.F = n.F; a.Kin = n.Kin; a.KB = n.KB; a.hidden = c.hidden; a.obs_dim = c.obs_dim; a.scan_row0 = c.scan_row0;
+  *tp = t; *ap = a;
+}
+
+int pgtt_perceive(pgtt_perceive_handle h, void* stream) {
+  if (!h) return fail(PGTT_E_ARG, "pgtt_perceive: null handle");
+  if (!h->bound) return fail(PGTT_E_STATE, "pgtt_perceive: no buffers bound (pgtt_perceive_bind first)");
+  HIP_TRY(hipSetDevice(h->device));
+  TrunkArgs t; HeadArgs a;
+  launch_args(h, &t, &a);
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(perceive_trunk_kernel, dim3(h->num_envs), dim3(kTrunkLanes), (size_t)n.lds_floats * sizeof(float), st, t);
+  hipLaunchKernelGGL(perceive_trunk_kernel, dim3(h->num_envs), dim3(kTrunkLanes), (size_t)h->net.lds_floats * sizeof(float), st, t);
   hipLaunchKernelGGL(perceive_head_kernel, dim3((h->num_envs + kEnvs - 1) / kEnvs), dim3(kHeadLanes), 0, st, a);
+  HIP_TRY(hipGetLastError());
+  return PGTT_OK;
+}
+
+int pgtt_perceive_memory_check(const PgttPerceiveConfig* cfg, int memory) {
+  if (int rc = resolve(cfg, nullptr, "pgtt_perceive_memory_check")) return rc;
+  return check_memory(memory, "pgtt_perceive_memory_check");
+}
+
+int pgtt_perceive_memory_packed_floats(const PgttPerceiveConfig* cfg, int memory, int which) {
+  if (int rc = resolve(cfg, nullptr, "pgtt_perceive_memory_packed_floats")) return rc;
+  if (int rc = check_memory(memory, "pgtt_perceive_memory_packed_floats")) return rc;
+  if (which == 0) return 3 * memory * cfg->hidden;
+  if (which == 1) return 3 * memory * memory;
+  if (which == 2) return kOutPad * memory;
+  return fail(PGTT_E_ARG, "pgtt_perceive_memory_packed_floats: which must be 0 (w_ih), 1 (w_hh) or 2 (w_out)");
+}
+
+int pgtt_perceive_set_memory(pgtt_perceive_handle h, const PgttPerceiveMemory* m) {
+  if (!h) return fail(PGTT_E_ARG, "pgtt_perceive_set_memory: null handle");
+  if (!h->bound) return fail(PGTT_E_STATE, "pgtt_perceive_set_memory: no buffers bound (pgtt_perceive_bind first)");
+  if (!m) { h->mem = PgttPerceiveMemory{}; h->has_mem = false; return PGTT_OK; }
+  if (int rc = check_memory(m->memory, "pgtt_perceive_set_memory")) return rc;
+  if (!m->w_ih || !m->w_hh || !m->w_out || !m->b_ih || !m->b_hh || !m->b_out || !m->mem)
+    return fail(PGTT_E_ARG, "pgtt_perceive_set_memory: w_ih, w_hh, w_out, b_ih, b_hh, b_out and mem are required");
+  for (const float* p : {m->w_ih, m->w_hh, m->w_out, m->b_out})      // read as float4
+    if (reinterpret_cast<uintptr_t>(p) % 16) return fail(PGTT_E_ARG, "pgtt_perceive_set_memory: w_ih, w_hh, w_out and b_out must be 16-byte aligned");
+  h->mem = *m;
+  h->has_mem = true;
+  return PGTT_OK;
+}
+
+int pgtt_perceive_recurrent(pgtt_perceive_handle h, const uint8_t* clear_mask, int clear_all, int use_done, void* stream) {
+  if (!h) return fail(PGTT_E_ARG, "pgtt_perceive_recurrent: null handle");
+  if (!h->bound) return fail(PGTT_E_STATE, "pgtt_perceive_recurrent: no buffers bound (pgtt_perceive_bind first)");
+  if (!h->has_mem) return fail(PGTT_E_STATE, "pgtt_perceive_recurrent: no memory set (pgtt_perceive_set_memory first)");
+  HIP_TRY(hipSetDevice(h->device));
+  TrunkArgs t; HeadArgs a;
+  launch_args(h, &t, &a);
+  const PgttPerceiveMemory& m = h->mem;
+  CellArgs c{};
+  c.w_ih = reinterpret_cast<const float4*>(m.w_ih); c.w_hh = reinterpret_cast<const float4*>(m.w_hh); c.w_out = reinterpret_cast<const float4*>(m.w_out);
+  c.b_ih = m.b_ih; c.b_hh = m.b_hh; c.b_out = m.b_out; c.done = m.done; c.clear_mask = clear_mask; c.mem = m.mem;
+  c.R = m.memory; c.clear_all = clear_all != 0; c.use_done = use_done != 0;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(perceive_trunk_kernel, dim3(h->num_envs), dim3(kTrunkLanes), (size_t)h->net.lds_floats * sizeof(float), st, t);
+  hipLaunchKernelGGL(perceive_recurrent_head_kernel, dim3((h->num_envs + kEnvs - 1) / kEnvs), dim3(kHeadLanes), 0, st, a, c);
   HIP_TRY(hipGetLastError());
   return PGTT_OK;
 }

@@ -49,7 +49,9 @@ class Joystick:
         is allocated, loaded, bound or launched.
         student: a perceive.ScanEstimator or the path of a saved one (needs depth): the student perception module (libpgtt_perceive.so) runs behind
         the camera after every step and reset; `env.student_obs` is the [N, obs_dim] observation with the 117 scan rows replaced by its estimate.  A
-        side output like the image.  None: the library is not opened.
+        side output like the image.  None: the library is not opened.  A recurrent estimator (perceive.config(memory=R)) keeps a memory per env,
+        `env.student_mem` [N, R]: reset() starts the reset envs' memory from zero, step() that of the envs whose episode just ended, as for the map
+        below, and the note on a deferred curriculum there applies to it too (`env.student.tick(use_done=True)` after curriculum_step()).
         elevation: True or elevation.ElevationMap's arguments over elevation.DEFAULTS, e.g. dict(grid=64, res=0.04, alpha=1.0) (needs depth, with the
         camera on the torso and every=1): a depth-fused elevation map per env (libpgtt_elevation.so) is ticked behind the camera - after reset() with
         the reset envs' maps cleared, after step() with the maps of the envs whose episode just ended cleared; `env.elevation_obs` is the
@@ -258,6 +260,11 @@ class Joystick:
         return None if self.student is None else self.student.obs
 
     @property
+    def student_mem(self) -> Optional[torch.Tensor]:
+        """[N, R] float32: the recurrent student's memory as its last tick left it, or None without a recurrent student"""
+        return None if self.student is None else self.student.mem
+
+    @property
     def elevation_obs(self) -> Optional[torch.Tensor]:
         """[N, obs_dim] float32: the observation with its scan rows sampled from the depth-fused elevation map, or None without one"""
         return None if self.elevation_map is None else self.elevation_map.obs
@@ -279,7 +286,8 @@ class Joystick:
     def curriculum_step(self) -> None:
         """the curriculum alone (pgtt_curriculum): what step() runs last when the curriculum is on; for callers of physics() / observe() and of
         step(action, curriculum=False).  The camera, the student and the elevation map were ticked by that step, before this restart: their
-        outputs for a restarted env are the old pose's until the next step, and its map keeps that one image of the old place (see `elevation`)"""
+        outputs for a restarted env are the old pose's until the next step, and its map - and a recurrent student's memory - keep that one image of
+        the old place (see `elevation`)"""
         native.check(self._lib.pgtt_curriculum(self._h, self._stream()))
 
     def curriculum_stats(self) -> Dict[str, Any]:
@@ -321,7 +329,10 @@ class Joystick:
         if self.depth_camera is not None:
             self.depth_camera.tick(force=True)
         if self.student is not None:
-            self.student.tick()
+            if self.student.memory:
+                self.student.tick(clear_mask=mask, clear_all=mask is None)
+            else:
+                self.student.tick()
         if self.elevation_map is not None:
             self.elevation_map.tick(clear_mask=mask, clear_all=mask is None)
         return self._obs()
@@ -338,7 +349,10 @@ class Joystick:
         if self.depth_camera is not None:
             self.depth_camera.tick()
         if self.student is not None:
-            self.student.tick()
+            if self.student.memory:
+                self.student.tick(use_done=True)
+            else:
+                self.student.tick()
         if self.elevation_map is not None:
             self.elevation_map.tick(use_done=True)
         info = {"metrics": self.buffers["metrics"], "episode_metrics": self.buffers["ep_metrics"]}

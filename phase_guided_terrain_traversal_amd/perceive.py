@@ -6,6 +6,9 @@
     sp.tick(); sp.est; sp.obs
     sp.load(est)                                     # repack in place after an optimiser step
 
+config(memory=R) puts a GRU cell of R values per env between the hidden layer and the scan rows (the recurrent form of pgtt_perceive.h):
+ScanEstimator.step / .sequence in torch, StudentPerception.mem and tick(clear_mask, clear_all, use_done) on the device.
+
 `Joystick(..., depth=dict(...), student=path_or_estimator)` owns one and ticks it behind the camera (env.student_obs).  The module is not imported
 by env.py unless a student is asked for.  The backward pass is torch autograd on ScanEstimator; the library is forward only.
 """
@@ -22,19 +25,24 @@ from . import _sidelib, abi, acting, depth as _depth
 
 # include/pgtt_perceive.h
 MAX_CONV, MAX_CH, MAX_PROP, MAX_HIDDEN, MAX_DIM, LDS_BYTES, NLAYER, OUT_PAD = 3, 64, 64, 512, 256, 61440, 5, 128
+MAX_MEMORY = 256
 NSCAN = abi.NSCAN
 SCAN_ROW0 = {"pgtt": 38, "baseline": 30}           # the scan rows sit between phase / joint_vel and gait_freq / last_act
 # the scan grid is 13 rows (x, ahead first) by 9 columns: the bands train_student.py reports
 BANDS = {"ahead": slice(0, 6 * abi.SCAN_W), "under": slice(6 * abi.SCAN_W, 7 * abi.SCAN_W), "behind": slice(7 * abi.SCAN_W, NSCAN)}
 
 
-def config(method: str = "pgtt", **overrides) -> Dict:
+def config(method: str = "pgtt", memory: int = 0, **overrides) -> Dict:
     """the default net for the task definition `method`: depth.DEFAULTS' 48 x 64 image -> 16 ch k5 s2 -> 32 ch k3 s2 -> 32 ch k3 s2 (F = 768), the
-    proprioceptive input = every observation row except the scan rows (54 for the PGTT task), hidden 512"""
+    proprioceptive input = every observation row except the scan rows (54 for the PGTT task), hidden 512, memory 0 (feed-forward; R > 0: a GRU cell
+    of R values per env behind the hidden layer).  A config dict without "memory" means 0, and memory = 0 leaves the key out: a feed-forward
+    student's saved config is what it always was."""
     od, row0 = abi.obs_dims(method)[0], SCAN_ROW0[method]
     c = dict(height=_depth.DEFAULTS["height"], width=_depth.DEFAULTS["width"], near=_depth.DEFAULTS["near"], far=_depth.DEFAULTS["far"],
              conv=[(16, 5, 2), (32, 3, 2), (32, 3, 2)], prop_rows=[r for r in range(od) if not row0 <= r < row0 + NSCAN], hidden=512,
              obs_dim=od, scan_row0=row0)
+    if memory:
+        c["memory"] = memory
     c.update(overrides)
     return c
 
@@ -54,7 +62,12 @@ class PgttPerceiveBuffers(C.Structure):
                 ("est", C.c_void_p), ("obs_out", C.c_void_p)]
 
 
-assert C.sizeof(PgttPerceiveConfig) == 328 and C.sizeof(PgttPerceiveBuffers) == 120
+class PgttPerceiveMemory(C.Structure):
+    _fields_ = [("memory", i32), ("w_ih", C.c_void_p), ("w_hh", C.c_void_p), ("w_out", C.c_void_p), ("b_ih", C.c_void_p), ("b_hh", C.c_void_p),
+                ("b_out", C.c_void_p), ("done", C.c_void_p), ("mem", C.c_void_p)]
+
+
+assert C.sizeof(PgttPerceiveConfig) == 328 and C.sizeof(PgttPerceiveBuffers) == 120 and C.sizeof(PgttPerceiveMemory) == 72
 
 
 class PerceiveError(RuntimeError):
@@ -66,7 +79,10 @@ SIDE = _sidelib.SideLib("perceive", PerceiveError, {
     "pgtt_perceive_check": (None, [cp]), "pgtt_perceive_latent_dim": (None, [cp]), "pgtt_perceive_packed_floats": (None, [cp, C.c_int]),
     "pgtt_perceive_create": (None, [cp, C.c_int, C.c_int, C.POINTER(vp)]), "pgtt_perceive_destroy": (None, [vp]),
     "pgtt_perceive_bind": (None, [vp, C.POINTER(PgttPerceiveBuffers)]), "pgtt_perceive": (None, [vp, vp]),
-}, {"pgtt_perceive_sizeof_config": PgttPerceiveConfig, "pgtt_perceive_sizeof_buffers": PgttPerceiveBuffers})
+    "pgtt_perceive_memory_check": (None, [cp, C.c_int]), "pgtt_perceive_memory_packed_floats": (None, [cp, C.c_int, C.c_int]),
+    "pgtt_perceive_set_memory": (None, [vp, C.POINTER(PgttPerceiveMemory)]), "pgtt_perceive_recurrent": (None, [vp, vp, C.c_int, C.c_int, vp]),
+}, {"pgtt_perceive_sizeof_config": PgttPerceiveConfig, "pgtt_perceive_sizeof_buffers": PgttPerceiveBuffers,
+    "pgtt_perceive_sizeof_memory": PgttPerceiveMemory})
 LIB_PATH, EXPORTS, lib, check, build_info = SIDE.path, SIDE.exports, SIDE.lib, SIDE.check, SIDE.build_info
 
 
@@ -113,6 +129,9 @@ def check_config(cfg: Dict) -> None:
             no("a conv layer's output would be empty")
     if lds_bytes(cfg) > LDS_BYTES:
         no(f"the activations ({lds_bytes(cfg)} bytes) do not fit the LDS budget of {LDS_BYTES}")
+    m = cfg.get("memory", 0)
+    if m != 0 and (m != int(m) or m % 16 or not 16 <= m <= MAX_MEMORY):
+        no("memory must be 0 or a multiple of 16 in [16, 256]")
 
 
 def config_struct(cfg: Dict) -> PgttPerceiveConfig:
@@ -166,12 +185,17 @@ class ScanEstimator(torch.nn.Module):
         cfg["conv"] = [tuple(int(v) for v in l) for l in cfg["conv"]]
         cfg["prop_rows"] = [int(r) for r in cfg["prop_rows"]]
         check_config(cfg)
+        if "memory" in cfg:
+            cfg["memory"] = int(cfg["memory"])
         self.cfg = cfg
+        self.memory = cfg.get("memory", 0)
         shapes = conv_shapes(cfg)
         self.convs = torch.nn.ModuleList(torch.nn.Conv2d(shapes[l][0], co, k, s) for l, (co, k, s) in enumerate(cfg["conv"]))
         self.latent_dim = shapes[-1][0] * shapes[-1][1] * shapes[-1][2]
         self.fc1 = torch.nn.Linear(self.latent_dim + len(cfg["prop_rows"]), cfg["hidden"])
-        self.fc2 = torch.nn.Linear(cfg["hidden"], NSCAN)
+        if self.memory:
+            self.gru = torch.nn.GRUCell(cfg["hidden"], self.memory)
+        self.fc2 = torch.nn.Linear(self.memory or cfg["hidden"], NSCAN)
         self.register_buffer("prop_index", torch.tensor(cfg["prop_rows"], dtype=torch.long), persistent=False)
 
     def latent(self, depth: torch.Tensor) -> torch.Tensor:
@@ -182,8 +206,41 @@ class ScanEstimator(torch.nn.Module):
 
     def forward(self, depth: torch.Tensor, obs: torch.Tensor) -> torch.Tensor:
         """depth [N, H, W], obs [N, obs_dim] -> est [N, 117]"""
+        if self.memory:
+            raise RuntimeError(f"this ScanEstimator is recurrent (memory = {self.memory}): call step(depth, obs, mem) or sequence(...), "
+                               "forward() has no memory to read")
+        return self.fc2(self.hidden(depth, obs))
+
+    def hidden(self, depth: torch.Tensor, obs: torch.Tensor) -> torch.Tensor:
+        """h = silu(W1 z + b1) [N, hidden]"""
         z = torch.cat([self.latent(depth), obs[:, self.prop_index]], dim=1)
-        return self.fc2(torch.nn.functional.silu(self.fc1(z)))
+        return torch.nn.functional.silu(self.fc1(z))
+
+    def step(self, depth: torch.Tensor, obs: torch.Tensor, mem: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """one recurrent tick: depth [N, H, W], obs [N, obs_dim], mem [N, R] -> (est [N, 117], mem1 [N, R])"""
+        if not self.memory:
+            raise RuntimeError("this ScanEstimator is feed-forward (memory = 0): call it, step() is the recurrent form's")
+        m1 = self.gru(self.hidden(depth, obs), mem)
+        return self.fc2(m1), m1
+
+    def sequence(self, depth: torch.Tensor, obs: torch.Tensor, mem0: torch.Tensor, clear: Optional[torch.Tensor] = None,
+                 detach_every: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+        """T ticks: depth [T, N, H, W], obs [T, N, obs_dim], mem0 [N, R], clear [T, N] (non-zero: the env's memory is zeroed before tick t)
+        -> (est [T, N, 117], memT [N, R]).  The trunk and the hidden layer run once over all T N images.  detach_every = L > 0 cuts the
+        gradient through the memory before ticks L, 2 L, ... (truncated back-propagation through time)."""
+        if not self.memory:
+            raise RuntimeError("this ScanEstimator is feed-forward (memory = 0): sequence() is the recurrent form's")
+        T, N = depth.shape[:2]
+        h = self.hidden(depth.flatten(0, 1), obs.flatten(0, 1)).view(T, N, -1)
+        mem, ms = mem0, []
+        for t in range(T):
+            if detach_every and t and t % detach_every == 0:
+                mem = mem.detach()
+            if clear is not None:
+                mem = torch.where(clear[t].bool()[:, None], torch.zeros_like(mem), mem)
+            mem = self.gru(h[t], mem)
+            ms.append(mem)
+        return self.fc2(torch.stack(ms)), mem
 
     def assemble(self, obs: torch.Tensor, est: torch.Tensor) -> torch.Tensor:
         """obs with the scan rows replaced by est: obs_out as torch ops"""
@@ -191,17 +248,26 @@ class ScanEstimator(torch.nn.Module):
         return torch.cat([obs[:, :r0], est, obs[:, r0 + NSCAN:]], dim=1)
 
     def layers(self):
+        """the modules with a `weight` and a `bias` (a recurrent estimator's GRUCell is not one: weight_ih / weight_hh)"""
         return list(self.convs) + [self.fc1, self.fc2]
 
     @torch.no_grad()
     def pack(self) -> Tuple[List[torch.Tensor], List[torch.Tensor]]:
-        """-> (weights, biases) in the kernel's layouts, fp32, one entry per layer of the net (the convs, fc1, fc2)"""
+        """-> (weights, biases) in the kernel's layouts, fp32, one entry per layer of the net: the convs, fc1, fc2; a recurrent estimator's are
+        the convs, fc1, w_ih / b_ih, w_hh / b_hh, w_out / b_out (PgttPerceiveMemory)"""
         ws = [pack_conv(c.weight.float()) for c in self.convs]
         bs = [c.bias.detach().float().clone() for c in self.convs]
-        for lin in (self.fc1, self.fc2):
-            w, b = acting.pack_linear(lin.weight, lin.bias)
+        for w, b in self._linears():
+            w, b = acting.pack_linear(w, b)
             ws.append(w); bs.append(b)
         return ws, bs
+
+    def _linears(self):
+        """[(weight, bias)] of the layers packed in the linear tile order"""
+        if self.memory:
+            return [(self.fc1.weight, self.fc1.bias), (self.gru.weight_ih, self.gru.bias_ih), (self.gru.weight_hh, self.gru.bias_hh),
+                    (self.fc2.weight, self.fc2.bias)]
+        return [(self.fc1.weight, self.fc1.bias), (self.fc2.weight, self.fc2.bias)]
 
     @torch.no_grad()
     def unpack(self, ws: Sequence[torch.Tensor], bs: Sequence[torch.Tensor]) -> None:
@@ -209,8 +275,8 @@ class ScanEstimator(torch.nn.Module):
         n = len(self.convs)
         for l, c in enumerate(self.convs):
             c.weight.copy_(unpack_conv(ws[l], c.out_channels, c.in_channels, c.kernel_size[0])); c.bias.copy_(bs[l])
-        for lin, w, b in ((self.fc1, ws[n], bs[n]), (self.fc2, ws[n + 1], bs[n + 1])):
-            lin.weight.copy_(unpack_linear(w, lin.out_features, lin.in_features)); lin.bias.copy_(b[:lin.out_features])
+        for (weight, bias), w, b in zip(self._linears(), ws[n:], bs[n:]):
+            weight.copy_(unpack_linear(w, weight.shape[0], weight.shape[1])); bias.copy_(b[:bias.shape[0]])
 
     def save(self, path: str) -> None:
         """.npz: the config (JSON) and every parameter"""
@@ -233,7 +299,8 @@ def scan_target(env) -> torch.Tensor:
 
 class StudentPerception(_sidelib.Handle):
     """The estimator of one Joystick with a depth camera, as libpgtt_perceive.so runs it: owns the handle, the packed weights, `latent` [N, F],
-    `est` [N, 117] and `obs` [N, obs_dim] (the obs_out buffer: the env's observation with the scan rows replaced by est).
+    `est` [N, 117] and `obs` [N, obs_dim] (the obs_out buffer: the env's observation with the scan rows replaced by est).  With a recurrent
+    estimator also `mem` [N, R], zeros at creation: the GRU state, read and written by every tick and cleared by its arguments.
     Runs on the env's device and current stream; reads env.depth and env.buffers["obs_state"] and writes nothing but its own tensors."""
     _prefix, _check = "pgtt_perceive", staticmethod(check)
 
@@ -258,6 +325,14 @@ class StudentPerception(_sidelib.Handle):
         self._w = [z(self._lib.pgtt_perceive_packed_floats(C.byref(self.config), l)) for l in self._layers]
         self._b = [z(co) for co, _, _ in cfg["conv"]] + [z(cfg["hidden"]), z(OUT_PAD)]
         assert self._lib.pgtt_perceive_latent_dim(C.byref(self.config)) == estimator.latent_dim
+        self.memory, self.mem, self._mask = estimator.memory, None, None
+        if self.memory:
+            # layer 4 of the feed-forward form stays a zero buffer the recurrent call never reads; the cell's own layers follow it
+            r = self.memory
+            check(self._lib.pgtt_perceive_memory_check(C.byref(self.config), r))
+            self._mw = [z(self._lib.pgtt_perceive_memory_packed_floats(C.byref(self.config), r, which)) for which in range(3)]
+            self._mb = [z(3 * r), z(3 * r), z(OUT_PAD)]
+            self.mem = z(n, r)
         self.load(estimator)
         self.bind()
 
@@ -269,18 +344,47 @@ class StudentPerception(_sidelib.Handle):
             b.w[l], b.b[l] = w.data_ptr(), bias.data_ptr()
         b.latent, b.est, b.obs_out = self.latent.data_ptr(), self.est.data_ptr(), self.obs.data_ptr()
         check(self._lib.pgtt_perceive_bind(self._h, C.byref(b)))
+        if self.memory:
+            check(self._lib.pgtt_perceive_set_memory(self._h, C.byref(self.memory_struct())))
+
+    def memory_struct(self) -> PgttPerceiveMemory:
+        """the recurrent form's pointers: this object's packed cell, its `mem` and the env's done flags (None when the env has none)"""
+        m = PgttPerceiveMemory()
+        m.memory = self.memory
+        m.w_ih, m.w_hh, m.w_out = (w.data_ptr() for w in self._mw)
+        m.b_ih, m.b_hh, m.b_out = (b.data_ptr() for b in self._mb)
+        done = self.env.buffers.get("done")
+        m.done = None if done is None else done.data_ptr()
+        m.mem = self.mem.data_ptr()
+        return m
 
     @torch.no_grad()
     def load(self, estimator: ScanEstimator) -> None:
         """repack the estimator's parameters in place: a captured graph keeps reading the same addresses"""
         ws, bs = estimator.pack()
-        for dst, src in zip(self._w + self._b, ws + bs):
+        if estimator.memory != self.memory:
+            raise ValueError(f"this StudentPerception was made for memory = {self.memory}, the estimator has {estimator.memory}")
+        dw, db = (self._w[:-1] + self._mw, self._b[:-1] + self._mb) if self.memory else (self._w, self._b)
+        for dst, src in zip(dw + db, ws + bs):
             assert dst.numel() == src.numel(), (dst.shape, src.shape)
             dst.copy_(src.to(dst.device))
 
-    def tick(self) -> torch.Tensor:
-        """one estimate for every env: two launches on the env's current stream, no synchronisation"""
-        check(self._lib.pgtt_perceive(self._h, torch.cuda.current_stream(self.env.device).cuda_stream))
+    def tick(self, clear_mask: Optional[torch.Tensor] = None, clear_all: bool = False, use_done: bool = False) -> torch.Tensor:
+        """one estimate for every env: two launches on the env's current stream, no synchronisation.  A recurrent estimator's tick reads and writes
+        `mem`; before it does, the memory of the envs with clear_mask[e] != 0 ([N] uint8 / bool), of every env (clear_all) or of the envs whose done
+        flag is set (use_done) reads as zero.  A feed-forward estimator has nothing to clear and refuses the arguments."""
+        stream = torch.cuda.current_stream(self.env.device).cuda_stream
+        if not self.memory:
+            if clear_mask is not None or clear_all or use_done:
+                raise ValueError("tick(clear_mask / clear_all / use_done) is the recurrent student's: this estimator has no memory")
+            check(self._lib.pgtt_perceive(self._h, stream))
+            return self.obs
+        mp = None
+        if clear_mask is not None:
+            self._mask = clear_mask.to(self.env.device, torch.uint8).contiguous()      # kept alive until the next tick: the launch is asynchronous
+            assert self._mask.shape == (self.env.num_envs,)
+            mp = self._mask.data_ptr()
+        check(self._lib.pgtt_perceive_recurrent(self._h, mp, int(bool(clear_all)), int(bool(use_done)), stream))
         return self.obs
 
     def set_terrain(self, terrain) -> None:

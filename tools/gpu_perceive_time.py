@@ -5,7 +5,9 @@ steps of small random actions; device events around 20 back-to-back calls after 
     python tools/gpu_perceive_time.py [--out profiles/NAME.txt]
 
 (i) pgtt_perceive (two launches); (ii) the torch fp32 ScanEstimator forward under no_grad plus the obs_out assembly as torch ops - what (i)
-replaces, the yardstick; (iii) the camera tick; (iv) the env step (no camera, no student)."""
+replaces, the yardstick; (iii) the camera tick; (iv) the env step (no camera, no student); (v) pgtt_perceive_recurrent, the default net with a GRU
+memory of 128 values per env (a second StudentPerception on the same image and observation); (vi) the torch fp32
+ScanEstimator.step + assembly that (v) replaces."""
 import argparse
 import os
 import sys
@@ -57,27 +59,40 @@ def main():
         env.step(act); plain.step(act)
     torch.cuda.synchronize()
     sp, obs, depth = env.student, env.buffers["obs_state"], env.depth
+    rest = perceive.ScanEstimator(perceive.config(memory=128)).cuda()
+    rsp = perceive.StudentPerception(env, rest)
 
     @torch.no_grad()
     def torch_path():
         return est.assemble(obs, est(depth, obs))
 
+    @torch.no_grad()
+    def torch_step():
+        e, m1 = rest.step(depth, obs, rsp.mem)
+        return rest.assemble(obs, e), m1
+
     rows = [("(i)   pgtt_perceive, two launches", window_us(sp.tick)),
             ("(ii)  torch fp32 ScanEstimator forward + obs_out assembly", window_us(torch_path)),
             ("(iii) camera tick (force)", window_us(lambda: env.depth_camera.tick(force=True))),
-            ("(iv)  env step, no camera, no student", window_us(lambda: plain.step(act)))]
+            ("(iv)  env step, no camera, no student", window_us(lambda: plain.step(act))),
+            ("(v)   pgtt_perceive_recurrent, memory 128, two launches", window_us(rsp.tick)),
+            ("(vi)  torch fp32 ScanEstimator.step + obs_out assembly", window_us(torch_step))]
     with torch.no_grad():
         agree = float((torch_path() - sp.tick()).abs().max())
+        want, m1 = torch_step()
+        ragree = max(float((want - rsp.tick()).abs().max()), float((m1 - rsp.mem).abs().max()))
     lines = [f"{n} envs, level4, 64x48, default net ({sum(p.numel() for p in est.parameters())} parameters); us per call, median [min, max] of 11 windows of 20 calls",
              f"libpgtt_perceive build: {perceive.build_info()}"]
     lines += [f"{name:60s} {m:9.1f} [{lo:.1f}, {hi:.1f}]" for name, (m, lo, hi) in rows]
     lines.append(f"(ii) / (i) = {rows[1][1][0] / rows[0][1][0]:.2f};  max |torch - kernel| over obs_out = {agree:.2e}")
+    lines.append(f"(v) / (i) = {rows[4][1][0] / rows[0][1][0]:.2f};  (vi) / (v) = {rows[5][1][0] / rows[4][1][0]:.2f};  "
+                 f"max |torch - kernel| over obs_out and mem = {ragree:.2e}  ({sum(p.numel() for p in rest.parameters())} parameters)")
     text = "\n".join(lines)
     print(text)
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         open(args.out, "w").write(text + "\n")
-    env.close(); plain.close()
+    rsp.close(); env.close(); plain.close()
 
 
 if __name__ == "__main__":

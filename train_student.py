@@ -10,6 +10,11 @@ env.step - so the data drifts from the teacher's states to the student's own (DA
 Every step's (depth, obs, scan_target) is kept; the iteration ends with Adam steps on a Huber loss over minibatches of it (torch autograd on the
 ScanEstimator: the library is forward only) and repacks the new weights into the kernel (StudentPerception.load).  It logs the RMSE per band of
 scan rows: the 6 x 9 cells ahead of the base, the 9 under it and the 6 x 9 behind it.
+
+`--memory R` distils the recurrent student (perceive.config(memory=R): a GRU cell of R values per env).  The roll-out then stays in
+[T, N] order with the flags of the envs that were restarted before each step and the memory the roll-out started from; a minibatch is a set of
+envs with all their T steps, the loss is the Huber loss over ScanEstimator.sequence() of them, and the gradient through the memory is cut every
+`--bptt` steps (default: the horizon, i.e. never inside a roll-out).
 """
 import argparse
 import os
@@ -47,27 +52,64 @@ class Collector:
     def __init__(self, env, teacher, horizon, seed=0):
         assert env.student is not None, "Collector needs Joystick(..., depth=..., student=...)"
         self.env, self.T = env, int(horizon)
+        if self.T < 1:
+            raise ValueError("Collector: horizon must be at least 1")
         self.mix = torch.zeros_like(env.buffers["obs_state"])
         self.actor = FusedActor(env, self.T, seed=seed, obs=self.mix)
         self.actor.load([(m.weight, m.bias) for m in teacher.layers], teacher.mean, teacher.std)
         self._ids = torch.arange(env.num_envs, device=env.device)[:, None]
+        # a recurrent student: the memory its tick on the next sample's image started from, and whether that tick cleared it.  The env was reset
+        # before the first roll-out and is stepped by the collector alone, so the first image met an empty memory.
+        self.recurrent = bool(env.student.memory)
+        if self.recurrent:
+            self._mem, self._clear = torch.zeros_like(env.student_mem), torch.ones(env.num_envs, dtype=torch.bool, device=env.device)
 
     @torch.no_grad()
     def collect(self, beta):
-        """-> (depth [T N, H, W], obs [T N, obs_dim], target [T N, 117]) of `horizon` steps, each taken BEFORE the step it precedes"""
+        """-> (depth [T N, H, W], obs [T N, obs_dim], target [T N, 117]) of `horizon` steps, each taken BEFORE the step it precedes.
+        With a recurrent student -> (depth [T, N, H, W], obs [T, N, obs_dim], target [T, N, 117], clear [T, N] bool, mem0 [N, R]): clear[t] says
+        that the student's tick on depth[t] started from an empty memory (the env was reset, or the step before ended its episode), mem0 is the
+        memory the tick on depth[0] started from.  mem0 was left by the weights the kernel ran during the roll-out before, not by the ones being
+        trained now: stored-state back-propagation through time, the usual approximation"""
         env = self.env
         true_rows = self._ids < round(float(beta) * env.num_envs)
-        depth, obs, target = [], [], []
+        depth, obs, target, clear = [], [], [], []
         self.actor.rewind()
         for _ in range(self.T):
             self.mix.copy_(torch.where(true_rows, env.buffers["obs_state"], env.student_obs))
             depth.append(env.depth.clone()); obs.append(env.buffers["obs_state"].clone()); target.append(perceive.scan_target(env))
+            if self.recurrent:
+                clear.append(self._clear)
+                after = env.student_mem.clone()                      # the memory after the tick on this sample's image
             self.actor.step()
+            if self.recurrent:
+                self._clear = env.buffers["done"] != 0               # the step's tick ran with use_done
+        if self.recurrent:
+            mem0, self._mem = self._mem, after
+            return torch.stack(depth), torch.stack(obs), torch.stack(target), torch.stack(clear), mem0
         return torch.cat(depth), torch.cat(obs), torch.cat(target)
+
+
+def sequence_loss(est, data, envs, bptt=0, reduction="mean"):
+    """Huber loss of a recurrent estimator over all T steps of the envs `envs` of a roll-out (depth, obs, target, clear, mem0): the memory starts
+    from mem0, is cleared where clear says so, and the gradient through it is cut every `bptt` steps (0: never)"""
+    depth, obs, target, clear, mem0 = data
+    pred, _ = est.sequence(depth[:, envs], obs[:, envs], mem0[envs], clear[:, envs], detach_every=bptt)
+    return torch.nn.functional.huber_loss(pred, target[:, envs], delta=HUBER_DELTA, reduction=reduction)
+
+
+def _env_batches(data, batch):
+    """slices of envs holding about `batch` samples each"""
+    T, n = data[0].shape[:2]
+    per = max(1, batch // T)
+    return [slice(i, i + per) for i in range(0, n, per)]
 
 
 def huber(est, data, batch=4096):
     """mean Huber loss of the estimator on (depth, obs, target), no gradient"""
+    if est.memory:
+        with torch.no_grad():
+            return sum(float(sequence_loss(est, data, s, reduction="sum")) for s in _env_batches(data, batch)) / data[2].numel()
     depth, obs, target = data
     total = 0.0
     with torch.no_grad():
@@ -79,24 +121,34 @@ def huber(est, data, batch=4096):
 
 def band_rmse(est, data, batch=4096):
     """{"ahead" | "under" | "behind": RMSE in metres over the band's scan rows}"""
-    depth, obs, target = data
+    depth, obs, target = data[:3]
     sq = torch.zeros(perceive.NSCAN, device=depth.device, dtype=torch.float64)
+    samples = target.numel() // perceive.NSCAN
     with torch.no_grad():
-        for i in range(0, depth.shape[0], batch):
-            s = slice(i, i + batch)
-            sq += ((est(depth[s], obs[s]) - target[s]).double() ** 2).sum(0)
-    return {k: float((sq[b].sum() / (depth.shape[0] * len(range(*b.indices(perceive.NSCAN))))).sqrt()) for k, b in perceive.BANDS.items()}
+        if est.memory:
+            for s in _env_batches(data, batch):
+                pred, _ = est.sequence(depth[:, s], obs[:, s], data[4][s], data[3][:, s])
+                sq += ((pred - target[:, s]).double() ** 2).sum((0, 1))
+        else:
+            for i in range(0, depth.shape[0], batch):
+                s = slice(i, i + batch)
+                sq += ((est(depth[s], obs[s]) - target[s]).double() ** 2).sum(0)
+    return {k: float((sq[b].sum() / (samples * len(range(*b.indices(perceive.NSCAN))))).sqrt()) for k, b in perceive.BANDS.items()}
 
 
-def fit(est, opt, data, steps, batch, generator):
-    """`steps` Adam steps on minibatches drawn without replacement (a new permutation when the data runs out) -> mean loss"""
-    depth, obs, target = data
-    n, total, perm, at = depth.shape[0], 0.0, None, 0
+def fit(est, opt, data, steps, batch, generator, bptt=0):
+    """`steps` Adam steps on minibatches drawn without replacement (a new permutation when the data runs out) -> mean loss.  A minibatch of a
+    recurrent estimator is `batch` ENVS of the roll-out with all their steps (sequence_loss, the gradient cut every `bptt` steps)"""
+    depth, obs, target = data[:3]
+    n, total, perm, at = (depth.shape[1] if est.memory else depth.shape[0]), 0.0, None, 0
     for _ in range(steps):
         if perm is None or at + batch > n:
             perm, at = torch.randperm(n, device=depth.device, generator=generator), 0
         idx = perm[at:at + batch]; at += batch
-        loss = torch.nn.functional.huber_loss(est(depth[idx], obs[idx]), target[idx], delta=HUBER_DELTA)
+        if est.memory:
+            loss = sequence_loss(est, data, idx, bptt)
+        else:
+            loss = torch.nn.functional.huber_loss(est(depth[idx], obs[idx]), target[idx], delta=HUBER_DELTA)
         opt.zero_grad(set_to_none=True)
         loss.backward()
         opt.step()
@@ -116,7 +168,14 @@ def make_env(args, est):
 
 def run(args):
     torch.manual_seed(args.seed)
-    est = (perceive.ScanEstimator.load(args.resume) if args.resume else perceive.ScanEstimator(perceive.config(args.method))).to(DEVICE)
+    if args.resume:
+        est = perceive.ScanEstimator.load(args.resume)
+        if args.memory and est.memory != args.memory:
+            raise SystemExit(f"--resume {args.resume} has memory = {est.memory}, --memory asks for {args.memory}")
+    else:
+        est = perceive.ScanEstimator(perceive.config(args.method, memory=args.memory))
+    est = est.to(DEVICE)
+    bptt = args.bptt or args.horizon
     env = make_env(args, est)
     col = Collector(env, load_teacher(args.teacher, DEVICE), args.horizon, seed=args.seed)
     opt = torch.optim.Adam(est.parameters(), lr=args.learning_rate)
@@ -128,8 +187,11 @@ def run(args):
         beta = b0 + (b1 - b0) * (it / max(1, args.iters - 1))
         data = col.collect(beta)
         before = huber(est, data)
-        n = data[0].shape[0]
-        loss = fit(est, opt, data, max(1, args.epochs * n // args.batch_size), min(args.batch_size, n), gen)
+        n = data[2].numel() // perceive.NSCAN
+        if est.memory:                                               # a minibatch is the envs that hold about batch_size samples
+            loss = fit(est, opt, data, max(1, args.epochs * n // args.batch_size), min(max(1, args.batch_size // args.horizon), args.num_envs), gen, bptt)
+        else:
+            loss = fit(est, opt, data, max(1, args.epochs * n // args.batch_size), min(args.batch_size, n), gen)
         env.student.load(est)
         rm = band_rmse(est, data)
         print(f"iter {it:3d}  beta {beta:.2f}  samples {n}  huber before {before:.5f}  train {loss:.5f}  rmse m  ahead {rm['ahead']:.4f}  under {rm['under']:.4f}  "
@@ -151,6 +213,8 @@ def make_parser():
     ap.add_argument("--num_envs", type=int, default=4096)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--horizon", type=int, default=16, help="steps rolled out (and kept) per iteration")
+    ap.add_argument("--memory", type=int, default=0, help="R > 0: the recurrent student, a GRU cell of R values per env (a multiple of 16, at most 256)")
+    ap.add_argument("--bptt", type=int, default=0, help="with --memory: cut the gradient through the memory every L steps (0 = --horizon)")
     ap.add_argument("--beta", type=str, default="1.0,0.0", help="b0,b1: share of the envs acting on the true observation, first and last iteration")
     ap.add_argument("--epochs", type=int, default=1, help="passes over an iteration's data")
     ap.add_argument("--batch_size", type=int, default=1024)
