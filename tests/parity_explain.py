@@ -8,6 +8,14 @@ both sides, every substep is judged on its own input against a* = the minimiser 
   * `cap`      the reference truncates Newton at `iterations` = 5 (go2/xmls/go2_mjx_feetonly.xml:17).  A side's acceleration is off a*
                (dt |a - a*| > 5e-4 or |a - a*| / (1 + |a*|) > 2e-3: a tenth of the bars) AND that side stopped because it ran out of iterations
                (niter == iterations); also when the fp64 oracle itself, at the reference's caps, is cut on that input (the edge of W).
+               Running out of iterations bounds nothing, so for the DEVICE the verdict has to be PROVEN (prove_cap; the anomaly records the `proof`):
+               `lifted` - the same side from the same input with the caps lifted to 64 x 60 (what pgtt_create accepts; the kernels read them at run
+               time) reaches a*, or the fp32 floor of the cost: the cap is what stopped it; else `no worse` - its gap above the minimum is at most
+               2 x max(the fp32 oracle's from the same input, FLOOR_ULPS); else `within spread` - it is no further from the fp32 oracle's answer than
+               2 x what that answer moves by under <= 2 roundings of the input; else `same point` - it IS the fp32 oracle's answer to OFF_DV / OFF_REL.
+               None of them: `unexplained`.  The oracle sides are the reference and keep the plain rule (`reference`).  Where no lifted replay
+               exists (the reset's forward pass) the last three apply alone.  profiles/cap_proofs.txt has the counts and the measurements
+               behind the factors; tests/test_parity_explain.py the faults this rejects (before: a fault on the cut solves was `cap` at any size).
   * `floor`    a side is off a* and stopped by the solver's improvement test, with a cost within FLOOR_ULPS fp32 roundings of the cost's terms of the
                minimum: the fp32 cost cannot resolve the remaining descent.
   * `sign`     the ACTIVE contact sets of a side and of the fp64 oracle differ on the same input, and every pair in the difference has
@@ -22,7 +30,8 @@ both sides, every substep is judged on its own input against a* = the minimiser 
                is not small, a replay that does not reproduce the control step's bits.
 
 The replay runs ONE mjx.step per call on the device (a second handle with ctrl_dt = sim_dt, same lane layout, the WHOLE batch; physics only) and must
-reproduce the bits of the control step it explains; the fp32 oracle's replay likewise.
+reproduce the bits of the control step it explains; the fp32 oracle's replay likewise.  A third handle, the second with lifted caps, answers each
+substep on which a requested env was cut once more from the same input (DeviceSubsteps.lift); it never writes into the other two.
 """
 from __future__ import annotations
 
@@ -37,6 +46,9 @@ from phase_guided_terrain_traversal_amd import abi
 SIGN_TOL = 1e-6            # north star: "a contact pair whose oracle |dist| < 1e-6 flips"; scaled by the size of the coordinates it is a difference of
 OFF_DV, OFF_REL = 5e-4, 2e-3
 LONG_ITER, LONG_LS = 100, 60
+LIFT_ITER, LIFT_LS = 64, 60   # the lifted replay of a SIDE: what pgtt_create accepts (solver iteration counts 1 .. 64)
+CAP_MARGIN = 2.0              # the project's usual margin over the reference; the 0.5 rule of reset_explained / scan_ensemble read the other way
+PROOFS = ("lifted", "no worse", "within spread", "same point", "reference")
 EPS32, FLOOR_ULPS = 2.0 ** -24, 8.0
 
 
@@ -104,9 +116,45 @@ def frame_tie(ms, ed: EnvData, inp, ctrl, D32: Dict, D64: Dict) -> str:
     return "" if not hits else f"(foot, box, centre-to-surface distance) {[(f, b, float(f'{d:.2g}')) for f, b, d in hits]}: the sphere centre lies on the surface of the box, the normal is the direction of a zero-length vector"
 
 
-def judge_substep(ms, ms_long, ed: EnvData, inp, ctrl, sub: Dict, side: str) -> List[Dict]:
+def prove_cap(ms, ed: EnvData, inp, ctrl, sub: Dict, D64: Dict, astar, gap: float, seed: int = 0) -> tuple:
+    """a DEVICE-side solve that is off a* and ran out of iterations: is the cap what stopped it, or does a fault hide behind it?  -> (proof, words);
+    proof "" = not proven.  Tried in this order (the measurements behind the factors: profiles/cap_proofs.txt):
+      `lifted`         the same side from the same input with the caps lifted to LIFT_ITER x LIFT_LS (sub["qacc_lifted"], where the provider has one)
+                       reaches a*, or stops within FLOOR_ULPS roundings of the minimum;
+      `no worse`       its gap above the minimum is at most CAP_MARGIN x max(the fp32 oracle's from the same input, FLOOR_ULPS);
+      `within spread`  it is no further from the fp32 oracle's answer on the same input than CAP_MARGIN x how far that answer moves under <=
+                       ENSEMBLE_ULPS roundings of the input (substep_ensemble), in dv and in rel - the 0.5 rule of reset_explained and scan_ensemble;
+      `same point`     it is the fp32 oracle's answer to OFF_DV / OFF_REL."""
+    dt = float(ms.timestep)
+    qpos, qvel, warm = inp
+    kw = dict(boxes=ed.boxes, box_friction=ed.box_friction, params=ed.params)
+    c_star, mag = cost_terms(D64, astar)
+    said = []
+    if sub.get("qacc_lifted") is not None:
+        ol = off_minimiser(sub["qacc_lifted"], astar, dt)
+        gl = (cost_terms(D64, sub["qacc_lifted"])[0] - c_star) / (EPS32 * mag)
+        if not is_off(*ol) or gl < FLOOR_ULPS:
+            return "lifted", f"with the caps lifted it ends at dv {ol[0]:.3g}, rel {ol[1]:.3g} of the minimiser, {gl:.3g} roundings above the minimum, after {int(sub.get('niter_lifted', -1))} iterations"
+        said.append(f"with the caps lifted it is STILL off the minimiser (dv {ol[0]:.3g}, rel {ol[1]:.3g}, {gl:.3g} roundings above the minimum, niter {int(sub.get('niter_lifted', -1))})")
+    D32 = oracle.forward(ms, qpos, qvel, ctrl, warm, fp64=False, **kw)
+    g32 = (cost_terms(D64, D32["qacc"])[0] - c_star) / (EPS32 * mag)
+    if gap <= CAP_MARGIN * max(g32, FLOOR_ULPS):
+        return "no worse", f"the fp32 oracle stops {g32:.3g} roundings above the minimum from the same input (niter {int(D32['niter'])})"
+    said.append(f"the fp32 oracle stops {g32:.3g} roundings above the minimum from the same input")
+    d = off_minimiser(sub["qacc"], D32["qacc"], dt)
+    sp = substep_ensemble(ms, ed, inp, ctrl, seed)
+    if d[0] <= CAP_MARGIN * sp[0] and d[1] <= CAP_MARGIN * sp[1]:
+        return "within spread", f"dv {d[0]:.3g}, rel {d[1]:.3g} from the fp32 oracle's answer, which moves by dv {sp[0]:.3g}, rel {sp[1]:.3g} under <= {ENSEMBLE_ULPS} roundings of the input"
+    if not is_off(*d):
+        return "same point", f"dv {d[0]:.3g}, rel {d[1]:.3g} from the fp32 oracle's answer on the same input"
+    said.append(f"it is dv {d[0]:.3g}, rel {d[1]:.3g} from the fp32 oracle's answer, which moves by dv {sp[0]:.3g}, rel {sp[1]:.3g} under input rounding")
+    return "", "; ".join(said)
+
+
+def judge_substep(ms, ms_long, ed: EnvData, inp, ctrl, sub: Dict, side: str, seed: int = 0) -> List[Dict]:
     """one side's substep against the minimiser a* of ITS OWN input (fp64 oracle, caps lifted) and, for the device, against the fp64 oracle's
-    contact set -> list of anomalies {side, substep-less class, dv, rel, detail}"""
+    contact set -> list of anomalies {side, substep-less class, dv, rel, detail; a `cap` also carries `proof`: how it was shown that the cap is what
+    stopped the solve (prove_cap), "reference" for the two oracle sides - they are what the device is held to}"""
     dt, iters = float(ms.timestep), int(ms.iterations)
     qpos, qvel, warm = inp
     kw = dict(boxes=ed.boxes, box_friction=ed.box_friction, params=ed.params)
@@ -137,7 +185,7 @@ def judge_substep(ms, ms_long, ed: EnvData, inp, ctrl, sub: Dict, side: str) -> 
             Dl = oracle.forward(model_copy(ms, ls_iterations=LONG_LS), qpos, qvel, ctrl, warm, fp64=True, **kw)
             if Dl["niter"] >= iters or not is_off(*off_minimiser(Dl["qacc"], astar, dt)):
                 cause64, which = "cap", "line-search round"
-        out.append(dict(side="fp64 oracle", cause=cause64, dv=o64[0], rel=o64[1],
+        out.append(dict(side="fp64 oracle", cause=cause64, dv=o64[0], rel=o64[1], **({"proof": "reference"} if cause64 == "cap" else {}),
                         detail=f"fp64 oracle cut at the {which} cap on the {side}'s input (dv {o64[0]:.3g}, rel {o64[1]:.3g}, niter {int(D64['niter'])})"))
     off = off_minimiser(sub["qacc"], astar, dt)
     if is_off(*off):
@@ -147,7 +195,14 @@ def judge_substep(ms, ms_long, ed: EnvData, inp, ctrl, sub: Dict, side: str) -> 
         gap = (c_side - c_star) / (EPS32 * mag)
         cause = "cap" if ni >= iters else ("floor" if gap < FLOOR_ULPS else "unexplained")
         detail = f"{side} off the minimiser (dv {off[0]:.3g}, rel {off[1]:.3g}) with niter {ni} of {iters}, cost above the minimum by {gap:.3g} fp32 roundings of its terms"
-        if cause == "unexplained":
+        proof = None
+        if cause == "cap":
+            # running out of iterations excuses a distance from a* only if the cap is shown to be what stopped the solve; the fp32 oracle is the reference
+            proof, words = ("reference", "") if side != "device" else prove_cap(ms, ed, inp, ctrl, sub, D64, astar, gap, seed)
+            if not proof:
+                cause = "unexplained"
+            detail += f"; {'cap not proven' if not proof else proof}: {words}" if words else ""
+        elif cause == "unexplained":
             # neither the cut nor the resolution of the cost.  Is it this side's arithmetic, or the fp32 ALGORITHM on this input?  The fp32 oracle on the
             # same input: if the side lands where it does, the question becomes why fp32 and fp64 differ here - a discrete geometric choice within rounding
             # of a tie (the face of a box nearest to a sphere centre INSIDE it: mjx _sphere_convex) gives the two precisions different constraint rows
@@ -156,7 +211,7 @@ def judge_substep(ms, ms_long, ed: EnvData, inp, ctrl, sub: Dict, side: str) -> 
                 tie = frame_tie(ms, ed, inp, ctrl, D32, D64)
                 if tie:
                     cause, detail = "tie", f"{side} = the fp32 oracle on the same input (niter {int(D32['niter'])}); fp32 and fp64 build different contact frames there: {tie}"
-        out.append(dict(side=side, cause=cause, dv=off[0], rel=off[1], gap_ulps=gap, niter=ni, detail=detail))
+        out.append(dict(side=side, cause=cause, dv=off[0], rel=off[1], gap_ulps=gap, niter=ni, detail=detail, **({"proof": proof} if cause == "cap" else {})))
     return out
 
 
@@ -181,7 +236,7 @@ def audit_substep(ms, ms_long, ed: EnvData, inp, ctrl, sub: Dict, seed: int = 0)
     the fp64 oracle's contact set) -> "minimiser"; or it shows why not -> "cap" / "floor" / "sign" / "tie" / "edge of W" (the fp64 oracle at the
     reference's caps is cut on this input) / "unstable" (the fp32 oracle's own answer moves at least half as far under <= 2 roundings of the input);
     anything else is "unexplained" """
-    an = judge_substep(ms, ms_long, ed, inp, ctrl, sub, "device")
+    an = judge_substep(ms, ms_long, ed, inp, ctrl, sub, "device", seed=seed)
     if not an:
         return dict(cause="minimiser", detail="")
     bad = [a for a in an if a["cause"] == "unexplained"]
@@ -193,6 +248,8 @@ def audit_substep(ms, ms_long, ed: EnvData, inp, ctrl, sub: Dict, seed: int = 0)
         return dict(cause="unexplained", detail=f"{b['detail']}; fp32 oracle under input rounding: dv {dv:.3g}, rel {rel:.3g}")
     top = max(an, key=lambda a: (a["dv"], a["rel"]))
     out = dict(cause="edge of W" if top["side"] == "fp64 oracle" else top["cause"], detail=top["detail"])
+    if out["cause"] == "cap":
+        out["proof"] = top["proof"]
     if out["cause"] in ("cap", "edge of W"):
         # a cut solve has no right answer to be compared with - but it has a QUALITY: how far above the minimum did the device stop, and how far does the
         # fp32 oracle stop from the same input?  (the caller compares the two populations: a slower-converging device would show here and nowhere else)
@@ -209,12 +266,12 @@ def audit_substep(ms, ms_long, ed: EnvData, inp, ctrl, sub: Dict, seed: int = 0)
     return out
 
 
-def euler_error(ms, inp, sub: Dict) -> float:
-    """mjx's semi-implicit Euler step (eulerdamp disabled, go2_mjx_feetonly.xml:18) from the substep's input and the DEVICE's acceleration, in fp64, against
-    the state the device integrated to -> largest |difference| / (1 + |value|) over qvel' and qpos' (free-joint quaternion: q (x) exp(dt w / 2), normalised)"""
+def euler_step(ms, inp, qacc) -> tuple:
+    """mjx's semi-implicit Euler step (eulerdamp disabled, go2_mjx_feetonly.xml:18) from a substep's input and an acceleration, in fp64 -> (qpos', qvel')
+    (free-joint quaternion: q (x) exp(dt w / 2), normalised)"""
     dt = float(ms.timestep)
     qpos, qvel = np.asarray(inp[0], np.float64), np.asarray(inp[1], np.float64)
-    a = np.asarray(sub["qacc"], np.float64)
+    a = np.asarray(qacc, np.float64)
     v = qvel + dt * a
     q = qpos.copy()
     q[:3] += dt * v[:3]; q[7:] += dt * v[6:]
@@ -226,6 +283,13 @@ def euler_error(ms, inp, sub: Dict) -> float:
         q[3:7] = [u[0]*r[0] - u[1]*r[1] - u[2]*r[2] - u[3]*r[3], u[0]*r[1] + u[1]*r[0] + u[2]*r[3] - u[3]*r[2],
                   u[0]*r[2] - u[1]*r[3] + u[2]*r[0] + u[3]*r[1], u[0]*r[3] + u[1]*r[2] - u[2]*r[1] + u[3]*r[0]]
     q[3:7] /= np.linalg.norm(q[3:7])
+    return q, v
+
+
+def euler_error(ms, inp, sub: Dict) -> float:
+    """euler_step from the substep's input and the DEVICE's acceleration against the state the device integrated to -> largest |difference| /
+    (1 + |value|) over qvel' and qpos'"""
+    q, v = euler_step(ms, inp, sub["qacc"])
     ev = np.abs(np.asarray(sub["qvel"], np.float64) - v) / (1 + np.abs(v))
     eq = np.abs(np.asarray(sub["qpos"], np.float64) - q) / (1 + np.abs(q))
     return float(max(ev.max(), eq.max()))
@@ -241,13 +305,32 @@ def audit_control_step(ms, hb, terrain, S0: np.ndarray, ctrl_rows: np.ndarray, d
         inp = (S0[:19, e].astype(np.float64), S0[19:37, e].astype(np.float64), S0[37:55, e].astype(np.float64))
         for s_, sub in enumerate(dev[i]):
             v = audit_substep(ms, ms_long, ed, inp, ctrl_rows[:, e].astype(np.float64), sub, seed=seed + 4 * e + s_)
-            out.append(dict(env=e, substep=s_, niter=int(sub["niter"]), euler=euler_error(ms, inp, sub), **v))
+            out.append(dict(env=e, substep=s_, niter=int(sub["niter"]), niter_lifted=sub.get("niter_lifted"), euler=euler_error(ms, inp, sub), **v))
+            inp = (sub["qpos"].astype(np.float64), sub["qvel"].astype(np.float64), sub["qacc"].astype(np.float64))
+    return out
+
+
+def audit_lifted(ms, hb, terrain, S0: np.ndarray, ctrl_rows: np.ndarray, dev: List[List[Dict]], cols, seed: int = 0) -> List[Dict]:
+    """the LIFTED replay of every substep of the envs `cols` (dev = their substeps, each with qacc_lifted / niter_lifted, taken from the capped run's inputs)
+    through audit_substep with the lifted caps as the model's: with LIFT_ITER x LIFT_LS rounds the cap excuses nothing, so `cap` / `edge of W` here mean a
+    solve that ran LIFT_ITER iterations and is still off a* -> records {env, substep, cause, detail, niter}"""
+    ms_lift = model_copy(ms, iterations=LIFT_ITER, ls_iterations=LIFT_LS)
+    ms_long = model_copy(ms, iterations=LONG_ITER, ls_iterations=LONG_LS)
+    out = []
+    for i, e in enumerate(cols):
+        e = int(e)
+        ed = env_data(hb, terrain, e)
+        inp = (S0[:19, e].astype(np.float64), S0[19:37, e].astype(np.float64), S0[37:55, e].astype(np.float64))
+        for s_, sub in enumerate(dev[i]):
+            lifted = dict(qacc=sub["qacc_lifted"], niter=sub["niter_lifted"], con=sub["con"], dist=sub["dist"])
+            v = audit_substep(ms_lift, ms_long, ed, inp, ctrl_rows[:, e].astype(np.float64), lifted, seed=seed + 4 * e + s_)
+            out.append(dict(env=e, substep=s_, niter=int(sub["niter_lifted"]), niter_capped=int(sub["niter"]), **v))
             inp = (sub["qpos"].astype(np.float64), sub["qvel"].astype(np.float64), sub["qacc"].astype(np.float64))
     return out
 
 
 def explain_physics(ms: abi.PgttModel, ed: EnvData, x0: np.ndarray, ctrl: np.ndarray, dev: List[Dict], final_dev: Optional[np.ndarray] = None,
-                    orc: Optional[List[Dict]] = None) -> Dict:
+                    orc: Optional[List[Dict]] = None, seed: int = 0) -> Dict:
     """x0 = rows [0:55] of the state BEFORE the control step (qpos 19, qvel 18, warm start 18), ctrl = the 12 motor targets, dev = the device's own
     substeps (dicts with qpos, qvel, qacc, niter, con [8][2], dist [8]), final_dev = rows [0:55] the product's control step ended with, orc = the
     fp32 oracle's OWN substeps from x0.  EVERY substep of either side is judged on its own input (judge_substep); the verdict is `unexplained` if
@@ -265,14 +348,14 @@ def explain_physics(ms: abi.PgttModel, ed: EnvData, x0: np.ndarray, ctrl: np.nda
             continue
         inp = (x0[:19].astype(np.float64), x0[19:37].astype(np.float64), x0[37:55].astype(np.float64))
         for s, sub in enumerate(subs):
-            for an in judge_substep(ms, ms_long, ed, inp, ctrl, sub, side):
+            for an in judge_substep(ms, ms_long, ed, inp, ctrl, sub, side, seed=seed + s):
                 anomalies.append(dict(an, substep=s))
             inp = (sub["qpos"].astype(np.float64), sub["qvel"].astype(np.float64), sub["qacc"].astype(np.float64))
     if not anomalies:
         return dict(cause="none", substep=-1, side="", detail="both sides sit on the minimiser of every substep, with the fp64 oracle's contact set", trail=[])
     bad = [an for an in anomalies if an["cause"] == "unexplained"]
     top = bad[0] if bad else max(anomalies, key=lambda an: (an["dv"], an["rel"]))
-    return dict(cause=top["cause"], substep=top["substep"], side=top["side"], detail=top["detail"], trail=anomalies)
+    return dict(cause=top["cause"], substep=top["substep"], side=top["side"], detail=top["detail"], trail=anomalies, **({"proof": top["proof"]} if top["cause"] == "cap" else {}))
 
 
 def fp32_chain(ms, ed: EnvData, x0: np.ndarray, ctrl: np.ndarray, nsub: int):
@@ -353,15 +436,36 @@ class DeviceSubsteps:
     """the HIP kernels, one mjx.step per launch: a second handle with ctrl_dt = sim_dt (n_substeps = 1) on the SAME lane layout and the SAME batch,
     physics only.  The whole batch is replayed, not the envs in question alone: the oct layout splits a wave's contact work by the number of box
     slots in use ANYWHERE in the wave, so an env's roundings depend on the company it keeps in its wave there (profiles/r06_wave_company.txt; quad and
-    hex do not)."""
+    hex do not).
 
-    def __init__(self, task, cfg, model, terrain, layout, n, opt: Dict[str, np.ndarray]):
+    A third handle, `lifted`, is the second one with the solver's caps lifted to LIFT_ITER x LIFT_LS (pgtt_create takes 1 .. 64, the kernels read them
+    at run time): whenever some requested env of a substep stopped at the iteration cap, the whole batch's INPUT state of that substep is copied into it
+    and it is launched once - every record of that substep then carries `qacc_lifted` / `niter_lifted`, what the device answers to the same question
+    without the cap (prove_cap).  It only ever reads the capped handle's state; nothing of it flows back into the capped sequence."""
+
+    def __init__(self, task, cfg, model, terrain, layout, n, opt: Dict[str, np.ndarray], lifted: bool = True, lift_all: bool = False):
         import torch
         from phase_guided_terrain_traversal_amd.env import Joystick
         cfg = dict(cfg)
         cfg["ctrl_dt"] = cfg["sim_dt"]
         kw = {kk: torch.from_numpy(np.ascontiguousarray(v)) for kk, v in opt.items()}
         self.env = Joystick(task, cfg, num_envs=n, terrain=terrain, device="cuda:0", debug_contacts=True, layout=layout, model=model, **kw)
+        self.iterations, self.launches = int(self.env.model["iterations"]), 0
+        self.lifted, self.lift_all = None, lift_all                         # lift_all: every substep, cut or not (audit_lifted)
+        if lifted:
+            kw = {kk: torch.from_numpy(np.ascontiguousarray(v)) for kk, v in opt.items()}        # its own copies of the DR rows
+            self.lifted = Joystick(task, cfg, num_envs=n, terrain=terrain, device="cuda:0", debug_contacts=True, layout=layout,
+                                   model=dict(self.env.model, iterations=LIFT_ITER, ls_iterations=LIFT_LS), **kw)
+
+    def lift(self, S_in, a) -> tuple:
+        """ONE launch of the lifted handle on the whole batch from the state rows S_in (a device tensor the capped handle no longer writes) ->
+        (qacc [18][N], niter [N])"""
+        import torch
+        self.lifted.buffers["state"].copy_(S_in)
+        self.lifted.physics(a)
+        torch.cuda.synchronize()
+        self.launches += 1
+        return self.lifted.buffers["state"][37:55].cpu().numpy(), self.lifted.buffers["dbg_niter"].cpu().numpy() & 0xFFFF
 
     def __call__(self, cols: np.ndarray, S0: np.ndarray, act: np.ndarray, ctrl: np.ndarray, nsub: int) -> List[List[Dict]]:
         import torch
@@ -370,25 +474,42 @@ class DeviceSubsteps:
         a = torch.from_numpy(np.ascontiguousarray(act)).cuda()
         out = [[] for _ in cols]
         for _ in range(nsub):
+            S_in = env.buffers["state"].clone() if self.lifted is not None else None
             env.physics(a)
             torch.cuda.synchronize()
             st = env.buffers["state"][:55].cpu().numpy()
             con, dist, ni = env.buffers["dbg_contact"].cpu().numpy(), env.buffers["dbg_dist"].cpu().numpy(), env.buffers["dbg_niter"].cpu().numpy() & 0xFFFF
+            ql = nl = None
+            if self.lifted is not None and len(cols) and (self.lift_all or (ni[np.asarray(cols)] >= self.iterations).any()):
+                ql, nl = self.lift(S_in, a)
             for i, e in enumerate(cols):
-                out[i].append(dict(qpos=st[:19, e].copy(), qvel=st[19:37, e].copy(), qacc=st[37:55, e].copy(), niter=int(ni[e]), con=con[e].copy(), dist=dist[e].copy()))
+                out[i].append(dict(qpos=st[:19, e].copy(), qvel=st[19:37, e].copy(), qacc=st[37:55, e].copy(), niter=int(ni[e]), con=con[e].copy(), dist=dist[e].copy(),
+                                   **({} if ql is None else dict(qacc_lifted=ql[:, e].copy(), niter_lifted=int(nl[e])))))
         return out
 
     def close(self):
         self.env.close()
+        if self.lifted is not None:
+            self.lifted.close()
 
 
 class OracleSubsteps:
     """CPU stand-in for the device (tests/test_parity_explain.py): another fp32 build of the oracle (-O3 -march=native: FMA contraction, other
-    vectorisation), one mjx.forward + Euler per substep"""
+    vectorisation), one mjx.forward + Euler per substep; and once more from the same input with the caps lifted to LIFT_ITER x LIFT_LS in the same
+    library (`qacc_lifted`, `niter_lifted`: DeviceSubsteps' lifted handle)"""
 
     def __init__(self, libpath: Optional[str], ms: abi.PgttModel, get_env_data: Callable[[int], EnvData]):
         self.L = C.CDLL(libpath) if libpath else None
         self.ms, self.get = ms, get_env_data
+        self.ms_lifted = model_copy(ms, iterations=LIFT_ITER, ls_iterations=LIFT_LS)
+
+    def substep(self, ed: EnvData, qpos, qvel, ctrl, warm) -> Dict:
+        kw = dict(boxes=ed.boxes, box_friction=ed.box_friction, params=ed.params, fp64=False, lib=self.L)
+        D = oracle.forward(self.ms, qpos, qvel, ctrl, warm, **kw)
+        Dl = oracle.forward(self.ms_lifted, qpos, qvel, ctrl, warm, **kw)
+        return dict(qpos=D["qpos_next"].astype(np.float32), qvel=D["qvel_next"].astype(np.float32), qacc=D["qacc"].astype(np.float32), niter=int(D["niter"]),
+                    con=np.stack([D["con_foot"], D["con_box"]], 1), dist=D["con_dist"].astype(np.float32),
+                    qacc_lifted=Dl["qacc"].astype(np.float32), niter_lifted=int(Dl["niter"]))
 
     def __call__(self, cols, S0, act, ctrl, nsub):
         out = []
@@ -398,11 +519,9 @@ class OracleSubsteps:
             qpos, qvel, warm = (S0[:19, e].astype(np.float64), S0[19:37, e].astype(np.float64), S0[37:55, e].astype(np.float64))
             subs = []
             for _ in range(nsub):
-                D = oracle.forward(self.ms, qpos, qvel, ctrl[:, e].astype(np.float64), warm, boxes=ed.boxes, box_friction=ed.box_friction, params=ed.params, fp64=False, lib=self.L)
-                con = np.stack([D["con_foot"], D["con_box"]], 1)
-                subs.append(dict(qpos=D["qpos_next"].astype(np.float32), qvel=D["qvel_next"].astype(np.float32), qacc=D["qacc"].astype(np.float32),
-                                 niter=int(D["niter"]), con=con, dist=D["con_dist"].astype(np.float32)))
-                qpos, qvel, warm = D["qpos_next"], D["qvel_next"], D["qacc"]
+                sub = self.substep(ed, qpos, qvel, ctrl[:, e].astype(np.float64), warm)
+                subs.append(sub)
+                qpos, qvel, warm = sub["qpos"].astype(np.float64), sub["qvel"].astype(np.float64), sub["qacc"].astype(np.float64)      # the fp32 build's outputs ARE floats
             out.append(subs)
         return out
 
@@ -427,6 +546,8 @@ class Ledger:
         out = {c: self.count(c) for c in ("cap", "floor", "sign", "tie", "unstable", "edge", "unexplained")}
         out["violations"] = len(self.records)
         out["cap_side"] = {side: sum(1 for r in self.records if r["cause"] == "cap" and r.get("side") == side) for side in ("device", "fp32 oracle", "fp64 oracle")}
+        # how each `cap` was shown to be one (prove_cap; "reference": the largest anomaly of the env-step is a cut on an oracle side)
+        out["cap_proof"] = {p: sum(1 for r in self.records if r["cause"] == "cap" and r.get("proof") == p) for p in PROOFS}
         return out
 
     def unexplained(self) -> List[Dict]:
@@ -452,7 +573,7 @@ def explain_step(ledger: Ledger, k: int, viol_envs: np.ndarray, viol_keys: Dict[
             ledger.add(step=k, env=e, keys=keys, cause="unexplained", substep=-1, side="fp32 oracle", detail="replay: the oracle's one-substep calls do not reproduce its own control step", trail=None)
             continue
         ed = env_data(hb, terrain, e)
-        v = explain_physics(ms, ed, S0[:55, e], ctrl_rows[:, e].astype(np.float64), dev[i], None if skip else final_dev_rows[:, e], orc[i])
+        v = explain_physics(ms, ed, S0[:55, e], ctrl_rows[:, e].astype(np.float64), dev[i], None if skip else final_dev_rows[:, e], orc[i], seed=1000 * k + 4 * e)
         if v["cause"] == "none" and "scan" in keys and scan_ctx is not None and not skip and not [kk for kk in keys if kk in PHYS_KEYS]:
             # physics identical to rounding on both sides; the scan differs: a ray on the edge of a box?
             spread = scan_ensemble(scan_ctx["cs"], ed, hb["state"][:19, e], final_dev_rows[:19, e], seed=1000 * k + e)
