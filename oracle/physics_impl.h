@@ -641,7 +641,10 @@ static void F(kbi)(const PgttModel* m, const R* solref, const R* solimp, R pos, 
   R imp_b = 1 - (1 / POW(1 - mid, power - 1))*POW(1 - imp_x, power);
   R imp_y = imp_x < mid ? imp_a : imp_b;
   R imp = dmin + imp_y*(dmax - dmin);
-  imp = imp < dmin ? dmin : (imp > dmax ? dmax : imp);
+  /* jp.clip(imp, dmin, dmax) = min(max(imp, dmin), dmax): with d0 > dwidth (no shipped model) the upper bound wins and imp = dmax, as in the
+     kernels' kbi(); an if / else-if chain would give dmin there (MJX itself was not at hand to confirm) */
+  imp = imp < dmin ? dmin : imp;
+  imp = imp > dmax ? dmax : imp;
   if (imp_x > 1) imp = dmax;
   *k_out = k; *b_out = b; *imp_out = imp;
 }

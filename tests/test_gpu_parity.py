@@ -350,10 +350,11 @@ def test_one_substep_launches_reproduce_the_control_step(layout):
         env.close()
 
 
-def audit_rollout(task, ter, dr, n, steps, layout, method="pgtt", min_minimiser=0.7, min_cut=50):
+def audit_rollout(task, ter, dr, n, steps, layout, method="pgtt", min_minimiser=0.7, min_cut=50, model=None):
     """the device's every substep along a rollout through parity_explain.audit_control_step -> tally of verdicts (asserts: none unexplained, the replay
-    reproduces the control step's bits, and the quality bar on the solves both sides cut)"""
-    env, hb, cs, ms = make_pair(task, n, ter, dr=dr, method=method)
+    reproduces the control step's bits, and the quality bar on the solves both sides cut).  `model`: another PgttModel dict than the task's (make_pair and
+    DeviceSubsteps take it from there); the lifted-caps variant for the solver-parameter models is tests/test_gpu_solver_params.py::run_case"""
+    env, hb, cs, ms = make_pair(task, n, ter, dr=dr, method=method, model=model)
     env.reset(3)
     rng = np.random.default_rng(4)
     for _ in range(12):                                                      # the landing
@@ -784,10 +785,13 @@ def test_config_values_are_read_not_assumed(method):
 
 
 def perturbed_model(task, axes=False, seed=9):
-    """PgttModel with every numeric field moved off the Go2's values (what a different MJCF of the same topology would compile to): link offsets, inertial
+    """PgttModel with the numeric fields moved off the Go2's values (what a different MJCF of the same topology would compile to): link offsets, inertial
     frames, masses, inertias, joint ranges (narrow: limit rows become active), joint and geom solver parameters, armature, damping, actuator gains / bias /
     ranges (tight force range: clipping becomes active), foot geometry, imu and foot sites, frictions, margins, a tilted gravity, impratio, solver tolerances
-    and iteration counts, the collision cuts (max_geom_pairs 17, max_contact_points 3), another keyframe"""
+    and iteration counts, the collision cuts (max_geom_pairs 17, max_contact_points 3), another keyframe.
+    LEFT AT THEIR DEFAULTS: the midpoint and power of all four solimp vectors (0.5, 2.0: kbi()'s power == 2 branch), and every solref stays in the standard
+    form above 2 dt with solmix weights well above mjMINVAL - the general power, the direct forms, the `min` rule, the mjMINVAL weights and the clamps are
+    tests/solver_param_cases.py and tests/test_gpu_solver_params.py"""
     m = {k: (np.array(v, dtype=np.float64, copy=True) if isinstance(v, (list, np.ndarray)) else v) for k, v in mjcf.load_model(task).items()}
     r = np.random.default_rng(seed)
     sc = lambda a, rel: np.asarray(a, np.float64) * (1 + r.uniform(-rel, rel, np.shape(a)))
@@ -822,8 +826,9 @@ def perturbed_model(task, axes=False, seed=9):
 
 @pytest.mark.parametrize("task", ["stairs", "flat_terrain"])
 def test_model_values_are_read_not_assumed(layout, task):
-    """the kernels take the robot from PgttModel, not from constants: a model of the same topology with EVERY numeric field changed (perturbed_model) goes
-    through the parity bar, oracle and kernels reading the same struct - narrow joint ranges and tight force ranges make limit rows and actuator clipping
+    """the kernels take the robot from PgttModel, not from constants: a model of the same topology with its numeric fields changed (perturbed_model; all but
+    solimp's midpoint and power, which keep 0.5 and 2.0, and with every solver parameter inside its standard range - those branches are held by
+    tests/test_gpu_solver_params.py) goes through the parity bar, oracle and kernels reading the same struct - narrow joint ranges and tight force ranges make limit rows and actuator clipping
     active, 6 Newton / 7 line-search iterations, max_geom_pairs = 17 and max_contact_points = 3 move every cut of the solver and the collision stage"""
     terrain = np.load(os.path.join(ASSETS, "terrains", "level4.npy")) if task == "stairs" else None
     st = run_parity(task, 128, terrain, steps=24, model=perturbed_model(task, axes=True), w_floor=0.55, cap_scale=2.0, med_tol=4e-6)        # hinge axes tilted by ~5 degrees too

@@ -1,7 +1,9 @@
 """The post-mortem of tests/parity_explain.py on the CPU, with NO GPU code involved: the "device" is the oracle's own -O3 -march=native fp32 build
 (FMA contraction, other vectorisation - a second fp32 evaluation of the same step, as the HIP kernels are), the oracle its portable fp32 build, the
 reference point its fp64 build.  Every env-step of W on which the two fp32 builds end up further apart than the bar must be explained by the
-5-iteration cut or by a contact distance within rounding of 0 - the statement tests/test_gpu_parity.py makes about the HIP kernels."""
+5-iteration cut or by a contact distance within rounding of 0 - the statement tests/test_gpu_parity.py makes about the HIP kernels.  At the end: the
+solver-parameter cases of tests/solver_param_cases.py through the lifted-caps audit, the source of the shares tests/test_gpu_solver_params.py holds the
+kernels to, and the negative control with the stand-in built from each case's twin model."""
 import ctypes as C
 import os
 import subprocess
@@ -271,3 +273,84 @@ def test_a_replay_that_misses_the_control_step_by_one_ulp_is_unexplained():
             off[row] = np.nextafter(off[row], np.float32(np.inf))
             v = X.explain_physics(ms, get(e), S0[:55, e], ctrl[:, e].astype(np.float64), dev[e], off)
             assert v["cause"] == "unexplained" and v["detail"].startswith("replay: one-substep launches do not reproduce the control step"), v
+
+
+# ---------------------------------------------------------------------------------------------------------------- the solver-parameter cases
+import solver_param_cases as SP
+
+SP_ENVS, SP_STEPS, SP_CRAFTED = 32, 3, 44             # the sizes of tests/test_gpu_solver_params.py: 4 x 32 x 3 + 44 = 428 solves
+
+
+def solver_case_audit(task, case, twin_device=False, n=SP_ENVS, steps=SP_STEPS, n_crafted=SP_CRAFTED):
+    """tests/test_gpu_solver_params.py on the CPU: the lifted-caps audit (X.audit_lifted) of the stand-in device on the case's model - every substep of
+    n envs x `steps` control steps after the landing, then ONE mjx.step from the crafted batch - with the judge holding the case's model and the
+    stand-in built from it, or (twin_device) from the TWIN: a device that ignored the parameter under test.
+    -> records {cause, niter, crafted, binding: the (kind, x, mid) of the rows with efc_force > 0 at a*}"""
+    fastpath = fast_build()
+    m = SP.model(task, case)
+    cs, ms, terrain, a, rng = SP.landed(task, m, max(n, n_crafted))
+    ms_dev = ms if not twin_device else abi.model_struct(SP.model(task, case, twin=True))
+    get = lambda e: X.env_data(a, terrain, e)
+    subs = X.OracleSubsteps(fastpath, ms_dev, get)
+    out = []
+
+    def judge(S0, ctrl, dev, cols, seed, crafted):
+        recs = X.audit_lifted(ms, a, terrain, S0, ctrl, dev, cols, seed=seed)
+        for r in recs:
+            i, s_ = int(r["env"]), r["substep"]
+            out.append(dict(r, crafted=crafted, binding=SP.binding_rows(ms, m, get(i), SP.substep_input(S0, dev, i, i, s_), ctrl[:, i].astype(np.float64))))
+
+    Sc, actc = SP.crafted(ms, m, a["state"][:, :n_crafted], get, n_crafted)
+    cols = np.arange(n_crafted)
+    ctrl = SP.motor_targets(m, actc)
+    judge(Sc, ctrl, subs(cols, Sc, actc, ctrl, 1), cols, 77, True)
+    cols = np.arange(n)
+    for k in range(steps):
+        S0 = a["state"].copy()
+        act = np.tanh(rng.normal(size=(a.n, 12)) * 0.6).astype(np.float32)
+        step_with(oracle.lib(), cs, ms, terrain, a, act)
+        ctrl = a["state"][abi.S_MOTOR_TARGETS:abi.S_MOTOR_TARGETS + 12]
+        judge(S0, ctrl, subs(cols, S0, act, ctrl, 4), cols, 1000 * k, False)
+    return out
+
+
+def share_of(recs):
+    return sum(r["cause"] in ("minimiser", "floor") for r in recs) / len(recs)
+
+
+def twin_rejection(recs, affected):
+    """(solves with a BINDING row of an affected kind, those of them that end `unexplained`)"""
+    hit = [r for r in recs if any(kind in affected for kind, _, _ in r["binding"])]
+    return len(hit), sum(r["cause"] == "unexplained" for r in hit)
+
+
+SP_PAIRS = [(c, t) for c in SP.CASES for t in ("stairs", "flat_terrain")]
+
+
+@pytest.mark.parametrize("case,task", SP_PAIRS)
+def test_solver_parameter_cases_on_the_stand_in(case, task):
+    """every solver-parameter case of tests/solver_param_cases.py through the lifted-caps audit on the stand-in device, level4 and flat, rollout and crafted
+    batch: every verdict is one of LIFTED_OK, no solve runs LIFT_ITER iterations and stays off a*.  The printed minimiser + floor share is what
+    tests/test_gpu_solver_params.py holds the kernels to (SP.STAND_IN_SHARE; a value measured here may not fall below the recorded one by more than the
+    two points the GPU test grants: then the record, not the kernel, is out of date)"""
+    recs = solver_case_audit(task, case)
+    tally = {}
+    for r in recs:
+        tally[r["cause"]] = tally.get(r["cause"], 0) + 1
+        assert r["cause"] in LIFTED_OK, (case, task, r)
+        assert r["niter"] < X.LIFT_ITER or r["cause"] in ("minimiser", "floor"), (case, task, r)
+    nb = sum(1 for r in recs if r["binding"])
+    print(f"\n[{case} {task}] lifted audit of {len(recs)} solves ({nb} with binding rows):", tally, f"; minimiser + floor: {share_of(recs):.4f} (recorded {SP.STAND_IN_SHARE[case, task]:.4f})")
+    assert len(recs) == 4 * SP_ENVS * SP_STEPS + SP_CRAFTED
+    assert share_of(recs) >= SP.STAND_IN_SHARE[case, task] - 0.02
+
+
+@pytest.mark.parametrize("case,task", [p for p in SP_PAIRS if p != ("solmix_b", "flat_terrain")])       # solmix_b changes the box pair alone: the flat task has none
+def test_a_device_that_ignores_the_parameter_is_rejected(case, task):
+    """the negative control: the stand-in device is built from the case's TWIN - the same model with only the parameter under test put back to its neutral
+    value, what a kernel that ignored it (for `power`: one that kept the power == 2 arithmetic) would compute with - while the judge keeps the case's model.
+    At least half of the solves with a BINDING row (efc_force > 0 at a*, fp64) of a kind the case affects end `unexplained` (measured: 90.7 - 99.3 %)"""
+    recs = solver_case_audit(task, case, twin_device=True)
+    nh, nu = twin_rejection(recs, SP.CASES[case]["affected"])
+    print(f"\n[{case} {task}] twin as the device: {nh} of {len(recs)} solves have a binding row of {SP.CASES[case]['affected']}, {nu} of them unexplained ({nu / max(nh, 1):.1%})")
+    assert nh >= 40 and nu >= 0.5 * nh, (case, task, nh, nu)
