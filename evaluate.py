@@ -12,7 +12,8 @@ final `termination` reward term is zero (:221-223), i.e. the robots that did not
 is built.  The policy comes from `--checkpoint_folder` (the newest `<env_steps>.pt` of `train.py`, or its `policy<index>.npz`) or from
 `--policy` (an .npz path or the name of a shipped policy); with `--student student.npz` (train_student.py) the policy acts on the observation
 whose scan rows the student perception module estimated from the onboard depth image, with `--elevation [grid,res,alpha]` on the observation whose
-scan rows are sampled from the depth-fused elevation map (elevation.py; nothing to train); the remaining flags of the reference's CLI are accepted and ignored.
+scan rows are sampled from the depth-fused elevation map (elevation.py; nothing to train; `--elevation_source lidar` fuses it from the onboard
+LiDAR's points instead, lidar.py); the remaining flags of the reference's CLI are accepted and ignored.
 """
 import argparse
 import os
@@ -157,7 +158,14 @@ def run_evaluation(args, num_eval_envs=NUM_EVAL_ENVS, seed=0, verbose=True):
             given = dict(zip(("grid", "res", "alpha"), (int(vals[0]),) + tuple(float(v) for v in vals[1:]))) if vals else True
         except ValueError:
             raise SystemExit(f"--elevation {elev}: grid must be an integer, res and alpha numbers")
-        kw.update(depth={}, elevation=given)
+        source = getattr(args, "elevation_source", "depth")
+        if source == "lidar":
+            # --elevation_source lidar: the map is fused from the world points of the onboard LiDAR (lidar.DEFAULTS), as the deployed mapping stack's is
+            kw.update(lidar={}, elevation=dict({} if given is True else given, source="lidar"))
+        else:
+            kw.update(depth={}, elevation=given)
+    elif getattr(args, "elevation_source", "depth") != "depth":
+        raise SystemExit("--elevation_source says what --elevation is fused from: give --elevation too")
     env = Joystick(args.task_name, cfg, num_envs=n, terrain=terrain, device=DEVICE, autoreset=True, **kw)
     if env.elevation_map is not None:
         acts_on = env.elevation_obs
@@ -175,10 +183,13 @@ def run_evaluation(args, num_eval_envs=NUM_EVAL_ENVS, seed=0, verbose=True):
     first = torch.ones(n, dtype=torch.bool, device=dev)                           # still inside its first episode
     ret = torch.zeros(n, device=dev); length = torch.zeros(n, device=dev); fell = torch.zeros(n, dtype=torch.bool, device=dev)
     terms = torch.zeros(abi.NMETRIC, n, device=dev)
+    known = torch.zeros(n, device=dev)                                            # with a map: the scan points it knew, summed over the first episode
     video = VideoRecorder(args, env, L) if getattr(args, "video", None) else None
     for t in range(L):
         if video is not None:
             video.capture(t)
+        if env.elevation_map is not None:
+            known += env.elevation_known.float().mean(1) * first.float()
         _, reward, done, info = env.step(pi(acts_on))
         w = first.float()
         ret += reward * w; length += w; terms += info["metrics"] * w
@@ -190,6 +201,8 @@ def run_evaluation(args, num_eval_envs=NUM_EVAL_ENVS, seed=0, verbose=True):
     sc = cfg["reward_config"]["scales"]
     out = {"survivors": survivors, "num_eval_envs": n, "episode_reward": float(ret.mean()), "avg_episode_length": float(length.mean()),
            "tracking_lin_vel": float(terms[i_lin].mean()) / (sc["tracking_lin_vel"] * L), "tracking_ang_vel": float(terms[i_ang].mean()) / (sc["tracking_ang_vel"] * L)}
+    if env.elevation_map is not None:
+        out["known_share"] = float((known / length.clamp(min=1)).mean())          # mean share of the 117 scan points the map knew when the policy acted
     if video is not None:
         out["video"] = video.write(verbose)
     env.close()
@@ -228,6 +241,8 @@ def make_parser():
     ap.add_argument("--student", type=str, default=None, help="a student.npz of train_student.py: the policy acts on the depth camera's estimate of the scan rows")
     ap.add_argument("--elevation", type=str, nargs="?", const="", default=None, metavar="GRID,RES,ALPHA",
                     help="the policy acts on the scan rows sampled from the depth-fused elevation map (elevation.py); optional grid[,res[,alpha]]")
+    ap.add_argument("--elevation_source", type=str, default="depth", choices=("depth", "lidar"),
+                    help="with --elevation: fuse the map from the depth camera's image (default) or from the onboard LiDAR's points (lidar.py)")
     configs.add_push_args(ap)
     ap.add_argument("--terrain_files", type=str, default=None, help="comma-separated level files stacked into one table (as train.py --terrain_files); evaluated on --level")
     ap.add_argument("--level", type=int, default=0, help="with --terrain_files: the level every evaluation env stands on (no curriculum at evaluation)")

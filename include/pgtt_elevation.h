@@ -60,6 +60,17 @@
  * new episode under its own pose.  With autoreset = 0 the state rows stay the finished episode's and done[e] stays as the step's termination
  * test gives it: use_done then clears the map at every call while done[e] != 0, so it holds that call's image alone, until the caller resets the
  * env (pgtt_reset with a mask) and passes the same mask as clear_mask.
+ *
+ * A point cloud in place of the image.  pgtt_elevation_bind_points() binds, next to the buffers, `points`: device [N][P][3], WORLD points, P >= 1
+ * (the points of pgtt_lidar.h, registered at the pose they were taken from; any other source of world points will do).  pgtt_elevation_points()
+ * then runs the six steps above in the same order with step 3 replaced - for every point k < P of the env:
+ *         skipped when one of its coordinates is NaN or not finite (a ray without a return)
+ *         skipped inside the self-filter box (the test of step 3, on the point itself)
+ *         skipped when its cell is outside the window
+ *         otherwise m[cell] = max(m[cell], p.z), with the same LDS atomic on the order-preserving key
+ * The camera fields of the config (width .. mount_quat) are not read by it; they must still be valid for pgtt_elevation_create.
+ * Both sources may feed one handle: bound by pgtt_elevation_bind_points with a depth image too, pgtt_elevation() is what it is on a handle bound
+ * by pgtt_elevation_bind.
  */
 #ifndef PGTT_ELEVATION_H_
 #define PGTT_ELEVATION_H_
@@ -116,6 +127,12 @@ int pgtt_elevation_bind(pgtt_elevation_handle h, const PgttElevationBuffers* buf
 /* one tick for all N envs: one launch, one workgroup of 256 lanes per env.  clear_mask: device uint8 [N] or NULL.
  * PGTT_E_STATE before pgtt_elevation_bind. */
 int pgtt_elevation(pgtt_elevation_handle h, const uint8_t* clear_mask, int clear_all, int use_done, void* stream);
+/* As pgtt_elevation_bind, but bufs->depth may be NULL, and `points` (device [N][P][3], world frame) is required with P >= 1 (PGTT_E_ARG).
+ * pgtt_elevation_bind afterwards unbinds the points. */
+int pgtt_elevation_bind_points(pgtt_elevation_handle h, const PgttElevationBuffers* bufs, const float* points, int P);
+/* one tick for all N envs from the bound points: one launch, as pgtt_elevation().  PGTT_E_STATE before pgtt_elevation_bind_points; pgtt_elevation()
+ * on a handle bound with depth == NULL is PGTT_E_STATE too. */
+int pgtt_elevation_points(pgtt_elevation_handle h, const uint8_t* clear_mask, int clear_all, int use_done, void* stream);
 int pgtt_elevation_sizeof_config(void);
 int pgtt_elevation_sizeof_buffers(void);
 /* "src=<SHA-256 of pgtt_elevation.hip and the files it includes>;flavor=product" */

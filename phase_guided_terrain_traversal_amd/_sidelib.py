@@ -1,8 +1,8 @@
-"""What the modules of the five side libraries share - render.py (libpgtt_render.so), depth.py (libpgtt_depth.so), perceive.py
-(libpgtt_perceive.so), elevation.py (libpgtt_elevation.so) and learn.py (libpgtt_learn.so): SideLib, which loads a side library through ctypes,
+"""What the modules of the six side libraries share - render.py (libpgtt_render.so), depth.py (libpgtt_depth.so), perceive.py
+(libpgtt_perceive.so), elevation.py (libpgtt_elevation.so), learn.py (libpgtt_learn.so) and lidar.py (libpgtt_lidar.so): SideLib, which loads a side library through ctypes,
 turns its return codes into the module's exception and parses its build info; the terrain / close methods of a handle's owner; and the three env
-pointers the two ray casters read.  Imported by those modules only: env.py does not reach it unless a depth camera, a student or an elevation map
-is asked for."""
+pointers the three ray casters read.  Imported by those modules only: env.py does not reach it unless a depth camera, a LiDAR, a student or an
+elevation map is asked for."""
 from __future__ import annotations
 
 import ctypes as C

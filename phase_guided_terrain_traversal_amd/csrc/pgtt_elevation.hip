@@ -1,10 +1,13 @@
-// pgtt_elevation.hip — libpgtt_elevation.so: the depth-fused elevation map (include/pgtt_elevation.h), one launch per call.
+// pgtt_elevation.hip — libpgtt_elevation.so: the elevation map fused from a depth image or from a point cloud (include/pgtt_elevation.h), one
+// launch per call.
 //
-// elevation_kernel, one workgroup of four waves per env.  LDS holds one word per map slot, `sh_m`: first the tick maximum as an
+// elevation_kernel<POINTS>, one workgroup of four waves per env; a template on the source, so that the image instantiation (POINTS = false) holds
+// no code of the other and is what it was before there were two.  LDS holds one word per map slot, `sh_m`: first the tick maximum as an
 // order-preserving integer key (0 = no pixel fell into the slot), then, after the fuse, the slot's fused height, which the scan is sampled from.
 //   phase A  lane 0 forms the base pose, the camera pose, the yaw's sine and cosine, the new origin and writes it; the other lanes zero sh_m.
 //   phase B  lanes 0 .. 2G - 1 mark, per axis, the slot rows / columns whose world cell differs between the old and the new window.
-//   phase C  every lane unprojects pixels (16-byte runs of the image when the pixel count allows) and raises sh_m[slot] with an LDS atomic maximum.
+//   phase C  every lane unprojects pixels (16-byte runs of the image when the pixel count allows) and raises sh_m[slot] with an LDS atomic maximum;
+//            with POINTS every lane reads world points instead (the contiguous 12-byte-per-lane run) and there is no camera.
 //   phase D  the persistent map streams through: 16-byte runs from HBM, stale slots to NaN, touched slots fused, the run written back only when
 //            one of its slots changed; the fused value replaces the key in sh_m.
 //   phase E  lanes 0 .. 116 sample the scan, the minimum over the known points is a wave reduction and one LDS exchange; est, known.
@@ -31,6 +34,7 @@ struct ElevArgs {
   int N, W, H, G, obs_dim, scan_row0, clear_all, use_done, self_on, vec_map, vec_img;
   float near_m, far_m, res, alpha, tu, tv, sdx, sdy;         // tu = tan(fovy / 2) W / H, tv = tan(fovy / 2)
   float mpos[3], mquat[4], self_half[3];
+  const float* points; int P;                                // the points entry: [N][P][3] world points
 };
 
 // what lane 0 stages for the workgroup
@@ -45,6 +49,7 @@ __device__ __forceinline__ int floor_mod(int a, int g) { const int r = a % g; re
 __device__ __forceinline__ unsigned key_of(float z) { const unsigned b = __float_as_uint(z); return b ^ ((unsigned)((int)b >> 31) | 0x80000000u); }
 __device__ __forceinline__ float value_of(unsigned k) { return __uint_as_float(k ^ (((k >> 31) - 1u) | 0x80000000u)); }
 
+template <bool POINTS>
 __global__ void __launch_bounds__(kLanes) elevation_kernel(ElevArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned sh_m[];      // [G * G]
   __shared__ float sh_p[P_N];
@@ -69,18 +74,20 @@ __global__ void __launch_bounds__(kLanes) elevation_kernel(ElevArgs a) {
     sh_p[P_BASE + 0] = bx; sh_p[P_BASE + 1] = by; sh_p[P_BASE + 2] = bz;
     sh_p[P_RB + 0] = r00; sh_p[P_RB + 1] = r01; sh_p[P_RB + 2] = r02; sh_p[P_RB + 3] = r10; sh_p[P_RB + 4] = r11; sh_p[P_RB + 5] = r12;
     sh_p[P_RB + 6] = r20; sh_p[P_RB + 7] = r21; sh_p[P_RB + 8] = r22;
-    sh_p[P_CAM + 0] = bx + r00 * a.mpos[0] + r01 * a.mpos[1] + r02 * a.mpos[2];
-    sh_p[P_CAM + 1] = by + r10 * a.mpos[0] + r11 * a.mpos[1] + r12 * a.mpos[2];
-    sh_p[P_CAM + 2] = bz + r20 * a.mpos[0] + r21 * a.mpos[1] + r22 * a.mpos[2];
-    // camera = base * mount; fwd = its +x, up = its +z, right = fwd x up
-    const float mw = a.mquat[0], mx = a.mquat[1], my = a.mquat[2], mz = a.mquat[3];
-    const float cw = qw * mw - qx * mx - qy * my - qz * mz, cx = qw * mx + qx * mw + qy * mz - qz * my;
-    const float cyq = qw * my - qx * mz + qy * mw + qz * mx, cz = qw * mz + qx * my - qy * mx + qz * mw;
-    const float fx = cw * cw + cx * cx - cyq * cyq - cz * cz, fy = 2.f * (cx * cyq + cw * cz), fz = 2.f * (cx * cz - cw * cyq);
-    const float ux = 2.f * (cx * cz + cw * cyq), uy = 2.f * (cyq * cz - cw * cx), uz = cw * cw - cx * cx - cyq * cyq + cz * cz;
-    sh_p[P_FWD + 0] = fx; sh_p[P_FWD + 1] = fy; sh_p[P_FWD + 2] = fz;
-    sh_p[P_UP + 0] = ux; sh_p[P_UP + 1] = uy; sh_p[P_UP + 2] = uz;
-    sh_p[P_RIGHT + 0] = fy * uz - fz * uy; sh_p[P_RIGHT + 1] = fz * ux - fx * uz; sh_p[P_RIGHT + 2] = fx * uy - fy * ux;
+    if constexpr (!POINTS) {
+      sh_p[P_CAM + 0] = bx + r00 * a.mpos[0] + r01 * a.mpos[1] + r02 * a.mpos[2];
+      sh_p[P_CAM + 1] = by + r10 * a.mpos[0] + r11 * a.mpos[1] + r12 * a.mpos[2];
+      sh_p[P_CAM + 2] = bz + r20 * a.mpos[0] + r21 * a.mpos[1] + r22 * a.mpos[2];
+      // camera = base * mount; fwd = its +x, up = its +z, right = fwd x up
+      const float mw = a.mquat[0], mx = a.mquat[1], my = a.mquat[2], mz = a.mquat[3];
+      const float cw = qw * mw - qx * mx - qy * my - qz * mz, cx = qw * mx + qx * mw + qy * mz - qz * my;
+      const float cyq = qw * my - qx * mz + qy * mw + qz * mx, cz = qw * mz + qx * my - qy * mx + qz * mw;
+      const float fx = cw * cw + cx * cx - cyq * cyq - cz * cz, fy = 2.f * (cx * cyq + cw * cz), fz = 2.f * (cx * cz - cw * cyq);
+      const float ux = 2.f * (cx * cz + cw * cyq), uy = 2.f * (cyq * cz - cw * cx), uz = cw * cw - cx * cx - cyq * cyq + cz * cz;
+      sh_p[P_FWD + 0] = fx; sh_p[P_FWD + 1] = fy; sh_p[P_FWD + 2] = fz;
+      sh_p[P_UP + 0] = ux; sh_p[P_UP + 1] = uy; sh_p[P_UP + 2] = uz;
+      sh_p[P_RIGHT + 0] = fy * uz - fz * uy; sh_p[P_RIGHT + 1] = fz * ux - fx * uz; sh_p[P_RIGHT + 2] = fx * uy - fy * ux;
+    }
     const float yaw = atan2f(2.0f * (qw * qz + qx * qy), 1.0f - 2.0f * (qy * qy + qz * qz));
     float sy, cy; sincosf(yaw, &sy, &cy);
     sh_p[P_SY] = sy; sh_p[P_CY] = cy;
@@ -108,7 +115,27 @@ __global__ void __launch_bounds__(kLanes) elevation_kernel(ElevArgs a) {
   }
 
   // ---- phase C: the tick maximum
-  {
+  if constexpr (POINTS) {
+    const float bpx = uni(sh_p[P_BASE + 0]), bpy = uni(sh_p[P_BASE + 1]), bpz = uni(sh_p[P_BASE + 2]);
+    const float b00 = uni(sh_p[P_RB + 0]), b01 = uni(sh_p[P_RB + 1]), b02 = uni(sh_p[P_RB + 2]), b10 = uni(sh_p[P_RB + 3]), b11 = uni(sh_p[P_RB + 4]);
+    const float b12 = uni(sh_p[P_RB + 5]), b20 = uni(sh_p[P_RB + 6]), b21 = uni(sh_p[P_RB + 7]), b22 = uni(sh_p[P_RB + 8]);
+    const int lox = sh_i[I_LOX], loy = sh_i[I_LOY], lmx = sh_i[I_LMX], lmy = sh_i[I_LMY];
+    const float* pts = a.points + (long)e * a.P * 3;
+    for (int k = tid; k < a.P; k += kLanes) {
+      const float px = pts[3 * k], py = pts[3 * k + 1], pz = pts[3 * k + 2];
+      if (!(fabsf(px) < INFINITY && fabsf(py) < INFINITY && fabsf(pz) < INFINITY)) continue;      // a NaN (no return) or a non-finite coordinate
+      if (a.self_on) {
+        const float dx = px - bpx, dy = py - bpy, dz = pz - bpz;             // R^T (p - base)
+        const float lx = b00 * dx + b10 * dy + b20 * dz, ly = b01 * dx + b11 * dy + b21 * dz, lz = b02 * dx + b12 * dy + b22 * dz;
+        if (fabsf(lx) <= a.self_half[0] && fabsf(ly) <= a.self_half[1] && fabsf(lz) <= a.self_half[2]) continue;
+      }
+      const int relx = cell_of(px, a.res) - lox, rely = cell_of(py, a.res) - loy;
+      if ((unsigned)relx >= (unsigned)G || (unsigned)rely >= (unsigned)G) continue;
+      int sx = relx + lmx, sy = rely + lmy;                            // (lo + rel) mod G
+      sx -= sx >= G ? G : 0; sy -= sy >= G ? G : 0;
+      atomicMax(&sh_m[sx * G + sy], key_of(pz));
+    }
+  } else {
     const float cpx = sh_p[P_CAM + 0], cpy = sh_p[P_CAM + 1], cpz = sh_p[P_CAM + 2];
     const float fx = sh_p[P_FWD + 0], fy = sh_p[P_FWD + 1], fz = sh_p[P_FWD + 2];
     const float rx = sh_p[P_RIGHT + 0], ry = sh_p[P_RIGHT + 1], rz = sh_p[P_RIGHT + 2];
@@ -270,7 +297,48 @@ struct pgtt_elevation_map {
   PgttElevationConfig cfg{};
   PgttElevationBuffers buf{};
   bool bound = false;
+  const float* points = nullptr;         // pgtt_elevation_bind_points; nullptr after pgtt_elevation_bind
+  int P = 0;
 };
+
+namespace {
+
+// what both bind calls ask of the buffers but the source
+int check_buffers(const PgttElevationBuffers* bufs, const char* who) {
+  const std::string p = std::string(who) + ": ";
+  if (!bufs->state || !bufs->map || !bufs->origin || !bufs->est || !bufs->known) return fail(PGTT_E_ARG, p + "state, map, origin, est and known are required");
+  if (bufs->obs_out && !bufs->obs) return fail(PGTT_E_ARG, p + "obs is required with obs_out");
+  return PGTT_OK;
+}
+
+// one tick from the image (points = false) or from the bound points
+int launch(pgtt_elevation_map* h, bool points, const uint8_t* clear_mask, int clear_all, int use_done, void* stream) {
+  HIP_TRY(hipSetDevice(h->device));
+  const PgttElevationConfig& c = h->cfg;
+  const PgttElevationBuffers& b = h->buf;
+  ElevArgs a{};
+  a.state = b.state; a.depth = b.depth; a.obs = b.obs; a.done = b.done; a.clear_mask = clear_mask;
+  a.map = b.map; a.origin = b.origin; a.est = b.est; a.known = b.known; a.obs_out = b.obs_out;
+  a.N = h->num_envs; a.W = c.width; a.H = c.height; a.G = c.grid; a.obs_dim = c.obs_dim; a.scan_row0 = c.scan_row0;
+  a.clear_all = clear_all ? 1 : 0; a.use_done = use_done ? 1 : 0;
+  a.self_on = (c.self_half[0] != 0.f || c.self_half[1] != 0.f || c.self_half[2] != 0.f) ? 1 : 0;
+  // 16-byte runs need every env's block to start on a 16-byte boundary
+  a.vec_map = ((c.grid * c.grid) % 4 == 0 && ((uintptr_t)b.map & 15) == 0) ? 1 : 0;
+  a.vec_img = ((c.width * c.height) % 4 == 0 && ((uintptr_t)b.depth & 15) == 0) ? 1 : 0;
+  const double th = std::tan(0.5 * (double)c.fovy_deg * 3.14159265358979323846 / 180.0);
+  a.near_m = c.near; a.far_m = c.far; a.res = c.res; a.alpha = c.alpha; a.tu = (float)(th * c.width / c.height); a.tv = (float)th;
+  a.sdx = c.scan_dist_x; a.sdy = c.scan_dist_y;
+  for (int i = 0; i < 3; i++) { a.mpos[i] = c.mount_pos[i]; a.self_half[i] = c.self_half[i]; }
+  for (int i = 0; i < 4; i++) a.mquat[i] = c.mount_quat[i];
+  a.points = h->points; a.P = h->P;
+  const size_t lds = (size_t)c.grid * c.grid * sizeof(unsigned);
+  if (points) hipLaunchKernelGGL(elevation_kernel<true>, dim3(h->num_envs), dim3(kLanes), lds, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL(elevation_kernel<false>, dim3(h->num_envs), dim3(kLanes), lds, (hipStream_t)stream, a);
+  HIP_TRY(hipGetLastError());
+  return PGTT_OK;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -308,32 +376,31 @@ int pgtt_elevation_bind(pgtt_elevation_handle h, const PgttElevationBuffers* buf
   if (bufs->obs_out && !bufs->obs) return fail(PGTT_E_ARG, "pgtt_elevation_bind: obs is required with obs_out");
   h->buf = *bufs;
   h->bound = true;
+  h->points = nullptr; h->P = 0;
+  return PGTT_OK;
+}
+
+int pgtt_elevation_bind_points(pgtt_elevation_handle h, const PgttElevationBuffers* bufs, const float* points, int P) {
+  if (!h || !bufs) return fail(PGTT_E_ARG, "pgtt_elevation_bind_points: null argument");
+  if (int rc = check_buffers(bufs, "pgtt_elevation_bind_points")) return rc;
+  if (!points || P < 1) return fail(PGTT_E_ARG, "pgtt_elevation_bind_points: points is required, with P >= 1");
+  h->buf = *bufs;
+  h->bound = true;
+  h->points = points; h->P = P;
   return PGTT_OK;
 }
 
 int pgtt_elevation(pgtt_elevation_handle h, const uint8_t* clear_mask, int clear_all, int use_done, void* stream) {
   if (!h) return fail(PGTT_E_ARG, "pgtt_elevation: null handle");
   if (!h->bound) return fail(PGTT_E_STATE, "pgtt_elevation: no buffers bound (pgtt_elevation_bind first)");
-  HIP_TRY(hipSetDevice(h->device));
-  const PgttElevationConfig& c = h->cfg;
-  const PgttElevationBuffers& b = h->buf;
-  ElevArgs a{};
-  a.state = b.state; a.depth = b.depth; a.obs = b.obs; a.done = b.done; a.clear_mask = clear_mask;
-  a.map = b.map; a.origin = b.origin; a.est = b.est; a.known = b.known; a.obs_out = b.obs_out;
-  a.N = h->num_envs; a.W = c.width; a.H = c.height; a.G = c.grid; a.obs_dim = c.obs_dim; a.scan_row0 = c.scan_row0;
-  a.clear_all = clear_all ? 1 : 0; a.use_done = use_done ? 1 : 0;
-  a.self_on = (c.self_half[0] != 0.f || c.self_half[1] != 0.f || c.self_half[2] != 0.f) ? 1 : 0;
-  // 16-byte runs need every env's block to start on a 16-byte boundary
-  a.vec_map = ((c.grid * c.grid) % 4 == 0 && ((uintptr_t)b.map & 15) == 0) ? 1 : 0;
-  a.vec_img = ((c.width * c.height) % 4 == 0 && ((uintptr_t)b.depth & 15) == 0) ? 1 : 0;
-  const double th = std::tan(0.5 * (double)c.fovy_deg * 3.14159265358979323846 / 180.0);
-  a.near_m = c.near; a.far_m = c.far; a.res = c.res; a.alpha = c.alpha; a.tu = (float)(th * c.width / c.height); a.tv = (float)th;
-  a.sdx = c.scan_dist_x; a.sdy = c.scan_dist_y;
-  for (int i = 0; i < 3; i++) { a.mpos[i] = c.mount_pos[i]; a.self_half[i] = c.self_half[i]; }
-  for (int i = 0; i < 4; i++) a.mquat[i] = c.mount_quat[i];
-  hipLaunchKernelGGL(elevation_kernel, dim3(h->num_envs), dim3(kLanes), (size_t)c.grid * c.grid * sizeof(unsigned), (hipStream_t)stream, a);
-  HIP_TRY(hipGetLastError());
-  return PGTT_OK;
+  if (!h->buf.depth) return fail(PGTT_E_STATE, "pgtt_elevation: the handle was bound without a depth image (pgtt_elevation_bind_points with depth == NULL)");
+  return launch(h, false, clear_mask, clear_all, use_done, stream);
+}
+
+int pgtt_elevation_points(pgtt_elevation_handle h, const uint8_t* clear_mask, int clear_all, int use_done, void* stream) {
+  if (!h) return fail(PGTT_E_ARG, "pgtt_elevation_points: null handle");
+  if (!h->points) return fail(PGTT_E_STATE, "pgtt_elevation_points: no points bound (pgtt_elevation_bind_points first)");
+  return launch(h, true, clear_mask, clear_all, use_done, stream);
 }
 
 }  // extern "C"

@@ -1,0 +1,417 @@
+// pgtt_lidar.hip — libpgtt_lidar.so: the scanning range sensor (include/pgtt_lidar.h), one workgroup per env.
+//
+// lidar_kernel, 256 lanes per env, the shape of depth_kernel (pgtt_depth.hip):
+//   phase A  lanes 0..3 run the forward kinematics of one leg each (the formulas of mjcf.kinematics_np; only when the mount is not on the
+//            torso or the robot is in the scene); every lane then forms the sensor basis from the mount body's pose.
+//            Lane b < B moves box b of the env's variant into the SENSOR frame (the ray origin is the frame's origin) and tests its bounding
+//            sphere against the sensor's reach: a scanner looks everywhere, so there is no cone, only |c| - r <= far.  Survivors are compacted
+//            into LDS in box order with a ballot and prefix counts: no atomics, so the list is deterministic.  The posed robot geoms go the
+//            same way.
+//   phase B  rays over lanes, 256 per pass.  Ray r's unit direction in the sensor frame is one 16-byte row of the pattern table, the same for
+//            every env (a coalesced read that L2 serves).  Every lane walks the same list (LDS broadcasts, wave-uniform trip count), takes
+//            the minimum with the plane, clamps, adds the noise, stores the range coalesced and the world point as a 12-byte-per-lane run.
+// Unlike the camera's (u, v, 1) rays a pattern direction may be exactly perpendicular to a box axis: hit_box states that case.
+// A tick that the sensor period skips returns at once in every workgroup (the decision reads counter[0] on the device); lidar_advance_kernel,
+// enqueued behind it, adds one to the counter.  Nothing is shared between envs: an env's scan does not depend on the batch.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+#include <vector>
+
+#include "../../include/pgtt_lidar.h"
+#include "pgtt_raycast.hip.h"
+#include "pgtt_raycast_host.h"
+
+namespace {
+
+constexpr int kLanes = 256;             // lanes per workgroup = per env
+constexpr int kWaves = kLanes / 64;
+constexpr int kBoxWords = 16;           // LDS box, sensor frame: ray origin in the box frame[3], axes r0 r1 r2 [9], half extents[3], pad
+constexpr int kGeomWords = 16;          // LDS geom, sensor frame: centre[3], axes r0 r1 r2 [9], size[3], type
+static_assert(PGTT_MAX_BOX <= kLanes && PGTT_RENDER_MAX_GEOM <= 64, "one lane per box, the geoms in one wave");
+
+struct LidarArgs {
+  const float* state;
+  const float* params;
+  const int32_t* variant;
+  float* range;
+  float* points;                        // or nullptr
+  int64_t* counter;
+  const float* boxes;                   // [T][B][kTabWords]
+  const PgttModel* model;
+  const PgttRenderGeom* geoms;
+  const float4* dirs;                   // [R]: unit direction in the sensor frame, pad
+  int N, T, B, ngeom;                   // ngeom = 0 when the robot is not in the scene
+  int R, mount_body, every, force;
+  float near_m, far_m;
+  float mpos[3], mquat[4];
+  float sigma, dropout;
+  unsigned long long seed;
+  long long env_off;
+};
+
+// Philox4x32-10, the env's generator (pgtt.h)
+__device__ __forceinline__ void philox4x32_10(unsigned k0, unsigned k1, unsigned& c0, unsigned& c1, unsigned& c2, unsigned& c3) {
+#pragma unroll
+  for (int r = 0; r < 10; r++) {
+    const unsigned h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
+    const unsigned h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
+    const unsigned n0 = h1 ^ c1 ^ k0, n2 = h0 ^ c3 ^ k1;
+    c0 = n0; c1 = l1; c2 = n2; c3 = l0;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+}
+
+// the sensor: world vector -> sensor frame (its own x, y, z axes)
+struct Sensor { V3 o, ax, ay, az; };
+__device__ __forceinline__ V3 to_sensor(const Sensor& s, V3 w) { return v3(dot(s.ax, w), dot(s.ay, w), dot(s.az, w)); }
+
+// May a ray from the origin, out to range far_m, touch the sphere (centre c in the sensor frame, radius r)?  A hit farther than far_m reads
+// far_m like a miss.  The slack (that of the camera's sphere_in_view) covers the fp32 rounding of the centre and of the test itself.
+__device__ __forceinline__ bool sphere_in_reach(V3 c, float r, float far_m) {
+  const float n = sqrtf(dot(c, c));
+  const float slack = 1e-3f * r + 1e-5f * (1.f + n);
+  return n - r <= far_m + slack;
+}
+
+// slab test of the ray t * d against a box record (origin in the box frame, axes, half extents): t of the entry (a ray that starts inside the
+// box does not see it).  A direction component that is exactly 0 along an axis: inside that slab the axis is no constraint, outside it is a miss.
+__device__ __forceinline__ float hit_box(const float* __restrict__ r, V3 d) {
+  float tn = -INFINITY, tf = INFINITY;
+#pragma unroll
+  for (int k = 0; k < 3; k++) {
+    const float dl = r[3 + 3 * k] * d.x + r[4 + 3 * k] * d.y + r[5 + 3 * k] * d.z;
+    const float ol = r[k], h = r[12 + k];
+    if (dl == 0.f) {
+      if (fabsf(ol) > h) tf = -INFINITY;
+    } else {
+      const float inv = __builtin_amdgcn_rcpf(dl);
+      const float t1 = (-h - ol) * inv, t2 = (h - ol) * inv;
+      tn = fmaxf(tn, fminf(t1, t2));
+      tf = fminf(tf, fmaxf(t1, t2));
+    }
+  }
+  return (tn <= tf && tn > 0.f) ? tn : INFINITY;
+}
+// sphere / capsule for a ray from the origin along the UNIT direction d: t = distance along the ray
+__device__ __forceinline__ float hit_sphere(V3 oc, V3 d, float r) {
+  const float b = dot(oc, d), cc = dot(oc, oc) - r * r, disc = b * b - cc;
+  if (disc < 0.f) return INFINITY;
+  const float t = -b - sqrtf(disc);
+  return t > 0.f ? t : INFINITY;
+}
+__device__ __forceinline__ float hit_capsule(V3 d, V3 c, V3 ax, float r, float hl) {
+  const V3 pa = c - hl * ax, ba = (2.f * hl) * ax, oa = -1.f * pa;
+  const float baba = dot(ba, ba), bard = dot(ba, d), baoa = dot(ba, oa), rdoa = dot(d, oa), oaoa = dot(oa, oa);
+  const float a = baba - bard * bard, b = baba * rdoa - baoa * bard, cc = baba * oaoa - baoa * baoa - r * r * baba;
+  const float h = b * b - a * cc;
+  if (h < 0.f) return INFINITY;
+  if (a > 0.f) {                                                         // a = 0: the ray runs along the axis and can only meet a cap
+    const float t = (-b - sqrtf(h)) / a, y = baoa + t * bard;
+    if (y > 0.f && y < baba) return t > 0.f ? t : INFINITY;
+    return hit_sphere(y <= 0.f ? oa : oa - ba, d, r);
+  }
+  return fminf(hit_sphere(oa, d, r), hit_sphere(oa - ba, d, r));
+}
+
+template <bool NOISE>
+__global__ void __launch_bounds__(kLanes) lidar_kernel(LidarArgs a) {
+  __shared__ float sh_pose[PGTT_NBODY][8];                              // xpos[3], xquat[4]
+  __shared__ __attribute__((aligned(16))) float sh_box[PGTT_MAX_BOX * kBoxWords];
+  __shared__ __attribute__((aligned(16))) float sh_geom[PGTT_RENDER_MAX_GEOM * kGeomWords];
+  __shared__ int sh_nbox[kWaves], sh_ngeom;
+  const long long tick = a.counter[0];
+  if (!a.force && (unsigned long long)tick % (unsigned)a.every != 0) return;       // the same decision in every workgroup
+  const int e = blockIdx.x, tid = threadIdx.x, N = a.N;
+  const int lane = tid & 63, wave = tid >> 6;
+
+  // ---- phase A: kinematics (lanes 0..3: the base, then one leg each)
+  const bool chain = a.mount_body != 0 || a.ngeom > 0;
+  if (tid < PGTT_NLEG) {
+    auto row = [&](int r) { return a.state[(size_t)r * N + e]; };
+    const PgttModel* m = a.model;
+    // this kernel's own statement of the chain, like the placement and the hit tests: see pgtt_raycast.hip.h
+    V3 xp = v3(row(PGTT_S_QPOS + 0), row(PGTT_S_QPOS + 1), row(PGTT_S_QPOS + 2));
+    Q4 xq;
+    {
+      const Q4 q = {row(PGTT_S_QPOS + 3), row(PGTT_S_QPOS + 4), row(PGTT_S_QPOS + 5), row(PGTT_S_QPOS + 6)};
+      const float n = sqrtf(q.w * q.w + q.x * q.x + q.y * q.y + q.z * q.z);
+      xq = {q.w / n, q.x / n, q.y / n, q.z / n};
+    }
+    if (tid == 0) {
+      sh_pose[0][0] = xp.x; sh_pose[0][1] = xp.y; sh_pose[0][2] = xp.z;
+      sh_pose[0][3] = xq.w; sh_pose[0][4] = xq.x; sh_pose[0][5] = xq.y; sh_pose[0][6] = xq.z;
+    }
+    if (chain) {
+      for (int k = 0; k < 3; k++) {                                     // hip, thigh, calf: each the child of the one before
+        const int b = 1 + 3 * tid + k;
+        xp = xp + qrot(xq, ld3(m->body_pos[b]));
+        const Q4 quat = qmul(xq, Q4{m->body_quat[b][0], m->body_quat[b][1], m->body_quat[b][2], m->body_quat[b][3]});
+        const float q0 = a.params ? a.params[(size_t)(PGTT_P_QPOS0 + b - 1) * N + e] : m->qpos0[7 + b - 1];
+        const float ang = row(PGTT_S_QPOS + 7 + b - 1) - q0;
+        float s, c; sincosf(0.5f * ang, &s, &c);
+        xq = qmul(quat, Q4{c, m->jnt_axis[b - 1][0] * s, m->jnt_axis[b - 1][1] * s, m->jnt_axis[b - 1][2] * s});
+        sh_pose[b][0] = xp.x; sh_pose[b][1] = xp.y; sh_pose[b][2] = xp.z;
+        sh_pose[b][3] = xq.w; sh_pose[b][4] = xq.x; sh_pose[b][5] = xq.y; sh_pose[b][6] = xq.z;
+      }
+    }
+  }
+  __syncthreads();
+
+  // ---- the sensor: body pose * mount pose
+  Sensor sen;
+  {
+    const float* bp = sh_pose[a.mount_body];
+    const Q4 bq = {bp[3], bp[4], bp[5], bp[6]};
+    sen.o = ld3(bp) + qrot(bq, v3(a.mpos[0], a.mpos[1], a.mpos[2]));
+    qaxes(qmul(bq, Q4{a.mquat[0], a.mquat[1], a.mquat[2], a.mquat[3]}), sen.ax, sen.ay, sen.az);
+  }
+
+  // ---- boxes of the env's variant -> sensor frame, culled, compacted in box order
+  int nbox = 0, ngeom = 0;
+  if (a.T > 0 || a.ngeom > 0) {                                          // the flat task without the robot: the plane alone, no list at all
+    float rec[kBoxWords];
+    bool keep = false;
+    if (a.T > 0 && tid < a.B) {
+      const int v = a.variant ? min(max(a.variant[e], 0), a.T - 1) : 0;
+      const float4* src = reinterpret_cast<const float4*>(a.boxes + ((size_t)v * a.B + tid) * kTabWords);
+      float w[kTabWords];
+#pragma unroll
+      for (int i = 0; i < kTabWords / 4; i++) { const float4 q = src[i]; w[4 * i] = q.x; w[4 * i + 1] = q.y; w[4 * i + 2] = q.z; w[4 * i + 3] = q.w; }
+      const V3 c = to_sensor(sen, ld3(w) - sen.o);
+      const V3 h = ld3(w + 12);
+      keep = sphere_in_reach(c, sqrtf(dot(h, h)), a.far_m);
+#pragma unroll
+      for (int k = 0; k < 3; k++) {
+        const V3 r = to_sensor(sen, ld3(w + 3 + 3 * k));
+        rec[3 + 3 * k] = r.x; rec[4 + 3 * k] = r.y; rec[5 + 3 * k] = r.z;
+        rec[k] = -dot(r, c);                                             // the ray origin (the sensor) in the box frame
+      }
+      rec[12] = h.x; rec[13] = h.y; rec[14] = h.z; rec[15] = 0.f;
+    }
+    const unsigned long long kept = __ballot(keep);
+    if (lane == 0) sh_nbox[wave] = __popcll(kept);
+
+    // ---- robot geoms (wave 0): posed, culled and compacted the same way
+    if (wave == 0 && a.ngeom > 0) {
+      float grec[kGeomWords];
+      bool gkeep = false;
+      if (tid < a.ngeom) {
+        const PgttRenderGeom G = a.geoms[tid];
+        const int b = min(max(G.body, 0), PGTT_NBODY - 1);
+        const Q4 bq = {sh_pose[b][3], sh_pose[b][4], sh_pose[b][5], sh_pose[b][6]};
+        const V3 c = to_sensor(sen, ld3(sh_pose[b]) + qrot(bq, ld3(G.pos)) - sen.o);
+        V3 r[3]; qaxes(qmul(bq, Q4{G.quat[0], G.quat[1], G.quat[2], G.quat[3]}), r[0], r[1], r[2]);
+        grec[0] = c.x; grec[1] = c.y; grec[2] = c.z;
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+          const V3 rc = to_sensor(sen, r[k]);
+          grec[3 + 3 * k] = rc.x; grec[4 + 3 * k] = rc.y; grec[5 + 3 * k] = rc.z;
+        }
+        grec[12] = G.size[0]; grec[13] = G.size[1]; grec[14] = G.size[2]; grec[15] = __int_as_float(G.type);
+        const float rb = G.type == PGTT_RENDER_SPHERE ? G.size[0]
+                         : (G.type == PGTT_RENDER_CAPSULE ? G.size[0] + G.size[1] : sqrtf(dot(ld3(G.size), ld3(G.size))));
+        gkeep = sphere_in_reach(c, rb, a.far_m);
+      }
+      const unsigned long long gk = __ballot(gkeep);
+      if (lane == 0) sh_ngeom = __popcll(gk);
+      if (gkeep) {
+        float* dst = sh_geom + __popcll(gk & ((1ull << lane) - 1ull)) * kGeomWords;
+#pragma unroll
+        for (int i = 0; i < kGeomWords; i++) dst[i] = grec[i];
+      }
+    }
+    __syncthreads();
+    int first = 0;
+#pragma unroll
+    for (int w = 0; w < kWaves; w++) { first += w < wave ? sh_nbox[w] : 0; nbox += sh_nbox[w]; }
+    if (a.ngeom > 0) ngeom = sh_ngeom;
+    if (keep) {
+      float4* dst = reinterpret_cast<float4*>(sh_box + (first + __popcll(kept & ((1ull << lane) - 1ull))) * kBoxWords);
+#pragma unroll
+      for (int i = 0; i < kBoxWords / 4; i++) dst[i] = make_float4(rec[4 * i], rec[4 * i + 1], rec[4 * i + 2], rec[4 * i + 3]);
+    }
+    __syncthreads();
+  }
+
+  // ---- phase B: rays over lanes
+  const V3 pn = v3(sen.ax.z, sen.ay.z, sen.az.z);                       // the plane's normal (world +z) in the sensor frame
+  const int R = a.R;
+  float* out = a.range + (size_t)e * R;
+  float* pts = a.points ? a.points + (size_t)e * R * 3 : nullptr;
+  for (int r = tid; r < R; r += kLanes) {
+    const float4 dv = a.dirs[r];
+    const V3 d = v3(dv.x, dv.y, dv.z);
+    float best = INFINITY;
+    {
+      const float den = dot(pn, d);
+      if (den != 0.f) {
+        const float t = -sen.o.z / den;
+        if (t > 0.f) best = t;
+      }
+    }
+    for (int k = 0; k < nbox; k++) best = fminf(best, hit_box(sh_box + k * kBoxWords, d));
+    for (int g = 0; g < ngeom; g++) {
+      const float* G = sh_geom + g * kGeomWords;
+      const int type = __float_as_int(G[15]);
+      const V3 c = ld3(G);
+      float t;
+      if (type == PGTT_RENDER_SPHERE) t = hit_sphere(-1.f * c, d, G[12]);
+      else if (type == PGTT_RENDER_CAPSULE) t = hit_capsule(d, c, ld3(G + 9), G[12], G[13]);
+      else {
+        float rb[kBoxWords];
+#pragma unroll
+        for (int i = 3; i < 15; i++) rb[i] = G[i];
+#pragma unroll
+        for (int i = 0; i < 3; i++) rb[i] = -dot(ld3(G + 3 + 3 * i), c);
+        t = hit_box(rb, d);
+      }
+      best = fminf(best, t);
+    }
+    float val = fminf(fmaxf(best, a.near_m), a.far_m);
+    if (NOISE) {
+      unsigned c0 = (unsigned)(a.env_off + e), c1 = (unsigned)tick, c2 = PGTT_RS_LIDAR, c3 = (unsigned)r;
+      philox4x32_10((unsigned)a.seed, (unsigned)(a.seed >> 32), c0, c1, c2, c3);
+      const float k24 = 1.0f / 16777216.0f;
+      const float u0 = (float)(c0 >> 8) * k24, u1 = (float)(c1 >> 8) * k24, u2 = (float)(c2 >> 8) * k24;
+      const float z = sqrtf(-2.f * logf(1.f - u1)) * cosf(6.283185307179586f * u2);
+      val = u0 < a.dropout ? a.far_m : fminf(fmaxf(val * (1.f + a.sigma * z), a.near_m), a.far_m);
+    }
+    out[r] = val;
+    if (pts) {
+      const float nanv = __uint_as_float(0x7fc00000u);
+      V3 p = v3(nanv, nanv, nanv);
+      if (val > a.near_m && val < a.far_m) p = sen.o + val * (d.x * sen.ax + d.y * sen.ay + d.z * sen.az);
+      float* dst = pts + 3 * (size_t)r;
+      dst[0] = p.x; dst[1] = p.y; dst[2] = p.z;
+    }
+  }
+}
+
+__global__ void __launch_bounds__(64) lidar_advance_kernel(int64_t* counter) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) counter[0] = counter[0] + 1;
+}
+
+// the checks of the config and of the pattern; `who` prefixes the message
+int resolve(const PgttLidarConfig* cfg, const float* dirs, int R, const char* who) {
+  const std::string p = std::string(who) + ": ";
+  if (!cfg) return fail(PGTT_E_ARG, p + "null config");
+  if (!(cfg->near > 0.f) || !(cfg->near < cfg->far) || !std::isfinite(cfg->far)) return fail(PGTT_E_ARG, p + "need 0 < near < far, finite");
+  if (cfg->mount_body < 0 || cfg->mount_body >= PGTT_NBODY) return fail(PGTT_E_ARG, p + "mount_body outside [0, PGTT_NBODY)");
+  if (cfg->every < 1) return fail(PGTT_E_ARG, p + "every must be >= 1");
+  if (cfg->see_robot != 0 && cfg->see_robot != 1) return fail(PGTT_E_ARG, p + "see_robot must be 0 or 1");
+  if (!(cfg->noise_sigma >= 0.f) || !std::isfinite(cfg->noise_sigma)) return fail(PGTT_E_ARG, p + "noise_sigma must be >= 0");
+  if (!(cfg->dropout >= 0.f) || !(cfg->dropout < 1.f)) return fail(PGTT_E_ARG, p + "dropout must be in [0, 1)");
+  double qn = 0.0;
+  for (int i = 0; i < 4; i++) qn += (double)cfg->mount_quat[i] * cfg->mount_quat[i];
+  if (!(qn > 0.0) || !std::isfinite(qn)) return fail(PGTT_E_ARG, p + "mount_quat must be a non-zero quaternion");
+  for (int i = 0; i < 3; i++)
+    if (!std::isfinite(cfg->mount_pos[i])) return fail(PGTT_E_ARG, p + "mount_pos must be finite");
+  if (R < 1 || R > PGTT_LIDAR_MAX_RAYS) return fail(PGTT_E_ARG, p + "R must be in [1, PGTT_LIDAR_MAX_RAYS]");
+  if (!dirs) return fail(PGTT_E_ARG, p + "null pattern");
+  for (int r = 0; r < R; r++) {
+    double n = 0.0;
+    for (int i = 0; i < 3; i++) n += (double)dirs[3 * r + i] * dirs[3 * r + i];
+    if (!(n > 0.0) || !std::isfinite(n)) return fail(PGTT_E_ARG, p + "pattern row " + std::to_string(r) + " is zero or not finite");
+  }
+  return PGTT_OK;
+}
+
+}  // namespace
+
+struct pgtt_lidar_scanner {
+  int num_envs = 0;
+  int ngeom = 0;
+  int R = 0;
+  PgttLidarConfig cfg{};
+  PgttLidarBuffers buf{};
+  bool bound = false;
+  float4* d_dirs = nullptr;
+  SceneTables scene;
+};
+
+extern "C" {
+
+PGTT_SIDE_EXPORTS(lidar, LIDAR)
+int pgtt_lidar_sizeof_config(void) { return (int)sizeof(PgttLidarConfig); }
+int pgtt_lidar_sizeof_buffers(void) { return (int)sizeof(PgttLidarBuffers); }
+
+int pgtt_lidar_check(const PgttLidarConfig* cfg, const float* dirs, int R) { return resolve(cfg, dirs, R, "pgtt_lidar_check"); }
+
+int pgtt_lidar_create(const PgttModel* model, const PgttLidarConfig* cfg, const float* dirs, int R, const PgttRenderGeom* geoms, int ngeom,
+                      int device, int num_envs, pgtt_lidar_handle* out) {
+  if (!model || !cfg || !out || (ngeom > 0 && !geoms)) return fail(PGTT_E_ARG, "pgtt_lidar_create: null argument");
+  *out = nullptr;
+  if (num_envs < 1) return fail(PGTT_E_ARG, "pgtt_lidar_create: num_envs must be >= 1");
+  if (int rc = resolve(cfg, dirs, R, "pgtt_lidar_create")) return rc;
+  if (int rc = check_geoms(geoms, ngeom, "pgtt_lidar_create")) return rc;
+  if (int rc = check_device(device, "pgtt_lidar_create")) return rc;
+  pgtt_lidar_scanner* h = new pgtt_lidar_scanner();
+  h->num_envs = num_envs; h->ngeom = ngeom; h->R = R; h->cfg = *cfg; h->scene.device = device;
+  double qn = 0.0;
+  for (int i = 0; i < 4; i++) qn += (double)cfg->mount_quat[i] * cfg->mount_quat[i];
+  qn = std::sqrt(qn);
+  for (int i = 0; i < 4; i++) h->cfg.mount_quat[i] = (float)(cfg->mount_quat[i] / qn);
+  // the pattern: unit rows (normalised in double), padded to 16 bytes
+  std::vector<float> tab((size_t)R * 4, 0.f);
+  for (int r = 0; r < R; r++) {
+    const double x = dirs[3 * r], y = dirs[3 * r + 1], z = dirs[3 * r + 2], n = std::sqrt(x * x + y * y + z * z);
+    tab[4 * r] = (float)(x / n); tab[4 * r + 1] = (float)(y / n); tab[4 * r + 2] = (float)(z / n);
+  }
+  auto upload = [&]() -> int {
+    if (int rc = h->scene.upload(model, geoms, ngeom)) return rc;
+    HIP_TRY(hipMalloc(&h->d_dirs, tab.size() * sizeof(float)));
+    HIP_TRY(hipMemcpy(h->d_dirs, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice));
+    return PGTT_OK;
+  };
+  if (int rc = upload()) { pgtt_lidar_destroy(h); return rc; }
+  *out = h;
+  return PGTT_OK;
+}
+
+int pgtt_lidar_destroy(pgtt_lidar_handle h) {
+  if (!h) return PGTT_OK;
+  h->scene.release();
+  if (h->d_dirs) hipFree(h->d_dirs);
+  delete h;
+  return PGTT_OK;
+}
+
+int pgtt_lidar_set_terrain(pgtt_lidar_handle h, const float* boxes, int T, int B) {
+  if (!h) return fail(PGTT_E_ARG, "null handle");
+  return h->scene.set_terrain(boxes, T, B, "pgtt_lidar_set_terrain");
+}
+
+int pgtt_lidar_bind(pgtt_lidar_handle h, const PgttLidarBuffers* bufs) {
+  if (!h || !bufs) return fail(PGTT_E_ARG, "pgtt_lidar_bind: null argument");
+  if (!bufs->state || !bufs->range || !bufs->counter) return fail(PGTT_E_ARG, "pgtt_lidar_bind: state, range and counter are required");
+  h->buf = *bufs;
+  h->bound = true;
+  return PGTT_OK;
+}
+
+int pgtt_lidar(pgtt_lidar_handle h, int force, void* stream) {
+  if (!h) return fail(PGTT_E_ARG, "pgtt_lidar: null handle");
+  if (!h->bound) return fail(PGTT_E_STATE, "pgtt_lidar: no buffers bound (pgtt_lidar_bind first)");
+  HIP_TRY(hipSetDevice(h->scene.device));
+  const PgttLidarConfig& c = h->cfg;
+  LidarArgs a{};
+  a.state = h->buf.state; a.params = h->buf.params; a.variant = h->buf.variant; a.range = h->buf.range; a.points = h->buf.points;
+  a.counter = h->buf.counter;
+  a.boxes = h->scene.d_boxes; a.model = h->scene.d_model; a.geoms = h->scene.d_geoms; a.dirs = h->d_dirs;
+  a.N = h->num_envs; a.T = h->scene.T; a.B = h->scene.B; a.ngeom = c.see_robot ? h->ngeom : 0;
+  a.R = h->R; a.mount_body = c.mount_body; a.every = c.every; a.force = force ? 1 : 0;
+  a.near_m = c.near; a.far_m = c.far;
+  for (int i = 0; i < 3; i++) a.mpos[i] = c.mount_pos[i];
+  for (int i = 0; i < 4; i++) a.mquat[i] = c.mount_quat[i];
+  a.sigma = c.noise_sigma; a.dropout = c.dropout; a.seed = c.seed; a.env_off = c.env_id_offset;
+  hipStream_t st = (hipStream_t)stream;
+  if (c.noise_sigma > 0.f || c.dropout > 0.f) hipLaunchKernelGGL(lidar_kernel<true>, dim3(h->num_envs), dim3(kLanes), 0, st, a);
+  else hipLaunchKernelGGL(lidar_kernel<false>, dim3(h->num_envs), dim3(kLanes), 0, st, a);
+  hipLaunchKernelGGL(lidar_advance_kernel, dim3(1), dim3(64), 0, st, h->buf.counter);
+  HIP_TRY(hipGetLastError());
+  return PGTT_OK;
+}
+
+}  // extern "C"

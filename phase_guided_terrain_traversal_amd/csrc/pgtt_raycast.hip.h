@@ -1,15 +1,16 @@
-// pgtt_raycast.hip.h — the device-side algebra that libpgtt_render.so (pgtt_render.hip) and libpgtt_depth.so (pgtt_depth.hip) share: V3 / Q4,
-// qmul, qaxes, qrot(q, v).  The host side of the same two libraries is pgtt_raycast_host.h.
-// NOT here, although both kernels state them: the forward kinematics of the body chain (the formulas of mjcf.kinematics_np), the placement of
+// pgtt_raycast.hip.h — the device-side algebra that libpgtt_render.so (pgtt_render.hip), libpgtt_depth.so (pgtt_depth.hip) and libpgtt_lidar.so
+// (pgtt_lidar.hip) share: V3 / Q4, qmul, qaxes, qrot(q, v).  The host side of the same three libraries is pgtt_raycast_host.h.
+// NOT here, although the kernels state them: the forward kinematics of the body chain (the formulas of mjcf.kinematics_np), the placement of
 // a PgttRenderGeom on its body, and the sphere / capsule tests.  Moved into shared helpers with their expressions unchanged, they make the
 // compiler pair and contract the fp32 products of the kernels differently.  Measured on an MI355X against the build before: a shared chain
 // moved body poses by one ulp (6e-8) and with them 0.2 % of the renderer's and 10 % of a thigh-mounted depth camera's pixels
 // (profiles/r10_ab_raycast_chain.txt); a shared placement and shared hit tests, the depth camera calling the renderer's forms with the ray
 // origin at zero, moved 1.5 % of the pixels of a thigh-mounted camera that sees the robot by up to 7e-6 m (profiles/r10_ab_raycast_hits.txt).
-// So each kernel keeps its own statement of these, and tests/test_gpu_render.py and tests/test_gpu_depth.py hold both against fp64 references.
-// Included by those two translation units only.  It does not include pgtt_common.hip.h (whose qrot(v, q) is the physics kernels' form): that
-// file is inside the physics source hash (srchash.py), and this one is inside the two side hashes only.  For the same reason the Philox copies
-// of pgtt_depth.hip and pgtt_policy.hip stay where they are.
+// So each kernel keeps its own statement of these (the LiDAR's, the third, likewise), and tests/test_gpu_render.py, tests/test_gpu_depth.py and
+// tests/test_gpu_lidar.py hold them against fp64 references.
+// Included by those three translation units only.  It does not include pgtt_common.hip.h (whose qrot(v, q) is the physics kernels' form): that
+// file is inside the physics source hash (srchash.py), and this one is inside the three side hashes only.  For the same reason the Philox copies
+// of pgtt_depth.hip, pgtt_lidar.hip and pgtt_policy.hip stay where they are.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -1,4 +1,4 @@
-// pgtt_raycast_host.h — the host side that libpgtt_render.so and libpgtt_depth.so share on top of the side libraries' prelude
+// pgtt_raycast_host.h — the host side that libpgtt_render.so, libpgtt_depth.so and libpgtt_lidar.so share on top of the side libraries' prelude
 // (pgtt_side_host.h: error string, HIP_TRY, check_device): the check of the robot primitives and the device copies of the scene (model,
 // primitives, the ray-ready terrain table).  Everything is in an anonymous namespace and nothing of it is exported.  `who` is the entry
 // point's name, the prefix of its messages.

@@ -11,7 +11,7 @@
 HIPCC ?= hipcc
 ARCH ?= gfx950
 PYTHON ?= python3
-LIBS ?= render depth perceive elevation learn
+LIBS ?= render depth perceive elevation learn lidar
 BUILD ?= build/side
 OUTDIR ?= ..
 SUFFIX ?=

@@ -1,4 +1,4 @@
-// pgtt_side_host.h — the host prelude of every side library (libpgtt_render.so, _depth, _perceive, _elevation, _learn): the thread-local error
+// pgtt_side_host.h — the host prelude of every side library (libpgtt_render.so, _depth, _perceive, _elevation, _learn, _lidar): the thread-local error
 // string, the check of the device index, and the two exports they all have, pgtt_<x>_last_error() and pgtt_<x>_build_info().  Everything but the
 // two exports is in an anonymous namespace: each library keeps its own error string and exports nothing of this.  `who` is the entry point's
 // name, the prefix of its messages.  No device code here.
@@ -29,7 +29,7 @@ int check_device(int device, const char* who) {
 }
 
 // `text` is a macro's name put through PGTT_SIDE_STR: "\"value\"" when the macro is defined as a string literal, its own name when it is not
-// defined - which is how one macro can hold the defaults of five pairs of names
+// defined - which is how one macro can hold the defaults of six pairs of names
 std::string literal_or(const char* text, const char* otherwise) {
   const std::string s(text);
   return s.size() >= 2 && s.front() == '"' ? s.substr(1, s.size() - 2) : otherwise;

@@ -1,13 +1,15 @@
 """Depth-fused elevation map: a geometric height scan per env (libpgtt_elevation.so, include/pgtt_elevation.h).  The onboard depth image is
 unprojected with the camera pose, fused into a rolling robot-centred map of world heights, and the observation's 117 scan rows are sampled from
-the map: what a deployed robot's elevation-mapping stack provides, with nothing to train.
+the map: what a deployed robot's elevation-mapping stack provides, with nothing to train.  With source="lidar" the map is fused from the world
+points of the env's LiDAR (lidar.py) instead: the sensor such a stack reads on the robot, which sees all round it.
 
     em = ElevationMap(env, grid=64, res=0.04, alpha=1.0)     # env: a Joystick with a torso depth camera of period 1
     em.tick(clear_all=True)                                  # one launch on the env's current stream, no synchronisation
     em.map, em.origin, em.est, em.known, em.obs              # [N, G, G] heights (NaN = unknown), [N, 2], [N, 117], [N, 117] uint8, [N, obs_dim]
 
-`Joystick(..., depth=dict(...), elevation=dict(...) | True)` owns one and ticks it behind the camera (env.elevation_obs).  The module is not imported
-by env.py unless an elevation map is asked for.
+`Joystick(..., depth=dict(...), elevation=dict(...) | True)` owns one and ticks it behind the camera (env.elevation_obs);
+`Joystick(..., lidar=dict(...), elevation=dict(source="lidar"))` one that is ticked behind the LiDAR.  The module is not imported by env.py unless
+an elevation map is asked for.
 """
 from __future__ import annotations
 
@@ -25,6 +27,9 @@ SCAN_ROW0 = {"pgtt": 38, "baseline": 30}           # perceive.SCAN_ROW0: the sca
 # Joystick(elevation=True) / evaluate.py --elevation: a 2.56 m window of 4 cm cells, the newest view replaces the old one, and a box around the
 # torso that drops the robot's own legs from a camera that sees them - settings, not measured facts about a robot
 DEFAULTS = dict(grid=64, res=0.04, alpha=1.0, self_half=(0.45, 0.25, 0.45))
+SOURCES = ("depth", "lidar")                       # ElevationMap(source=...): what the map is fused from; "depth" unless said otherwise
+# the camera fields of a map that is fused from points: never read by pgtt_elevation_points, but pgtt_elevation_create checks them
+PLACEHOLDER_CAMERA = dict(width=1, height=1, fovy=90.0, near=0.1, far=1.0)
 
 f, i32 = C.c_float, C.c_int32
 
@@ -52,6 +57,8 @@ SIDE = _sidelib.SideLib("elevation", ElevationError, {
     "pgtt_elevation_check": (None, [cp]), "pgtt_elevation_create": (None, [cp, C.c_int, C.c_int, C.POINTER(vp)]),
     "pgtt_elevation_destroy": (None, [vp]), "pgtt_elevation_bind": (None, [vp, C.POINTER(PgttElevationBuffers)]),
     "pgtt_elevation": (None, [vp, vp, C.c_int, C.c_int, vp]),
+    "pgtt_elevation_bind_points": (None, [vp, C.POINTER(PgttElevationBuffers), vp, C.c_int]),
+    "pgtt_elevation_points": (None, [vp, vp, C.c_int, C.c_int, vp]),
 }, {"pgtt_elevation_sizeof_config": PgttElevationConfig, "pgtt_elevation_sizeof_buffers": PgttElevationBuffers})
 LIB_PATH, EXPORTS, lib, check, build_info = SIDE.path, SIDE.exports, SIDE.lib, SIDE.check, SIDE.build_info
 
@@ -75,28 +82,45 @@ def config_struct(width, height, fovy, near, far, mount_pos=(0.0, 0.0, 0.0), mou
 
 
 class ElevationMap(_sidelib.Handle):
-    """The elevation map of one Joystick with a depth camera: owns the handle and the tensors `map` [N, G, G] (world heights, NaN = unknown; world
-    cell (ix, iy) at map[ix mod G, iy mod G]), `origin` [N, 2] int32 (the base's cell), `est` [N, 117], `known` [N, 117] uint8 and `obs`
-    [N, obs_dim] (the obs_out buffer: the env's observation with the scan rows replaced by est).  The camera's intrinsics and mount are those of
-    env.depth_camera.  grid / res: the window is grid x grid cells of res metres; alpha: fusion gain in (0, 1], 1 = the newest view replaces the
-    old; self_half: half extents of a box in the base frame whose points are dropped (the robot's own body in a see_robot camera), zeros = none.
-    The defaults are settings, not facts.
-    Runs on the env's device and current stream; reads env.depth, env.buffers["state" | "obs_state" | "done"] and writes nothing but its own tensors."""
+    """The elevation map of one Joystick with a depth camera or a LiDAR: owns the handle and the tensors `map` [N, G, G] (world heights, NaN =
+    unknown; world cell (ix, iy) at map[ix mod G, iy mod G]), `origin` [N, 2] int32 (the base's cell), `est` [N, 117], `known` [N, 117] uint8 and
+    `obs` [N, obs_dim] (the obs_out buffer: the env's observation with the scan rows replaced by est).  source="depth": the camera's intrinsics
+    and mount are those of env.depth_camera; source="lidar": the map is fused from env.lidar_scanner.points, world points that need no camera (the
+    config's camera fields hold placeholders).  grid / res: the window is grid x grid cells of res metres; alpha: fusion gain in (0, 1], 1 = the
+    newest view replaces the old; self_half: half extents of a box in the base frame whose points are dropped (the robot's own body in a sensor
+    that sees it), zeros = none.  The defaults are settings, not facts.
+    Runs on the env's device and current stream; reads env.depth or the LiDAR's points, env.buffers["state" | "obs_state" | "done"] and writes nothing
+    but its own tensors."""
     _prefix, _check = "pgtt_elevation", staticmethod(check)
 
-    def __init__(self, env, grid: int = 64, res: float = 0.04, alpha: float = 1.0, self_half: Sequence[float] = (0.45, 0.25, 0.45)):
-        cam = getattr(env, "depth_camera", None)
-        if cam is None:
-            raise ValueError("ElevationMap needs an env with a depth camera: Joystick(..., depth=dict(...))")
-        cc = cam.config
-        if cc.mount_body != 0:
-            raise ValueError(f"ElevationMap supports a camera on the torso only (mount_body == 0), not on body {cc.mount_body}")
-        if cc.every != 1:
-            raise ValueError(f"ElevationMap needs a camera of period 1 (every={cc.every}): a stale image under a moved pose would be unprojected wrongly")
+    def __init__(self, env, grid: int = 64, res: float = 0.04, alpha: float = 1.0, self_half: Sequence[float] = (0.45, 0.25, 0.45),
+                 source: str = "depth"):
+        if source not in SOURCES:
+            raise ValueError(f"ElevationMap: source must be one of {SOURCES}, not {source!r}")
+        self.source = source
+        if source == "lidar":
+            lid = getattr(env, "lidar_scanner", None)
+            if lid is None or lid.points is None:
+                raise ValueError("ElevationMap(source='lidar') needs an env with a LiDAR that writes points: Joystick(..., lidar=dict(...))")
+            if lid.config.every != 1:
+                raise ValueError(f"ElevationMap needs a LiDAR of period 1 (every={lid.config.every}): the map would fuse a stale scan again at every tick")
+            od = env.observation_size["state"]
+            self.config = config_struct(**PLACEHOLDER_CAMERA, grid=grid, res=res, alpha=alpha, self_half=self_half,
+                                        scan_dist_x=env.config["scan_dist_x"], scan_dist_y=env.config["scan_dist_y"], obs_dim=od,
+                                        scan_row0=SCAN_ROW0[env.method])
+        else:
+            cam = getattr(env, "depth_camera", None)
+            if cam is None:
+                raise ValueError("ElevationMap needs an env with a depth camera: Joystick(..., depth=dict(...))")
+            cc = cam.config
+            if cc.mount_body != 0:
+                raise ValueError(f"ElevationMap supports a camera on the torso only (mount_body == 0), not on body {cc.mount_body}")
+            if cc.every != 1:
+                raise ValueError(f"ElevationMap needs a camera of period 1 (every={cc.every}): a stale image under a moved pose would be unprojected wrongly")
+            od = env.observation_size["state"]
+            self.config = config_struct(cc.width, cc.height, cc.fovy_deg, cc.near, cc.far, list(cc.mount_pos), list(cc.mount_quat), cc.mount_body, grid, res,
+                                        alpha, self_half, env.config["scan_dist_x"], env.config["scan_dist_y"], od, SCAN_ROW0[env.method])
         self.env, self.grid, self.res, self.alpha = env, int(grid), float(res), float(alpha)
-        od = env.observation_size["state"]
-        self.config = config_struct(cc.width, cc.height, cc.fovy_deg, cc.near, cc.far, list(cc.mount_pos), list(cc.mount_quat), cc.mount_body, grid, res,
-                                    alpha, self_half, env.config["scan_dist_x"], env.config["scan_dist_y"], od, SCAN_ROW0[env.method])
         self._lib = lib()
         self._h = C.c_void_p()
         check(self._lib.pgtt_elevation_create(C.byref(self.config), env.device.index or 0, env.num_envs, C.byref(self._h)))
@@ -110,24 +134,30 @@ class ElevationMap(_sidelib.Handle):
         self.bind()
 
     def bind(self) -> None:
-        """(re)bind: the env's state, image, observation and done flags, this object's outputs"""
+        """(re)bind: the env's state, image or points, observation and done flags, this object's outputs"""
         b = PgttElevationBuffers()
         eb = self.env.buffers
-        b.state, b.depth, b.obs = eb["state"].data_ptr(), self.env.depth.data_ptr(), eb["obs_state"].data_ptr()
+        b.state, b.obs = eb["state"].data_ptr(), eb["obs_state"].data_ptr()
         b.done = eb["done"].data_ptr() if eb.get("done") is not None else None
         b.map, b.origin, b.est, b.known, b.obs_out = (t.data_ptr() for t in (self.map, self.origin, self.est, self.known, self.obs))
-        check(self._lib.pgtt_elevation_bind(self._h, C.byref(b)))
+        if self.source == "lidar":
+            pts = self.env.lidar_scanner.points
+            check(self._lib.pgtt_elevation_bind_points(self._h, C.byref(b), pts.data_ptr(), pts.shape[1]))
+        else:
+            b.depth = self.env.depth.data_ptr()
+            check(self._lib.pgtt_elevation_bind(self._h, C.byref(b)))
 
     def tick(self, clear_mask: Optional[torch.Tensor] = None, clear_all: bool = False, use_done: bool = False) -> torch.Tensor:
-        """integrate the env's current image under its current pose and sample the scan: one launch on the env's current stream, no
-        synchronisation.  Before integrating, the maps of the envs with clear_mask[e] != 0 ([N] uint8 / bool), of every env (clear_all) or of the
-        envs whose done flag is set (use_done) are cleared."""
+        """integrate the env's current image (or LiDAR points) under its current pose and sample the scan: one launch on the env's current stream,
+        no synchronisation.  Before integrating, the maps of the envs with clear_mask[e] != 0 ([N] uint8 / bool), of every env (clear_all) or of
+        the envs whose done flag is set (use_done) are cleared."""
         mp = None
         if clear_mask is not None:
             self._mask = clear_mask.to(self.env.device, torch.uint8).contiguous()      # kept alive until the next tick: the launch is asynchronous
             assert self._mask.shape == (self.env.num_envs,)
             mp = self._mask.data_ptr()
-        check(self._lib.pgtt_elevation(self._h, mp, int(bool(clear_all)), int(bool(use_done)), torch.cuda.current_stream(self.env.device).cuda_stream))
+        fn = self._lib.pgtt_elevation_points if self.source == "lidar" else self._lib.pgtt_elevation
+        check(fn(self._h, mp, int(bool(clear_all)), int(bool(use_done)), torch.cuda.current_stream(self.env.device).cuda_stream))
         return self.obs
 
     def world_cells(self) -> torch.Tensor:

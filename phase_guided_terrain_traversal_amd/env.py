@@ -30,7 +30,7 @@ class Joystick:
                  model: Optional[Dict[str, Any]] = None, layout: Optional[str] = None, observe_form: Optional[str] = None,
                  test_hooks: bool = False, interval_sums: bool = False, push: Optional[Dict[str, Any]] = None, xfrc: bool = False,
                  curriculum: Optional[Dict[str, Any]] = None, level: Optional[torch.Tensor] = None, depth: Optional[Dict[str, Any]] = None, student=None,
-                 elevation=None):
+                 elevation=None, lidar: Optional[Dict[str, Any]] = None):
         """layout: "auto" | "quad" | "oct" | "hex" lane layout of physics_kernel (PgttConfig.lane_layout; results are bit-identical
         across batch sizes and shards within one layout); observe_form: "fused" | "split"; test_hooks: allow set_test_overrides
         (fixture replay only); interval_sums: keep per-env running sums of the step outputs for a logging trainer (PgttBuffers.interval_sums);
@@ -59,12 +59,28 @@ class Joystick:
         `env.elevation_map` is the ElevationMap.  A side output like the image; may be combined with student.  None: the library is not opened.
         The map has memory, so what moves an env must clear it: reset() and step() do, set_terrain() forgets every map, but with a deferred
         curriculum (step(action, curriculum=False), then curriculum_step()) the envs are restarted AFTER the step's tick, as they are after the
-        camera's - such a caller ticks the camera and then `env.elevation_map.tick(use_done=True)` once more after curriculum_step()."""
+        camera's - such a caller ticks the camera and then `env.elevation_map.tick(use_done=True)` once more after curriculum_step().
+        lidar: an onboard LiDAR (lidar.LidarScanner's arguments over lidar.DEFAULTS, e.g. dict(n_az=128, n_el=16, az_deg=(-180, 180),
+        el_deg=(-85, 10), near=0.05, far=3.0, mount_pos=(0.29, 0.0, -0.04), every=1, see_robot=True) or dict(pattern=[R, 3] directions, ...); the
+        defaults are placeholders for a chin-mounted hemispherical scanner - settings, not facts): `env.lidar` is the [N, R] range scan,
+        `env.lidar_points` the [N, R, 3] world points of its returns, `env.lidar_scanner` the LidarScanner; ticked next to the camera, after every
+        step and (with force) reset.  A side output like the image.  None: the library is not opened.
+        elevation=dict(source="lidar", ...) fuses the map from the LiDAR's points instead of the image: it needs lidar (with every=1, on any body:
+        the points are world points) and no depth; clearing goes exactly as for the camera-fed map."""
         if student is not None and depth is None:
             raise ValueError("Joystick(student=...) needs depth=dict(...): the student reads the onboard depth image")
-        if elevation is not None and elevation is not False and depth is None:
+        wants_map = elevation is not None and elevation is not False
+        map_source = "depth" if not wants_map or elevation is True else dict(elevation).get("source", "depth")
+        if wants_map and map_source not in ("depth", "lidar"):
+            raise ValueError(f"Joystick(elevation=dict(source=...)): source must be 'depth' or 'lidar', not {map_source!r}")
+        if wants_map and map_source == "lidar":
+            if lidar is None:
+                raise ValueError("Joystick(elevation=dict(source='lidar')) needs lidar=dict(...): the elevation map is fused from the LiDAR's points")
+            if int(dict(lidar).get("every", 1)) != 1:
+                raise ValueError("Joystick(elevation=dict(source='lidar')) needs a LiDAR with every=1: the map would fuse a stale scan again at every tick")
+        if wants_map and map_source == "depth" and depth is None:
             raise ValueError("Joystick(elevation=...) needs depth=dict(...): the elevation map is fused from the onboard depth image")
-        if elevation is not None and elevation is not False and (int(dict(depth).get("every", 1)) != 1 or int(dict(depth).get("mount_body", 0)) != 0):
+        if wants_map and map_source == "depth" and (int(dict(depth).get("every", 1)) != 1 or int(dict(depth).get("mount_body", 0)) != 0):
             raise ValueError("Joystick(elevation=...) needs a camera on the torso (mount_body=0) with every=1: a stale image under a moved pose "
                              "would be unprojected wrongly")
         self.level_start = None
@@ -168,6 +184,10 @@ class Joystick:
         if depth is not None:
             from . import depth as _depth                     # libpgtt_depth.so is opened only here
             self.depth_camera = _depth.DepthCamera(self, **_depth.settings(depth))
+        self.lidar_scanner = None
+        if lidar is not None:
+            from . import lidar as _lidar                     # libpgtt_lidar.so is opened only here
+            self.lidar_scanner = _lidar.LidarScanner(self, **_lidar.settings(lidar))
         self.student = None
         if student is not None:
             from . import perceive as _perceive               # libpgtt_perceive.so is opened only here
@@ -255,6 +275,16 @@ class Joystick:
         return None if self.depth_camera is None else self.depth_camera.image
 
     @property
+    def lidar(self) -> Optional[torch.Tensor]:
+        """[N, R] float32 range scan of the onboard LiDAR (metres along the ray, `far` on a miss), or None without one"""
+        return None if self.lidar_scanner is None else self.lidar_scanner.ranges
+
+    @property
+    def lidar_points(self) -> Optional[torch.Tensor]:
+        """[N, R, 3] float32 world points of the LiDAR's returns (NaN where a ray has none), or None without a LiDAR"""
+        return None if self.lidar_scanner is None else self.lidar_scanner.points
+
+    @property
     def student_obs(self) -> Optional[torch.Tensor]:
         """[N, obs_dim] float32: the observation with its scan rows replaced by the student's estimate from the depth image, or None without one"""
         return None if self.student is None else self.student.obs
@@ -302,7 +332,7 @@ class Joystick:
                 "mean_level": float(self.buffers["level"].float().mean())}
 
     def set_terrain(self, terrain: np.ndarray) -> None:
-        """replace the resident terrain table (the depth camera's too; an elevation map forgets what it saw of the old one).  The tables are
+        """replace the resident terrain table (the depth camera's and the LiDAR's too; an elevation map forgets what it saw of the old one).  The tables are
         reallocated: a graph captured before this call still points at the old ones and must be captured again, not replayed"""
         t = np.ascontiguousarray(terrain, dtype=np.float32)
         assert t.ndim == 3 and t.shape[2] == 10 and t.shape[1] <= abi.MAX_BOX
@@ -310,6 +340,8 @@ class Joystick:
         self.terrain = t
         if getattr(self, "depth_camera", None) is not None:
             self.depth_camera.set_terrain(t)
+        if getattr(self, "lidar_scanner", None) is not None:
+            self.lidar_scanner.set_terrain(t)
         if getattr(self, "elevation_map", None) is not None:
             self.elevation_map.map.fill_(float("nan"))                # heights of the old terrain: the next tick starts from an empty map
 
@@ -328,6 +360,8 @@ class Joystick:
         native.check(self._lib.pgtt_reset(self._h, self._seed, self.env_id_offset, mp, self._stream()))
         if self.depth_camera is not None:
             self.depth_camera.tick(force=True)
+        if self.lidar_scanner is not None:
+            self.lidar_scanner.tick(force=True)
         if self.student is not None:
             if self.student.memory:
                 self.student.tick(clear_mask=mask, clear_all=mask is None)
@@ -348,6 +382,8 @@ class Joystick:
         native.check(self._lib.pgtt_step(self._h, a.data_ptr(), self._stream()))
         if self.depth_camera is not None:
             self.depth_camera.tick()
+        if self.lidar_scanner is not None:
+            self.lidar_scanner.tick()
         if self.student is not None:
             if self.student.memory:
                 self.student.tick(use_done=True)
@@ -408,6 +444,9 @@ class Joystick:
         if getattr(self, "depth_camera", None) is not None:
             self.depth_camera.close()
             self.depth_camera = None
+        if getattr(self, "lidar_scanner", None) is not None:
+            self.lidar_scanner.close()
+            self.lidar_scanner = None
         if getattr(self, "_h", None):
             self._lib.pgtt_destroy(self._h)
             self._h = C.c_void_p()

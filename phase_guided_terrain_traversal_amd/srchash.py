@@ -4,7 +4,7 @@ and csrc/flags.mk, the make fragment that holds the compile flags of that unit. 
 change the kernel).  The task-side kernels, the host code and the other rules of the Makefile are not covered: a change there leaves the hash,
 and with it the counters recorded under profiles/, valid.  EXTRA flags and the 1-ulp division are what the build's flavor says.
 
-The side libraries (csrc/pgtt_side.mk) embed a hash of their own, side_sha256("render" | "depth" | "perceive" | "elevation" | "learn"): the
+The side libraries (csrc/pgtt_side.mk) embed a hash of their own, side_sha256("render" | "depth" | "perceive" | "elevation" | "learn" | "lidar"): the
 include closure of their one translation unit, normalised the same way.  SIDE_SOURCES is the one statement of what a side library is built from:
 the hash, the make file's prerequisites and the closure test of tests/test_abi.py read it.  `python3 srchash.py` prints the physics hash,
 `python3 srchash.py render` a side hash, `python3 srchash.py --files render` the files that hash covers, one per line."""
@@ -22,7 +22,8 @@ SIDE_SOURCES = {"render": (("pgtt_render.hip",) + _RAYCAST, ("pgtt_render.h", "p
                 "depth": (("pgtt_depth.hip",) + _RAYCAST, ("pgtt_depth.h", "pgtt_render.h", "pgtt.h")),
                 "perceive": (("pgtt_perceive.hip",) + _PRELUDE, ("pgtt_perceive.h", "pgtt.h")),
                 "elevation": (("pgtt_elevation.hip",) + _PRELUDE, ("pgtt_elevation.h", "pgtt.h")),
-                "learn": (("pgtt_learn.hip",) + _PRELUDE, ("pgtt_learn.h", "pgtt.h"))}
+                "learn": (("pgtt_learn.hip",) + _PRELUDE, ("pgtt_learn.h", "pgtt.h")),
+                "lidar": (("pgtt_lidar.hip",) + _RAYCAST, ("pgtt_lidar.h", "pgtt_render.h", "pgtt.h"))}
 
 
 def hashed_files(pkg: str = _HERE):

@@ -1,0 +1,106 @@
+"""Times of the LiDAR and of the point-fed elevation map, with the protocol of DESIGN.md 14: 4096 envs, level4 with per-env variants
+from domain_randomize(seed=0), the default pattern of lidar.DEFAULTS, poses after 40 control steps of small random actions; device events around
+20 back-to-back calls after 5 warm-up calls, median [min, max] of 11 such windows, everything in one job.
+
+    python tools/gpu_lidar_time.py [--out profiles/NAME.txt] [--eval]
+
+(i) the LiDAR tick with the robot in the scene; (ii) without it; (iii) pgtt_elevation_points; and for scale, in the same job, (iv) the camera
+tick, (v) pgtt_elevation() and (vi) the env step (no sensor).  None of the figures is a pass criterion.
+--eval: evaluate.py's rollout of policy177 on level4, 1000 envs, full domain randomisation, one deterministic episode - on the true observation,
+on the depth-fused map and on the LiDAR-fused map, with the mean share of known scan points of the two maps."""
+import argparse
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from phase_guided_terrain_traversal_amd import configs, elevation, lidar, mjcf, perceive  # noqa: E402
+from phase_guided_terrain_traversal_amd.env import Joystick  # noqa: E402
+from phase_guided_terrain_traversal_amd.randomize import domain_randomize  # noqa: E402
+
+
+def window_us(fn, calls=20, warm=5, windows=11):
+    for _ in range(warm):
+        fn()
+    out = []
+    for _ in range(windows):
+        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        s.record()
+        for _ in range(calls):
+            fn()
+        e.record()
+        e.synchronize()
+        out.append(1e3 * s.elapsed_time(e) / calls)
+    return float(np.median(out)), min(out), max(out)
+
+
+def evaluation(n=1000):
+    import evaluate
+    base = ["--policy", "policy177", "--terrain_file", "level4"]
+    lines = [f"evaluate.py: policy177, level4, {n} envs, full DR, one deterministic episode"]
+    for name, extra in (("true observation", []), ("depth-fused map", ["--elevation"]), ("LiDAR-fused map", ["--elevation", "--elevation_source", "lidar"])):
+        r = evaluate.run_evaluation(evaluate.make_parser().parse_args(base + extra), num_eval_envs=n, verbose=False)
+        known = f", known scan points {r['known_share']:.3f}" if "known_share" in r else ""
+        lines.append(f"  {name:18s} survivors {r['survivors']} / {n}, reward {r['episode_reward']:.2f}, length {r['avg_episode_length']:.1f}, "
+                     f"tracking lin {r['tracking_lin_vel']:.3f} ang {r['tracking_ang_vel']:.3f}{known}")
+    return lines
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--num_envs", type=int, default=4096)
+    ap.add_argument("--out", type=str, default=None)
+    ap.add_argument("--eval", action="store_true")
+    args = ap.parse_args()
+    n = args.num_envs
+    terrain = np.load(os.path.join(ROOT, "phase_guided_terrain_traversal_amd", "assets", "terrains", "level4.npy"))
+    dr = domain_randomize(mjcf.load_model("stairs"), n, seed=0, terrain=terrain)
+    kw = dict(params=torch.from_numpy(dr["params"]), variant=torch.from_numpy(dr["variant"]), box_friction=torch.from_numpy(dr["box_friction"]))
+    cfg = configs.training_config()
+    env = Joystick("stairs", cfg, num_envs=n, terrain=terrain, device="cuda:0", lidar={}, elevation=dict(source="lidar"), **kw)
+    cam = Joystick("stairs", cfg, num_envs=n, terrain=terrain, device="cuda:0", depth={}, elevation=True, **kw)
+    plain = Joystick("stairs", cfg, num_envs=n, terrain=terrain, device="cuda:0", **kw)
+    g = torch.Generator().manual_seed(1)
+    for e in (env, cam, plain):
+        e.reset(0)
+    for _ in range(40):
+        act = (0.2 * torch.randn(n, 12, generator=g)).clamp(-1, 1).cuda()
+        for e in (env, cam, plain):
+            e.step(act)
+    blind = lidar.LidarScanner(env, **lidar.settings(dict(see_robot=False)))
+    torch.cuda.synchronize()
+    lid, em = env.lidar_scanner, env.elevation_map
+    rows = [("(i)   LiDAR tick (force), robot in the scene", window_us(lambda: lid.tick(force=True))),
+            ("(ii)  LiDAR tick (force), terrain only", window_us(lambda: blind.tick(force=True))),
+            ("(iii) pgtt_elevation_points, one launch", window_us(em.tick)),
+            ("(iv)  camera tick (force)", window_us(lambda: cam.depth_camera.tick(force=True))),
+            ("(v)   pgtt_elevation, one launch", window_us(cam.elevation_map.tick)),
+            ("(vi)  env step, no sensor", window_us(lambda: plain.step(act)))]
+    returns = float((torch.isfinite(lid.points).all(-1)).float().mean())
+    known_l, known_c = float((em.known > 0).float().mean()), float((cam.elevation_map.known > 0).float().mean())
+    c, cc = em.config, cam.depth_camera.config
+    lines = [f"{n} envs, level4, {lid.num_rays} rays (lidar.DEFAULTS), camera {cc.width}x{cc.height}, G = {c.grid}, res = {c.res:.3f}; us per call, median [min, max] of 11 windows "
+             "of 20 calls",
+             f"libpgtt_lidar build: {lidar.build_info()}", f"libpgtt_elevation build: {elevation.build_info()}"]
+    lines += [f"{name:50s} {m:9.1f} [{lo:.1f}, {hi:.1f}]" for name, (m, lo, hi) in rows]
+    lines.append(f"rays with a return inside (near, far): {returns:.3f}; (i) per ray {1e3 * rows[0][1][0] / (n * lid.num_rays):.3f} ns, (iv) per pixel "
+                 f"{1e3 * rows[3][1][0] / (n * cc.width * cc.height):.3f} ns")
+    lines.append(f"known scan points after 41 ticks of small random actions: LiDAR-fused map {known_l:.3f}, depth-fused map {known_c:.3f}")
+    for k, sl in perceive.BANDS.items():                                          # the scan rows by where they lie relative to the base
+        lines.append(f"  band {k:7s} LiDAR-fused {float((em.known[:, sl] > 0).float().mean()):.3f}, depth-fused {float((cam.elevation_map.known[:, sl] > 0).float().mean()):.3f}")
+    blind.close(); env.close(); cam.close(); plain.close()
+    if args.eval:
+        lines += evaluation()
+    text = "\n".join(lines)
+    print(text)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        open(args.out, "w").write(text + "\n")
+
+
+if __name__ == "__main__":
+    main()
