@@ -246,7 +246,9 @@ PG_INL void task_rewards(const float* sh_st, const float* sh_fr, const float* sh
       float q = sh_st[PGTT_S_QPOS + 7 + i], dq = q - m->key_qpos[7 + i];
       sa += on * fabsf(dq);
       pose += on * ((dq * dq) * ((i % 3) == 0 ? 1.0f : 0.1f));
-      float lo = m->jnt_range[i][0] * cfg->soft_joint_pos_limit_factor, hi = m->jnt_range[i][1] * cfg->soft_joint_pos_limit_factor;
+      // the reference holds the soft limits as float32 constants (go2/base.py:78-79): the product is ROUNDED before a joint is compared with it.
+      // Contracted into q - range * factor it is not, and a joint exactly at its limit pays the product's rounding error instead of 0
+      float lo = mul_unfused(m->jnt_range[i][0], cfg->soft_joint_pos_limit_factor), hi = mul_unfused(m->jnt_range[i][1], cfg->soft_joint_pos_limit_factor);
       lim += on * (-fminf(q - lo, 0.f) + fmaxf(q - hi, 0.f));
       float f = sh_fr[PGTT_F_ACT_FORCE + i];
       s2 += on * (f * f); s1 += on * fabsf(f);

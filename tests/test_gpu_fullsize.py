@@ -230,16 +230,13 @@ def test_task_layer_is_the_oracles_on_the_devices_own_physics_every_env_step(met
     step - and observations (171 + 215; noise draws included), reward, done, the 22 metrics, every `info` row after the step (command resampling, phase,
     air time, swing peak, H_max / H_min, histories, last contact, the counters) must agree to fp32 rounding.  No solver sits in between, so nothing is
     amplified: the ~22 % of env-steps outside W are covered like the rest."""
-    import ctypes as C
     from oracle import oracle
-    from test_golden_task import PostIn
+    from task_edge_cases import oracle_task_post, post_in
     n, steps, seed = 256, 60, 11
     cfg = configs.training_config(method)
     env, terrain, variant = make(n=n, cfg=cfg, autoreset=False)
     cs, ms = abi.config_struct(dict(env.config)), abi.model_struct(env.model)
     od, pd = abi.obs_dims(method)
-    L = oracle.lib()
-    L.pgtt_oracle_task_post_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_uint32]
     hb = oracle.HostBuffers(1, method=method)
     env.reset(seed)
     worst = {}
@@ -255,25 +252,7 @@ def test_task_layer_is_the_oracles_on_the_devices_own_physics_every_env_step(met
         Fr = g["frame"]
         for e in range(n):
             hb["state"][:, 0] = S0[:, e]; hb["istate"][:, 0] = I0[:, e]
-            pin = PostIn()
-            q = g["state"][:19, e].astype(np.float64)
-            np.ctypeslib.as_array(pin.qpos)[:] = q
-            np.ctypeslib.as_array(pin.qvel)[:] = g["state"][19:37, e]
-            sd = np.zeros(49)
-            sd[0:3] = Fr[abi.F_GYRO:abi.F_GYRO + 3, e]; sd[3:6] = Fr[abi.F_ACCEL:abi.F_ACCEL + 3, e]; sd[6:10] = q[3:7]
-            sd[13:16] = Fr[abi.F_GLOBAL_LINVEL:abi.F_GLOBAL_LINVEL + 3, e]; sd[16:19] = Fr[abi.F_GLOBAL_ANGVEL:abi.F_GLOBAL_ANGVEL + 3, e]
-            sd[19:22] = Fr[abi.F_LOCAL_LINVEL:abi.F_LOCAL_LINVEL + 3, e]; sd[22:25] = Fr[abi.F_UPVECTOR:abi.F_UPVECTOR + 3, e]
-            sd[25:37] = Fr[abi.F_FEET_POS:abi.F_FEET_POS + 12, e]; sd[37:49] = Fr[abi.F_FEET_VEL:abi.F_FEET_VEL + 12, e]
-            np.ctypeslib.as_array(pin.sensordata)[:] = sd
-            mat = np.zeros(9); mat[6:9] = -Fr[abi.F_GRAVITY:abi.F_GRAVITY + 3, e]          # the task layer reads the IMU frame's third row only (gravity)
-            np.ctypeslib.as_array(pin.site_imu_mat)[:] = mat
-            np.ctypeslib.as_array(pin.site_foot_z)[:] = Fr[abi.F_FOOT_SITE_Z:abi.F_FOOT_SITE_Z + 4, e]
-            np.ctypeslib.as_array(pin.actuator_force)[:] = Fr[abi.F_ACT_FORCE:abi.F_ACT_FORCE + 12, e]
-            np.ctypeslib.as_array(pin.action)[:] = act[e]
-            np.ctypeslib.as_array(pin.scan_z)[:] = g["scan_z"][e]
-            np.ctypeslib.as_array(pin.contact)[:] = Fr[abi.F_CONTACT:abi.F_CONTACT + 4, e].astype(np.int32)
-            b = hb.struct()
-            L.pgtt_oracle_task_post_ex(C.byref(cs), C.byref(ms), C.byref(b), C.byref(pin), 0, C.c_uint64(seed), C.c_uint32(e))
+            oracle_task_post(cs, ms, hb, post_in(g["state"][:, e], Fr[:, e], g["scan_z"][e], act[e]), 0, seed, e)
             errs = dict(obs=np.abs(hb["obs_state"][0] - g["obs_state"][e]).max(), priv=np.abs(hb["obs_priv"][0] - g["obs_priv"][e]).max(),
                         reward=abs(float(hb["reward"][0]) - float(g["reward"][e])), metrics=(np.abs(hb["metrics"][:, 0] - g["metrics"][:, e]) / (1 + np.abs(hb["metrics"][:, 0]))).max(),
                         info=np.abs(hb["state"][abi.S_CMD:, 0] - g["state"][abi.S_CMD:, e]).max())
