@@ -13,7 +13,7 @@ is built.  The policy comes from `--checkpoint_folder` (the newest `<env_steps>.
 `--policy` (an .npz path or the name of a shipped policy); with `--student student.npz` (train_student.py) the policy acts on the observation
 whose scan rows the student perception module estimated from the onboard depth image, with `--elevation [grid,res,alpha]` on the observation whose
 scan rows are sampled from the depth-fused elevation map (elevation.py; nothing to train; `--elevation_source lidar` fuses it from the onboard
-LiDAR's points instead, lidar.py); the remaining flags of the reference's CLI are accepted and ignored.
+LiDAR's points instead, lidar.py; `--elevation_fill [K]` closes the map's holes first and the policy acts on the filled scan); the remaining flags of the reference's CLI are accepted and ignored.
 """
 import argparse
 import os
@@ -158,6 +158,13 @@ def run_evaluation(args, num_eval_envs=NUM_EVAL_ENVS, seed=0, verbose=True):
             given = dict(zip(("grid", "res", "alpha"), (int(vals[0]),) + tuple(float(v) for v in vals[1:]))) if vals else True
         except ValueError:
             raise SystemExit(f"--elevation {elev}: grid must be an integer, res and alpha numbers")
+        fill = getattr(args, "elevation_fill", None)
+        if fill is not None:
+            # --elevation_fill [K]: the map's holes are closed behind every tick (K passes, 16 unless given) and the policy acts on
+            # env.elevation_filled_obs, the observation whose scan rows are sampled from the filled map
+            if fill is not True and not 1 <= fill <= 95:                 # a caller that built the namespace without the parser
+                raise SystemExit(f"--elevation_fill {fill}: the number of passes must be in [1, 95]")
+            given = dict({} if given is True else given, fill=fill)
         source = getattr(args, "elevation_source", "depth")
         if source == "lidar":
             # --elevation_source lidar: the map is fused from the world points of the onboard LiDAR (lidar.DEFAULTS), as the deployed mapping stack's is
@@ -166,8 +173,12 @@ def run_evaluation(args, num_eval_envs=NUM_EVAL_ENVS, seed=0, verbose=True):
             kw.update(depth={}, elevation=given)
     elif getattr(args, "elevation_source", "depth") != "depth":
         raise SystemExit("--elevation_source says what --elevation is fused from: give --elevation too")
+    elif getattr(args, "elevation_fill", None) is not None:
+        raise SystemExit("--elevation_fill fills the holes of --elevation's map: give --elevation too")
     env = Joystick(args.task_name, cfg, num_envs=n, terrain=terrain, device=DEVICE, autoreset=True, **kw)
-    if env.elevation_map is not None:
+    if env.elevation_filled_obs is not None:
+        acts_on = env.elevation_filled_obs
+    elif env.elevation_map is not None:
         acts_on = env.elevation_obs
     elif env.student is not None:
         acts_on = env.student_obs
@@ -184,12 +195,15 @@ def run_evaluation(args, num_eval_envs=NUM_EVAL_ENVS, seed=0, verbose=True):
     ret = torch.zeros(n, device=dev); length = torch.zeros(n, device=dev); fell = torch.zeros(n, dtype=torch.bool, device=dev)
     terms = torch.zeros(abi.NMETRIC, n, device=dev)
     known = torch.zeros(n, device=dev)                                            # with a map: the scan points it knew, summed over the first episode
+    covered = torch.zeros(n, device=dev)                                          # with a fill: the scan points it knew or filled
     video = VideoRecorder(args, env, L) if getattr(args, "video", None) else None
     for t in range(L):
         if video is not None:
             video.capture(t)
         if env.elevation_map is not None:
             known += env.elevation_known.float().mean(1) * first.float()
+        if env.elevation_dist is not None:
+            covered += (env.elevation_dist != 255).float().mean(1) * first.float()
         _, reward, done, info = env.step(pi(acts_on))
         w = first.float()
         ret += reward * w; length += w; terms += info["metrics"] * w
@@ -203,6 +217,8 @@ def run_evaluation(args, num_eval_envs=NUM_EVAL_ENVS, seed=0, verbose=True):
            "tracking_lin_vel": float(terms[i_lin].mean()) / (sc["tracking_lin_vel"] * L), "tracking_ang_vel": float(terms[i_ang].mean()) / (sc["tracking_ang_vel"] * L)}
     if env.elevation_map is not None:
         out["known_share"] = float((known / length.clamp(min=1)).mean())          # mean share of the 117 scan points the map knew when the policy acted
+    if env.elevation_dist is not None:
+        out["covered_share"] = float((covered / length.clamp(min=1)).mean())      # ... that the map knew or the fill reached (dist != 255)
     if video is not None:
         out["video"] = video.write(verbose)
     env.close()
@@ -215,6 +231,17 @@ def run_evaluation(args, num_eval_envs=NUM_EVAL_ENVS, seed=0, verbose=True):
 def run_training(args):
     """the name evaluate_multiple.py imports (training/evaluate_multiple.py:7): number of evaluation envs that did not fall"""
     return run_evaluation(args)["survivors"]
+
+
+def fill_passes(text):
+    """--elevation_fill K: an integer in [1, 95] (elevation.MAX_FILL); the flag without a value is True, elevation.FILL_PASSES"""
+    try:
+        k = int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"{text!r} is not a number of passes")
+    if not 1 <= k <= 95:
+        raise argparse.ArgumentTypeError(f"the number of passes must be in [1, 95], not {k}")
+    return k
 
 
 def make_parser():
@@ -243,6 +270,8 @@ def make_parser():
                     help="the policy acts on the scan rows sampled from the depth-fused elevation map (elevation.py); optional grid[,res[,alpha]]")
     ap.add_argument("--elevation_source", type=str, default="depth", choices=("depth", "lidar"),
                     help="with --elevation: fuse the map from the depth camera's image (default) or from the onboard LiDAR's points (lidar.py)")
+    ap.add_argument("--elevation_fill", type=fill_passes, nargs="?", const=True, default=None, metavar="K",
+                    help="with --elevation: close the map's holes with K passes (16 unless given) behind every tick; the policy acts on the filled scan")
     configs.add_push_args(ap)
     ap.add_argument("--terrain_files", type=str, default=None, help="comma-separated level files stacked into one table (as train.py --terrain_files); evaluated on --level")
     ap.add_argument("--level", type=int, default=0, help="with --terrain_files: the level every evaluation env stands on (no curriculum at evaluation)")

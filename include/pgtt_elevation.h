@@ -71,6 +71,28 @@
  * The camera fields of the config (width .. mount_quat) are not read by it; they must still be valid for pgtt_elevation_create.
  * Both sources may feed one handle: bound by pgtt_elevation_bind_points with a depth image too, pgtt_elevation() is what it is on a handle bound
  * by pgtt_elevation_bind.
+ *
+ * Hole filling.  pgtt_elevation_fill() is a launch of its own behind a tick.  It READS what the tick left - `map`, `origin`, `state` and `obs` as
+ * they are bound - and writes only the outputs of PgttElevationFill: never `map`, `origin`, `est`, `known` or the tick's `obs_out`.  A filled height
+ * is a hypothesis (what a sensor cannot see is usually lower than what it can): it is never fused, and the next tick does not see it.
+ * Per env, with lo = origin - G/2: the window cell (a, b), 0 <= a, b < G, is world cell (lo_x + a, lo_y + b), stored at slot
+ * ((lo_x + a) mod G, (lo_y + b) mod G) as above.
+ *   Start.   D(a, b) = 0 where the cell is not NaN, else 255; W = the map.
+ *   Pass p = 1 .. passes.  Every cell that still has D = 255 looks at its up to eight neighbours (a +- 1, b +- 1) INSIDE THE WINDOW - the window's
+ *            edges are edges; the toroidal storage does not connect the far sides - and of them at those that were known at the end of pass
+ *            p - 1 (D < p).  If there is one: W = the minimum of their values, D = p.  A cell filled in pass p is not a source in pass p (a Jacobi
+ *            pass), so the result does not depend on the order of the lanes, and D is the Chebyshev distance inside the window to the nearest
+ *            measured cell, for distances up to `passes`.
+ *   Minimum. In the total order of the tick maximum's integer key: -0 < +0, the infinities are ordinary values, and the result is one of the inputs
+ *            bit for bit.
+ *   Stopping after a pass that filled nothing has no visible effect, and is done.  1 <= passes <= PGTT_ELEVATION_MAX_GRID - 1: more cannot fill
+ *            anything in a window of 96 cells, and D fits a byte with 255 free.
+ *   Sample.  Step 5 on the filled window: z[i], dist[i] = W, D of the cell that contains scan point i; dist[i] = 255 outside the window or where the
+ *            cell is still unknown.  A point with dist = 255 takes the minimum (in the key's order) over the others; every z is 0 when there are
+ *            none.  est[i] = z[i] - min z.
+ *   Assemble.  Step 6 into the fill's own obs_out.
+ *   Dense.   map_out is W and dist_out is D, both in the map's slot layout; a cell that is still unknown is NaN.
+ * An origin outside +-2^30 (a map never ticked) is taken as +-2^30.  One launch, one workgroup per env, W and D of the window and a border of one cell in LDS: 5 (G + 2)^2 bytes.
  */
 #ifndef PGTT_ELEVATION_H_
 #define PGTT_ELEVATION_H_
@@ -133,6 +155,24 @@ int pgtt_elevation_bind_points(pgtt_elevation_handle h, const PgttElevationBuffe
 /* one tick for all N envs from the bound points: one launch, as pgtt_elevation().  PGTT_E_STATE before pgtt_elevation_bind_points; pgtt_elevation()
  * on a handle bound with depth == NULL is PGTT_E_STATE too. */
 int pgtt_elevation_points(pgtt_elevation_handle h, const uint8_t* clear_mask, int clear_all, int use_done, void* stream);
+
+/* device pointers of the hole filling's outputs, caller-owned, sized for N */
+typedef struct PgttElevationFill {
+  float* est;                            /* [N][PGTT_NSCAN], required */
+  uint8_t* dist;                         /* [N][PGTT_NSCAN], required: 0 measured, 1..passes the pass that filled it, 255 unknown */
+  float* obs_out;                        /* [N][obs_dim] or NULL */
+  float* map_out;                        /* [N][G][G] or NULL */
+  uint8_t* dist_out;                     /* [N][G][G] or NULL */
+} PgttElevationFill;
+
+/* PGTT_E_ARG for a NULL struct, a NULL required pointer or passes outside 1 .. PGTT_ELEVATION_MAX_GRID - 1.  May be called before or after the
+ * buffers are bound; the binding persists across later pgtt_elevation_bind / pgtt_elevation_bind_points. */
+int pgtt_elevation_bind_fill(pgtt_elevation_handle h, const PgttElevationFill* out, int passes);
+/* the hole filling for all N envs: one launch on `stream`, one workgroup of 256 lanes per env, no allocation and no synchronisation, so it can be
+ * captured.  PGTT_E_STATE before the buffers are bound (either kind of bind) or before pgtt_elevation_bind_fill; PGTT_E_ARG when the fill's obs_out
+ * is bound and the buffers' obs is NULL. */
+int pgtt_elevation_fill(pgtt_elevation_handle h, void* stream);
+int pgtt_elevation_sizeof_fill(void);
 int pgtt_elevation_sizeof_config(void);
 int pgtt_elevation_sizeof_buffers(void);
 /* "src=<SHA-256 of pgtt_elevation.hip and the files it includes>;flavor=product" */

@@ -13,6 +13,18 @@
 //   phase E  lanes 0 .. 116 sample the scan, the minimum over the known points is a wave reduction and one LDS exchange; est, known.
 //   phase F  obs_out = obs with the scan rows replaced.
 // The phases are separated by workgroup barriers.  No global atomics, no scratch; nothing is shared between envs.
+//
+// fill_kernel, the hole filling behind a tick: one workgroup of four waves per env again.  LDS holds the window in WINDOW order inside a border of one
+// cell, one key word (key_of the value; kNoKey = a hole or the border) and one byte `D` per cell: 5 (G + 2)^2 bytes, 48020 at G = 96, under the
+// 64 KB that need no launch attribute.  The border makes the window's edges edges and keeps every neighbour's index in range.
+//   load     the map streams in as in phase D (16-byte runs, dwords for an odd G), every slot to its window cell; lane 0 stages the base position, the
+//            yaw's sine and cosine and the window of the stored origin.
+//   pass p   every hole takes the minimum key over its neighbours with D < p, and D = p.  A cell written in this pass reads as a hole or as a key
+//            with D = p or still 255, none of them a source, so one barrier per pass suffices and there are no atomics; a flag every lane reads
+//            alike ends the loop after a pass that filled nothing.
+//   sample   lanes 0 .. 116 read the key and D at the scan points (scan_slot, the tick's); the minimum over the covered points is taken on the keys.
+//   out      est, dist, obs_out (assemble, the tick's), map_out and dist_out in the map's slot layout.
+// It writes nothing the tick reads.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -26,6 +38,7 @@ namespace {
 constexpr int kLanes = 256;                       // four waves per env
 constexpr int kMaxG = PGTT_ELEVATION_MAX_GRID;
 constexpr float kCellClamp = 1.0e9f;              // |cell index| stays below 2^30: a far-away or NaN coordinate cannot overflow the integer window test
+static_assert(5 * (kMaxG + 2) * (kMaxG + 2) + 1024 <= 65536 && kMaxG - 1 < 255, "the fill's W and D with its staging stay under 64 KB of LDS; D fits a byte with 255 free");
 static_assert(PGTT_NSCAN <= 128 && 2 * kMaxG <= kLanes && 4 * kMaxG * kMaxG <= 36864, "two waves sample the scan; one lane per slot row and column");
 
 struct ElevArgs {
@@ -48,6 +61,34 @@ __device__ __forceinline__ int floor_mod(int a, int g) { const int r = a % g; re
 // fp32 -> a key whose unsigned order is the order of the floats; no finite value maps to 0
 __device__ __forceinline__ unsigned key_of(float z) { const unsigned b = __float_as_uint(z); return b ^ ((unsigned)((int)b >> 31) | 0x80000000u); }
 __device__ __forceinline__ float value_of(unsigned k) { return __uint_as_float(k ^ (((k >> 31) - 1u) | 0x80000000u)); }
+
+// the sine and cosine of the yaw of a normalised base quaternion
+__device__ __forceinline__ void yaw_sincos(float qw, float qx, float qy, float qz, float& sy, float& cy) {
+  const float yaw = atan2f(2.0f * (qw * qz + qx * qy), 1.0f - 2.0f * (qy * qy + qz * qz));
+  sincosf(yaw, &sy, &cy);
+}
+// the slot of the cell that contains scan point i = 9 r + c, or -1 outside the window.  pose: P_BASE, P_SY, P_CY; win: I_LOX .. I_LMY
+__device__ __forceinline__ int scan_slot(int i, const float* pose, const int* win, float sdx, float sdy, float res, int G) {
+  const int r = i / PGTT_SCAN_W, c = i - r * PGTT_SCAN_W;
+  const float ox = ((float)(PGTT_SCAN_H - 1) * 0.5f - (float)r) * sdx, oy = ((float)(PGTT_SCAN_W - 1) * 0.5f - (float)c) * sdy;
+  const float sy = pose[P_SY], cy = pose[P_CY];
+  const float wx = pose[P_BASE + 0] + (ox * cy + oy * (-sy)), wy = pose[P_BASE + 1] + (ox * sy + oy * cy);
+  const int relx = cell_of(wx, res) - win[I_LOX], rely = cell_of(wy, res) - win[I_LOY];
+  int slot = -1;
+  if ((unsigned)relx < (unsigned)G && (unsigned)rely < (unsigned)G) {
+    int sx = relx + win[I_LMX], sy2 = rely + win[I_LMY];
+    sx -= sx >= G ? G : 0; sy2 -= sy2 >= G ? G : 0;
+    slot = sx * G + sy2;
+  }
+  return slot;
+}
+// env e's row of obs_out = its row of obs with the scan rows replaced by est (LDS)
+__device__ __forceinline__ void assemble(float* obs_out, const float* obs, const float* est, int e, int od, int row0, int tid) {
+  for (int k = tid; k < od; k += kLanes) {
+    const int j = k - row0;
+    obs_out[(long)e * od + k] = (j >= 0 && j < PGTT_NSCAN) ? est[j] : obs[(long)e * od + k];
+  }
+}
 
 template <bool POINTS>
 __global__ void __launch_bounds__(kLanes) elevation_kernel(ElevArgs a) {
@@ -88,8 +129,7 @@ __global__ void __launch_bounds__(kLanes) elevation_kernel(ElevArgs a) {
       sh_p[P_UP + 0] = ux; sh_p[P_UP + 1] = uy; sh_p[P_UP + 2] = uz;
       sh_p[P_RIGHT + 0] = fy * uz - fz * uy; sh_p[P_RIGHT + 1] = fz * ux - fx * uz; sh_p[P_RIGHT + 2] = fx * uy - fy * ux;
     }
-    const float yaw = atan2f(2.0f * (qw * qz + qx * qy), 1.0f - 2.0f * (qy * qy + qz * qz));
-    float sy, cy; sincosf(yaw, &sy, &cy);
+    float sy, cy; yaw_sincos(qw, qx, qy, qz, sy, cy);
     sh_p[P_SY] = sy; sh_p[P_CY] = cy;
     // clear, the old and the new window
     const bool clear = a.clear_all || (a.clear_mask && a.clear_mask[e]) || (a.use_done && a.done && a.done[e] != 0.f);
@@ -230,15 +270,9 @@ __global__ void __launch_bounds__(kLanes) elevation_kernel(ElevArgs a) {
   float z = 0.f;
   bool kn = false;
   if (tid < PGTT_NSCAN) {
-    const int r = tid / PGTT_SCAN_W, c = tid - r * PGTT_SCAN_W;
-    const float ox = ((float)(PGTT_SCAN_H - 1) * 0.5f - (float)r) * a.sdx, oy = ((float)(PGTT_SCAN_W - 1) * 0.5f - (float)c) * a.sdy;
-    const float sy = sh_p[P_SY], cy = sh_p[P_CY];
-    const float wx = sh_p[P_BASE + 0] + (ox * cy + oy * (-sy)), wy = sh_p[P_BASE + 1] + (ox * sy + oy * cy);
-    const int relx = cell_of(wx, a.res) - sh_i[I_LOX], rely = cell_of(wy, a.res) - sh_i[I_LOY];
-    if ((unsigned)relx < (unsigned)G && (unsigned)rely < (unsigned)G) {
-      int sx = relx + sh_i[I_LMX], sy2 = rely + sh_i[I_LMY];
-      sx -= sx >= G ? G : 0; sy2 -= sy2 >= G ? G : 0;
-      z = __uint_as_float(sh_m[sx * G + sy2]);
+    const int slot = scan_slot(tid, sh_p, sh_i, a.sdx, a.sdy, a.res, G);
+    if (slot >= 0) {
+      z = __uint_as_float(sh_m[slot]);
       kn = z == z;
     }
   }
@@ -258,11 +292,173 @@ __global__ void __launch_bounds__(kLanes) elevation_kernel(ElevArgs a) {
   // ---- phase F: obs_out = obs with the scan rows replaced
   if (a.obs_out) {
     __syncthreads();
-    const int od = a.obs_dim;
-    for (int k = tid; k < od; k += kLanes) {
-      const int j = k - a.scan_row0;
-      a.obs_out[(long)e * od + k] = (j >= 0 && j < PGTT_NSCAN) ? sh_est[j] : a.obs[(long)e * od + k];
+    assemble(a.obs_out, a.obs, sh_est, e, a.obs_dim, a.scan_row0, tid);
+  }
+}
+
+struct FillArgs {
+  const float* state; const float* obs; const float* map; const int32_t* origin;
+  float* est; uint8_t* dist; float* obs_out; float* map_out; uint8_t* dist_out;
+  int N, G, obs_dim, scan_row0, passes, vec_map, vec_out, vec_dist;
+  float res, sdx, sdy;
+};
+
+constexpr unsigned kNoKey = 0xffffffffu;          // above the key of every value but a NaN's, and a NaN is never a source
+constexpr int kUnknown = 255;
+
+__global__ void __launch_bounds__(kLanes) fill_kernel(FillArgs a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned sh_k[];      // [(G + 2)^2] keys in WINDOW order inside a border, then as many D bytes
+  __shared__ float sh_p[P_N];
+  __shared__ int sh_i[I_N];
+  __shared__ float sh_est[PGTT_NSCAN];
+  __shared__ unsigned sh_red[2];
+  __shared__ int sh_any[3];                                            // pass p raises [p % 3] and lowers [(p + 1) % 3]: nobody still reads that one
+  const int e = blockIdx.x, tid = threadIdx.x, G = a.G, GG = G * G, S = G + 2;
+  const long N = a.N;
+  unsigned char* sh_d = reinterpret_cast<unsigned char*>(sh_k + S * S);
+  // the origin as the tick left it; one outside the tick's clamp (a map never ticked) is as far away as the clamp.  Every lane forms the window
+  // (two broadcast reads), so the load needs no barrier in front of it
+  const int ox = min(max(a.origin[2 * (long)e], -(1 << 30)), 1 << 30), oy = min(max(a.origin[2 * (long)e + 1], -(1 << 30)), 1 << 30);
+  const int lox = ox - G / 2, loy = oy - G / 2, lmx = floor_mod(lox, G), lmy = floor_mod(loy, G);
+  // slot (sx, sy) -> its place in the bordered window: row (sx - lmx) mod G, column (sy - lmy) mod G, both + 1
+  auto place = [&](int sx, int sy) {
+    int wa = sx - lmx, wb = sy - lmy;
+    wa += wa < 0 ? G : 0; wb += wb < 0 ? G : 0;
+    return (wa + 1) * S + wb + 1;
+  };
+
+  // ---- load: the pose (lane 0); the border, which is never a source and never filled; the keys and D of the map's slots
+  if (tid == 0) {
+    const float* St = a.state + e;
+    float qw = St[(PGTT_S_QPOS + 3) * N], qx = St[(PGTT_S_QPOS + 4) * N], qy = St[(PGTT_S_QPOS + 5) * N], qz = St[(PGTT_S_QPOS + 6) * N];
+    const float qn = sqrtf(qw * qw + qx * qx + qy * qy + qz * qz);
+    qw /= qn; qx /= qn; qy /= qn; qz /= qn;
+    sh_p[P_BASE + 0] = St[(PGTT_S_QPOS + 0) * N]; sh_p[P_BASE + 1] = St[(PGTT_S_QPOS + 1) * N];
+    float sy, cy; yaw_sincos(qw, qx, qy, qz, sy, cy);
+    sh_p[P_SY] = sy; sh_p[P_CY] = cy;
+    sh_i[I_LOX] = lox; sh_i[I_LOY] = loy; sh_i[I_LMX] = lmx; sh_i[I_LMY] = lmy;
+    sh_any[0] = 0; sh_any[1] = 0; sh_any[2] = 0;
+  }
+  for (int i = tid; i < S; i += kLanes) {
+    const int edge[4] = {i, (S - 1) * S + i, i * S, i * S + S - 1};
+#pragma unroll
+    for (int k = 0; k < 4; k++) { sh_k[edge[k]] = kNoKey; sh_d[edge[k]] = kUnknown; }
+  }
+  {
+    const float* mp = a.map + (long)e * GG;
+    auto put = [&](float h, int sx, int sy) {
+      const int c = place(sx, sy);
+      sh_k[c] = h != h ? kNoKey : key_of(h);
+      sh_d[c] = h != h ? kUnknown : 0;
+    };
+    if (a.vec_map) {
+      for (int s = 4 * tid; s < GG; s += 4 * kLanes) {
+        const float4 hv = *reinterpret_cast<const float4*>(mp + s);
+        int sx = s / G, sy = s - sx * G;
+        const float h[4] = {hv.x, hv.y, hv.z, hv.w};
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+          put(h[k], sx, sy);
+          sy++;
+          if (sy == G) { sy = 0; sx++; }
+        }
+      }
+    } else {
+      for (int s = tid; s < GG; s += kLanes) { const int sx = s / G; put(mp[s], sx, s - sx * G); }
     }
+  }
+  __syncthreads();
+
+  // ---- the passes: eight rows of 32 lanes walk the window.  A hole reads its eight neighbours' keys; the border and the holes read kNoKey, so a
+  // hole with nothing around it costs eight reads and no read of D.  A neighbour that holds a key is a source iff its D < p: one filled in this pass
+  // reads D = p, or still 255, and is none either way - so W and D need one barrier per pass and no atomics.
+  {
+    const int tx = tid & 31, ty = tid >> 5;
+    for (int p = 1; p <= a.passes; p++) {
+      if (tid == 0) sh_any[(p + 1) % 3] = 0;
+      bool filled = false;
+      for (int wa = ty; wa < G; wa += kLanes / 32) {
+        for (int wb = tx; wb < G; wb += 32) {
+          const int c = (wa + 1) * S + wb + 1;                         // S + 1 <= c <= S * S - S - 2: every neighbour is inside [0, S * S)
+          if (sh_k[c] != kNoKey) continue;
+          const int nb[8] = {c - S - 1, c - S, c - S + 1, c - 1, c + 1, c + S - 1, c + S, c + S + 1};
+          unsigned best = kNoKey;
+#pragma unroll
+          for (int k = 0; k < 8; k++) {
+            const unsigned key = sh_k[nb[k]];
+            if (key != kNoKey && (int)sh_d[nb[k]] < p) best = min(best, key);
+          }
+          if (best != kNoKey) {
+            sh_d[c] = (unsigned char)p;
+            sh_k[c] = best;
+            filled = true;
+          }
+        }
+      }
+      if (filled) sh_any[p % 3] = 1;
+      __syncthreads();
+      if (!sh_any[p % 3]) break;                                       // every lane reads the same word: the branch is uniform
+    }
+  }
+
+  // ---- sample: the scan on the filled window
+  unsigned zk = kNoKey;
+  int d = kUnknown;
+  if (tid < PGTT_NSCAN) {
+    const int slot = scan_slot(tid, sh_p, sh_i, a.sdx, a.sdy, a.res, G);
+    if (slot >= 0) {
+      const int sx = slot / G, c = place(sx, slot - sx * G);
+      d = sh_d[c];
+      zk = d != kUnknown ? sh_k[c] : kNoKey;
+    }
+  }
+  unsigned kmin = zk;
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) kmin = min(kmin, (unsigned)__shfl_xor((int)kmin, off, 64));
+  if (tid < 128 && (tid & 63) == 0) sh_red[tid >> 6] = kmin;
+  __syncthreads();
+  kmin = min(sh_red[0], sh_red[1]);
+  if (tid < PGTT_NSCAN) {
+    const float zmin = kmin != kNoKey ? value_of(kmin) : 0.f;
+    const float es = (d != kUnknown ? value_of(zk) : zmin) - zmin;
+    sh_est[tid] = es;
+    a.est[(long)e * PGTT_NSCAN + tid] = es;
+    a.dist[(long)e * PGTT_NSCAN + tid] = (uint8_t)d;
+  }
+
+  // ---- out: the dense window in the map's slot layout; obs_out
+  if (a.map_out || a.dist_out) {
+    float* mo = a.map_out ? a.map_out + (long)e * GG : nullptr;
+    uint8_t* dd = a.dist_out ? a.dist_out + (long)e * GG : nullptr;
+    const unsigned nanv = 0x7fc00000u;
+    if (a.vec_out && a.vec_dist) {
+      for (int s = 4 * tid; s < GG; s += 4 * kLanes) {
+        int sx = s / G, sy = s - sx * G;
+        unsigned w[4], d4 = 0;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+          const int c = place(sx, sy);
+          const unsigned dk = sh_d[c];
+          w[k] = dk != kUnknown ? __float_as_uint(value_of(sh_k[c])) : nanv;
+          d4 |= dk << (8 * k);
+          sy++;
+          if (sy == G) { sy = 0; sx++; }
+        }
+        if (mo) *reinterpret_cast<uint4*>(mo + s) = make_uint4(w[0], w[1], w[2], w[3]);
+        if (dd) *reinterpret_cast<unsigned*>(dd + s) = d4;
+      }
+    } else {
+      for (int s = tid; s < GG; s += kLanes) {
+        const int sx = s / G, c = place(sx, s - sx * G);
+        const unsigned dk = sh_d[c];
+        if (mo) mo[s] = __uint_as_float(dk != kUnknown ? __float_as_uint(value_of(sh_k[c])) : nanv);
+        if (dd) dd[s] = (uint8_t)dk;
+      }
+    }
+  }
+  if (a.obs_out) {
+    __syncthreads();
+    assemble(a.obs_out, a.obs, sh_est, e, a.obs_dim, a.scan_row0, tid);
   }
 }
 
@@ -299,6 +495,8 @@ struct pgtt_elevation_map {
   bool bound = false;
   const float* points = nullptr;         // pgtt_elevation_bind_points; nullptr after pgtt_elevation_bind
   int P = 0;
+  PgttElevationFill fill{};              // pgtt_elevation_bind_fill; kept by the other two binds
+  int passes = 0;                        // 0 = no fill bound
 };
 
 namespace {
@@ -345,6 +543,7 @@ extern "C" {
 PGTT_SIDE_EXPORTS(elevation, ELEVATION)
 int pgtt_elevation_sizeof_config(void) { return (int)sizeof(PgttElevationConfig); }
 int pgtt_elevation_sizeof_buffers(void) { return (int)sizeof(PgttElevationBuffers); }
+int pgtt_elevation_sizeof_fill(void) { return (int)sizeof(PgttElevationFill); }
 
 int pgtt_elevation_check(const PgttElevationConfig* cfg) { return resolve(cfg, "pgtt_elevation_check"); }
 
@@ -401,6 +600,39 @@ int pgtt_elevation_points(pgtt_elevation_handle h, const uint8_t* clear_mask, in
   if (!h) return fail(PGTT_E_ARG, "pgtt_elevation_points: null handle");
   if (!h->points) return fail(PGTT_E_STATE, "pgtt_elevation_points: no points bound (pgtt_elevation_bind_points first)");
   return launch(h, true, clear_mask, clear_all, use_done, stream);
+}
+
+int pgtt_elevation_bind_fill(pgtt_elevation_handle h, const PgttElevationFill* out, int passes) {
+  if (!h || !out) return fail(PGTT_E_ARG, "pgtt_elevation_bind_fill: null argument");
+  if (!out->est || !out->dist) return fail(PGTT_E_ARG, "pgtt_elevation_bind_fill: est and dist are required");
+  if (passes < 1 || passes > PGTT_ELEVATION_MAX_GRID - 1) return fail(PGTT_E_ARG, "pgtt_elevation_bind_fill: passes must be in [1, 95]");
+  h->fill = *out;
+  h->passes = passes;
+  return PGTT_OK;
+}
+
+int pgtt_elevation_fill(pgtt_elevation_handle h, void* stream) {
+  if (!h) return fail(PGTT_E_ARG, "pgtt_elevation_fill: null handle");
+  if (!h->bound) return fail(PGTT_E_STATE, "pgtt_elevation_fill: no buffers bound (pgtt_elevation_bind or pgtt_elevation_bind_points first)");
+  if (!h->passes) return fail(PGTT_E_STATE, "pgtt_elevation_fill: no outputs bound (pgtt_elevation_bind_fill first)");
+  if (h->fill.obs_out && !h->buf.obs) return fail(PGTT_E_ARG, "pgtt_elevation_fill: obs is required with the fill's obs_out");
+  HIP_TRY(hipSetDevice(h->device));
+  const PgttElevationConfig& c = h->cfg;
+  const PgttElevationFill& o = h->fill;
+  FillArgs a{};
+  a.state = h->buf.state; a.obs = h->buf.obs; a.map = h->buf.map; a.origin = h->buf.origin;
+  a.est = o.est; a.dist = o.dist; a.obs_out = o.obs_out; a.map_out = o.map_out; a.dist_out = o.dist_out;
+  a.N = h->num_envs; a.G = c.grid; a.obs_dim = c.obs_dim; a.scan_row0 = c.scan_row0; a.passes = h->passes;
+  // 16-byte (map, map_out) and 4-byte (dist_out) runs need every env's block to start on such a boundary
+  const bool quads = (c.grid * c.grid) % 4 == 0;
+  a.vec_map = (quads && ((uintptr_t)a.map & 15) == 0) ? 1 : 0;
+  a.vec_out = (quads && ((uintptr_t)o.map_out & 15) == 0) ? 1 : 0;
+  a.vec_dist = (quads && ((uintptr_t)o.dist_out & 3) == 0) ? 1 : 0;          // a NULL output counts as aligned: it is not written
+  a.res = c.res; a.sdx = c.scan_dist_x; a.sdy = c.scan_dist_y;
+  const size_t lds = (size_t)(c.grid + 2) * (c.grid + 2) * (sizeof(unsigned) + 1);
+  hipLaunchKernelGGL(fill_kernel, dim3(h->num_envs), dim3(kLanes), lds, (hipStream_t)stream, a);
+  HIP_TRY(hipGetLastError());
+  return PGTT_OK;
 }
 
 }  // extern "C"

@@ -7,6 +7,9 @@ points of the env's LiDAR (lidar.py) instead: the sensor such a stack reads on t
     em.tick(clear_all=True)                                  # one launch on the env's current stream, no synchronisation
     em.map, em.origin, em.est, em.known, em.obs              # [N, G, G] heights (NaN = unknown), [N, 2], [N, 117], [N, 117] uint8, [N, obs_dim]
 
+    em = ElevationMap(env, fill=16)                          # hole filling behind every tick: a second launch with outputs of its own
+    em.filled_est, em.filled_dist, em.filled_obs             # [N, 117], [N, 117] uint8 (0 measured, 1..16 the pass that filled it, 255 unknown), [N, obs_dim]
+
 `Joystick(..., depth=dict(...), elevation=dict(...) | True)` owns one and ticks it behind the camera (env.elevation_obs);
 `Joystick(..., lidar=dict(...), elevation=dict(source="lidar"))` one that is ticked behind the LiDAR.  The module is not imported by env.py unless
 an elevation map is asked for.
@@ -27,6 +30,10 @@ SCAN_ROW0 = {"pgtt": 38, "baseline": 30}           # perceive.SCAN_ROW0: the sca
 # Joystick(elevation=True) / evaluate.py --elevation: a 2.56 m window of 4 cm cells, the newest view replaces the old one, and a box around the
 # torso that drops the robot's own legs from a camera that sees them - settings, not measured facts about a robot
 DEFAULTS = dict(grid=64, res=0.04, alpha=1.0, self_half=(0.45, 0.25, 0.45))
+# fill=True: the self box's 0.45 m is 12 cells of 4 cm, and 16 passes reach 0.64 m - a setting too; fill=0, the default, fills nothing
+FILL_PASSES = 16
+MAX_FILL = MAX_GRID - 1
+DIST_UNKNOWN = 255                                 # filled_dist of a scan point (filled_dist_map of a cell) that no pass reached
 SOURCES = ("depth", "lidar")                       # ElevationMap(source=...): what the map is fused from; "depth" unless said otherwise
 # the camera fields of a map that is fused from points: never read by pgtt_elevation_points, but pgtt_elevation_create checks them
 PLACEHOLDER_CAMERA = dict(width=1, height=1, fovy=90.0, near=0.1, far=1.0)
@@ -45,7 +52,11 @@ class PgttElevationBuffers(C.Structure):
                 ("origin", C.c_void_p), ("est", C.c_void_p), ("known", C.c_void_p), ("obs_out", C.c_void_p)]
 
 
-assert C.sizeof(PgttElevationConfig) == 92 and C.sizeof(PgttElevationBuffers) == 72
+class PgttElevationFill(C.Structure):
+    _fields_ = [("est", C.c_void_p), ("dist", C.c_void_p), ("obs_out", C.c_void_p), ("map_out", C.c_void_p), ("dist_out", C.c_void_p)]
+
+
+assert C.sizeof(PgttElevationConfig) == 92 and C.sizeof(PgttElevationBuffers) == 72 and C.sizeof(PgttElevationFill) == 40
 
 
 class ElevationError(RuntimeError):
@@ -59,7 +70,9 @@ SIDE = _sidelib.SideLib("elevation", ElevationError, {
     "pgtt_elevation": (None, [vp, vp, C.c_int, C.c_int, vp]),
     "pgtt_elevation_bind_points": (None, [vp, C.POINTER(PgttElevationBuffers), vp, C.c_int]),
     "pgtt_elevation_points": (None, [vp, vp, C.c_int, C.c_int, vp]),
-}, {"pgtt_elevation_sizeof_config": PgttElevationConfig, "pgtt_elevation_sizeof_buffers": PgttElevationBuffers})
+    "pgtt_elevation_bind_fill": (None, [vp, C.POINTER(PgttElevationFill), C.c_int]), "pgtt_elevation_fill": (None, [vp, vp]),
+}, {"pgtt_elevation_sizeof_config": PgttElevationConfig, "pgtt_elevation_sizeof_buffers": PgttElevationBuffers,
+    "pgtt_elevation_sizeof_fill": PgttElevationFill})
 LIB_PATH, EXPORTS, lib, check, build_info = SIDE.path, SIDE.exports, SIDE.lib, SIDE.check, SIDE.build_info
 
 
@@ -89,12 +102,21 @@ class ElevationMap(_sidelib.Handle):
     config's camera fields hold placeholders).  grid / res: the window is grid x grid cells of res metres; alpha: fusion gain in (0, 1], 1 = the
     newest view replaces the old; self_half: half extents of a box in the base frame whose points are dropped (the robot's own body in a sensor
     that sees it), zeros = none.  The defaults are settings, not facts.
+    fill = K > 0 (True = FILL_PASSES): after every tick a second launch closes the map's holes on a copy - K Jacobi passes, an unknown cell takes the
+    minimum of its known neighbours inside the window - and samples the scan from it: `filled_est` [N, 117], `filled_dist` [N, 117] uint8 (0 = a
+    measured cell, p = filled in pass p, 255 = still unknown) and `filled_obs` [N, obs_dim]; with dense=True also `filled_map` [N, G, G] (the layout
+    of `map`) and `filled_dist_map` [N, G, G] uint8.  The map and the other outputs never see a filled height.  fill = 0: none of this exists.
     Runs on the env's device and current stream; reads env.depth or the LiDAR's points, env.buffers["state" | "obs_state" | "done"] and writes nothing
     but its own tensors."""
     _prefix, _check = "pgtt_elevation", staticmethod(check)
 
     def __init__(self, env, grid: int = 64, res: float = 0.04, alpha: float = 1.0, self_half: Sequence[float] = (0.45, 0.25, 0.45),
-                 source: str = "depth"):
+                 source: str = "depth", fill: int = 0, dense: bool = False):
+        self.passes = FILL_PASSES if fill is True else int(fill or 0)
+        if self.passes < 0 or self.passes > MAX_FILL:
+            raise ValueError(f"ElevationMap: fill must be 0 (none), True or a number of passes in [1, {MAX_FILL}], not {fill!r}")
+        if dense and not self.passes:
+            raise ValueError("ElevationMap: dense=True asks for the filled map, so it needs fill > 0")
         if source not in SOURCES:
             raise ValueError(f"ElevationMap: source must be one of {SOURCES}, not {source!r}")
         self.source = source
@@ -131,6 +153,14 @@ class ElevationMap(_sidelib.Handle):
         self.known = torch.zeros((n, NSCAN), dtype=torch.uint8, device=dev)
         self.obs = torch.zeros((n, od), dtype=torch.float32, device=dev)
         self._mask = None
+        if self.passes:
+            self.filled_est = torch.zeros((n, NSCAN), dtype=torch.float32, device=dev)
+            self.filled_dist = torch.full((n, NSCAN), DIST_UNKNOWN, dtype=torch.uint8, device=dev)
+            self.filled_obs = torch.zeros((n, od), dtype=torch.float32, device=dev)
+            if dense:
+                self.filled_map = torch.full((n, self.grid, self.grid), float("nan"), dtype=torch.float32, device=dev)
+                self.filled_dist_map = torch.full((n, self.grid, self.grid), DIST_UNKNOWN, dtype=torch.uint8, device=dev)
+        self.dense = bool(dense)
         self.bind()
 
     def bind(self) -> None:
@@ -146,19 +176,36 @@ class ElevationMap(_sidelib.Handle):
         else:
             b.depth = self.env.depth.data_ptr()
             check(self._lib.pgtt_elevation_bind(self._h, C.byref(b)))
+        if self.passes:
+            o = PgttElevationFill()
+            o.est, o.dist, o.obs_out = self.filled_est.data_ptr(), self.filled_dist.data_ptr(), self.filled_obs.data_ptr()
+            if self.dense:
+                o.map_out, o.dist_out = self.filled_map.data_ptr(), self.filled_dist_map.data_ptr()
+            check(self._lib.pgtt_elevation_bind_fill(self._h, C.byref(o), self.passes))
 
     def tick(self, clear_mask: Optional[torch.Tensor] = None, clear_all: bool = False, use_done: bool = False) -> torch.Tensor:
         """integrate the env's current image (or LiDAR points) under its current pose and sample the scan: one launch on the env's current stream,
         no synchronisation.  Before integrating, the maps of the envs with clear_mask[e] != 0 ([N] uint8 / bool), of every env (clear_all) or of
-        the envs whose done flag is set (use_done) are cleared."""
+        the envs whose done flag is set (use_done) are cleared.  With fill > 0 the hole filling is enqueued behind it."""
         mp = None
         if clear_mask is not None:
             self._mask = clear_mask.to(self.env.device, torch.uint8).contiguous()      # kept alive until the next tick: the launch is asynchronous
             assert self._mask.shape == (self.env.num_envs,)
             mp = self._mask.data_ptr()
         fn = self._lib.pgtt_elevation_points if self.source == "lidar" else self._lib.pgtt_elevation
-        check(fn(self._h, mp, int(bool(clear_all)), int(bool(use_done)), torch.cuda.current_stream(self.env.device).cuda_stream))
+        stream = torch.cuda.current_stream(self.env.device).cuda_stream
+        check(fn(self._h, mp, int(bool(clear_all)), int(bool(use_done)), stream))
+        if self.passes:
+            check(self._lib.pgtt_elevation_fill(self._h, stream))
         return self.obs
+
+    def fill(self) -> torch.Tensor:
+        """the hole filling alone, on `map`, `origin` and the env's state and observation as they are: one launch on the env's current stream, no
+        synchronisation.  -> filled_obs"""
+        if not self.passes:
+            raise ElevationError("ElevationMap.fill(): this map was made with fill=0")
+        check(self._lib.pgtt_elevation_fill(self._h, torch.cuda.current_stream(self.env.device).cuda_stream))
+        return self.filled_obs
 
     def world_cells(self) -> torch.Tensor:
         """[N, G, G, 2] int64: the world cell (ix, iy) each slot of `map` holds under the current window"""

@@ -57,6 +57,9 @@ class Joystick:
         the reset envs' maps cleared, after step() with the maps of the envs whose episode just ended cleared; `env.elevation_obs` is the
         [N, obs_dim] observation with the 117 scan rows sampled from the map, `env.elevation_known` [N, 117] says which of them the map knew,
         `env.elevation_map` is the ElevationMap.  A side output like the image; may be combined with student.  None: the library is not opened.
+        elevation=dict(fill=K, ...) (K passes, True = 16; dense=True keeps the filled map too) closes the map's holes behind every tick, on a copy:
+        `env.elevation_filled_obs` [N, obs_dim] has the scan rows sampled from the filled map and `env.elevation_dist` [N, 117] uint8 says how each
+        was come by (0 measured, p = filled in pass p, 255 unknown); elevation_obs and elevation_known stay what they are without it.
         The map has memory, so what moves an env must clear it: reset() and step() do, set_terrain() forgets every map, but with a deferred
         curriculum (step(action, curriculum=False), then curriculum_step()) the envs are restarted AFTER the step's tick, as they are after the
         camera's - such a caller ticks the camera and then `env.elevation_map.tick(use_done=True)` once more after curriculum_step().
@@ -303,6 +306,16 @@ class Joystick:
     def elevation_known(self) -> Optional[torch.Tensor]:
         """[N, 117] uint8: 1 where the elevation map knew the scan point's cell, or None without a map"""
         return None if self.elevation_map is None else self.elevation_map.known
+
+    @property
+    def elevation_filled_obs(self) -> Optional[torch.Tensor]:
+        """[N, obs_dim] float32: the observation with its scan rows sampled from the hole-filled elevation map, or None without a map that fills"""
+        return getattr(self.elevation_map, "filled_obs", None)
+
+    @property
+    def elevation_dist(self) -> Optional[torch.Tensor]:
+        """[N, 117] uint8: 0 where the scan point's cell was measured, p where pass p filled it, 255 where it is unknown; None without a map that fills"""
+        return getattr(self.elevation_map, "filled_dist", None)
 
     def push_step(self) -> None:
         """the push scheduler alone (pgtt_push): what step() runs first when pushes are on; for callers of physics() / observe()"""

@@ -2,12 +2,17 @@
 from domain_randomize(seed=0), 64x48 images of the default camera, G = 64, poses after 40 control steps of small random actions; device events
 around 20 back-to-back calls after 5 warm-up calls, median [min, max] of 11 such windows.
 
-    python tools/gpu_elevation_time.py [--out profiles/NAME.txt] [--accuracy]
+    python tools/gpu_elevation_time.py [--out profiles/NAME.txt] [--accuracy] [--fill K[,K...]] [--eval]
 
 (i) pgtt_elevation (one launch); (ii) the same six steps as torch ops (scatter_reduce_ with amax) - what (i) replaces, the yardstick; (iii) the
 camera tick; (iv) the student's two launches; (v) the env step (no camera).
 --accuracy: policy177 acting on the true observation, 1000 envs, full domain randomisation, auto-reset; after 50 steps, 200 steps of RMSE of the map's
-est against perceive.scan_target over the known points, per band, and the known share per band."""
+est against perceive.scan_target over the known points, per band, and the known share per band.
+--fill 4,16,63: (vi) pgtt_elevation_fill alone with each number of passes, on the map the 41 ticks left, in the same windows; with
+--accuracy the env fills with the first of them, and the RMSE of filled_est is reported over the covered points (dist != 255) per band and per
+bucket of dist (0 = measured, 1-4, 5-8, 9+ = the pass that filled the cell).
+--eval: evaluate.py's rollout of policy177 on level4, 1000 envs, full domain randomisation, one deterministic episode - on the true observation, on
+the depth-fused and the LiDAR-fused map, and on each of the two filled (--elevation_fill, 16 passes), with the known and the covered share."""
 import argparse
 import math
 import os
@@ -135,12 +140,20 @@ class TorchElevation:
         return torch.cat([obs[:, :self.r0], est, obs[:, self.r0 + abi.NSCAN:]], 1), est, known
 
 
-def accuracy(terrain, steps_warm=50, steps=200, n=1000):
+DIST_BUCKETS = (("0", 0, 0), ("1-4", 1, 4), ("5-8", 5, 8), ("9+", 9, 254))
+
+
+def accuracy(terrain, steps_warm=50, steps=200, n=1000, fill=0):
     dr = domain_randomize(mjcf.load_model("stairs"), n, seed=0, terrain=terrain)
     kw = dict(params=torch.from_numpy(dr["params"]), variant=torch.from_numpy(dr["variant"]), box_friction=torch.from_numpy(dr["box_friction"]))
-    env = Joystick("stairs", configs.evaluation_config("pgtt"), num_envs=n, terrain=terrain, device="cuda:0", autoreset=True, depth={}, elevation=True, **kw)
+    env = Joystick("stairs", configs.evaluation_config("pgtt"), num_envs=n, terrain=terrain, device="cuda:0", autoreset=True, depth={},
+                   elevation=dict(fill=fill) if fill else True, **kw)
     pi = load_policy("policy177", "cuda:0")
     env.reset(0)
+    fse = {k: 0.0 for k in perceive.BANDS}
+    fcnt = {k: 0.0 for k in perceive.BANDS}
+    bse = {k: 0.0 for k, _, _ in DIST_BUCKETS}
+    bcnt = {k: 0.0 for k, _, _ in DIST_BUCKETS}
     se = {k: 0.0 for k in perceive.BANDS}
     cnt = {k: 0.0 for k in perceive.BANDS}
     tot = {k: 0.0 for k in perceive.BANDS}
@@ -157,6 +170,14 @@ def accuracy(terrain, steps_warm=50, steps=200, n=1000):
             err, known = env.elevation_map.est - perceive.scan_target(env), (env.elevation_known > 0) & live
             for k, sl in perceive.BANDS.items():
                 se[k] += float((err[:, sl] ** 2 * known[:, sl]).sum()); cnt[k] += float(known[:, sl].sum()); tot[k] += float(live.sum()) * (sl.stop - sl.start)
+            if fill:
+                ferr, dist = env.elevation_map.filled_est - perceive.scan_target(env), env.elevation_dist
+                covered = (dist != elevation.DIST_UNKNOWN) & live
+                for k, sl in perceive.BANDS.items():
+                    fse[k] += float((ferr[:, sl] ** 2 * covered[:, sl]).sum()); fcnt[k] += float(covered[:, sl].sum())
+                for k, lo, hi in DIST_BUCKETS:
+                    m = (dist >= lo) & (dist <= hi) & live
+                    bse[k] += float((ferr ** 2 * m).sum()); bcnt[k] += float(m.sum())
             young = known & (age < 50)[:, None]
             fresh_se += float((err ** 2 * young).sum()); fresh_cnt += float(young.sum())
     env.close()
@@ -166,6 +187,28 @@ def accuracy(terrain, steps_warm=50, steps=200, n=1000):
     allse, allcnt = sum(se.values()), sum(cnt.values())
     lines.append(f"  all     rmse {math.sqrt(allse / max(allcnt, 1)):.4f} m; within 50 steps of a reset: rmse {math.sqrt(fresh_se / max(fresh_cnt, 1)):.4f} m on {fresh_cnt / max(allcnt, 1):.3f} of the known points; "
                  f"older: rmse {math.sqrt((allse - fresh_se) / max(allcnt - fresh_cnt, 1)):.4f} m")
+    if fill:
+        lines.append(f"filled with {fill} passes: filled_est against perceive.scan_target over the covered points (dist != 255)")
+        for k in perceive.BANDS:
+            lines.append(f"  {k:7s} rmse {math.sqrt(fse[k] / max(fcnt[k], 1)):.4f} m, covered share {fcnt[k] / max(tot[k], 1):.3f}")
+        alltot = sum(tot.values())
+        lines.append(f"  all     rmse {math.sqrt(sum(fse.values()) / max(sum(fcnt.values()), 1)):.4f} m, covered share {sum(fcnt.values()) / max(alltot, 1):.3f}")
+        for k, _, _ in DIST_BUCKETS:
+            lines.append(f"  dist {k:4s} rmse {math.sqrt(bse[k] / max(bcnt[k], 1)):.4f} m on {bcnt[k] / max(alltot, 1):.3f} of the points")
+    return lines
+
+
+def evaluation(n=1000):
+    import evaluate
+    base = ["--policy", "policy177", "--terrain_file", "level4"]
+    lines = [f"evaluate.py: policy177, level4, {n} envs, full DR, one deterministic episode"]
+    lidar = ["--elevation", "--elevation_source", "lidar"]
+    for name, extra in (("true observation", []), ("depth-fused map", ["--elevation"]), ("depth-fused map, filled", ["--elevation", "--elevation_fill"]),
+                        ("LiDAR-fused map", lidar), ("LiDAR-fused map, filled", lidar + ["--elevation_fill"])):
+        r = evaluate.run_evaluation(evaluate.make_parser().parse_args(base + extra), num_eval_envs=n, verbose=False)
+        shares = (f", known scan points {r['known_share']:.3f}" if "known_share" in r else "") + (f", covered {r['covered_share']:.3f}" if "covered_share" in r else "")
+        lines.append(f"  {name:24s} survivors {r['survivors']} / {n}, reward {r['episode_reward']:.2f}, length {r['avg_episode_length']:.1f}, "
+                     f"tracking lin {r['tracking_lin_vel']:.3f} ang {r['tracking_ang_vel']:.3f}{shares}")
     return lines
 
 
@@ -174,7 +217,10 @@ def main():
     ap.add_argument("--num_envs", type=int, default=4096)
     ap.add_argument("--out", type=str, default=None)
     ap.add_argument("--accuracy", action="store_true")
+    ap.add_argument("--fill", type=str, default=None, metavar="K[,K...]", help="time pgtt_elevation_fill with these numbers of passes; --accuracy fills with the first")
+    ap.add_argument("--eval", action="store_true")
     args = ap.parse_args()
+    passes = [int(k) for k in args.fill.split(",")] if args.fill else []
     n = args.num_envs
     terrain = np.load(os.path.join(ROOT, "phase_guided_terrain_traversal_amd", "assets", "terrains", "level4.npy"))
     dr = domain_randomize(mjcf.load_model("stairs"), n, seed=0, terrain=terrain)
@@ -203,6 +249,15 @@ def main():
             ("(iii) camera tick (force)", window_us(lambda: env.depth_camera.tick(force=True))),
             ("(iv)  pgtt_perceive, two launches", window_us(env.student.tick)),
             ("(v)   env step, no camera", window_us(lambda: plain.step(act)))]
+    for k in passes:
+        # a map of its own with the ticked one's contents: the fill reads `map` and `origin` and writes neither
+        fm = elevation.ElevationMap(env, **{**elevation.DEFAULTS, "fill": k})
+        fm.map.copy_(em.map); fm.origin.copy_(em.origin)
+        us = window_us(fm.fill)
+        torch.cuda.synchronize()
+        share = float((fm.filled_dist != elevation.DIST_UNKNOWN).float().mean())
+        rows.append((f"(vi)  pgtt_elevation_fill, {k} passes (covers {share:.3f} of the scan points; the map knows {float((em.known > 0).float().mean()):.3f})", us))
+        fm.close()
     c = em.config
     traffic = n * (2 * 4 * c.grid ** 2 + 4 * c.width * c.height + 2 * 4 * c.obs_dim + 5 * abi.NSCAN)
     lines = [f"{n} envs, level4, {c.width}x{c.height}, G = {c.grid}, res = {c.res:.3f}, alpha = {c.alpha}; us per call, median [min, max] of 11 windows of 20 calls",
@@ -213,7 +268,9 @@ def main():
     lines.append(f"torch statement against the kernel after 41 ticks: known flags equal on {same_known:.5f} of the points, max |est difference| where both know = {agree:.2e}")
     env.close(); plain.close()
     if args.accuracy:
-        lines += accuracy(terrain)
+        lines += accuracy(terrain, fill=passes[0] if passes else 0)
+    if args.eval:
+        lines += evaluation()
     text = "\n".join(lines)
     print(text)
     if args.out:
