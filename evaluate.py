@@ -13,7 +13,8 @@ is built.  The policy comes from `--checkpoint_folder` (the newest `<env_steps>.
 `--policy` (an .npz path or the name of a shipped policy); with `--student student.npz` (train_student.py) the policy acts on the observation
 whose scan rows the student perception module estimated from the onboard depth image, with `--elevation [grid,res,alpha]` on the observation whose
 scan rows are sampled from the depth-fused elevation map (elevation.py; nothing to train; `--elevation_source lidar` fuses it from the onboard
-LiDAR's points instead, lidar.py; `--elevation_fill [K]` closes the map's holes first and the policy acts on the filled scan); the remaining flags of the reference's CLI are accepted and ignored.
+LiDAR's points instead, lidar.py; `--elevation_fill [K]` closes the map's holes first and the policy acts on the filled scan; `--sensor_every M`
+runs that sensor at one control step in M and lets the map follow it); the remaining flags of the reference's CLI are accepted and ignored.
 """
 import argparse
 import os
@@ -166,15 +167,25 @@ def run_evaluation(args, num_eval_envs=NUM_EVAL_ENVS, seed=0, verbose=True):
                 raise SystemExit(f"--elevation_fill {fill}: the number of passes must be in [1, 95]")
             given = dict({} if given is True else given, fill=fill)
         source = getattr(args, "elevation_source", "depth")
+        # --sensor_every M: the sensor that feeds the map takes new data at one control step in M; for M > 1 the map follows it (follow_sensor):
+        # it fuses on those steps and in between samples the held map at the current pose
+        every = int(getattr(args, "sensor_every", 1))
+        if every < 1:
+            raise SystemExit(f"--sensor_every {every}: the sensor's period must be >= 1")
+        sensor = {} if every == 1 else dict(every=every)
+        if every > 1:
+            given = dict({} if given is True else given, follow_sensor=True)
         if source == "lidar":
             # --elevation_source lidar: the map is fused from the world points of the onboard LiDAR (lidar.DEFAULTS), as the deployed mapping stack's is
-            kw.update(lidar={}, elevation=dict({} if given is True else given, source="lidar"))
+            kw.update(lidar=sensor, elevation=dict({} if given is True else given, source="lidar"))
         else:
-            kw.update(depth={}, elevation=given)
+            kw.update(depth=sensor, elevation=given)
     elif getattr(args, "elevation_source", "depth") != "depth":
         raise SystemExit("--elevation_source says what --elevation is fused from: give --elevation too")
     elif getattr(args, "elevation_fill", None) is not None:
         raise SystemExit("--elevation_fill fills the holes of --elevation's map: give --elevation too")
+    elif int(getattr(args, "sensor_every", 1)) != 1:
+        raise SystemExit("--sensor_every is the period of the sensor that feeds --elevation's map: give --elevation too")
     env = Joystick(args.task_name, cfg, num_envs=n, terrain=terrain, device=DEVICE, autoreset=True, **kw)
     if env.elevation_filled_obs is not None:
         acts_on = env.elevation_filled_obs
@@ -272,6 +283,8 @@ def make_parser():
                     help="with --elevation: fuse the map from the depth camera's image (default) or from the onboard LiDAR's points (lidar.py)")
     ap.add_argument("--elevation_fill", type=fill_passes, nargs="?", const=True, default=None, metavar="K",
                     help="with --elevation: close the map's holes with K passes (16 unless given) behind every tick; the policy acts on the filled scan")
+    ap.add_argument("--sensor_every", type=int, default=1, metavar="M",
+                    help="with --elevation: the sensor that feeds the map runs at one control step in M; for M > 1 the map follows it, holding in between")
     configs.add_push_args(ap)
     ap.add_argument("--terrain_files", type=str, default=None, help="comma-separated level files stacked into one table (as train.py --terrain_files); evaluated on --level")
     ap.add_argument("--level", type=int, default=0, help="with --terrain_files: the level every evaluation env stands on (no curriculum at evaluation)")

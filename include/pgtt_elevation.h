@@ -19,7 +19,8 @@
  * Only a camera on the torso is supported (mount_body == 0, anything else is PGTT_E_ARG), so no forward kinematics is needed:
  *     camera pose = base pose * mount pose,   base pose = rows PGTT_S_QPOS + 0..6 of `state`, the quaternion normalised first.
  * mount_quat is normalised by pgtt_elevation_create.  The image is taken as the pose's own: a caller whose sensor period is above 1 would
- * unproject a stale image under a moved pose, and must not use this library.
+ * unproject a stale image under a moved pose, and must not call pgtt_elevation() or pgtt_elevation_points() on the steps its sensor skips - such
+ * a caller uses pgtt_elevation_follow() ("Following a slower sensor" below).
  *
  * Map.  Per env, map[G][G] (G = cfg.grid) holds world-z heights in metres; NaN = unknown.  The window is world-aligned and toroidal, with
  * square cells of side `res`:
@@ -93,6 +94,31 @@
  *   Assemble.  Step 6 into the fill's own obs_out.
  *   Dense.   map_out is W and dist_out is D, both in the map's slot layout; a cell that is still unknown is NaN.
  * An origin outside +-2^30 (a map never ticked) is taken as +-2^30.  One launch, one workgroup per env, W and D of the window and a border of one cell in LDS: 5 (G + 2)^2 bytes.
+ *
+ * Following a slower sensor.  A sensor of period `every` > 1 (PgttDepthConfig.every, PgttLidarConfig.every) recomputes its image or points at one
+ * call in `every` and decides that on the device, from its counter.  A tick on the other steps would unproject a stale image under a moved pose, or
+ * fuse a stale point cloud once more, which for alpha < 1 weights it again.  pgtt_elevation_follow() is the call for such a sensor: it fuses when
+ * the sensor has new data and, in between, leaves the map alone and answers the height queries at the current pose - what a robot's mapping stack
+ * does.  pgtt_elevation_bind_rate() hands it the SENSOR's device counter and period; it is called BEHIND the sensor's call of the same step, with the
+ * `force` that call was given.  With c = counter[0] - 1, the counter's value before the sensor's call (which has advanced it by one), the call is
+ *     fresh   when force != 0, or c >= 0 and c mod every == 0: the sensor's own rule, evaluated on the device,
+ *     a hold  otherwise.
+ * There is no read-back, no synchronisation and no allocation: at most two launches on `stream`, of which one returns at once in every workgroup,
+ * so the step stays one capturable sequence.
+ *   Fresh call.  The six steps of pgtt_elevation() - or of pgtt_elevation_points(), by which bind was made last - in the same order; every output
+ *            has the same bits.
+ *   Hold call.   Per env:
+ *     1. Clear.  The rule of step 1: clear_all, clear_mask[e], or use_done and done[e] != 0.  A cleared env's whole map becomes NaN and its
+ *        origin[e] the cell of its current base position.
+ *     2. Nothing else is written: the `map` and `origin` of an env that is not cleared are not touched.  No recentring, no fusion.
+ *     3. Sample.  Step 5 at the CURRENT pose, from the window that origin[e] describes: the origin just written for a cleared env, otherwise the
+ *        origin as the last fresh call left it (one outside +-2^30 is taken as +-2^30, as pgtt_elevation_fill does).  A scan point whose cell has
+ *        left that window is unknown.  known, the minimum over the known points and est = z - min z are those of step 5; all 0 when nothing is
+ *        known.
+ *     4. Assemble.  Step 6 into obs_out.
+ * An env's outputs depend on its own rows only.  pgtt_elevation_fill() is what it was: it reads `map`, `origin` and `state` as they stand, so behind
+ * a hold call it fills and samples the held window at the current pose.  Not covered: an image fused later than it was taken (that needs the pose
+ * of its capture), sensor phases per env, latency.
  */
 #ifndef PGTT_ELEVATION_H_
 #define PGTT_ELEVATION_H_
@@ -172,6 +198,13 @@ int pgtt_elevation_bind_fill(pgtt_elevation_handle h, const PgttElevationFill* o
  * captured.  PGTT_E_STATE before the buffers are bound (either kind of bind) or before pgtt_elevation_bind_fill; PGTT_E_ARG when the fill's obs_out
  * is bound and the buffers' obs is NULL. */
 int pgtt_elevation_fill(pgtt_elevation_handle h, void* stream);
+/* counter: the SENSOR's device counter (PgttDepthBuffers.counter or PgttLidarBuffers.counter), every: that sensor's period, >= 1.
+ * PGTT_E_ARG for a NULL counter or every < 1.  May be called before or after the buffers are bound and persists across later binds, like
+ * pgtt_elevation_bind_fill. */
+int pgtt_elevation_bind_rate(pgtt_elevation_handle h, const int64_t* counter, int every);
+/* Called BEHIND the sensor's call of the same step, with the `force` that call was given.  PGTT_E_STATE before a bind of the buffers or before
+ * pgtt_elevation_bind_rate.  The image or the points are used, by which bind was made last (as pgtt_elevation / pgtt_elevation_points). */
+int pgtt_elevation_follow(pgtt_elevation_handle h, const uint8_t* clear_mask, int clear_all, int use_done, int force, void* stream);
 int pgtt_elevation_sizeof_fill(void);
 int pgtt_elevation_sizeof_config(void);
 int pgtt_elevation_sizeof_buffers(void);

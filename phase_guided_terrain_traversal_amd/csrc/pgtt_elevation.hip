@@ -25,6 +25,15 @@
 //   sample   lanes 0 .. 116 read the key and D at the scan points (scan_slot, the tick's); the minimum over the covered points is taken on the keys.
 //   out      est, dist, obs_out (assemble, the tick's), map_out and dist_out in the map's slot layout.
 // It writes nothing the tick reads.
+//
+// Following a slower sensor (pgtt_elevation_follow): two launches, of which one does the work.  Both read the sensor's counter on the device and
+// decide alike, in every workgroup, whether the call is fresh (fresh_call, the sensor's own rule one step later).
+//   elevation_kernel<POINTS, true>  the gated instantiation: the tick above on a fresh call, returns at once on a hold call.
+//   elevation_hold_kernel           returns at once on a fresh call.  On a hold call it leaves the map alone and samples the scan at the current
+//            pose from the window the stored origin describes.  Two envs per workgroup, two waves per env; the map is not staged in LDS: a hold
+//            needs 117 of its cells, gathered from global memory.  Lane 0 of each env stages the pose and the window (and writes the origin of a
+//            cleared env); a cleared env's map goes out as NaN in 16-byte runs; the minimum is phase E's wave reduction and LDS exchange; est,
+//            known, obs_out.  No atomics.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -48,6 +57,7 @@ struct ElevArgs {
   float near_m, far_m, res, alpha, tu, tv, sdx, sdy;         // tu = tan(fovy / 2) W / H, tv = tan(fovy / 2)
   float mpos[3], mquat[4], self_half[3];
   const float* points; int P;                                // the points entry: [N][P][3] world points
+  const int64_t* counter; int every, force;                  // the gated instantiations alone (pgtt_elevation_follow)
 };
 
 // what lane 0 stages for the workgroup
@@ -90,8 +100,17 @@ __device__ __forceinline__ void assemble(float* obs_out, const float* obs, const
   }
 }
 
-template <bool POINTS>
+// the sensor's rule, seen from behind the sensor's call, which has advanced the counter by one: every lane of every workgroup decides alike
+__device__ __forceinline__ bool fresh_call(const int64_t* counter, int every, int force) {
+  const long long c = counter[0] - 1;
+  return force || (c >= 0 && (unsigned long long)c % (unsigned)every == 0);
+}
+
+template <bool POINTS, bool GATED = false>
 __global__ void __launch_bounds__(kLanes) elevation_kernel(ElevArgs a) {
+  if constexpr (GATED) {
+    if (!fresh_call(a.counter, a.every, a.force)) return;              // a hold call: elevation_hold_kernel's
+  }
   extern __shared__ __attribute__((aligned(16))) unsigned sh_m[];      // [G * G]
   __shared__ float sh_p[P_N];
   __shared__ int sh_i[I_N];
@@ -296,6 +315,102 @@ __global__ void __launch_bounds__(kLanes) elevation_kernel(ElevArgs a) {
   }
 }
 
+struct HoldArgs {
+  const float* state; const float* obs; const float* done; const uint8_t* clear_mask; const int64_t* counter;
+  float* map; int32_t* origin; float* est; uint8_t* known; float* obs_out;
+  int N, G, obs_dim, scan_row0, clear_all, use_done, vec_map, every, force;
+  float res, sdx, sdy;
+};
+
+constexpr int kHoldLanes = 128;                   // two waves per env: phase E's reduction, lane for lane
+constexpr int kHoldEnvs = kLanes / kHoldLanes;    // envs per workgroup
+
+__global__ void __launch_bounds__(kLanes) elevation_hold_kernel(HoldArgs a) {
+  __shared__ float sh_p[kHoldEnvs][P_N];
+  __shared__ int sh_i[kHoldEnvs][I_N];
+  __shared__ float sh_est[kHoldEnvs][PGTT_NSCAN];
+  __shared__ float sh_red[kHoldEnvs][2];
+  if (fresh_call(a.counter, a.every, a.force)) return;                 // a fresh call: the gated elevation_kernel's
+  const int tid = threadIdx.x, half = tid / kHoldLanes, lt = tid - half * kHoldLanes, G = a.G, GG = G * G;
+  const int e = blockIdx.x * kHoldEnvs + half;
+  const long N = a.N;
+  const bool live = e < a.N;                                           // the last workgroup of an odd N: its second half only keeps the barriers
+
+  // ---- the pose, the clear and the window (lane 0 of the env)
+  if (live && lt == 0) {
+    const float* S = a.state + e;
+    const float bx = S[(PGTT_S_QPOS + 0) * N], by = S[(PGTT_S_QPOS + 1) * N];
+    float qw = S[(PGTT_S_QPOS + 3) * N], qx = S[(PGTT_S_QPOS + 4) * N], qy = S[(PGTT_S_QPOS + 5) * N], qz = S[(PGTT_S_QPOS + 6) * N];
+    const float qn = sqrtf(qw * qw + qx * qx + qy * qy + qz * qz);
+    qw /= qn; qx /= qn; qy /= qn; qz /= qn;
+    sh_p[half][P_BASE + 0] = bx; sh_p[half][P_BASE + 1] = by;
+    float sy, cy; yaw_sincos(qw, qx, qy, qz, sy, cy);
+    sh_p[half][P_SY] = sy; sh_p[half][P_CY] = cy;
+    const bool clear = a.clear_all || (a.clear_mask && a.clear_mask[e]) || (a.use_done && a.done && a.done[e] != 0.f);
+    int ox, oy;
+    if (clear) {
+      // a cleared env takes the cell of its current base position, as a tick's clear does
+      ox = cell_of(bx, a.res); oy = cell_of(by, a.res);
+      a.origin[2 * (long)e] = ox; a.origin[2 * (long)e + 1] = oy;
+    } else {
+      // the origin as the last fresh call left it; one outside the tick's clamp is as far away as the clamp (fill_kernel's rule)
+      ox = min(max(a.origin[2 * (long)e], -(1 << 30)), 1 << 30); oy = min(max(a.origin[2 * (long)e + 1], -(1 << 30)), 1 << 30);
+    }
+    const int lox = ox - G / 2, loy = oy - G / 2;
+    sh_i[half][I_LOX] = lox; sh_i[half][I_LOY] = loy; sh_i[half][I_LMX] = floor_mod(lox, G); sh_i[half][I_LMY] = floor_mod(loy, G);
+    sh_i[half][I_CLEAR] = clear ? 1 : 0;
+  }
+  __syncthreads();
+
+  // ---- a cleared env: the whole map becomes NaN and nothing is known; any other env: the scan's cells are gathered from the map as it stands
+  float z = 0.f;
+  bool kn = false;
+  if (live) {
+    float* mp = a.map + (long)e * GG;
+    if (sh_i[half][I_CLEAR]) {
+      const float nanv = __uint_as_float(0x7fc00000u);
+      if (a.vec_map) {
+        const float4 n4 = make_float4(nanv, nanv, nanv, nanv);
+        for (int s = 4 * lt; s < GG; s += 4 * kHoldLanes) *reinterpret_cast<float4*>(mp + s) = n4;
+      } else {
+        for (int s = lt; s < GG; s += kHoldLanes) mp[s] = nanv;
+      }
+    } else if (lt < PGTT_NSCAN) {
+      const int slot = scan_slot(lt, sh_p[half], sh_i[half], a.sdx, a.sdy, a.res, G);
+      if (slot >= 0) {
+        z = mp[slot];
+        kn = z == z;
+      }
+    }
+  }
+
+  // ---- the minimum over the known points, est and known: phase E
+  float zmin = kn ? z : INFINITY;
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) zmin = fminf(zmin, __shfl_xor(zmin, off, 64));
+  if ((lt & 63) == 0) sh_red[half][lt >> 6] = zmin;
+  __syncthreads();
+  zmin = fminf(sh_red[half][0], sh_red[half][1]);
+  if (live && lt < PGTT_NSCAN) {
+    const float es = (kn && zmin < INFINITY) ? z - zmin : 0.f;
+    sh_est[half][lt] = es;
+    a.est[(long)e * PGTT_NSCAN + lt] = es;
+    a.known[(long)e * PGTT_NSCAN + lt] = kn ? 1 : 0;
+  }
+
+  // ---- obs_out = obs with the scan rows replaced: phase F
+  if (a.obs_out) {
+    __syncthreads();
+    if (live) {
+      const int od = a.obs_dim;
+      for (int k = lt; k < od; k += kHoldLanes) {
+        const int j = k - a.scan_row0;
+        a.obs_out[(long)e * od + k] = (j >= 0 && j < PGTT_NSCAN) ? sh_est[half][j] : a.obs[(long)e * od + k];
+      }
+    }
+  }
+}
+
 struct FillArgs {
   const float* state; const float* obs; const float* map; const int32_t* origin;
   float* est; uint8_t* dist; float* obs_out; float* map_out; uint8_t* dist_out;
@@ -497,6 +612,8 @@ struct pgtt_elevation_map {
   int P = 0;
   PgttElevationFill fill{};              // pgtt_elevation_bind_fill; kept by the other two binds
   int passes = 0;                        // 0 = no fill bound
+  const int64_t* counter = nullptr;      // pgtt_elevation_bind_rate; kept by the other binds
+  int every = 0;                         // 0 = no rate bound
 };
 
 namespace {
@@ -509,8 +626,9 @@ int check_buffers(const PgttElevationBuffers* bufs, const char* who) {
   return PGTT_OK;
 }
 
-// one tick from the image (points = false) or from the bound points
-int launch(pgtt_elevation_map* h, bool points, const uint8_t* clear_mask, int clear_all, int use_done, void* stream) {
+// one tick from the image (points = false) or from the bound points; follow: the gated tick and the hold behind the sensor's counter, `force` as
+// the sensor's call was given
+int launch(pgtt_elevation_map* h, bool points, const uint8_t* clear_mask, int clear_all, int use_done, void* stream, bool follow = false, int force = 0) {
   HIP_TRY(hipSetDevice(h->device));
   const PgttElevationConfig& c = h->cfg;
   const PgttElevationBuffers& b = h->buf;
@@ -530,8 +648,23 @@ int launch(pgtt_elevation_map* h, bool points, const uint8_t* clear_mask, int cl
   for (int i = 0; i < 4; i++) a.mquat[i] = c.mount_quat[i];
   a.points = h->points; a.P = h->P;
   const size_t lds = (size_t)c.grid * c.grid * sizeof(unsigned);
-  if (points) hipLaunchKernelGGL(elevation_kernel<true>, dim3(h->num_envs), dim3(kLanes), lds, (hipStream_t)stream, a);
-  else hipLaunchKernelGGL(elevation_kernel<false>, dim3(h->num_envs), dim3(kLanes), lds, (hipStream_t)stream, a);
+  if (follow) {
+    a.counter = h->counter; a.every = h->every; a.force = force ? 1 : 0;
+    if (points) hipLaunchKernelGGL((elevation_kernel<true, true>), dim3(h->num_envs), dim3(kLanes), lds, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL((elevation_kernel<false, true>), dim3(h->num_envs), dim3(kLanes), lds, (hipStream_t)stream, a);
+    HIP_TRY(hipGetLastError());
+    HoldArgs o{};
+    o.state = b.state; o.obs = b.obs; o.done = b.done; o.clear_mask = clear_mask; o.counter = h->counter;
+    o.map = b.map; o.origin = b.origin; o.est = b.est; o.known = b.known; o.obs_out = b.obs_out;
+    o.N = h->num_envs; o.G = c.grid; o.obs_dim = c.obs_dim; o.scan_row0 = c.scan_row0; o.clear_all = a.clear_all; o.use_done = a.use_done;
+    o.vec_map = a.vec_map; o.every = h->every; o.force = a.force;
+    o.res = c.res; o.sdx = c.scan_dist_x; o.sdy = c.scan_dist_y;
+    hipLaunchKernelGGL(elevation_hold_kernel, dim3((h->num_envs + kHoldEnvs - 1) / kHoldEnvs), dim3(kLanes), 0, (hipStream_t)stream, o);
+  } else if (points) {
+    hipLaunchKernelGGL(elevation_kernel<true>, dim3(h->num_envs), dim3(kLanes), lds, (hipStream_t)stream, a);
+  } else {
+    hipLaunchKernelGGL(elevation_kernel<false>, dim3(h->num_envs), dim3(kLanes), lds, (hipStream_t)stream, a);
+  }
   HIP_TRY(hipGetLastError());
   return PGTT_OK;
 }
@@ -600,6 +733,22 @@ int pgtt_elevation_points(pgtt_elevation_handle h, const uint8_t* clear_mask, in
   if (!h) return fail(PGTT_E_ARG, "pgtt_elevation_points: null handle");
   if (!h->points) return fail(PGTT_E_STATE, "pgtt_elevation_points: no points bound (pgtt_elevation_bind_points first)");
   return launch(h, true, clear_mask, clear_all, use_done, stream);
+}
+
+int pgtt_elevation_bind_rate(pgtt_elevation_handle h, const int64_t* counter, int every) {
+  if (!h) return fail(PGTT_E_ARG, "pgtt_elevation_bind_rate: null handle");
+  if (!counter) return fail(PGTT_E_ARG, "pgtt_elevation_bind_rate: counter is required (the sensor's device counter)");
+  if (every < 1) return fail(PGTT_E_ARG, "pgtt_elevation_bind_rate: every must be >= 1");
+  h->counter = counter;
+  h->every = every;
+  return PGTT_OK;
+}
+
+int pgtt_elevation_follow(pgtt_elevation_handle h, const uint8_t* clear_mask, int clear_all, int use_done, int force, void* stream) {
+  if (!h) return fail(PGTT_E_ARG, "pgtt_elevation_follow: null handle");
+  if (!h->bound) return fail(PGTT_E_STATE, "pgtt_elevation_follow: no buffers bound (pgtt_elevation_bind or pgtt_elevation_bind_points first)");
+  if (!h->every) return fail(PGTT_E_STATE, "pgtt_elevation_follow: no sensor rate bound (pgtt_elevation_bind_rate first)");
+  return launch(h, h->points != nullptr, clear_mask, clear_all, use_done, stream, true, force);
 }
 
 int pgtt_elevation_bind_fill(pgtt_elevation_handle h, const PgttElevationFill* out, int passes) {

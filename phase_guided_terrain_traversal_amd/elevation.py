@@ -10,6 +10,9 @@ points of the env's LiDAR (lidar.py) instead: the sensor such a stack reads on t
     em = ElevationMap(env, fill=16)                          # hole filling behind every tick: a second launch with outputs of its own
     em.filled_est, em.filled_dist, em.filled_obs             # [N, 117], [N, 117] uint8 (0 measured, 1..16 the pass that filled it, 255 unknown), [N, obs_dim]
 
+    em = ElevationMap(env, follow_sensor=True)               # env's sensor may have any period: tick() behind the sensor's tick fuses when the
+    em.tick(use_done=True, force=False)                      # sensor has new data and otherwise samples the held map at the current pose
+
 `Joystick(..., depth=dict(...), elevation=dict(...) | True)` owns one and ticks it behind the camera (env.elevation_obs);
 `Joystick(..., lidar=dict(...), elevation=dict(source="lidar"))` one that is ticked behind the LiDAR.  The module is not imported by env.py unless
 an elevation map is asked for.
@@ -71,6 +74,7 @@ SIDE = _sidelib.SideLib("elevation", ElevationError, {
     "pgtt_elevation_bind_points": (None, [vp, C.POINTER(PgttElevationBuffers), vp, C.c_int]),
     "pgtt_elevation_points": (None, [vp, vp, C.c_int, C.c_int, vp]),
     "pgtt_elevation_bind_fill": (None, [vp, C.POINTER(PgttElevationFill), C.c_int]), "pgtt_elevation_fill": (None, [vp, vp]),
+    "pgtt_elevation_bind_rate": (None, [vp, vp, C.c_int]), "pgtt_elevation_follow": (None, [vp, vp, C.c_int, C.c_int, C.c_int, vp]),
 }, {"pgtt_elevation_sizeof_config": PgttElevationConfig, "pgtt_elevation_sizeof_buffers": PgttElevationBuffers,
     "pgtt_elevation_sizeof_fill": PgttElevationFill})
 LIB_PATH, EXPORTS, lib, check, build_info = SIDE.path, SIDE.exports, SIDE.lib, SIDE.check, SIDE.build_info
@@ -106,12 +110,16 @@ class ElevationMap(_sidelib.Handle):
     minimum of its known neighbours inside the window - and samples the scan from it: `filled_est` [N, 117], `filled_dist` [N, 117] uint8 (0 = a
     measured cell, p = filled in pass p, 255 = still unknown) and `filled_obs` [N, obs_dim]; with dense=True also `filled_map` [N, G, G] (the layout
     of `map`) and `filled_dist_map` [N, G, G] uint8.  The map and the other outputs never see a filled height.  fill = 0: none of this exists.
+    follow_sensor=True: the sensor may have any period (every=K).  tick() is then pgtt_elevation_follow: called behind the sensor's tick with the
+    same `force`, it decides on the device, from the sensor's counter, whether the sensor has just taken new data - then it is the tick it always
+    was - or not: then the map and the origin are left alone (but for the clears) and the scan is sampled from the held map at the current pose.
+    follow_sensor=False, the default: a sensor of period 1 is required and tick() enqueues what it always did.
     Runs on the env's device and current stream; reads env.depth or the LiDAR's points, env.buffers["state" | "obs_state" | "done"] and writes nothing
     but its own tensors."""
     _prefix, _check = "pgtt_elevation", staticmethod(check)
 
     def __init__(self, env, grid: int = 64, res: float = 0.04, alpha: float = 1.0, self_half: Sequence[float] = (0.45, 0.25, 0.45),
-                 source: str = "depth", fill: int = 0, dense: bool = False):
+                 source: str = "depth", fill: int = 0, dense: bool = False, follow_sensor: bool = False):
         self.passes = FILL_PASSES if fill is True else int(fill or 0)
         if self.passes < 0 or self.passes > MAX_FILL:
             raise ValueError(f"ElevationMap: fill must be 0 (none), True or a number of passes in [1, {MAX_FILL}], not {fill!r}")
@@ -119,12 +127,12 @@ class ElevationMap(_sidelib.Handle):
             raise ValueError("ElevationMap: dense=True asks for the filled map, so it needs fill > 0")
         if source not in SOURCES:
             raise ValueError(f"ElevationMap: source must be one of {SOURCES}, not {source!r}")
-        self.source = source
+        self.source, self.follow_sensor = source, bool(follow_sensor)
         if source == "lidar":
             lid = getattr(env, "lidar_scanner", None)
             if lid is None or lid.points is None:
                 raise ValueError("ElevationMap(source='lidar') needs an env with a LiDAR that writes points: Joystick(..., lidar=dict(...))")
-            if lid.config.every != 1:
+            if lid.config.every != 1 and not self.follow_sensor:
                 raise ValueError(f"ElevationMap needs a LiDAR of period 1 (every={lid.config.every}): the map would fuse a stale scan again at every tick")
             od = env.observation_size["state"]
             self.config = config_struct(**PLACEHOLDER_CAMERA, grid=grid, res=res, alpha=alpha, self_half=self_half,
@@ -137,7 +145,7 @@ class ElevationMap(_sidelib.Handle):
             cc = cam.config
             if cc.mount_body != 0:
                 raise ValueError(f"ElevationMap supports a camera on the torso only (mount_body == 0), not on body {cc.mount_body}")
-            if cc.every != 1:
+            if cc.every != 1 and not self.follow_sensor:
                 raise ValueError(f"ElevationMap needs a camera of period 1 (every={cc.every}): a stale image under a moved pose would be unprojected wrongly")
             od = env.observation_size["state"]
             self.config = config_struct(cc.width, cc.height, cc.fovy_deg, cc.near, cc.far, list(cc.mount_pos), list(cc.mount_quat), cc.mount_body, grid, res,
@@ -161,6 +169,10 @@ class ElevationMap(_sidelib.Handle):
                 self.filled_map = torch.full((n, self.grid, self.grid), float("nan"), dtype=torch.float32, device=dev)
                 self.filled_dist_map = torch.full((n, self.grid, self.grid), DIST_UNKNOWN, dtype=torch.uint8, device=dev)
         self.dense = bool(dense)
+        if self.follow_sensor:
+            sensor = env.lidar_scanner if source == "lidar" else env.depth_camera
+            self.sensor_counter, self.sensor_every = sensor.counter, int(sensor.config.every)
+            check(self._lib.pgtt_elevation_bind_rate(self._h, self.sensor_counter.data_ptr(), self.sensor_every))
         self.bind()
 
     def bind(self) -> None:
@@ -183,18 +195,24 @@ class ElevationMap(_sidelib.Handle):
                 o.map_out, o.dist_out = self.filled_map.data_ptr(), self.filled_dist_map.data_ptr()
             check(self._lib.pgtt_elevation_bind_fill(self._h, C.byref(o), self.passes))
 
-    def tick(self, clear_mask: Optional[torch.Tensor] = None, clear_all: bool = False, use_done: bool = False) -> torch.Tensor:
+    def tick(self, clear_mask: Optional[torch.Tensor] = None, clear_all: bool = False, use_done: bool = False, force: bool = False) -> torch.Tensor:
         """integrate the env's current image (or LiDAR points) under its current pose and sample the scan: one launch on the env's current stream,
         no synchronisation.  Before integrating, the maps of the envs with clear_mask[e] != 0 ([N] uint8 / bool), of every env (clear_all) or of
-        the envs whose done flag is set (use_done) are cleared.  With fill > 0 the hole filling is enqueued behind it."""
+        the envs whose done flag is set (use_done) are cleared.  With fill > 0 the hole filling is enqueued behind it.
+        With follow_sensor (two launches, one of which returns at once) this is so on the calls behind a sensor tick that took new data - `force`
+        is what that sensor tick was given; on the others the clears are made, nothing else of the map changes and the scan is sampled from it at
+        the current pose.  `force` is not read without follow_sensor."""
         mp = None
         if clear_mask is not None:
             self._mask = clear_mask.to(self.env.device, torch.uint8).contiguous()      # kept alive until the next tick: the launch is asynchronous
             assert self._mask.shape == (self.env.num_envs,)
             mp = self._mask.data_ptr()
-        fn = self._lib.pgtt_elevation_points if self.source == "lidar" else self._lib.pgtt_elevation
         stream = torch.cuda.current_stream(self.env.device).cuda_stream
-        check(fn(self._h, mp, int(bool(clear_all)), int(bool(use_done)), stream))
+        if self.follow_sensor:
+            check(self._lib.pgtt_elevation_follow(self._h, mp, int(bool(clear_all)), int(bool(use_done)), int(bool(force)), stream))
+        else:
+            fn = self._lib.pgtt_elevation_points if self.source == "lidar" else self._lib.pgtt_elevation
+            check(fn(self._h, mp, int(bool(clear_all)), int(bool(use_done)), stream))
         if self.passes:
             check(self._lib.pgtt_elevation_fill(self._h, stream))
         return self.obs

@@ -69,21 +69,27 @@ class Joystick:
         `env.lidar_points` the [N, R, 3] world points of its returns, `env.lidar_scanner` the LidarScanner; ticked next to the camera, after every
         step and (with force) reset.  A side output like the image.  None: the library is not opened.
         elevation=dict(source="lidar", ...) fuses the map from the LiDAR's points instead of the image: it needs lidar (with every=1, on any body:
-        the points are world points) and no depth; clearing goes exactly as for the camera-fed map."""
+        the points are world points) and no depth; clearing goes exactly as for the camera-fed map.
+        elevation=dict(follow_sensor=True, ...) lifts the two `every=1` conditions: the sensor that feeds the map may have any period (depth=dict(every=3),
+        or lidar=dict(every=3) with source="lidar"; the camera still sits on the torso).  The map then fuses on the steps on which that sensor takes
+        new data - reset() forces one - and on the steps in between it is left as it is, but for the clears, while elevation_obs, elevation_known and
+        the filled outputs are sampled from it at the current pose on every step (pgtt_elevation_follow).  With every=1 the bits are those of an env
+        without the flag."""
         if student is not None and depth is None:
             raise ValueError("Joystick(student=...) needs depth=dict(...): the student reads the onboard depth image")
         wants_map = elevation is not None and elevation is not False
         map_source = "depth" if not wants_map or elevation is True else dict(elevation).get("source", "depth")
+        follows = wants_map and elevation is not True and bool(dict(elevation).get("follow_sensor", False))
         if wants_map and map_source not in ("depth", "lidar"):
             raise ValueError(f"Joystick(elevation=dict(source=...)): source must be 'depth' or 'lidar', not {map_source!r}")
         if wants_map and map_source == "lidar":
             if lidar is None:
                 raise ValueError("Joystick(elevation=dict(source='lidar')) needs lidar=dict(...): the elevation map is fused from the LiDAR's points")
-            if int(dict(lidar).get("every", 1)) != 1:
+            if int(dict(lidar).get("every", 1)) != 1 and not follows:
                 raise ValueError("Joystick(elevation=dict(source='lidar')) needs a LiDAR with every=1: the map would fuse a stale scan again at every tick")
         if wants_map and map_source == "depth" and depth is None:
             raise ValueError("Joystick(elevation=...) needs depth=dict(...): the elevation map is fused from the onboard depth image")
-        if wants_map and map_source == "depth" and (int(dict(depth).get("every", 1)) != 1 or int(dict(depth).get("mount_body", 0)) != 0):
+        if wants_map and map_source == "depth" and ((int(dict(depth).get("every", 1)) != 1 and not follows) or int(dict(depth).get("mount_body", 0)) != 0):
             raise ValueError("Joystick(elevation=...) needs a camera on the torso (mount_body=0) with every=1: a stale image under a moved pose "
                              "would be unprojected wrongly")
         self.level_start = None
@@ -381,7 +387,7 @@ class Joystick:
             else:
                 self.student.tick()
         if self.elevation_map is not None:
-            self.elevation_map.tick(clear_mask=mask, clear_all=mask is None)
+            self.elevation_map.tick(clear_mask=mask, clear_all=mask is None, force=True)
         return self._obs()
 
     def step(self, action: torch.Tensor, curriculum: bool = True):
@@ -403,7 +409,7 @@ class Joystick:
             else:
                 self.student.tick()
         if self.elevation_map is not None:
-            self.elevation_map.tick(use_done=True)
+            self.elevation_map.tick(use_done=True, force=False)
         info = {"metrics": self.buffers["metrics"], "episode_metrics": self.buffers["ep_metrics"]}
         return self._obs(), self.buffers["reward"], self.buffers["done"], info
 

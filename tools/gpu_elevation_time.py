@@ -2,7 +2,7 @@
 from domain_randomize(seed=0), 64x48 images of the default camera, G = 64, poses after 40 control steps of small random actions; device events
 around 20 back-to-back calls after 5 warm-up calls, median [min, max] of 11 such windows.
 
-    python tools/gpu_elevation_time.py [--out profiles/NAME.txt] [--accuracy] [--fill K[,K...]] [--eval]
+    python tools/gpu_elevation_time.py [--out profiles/NAME.txt] [--accuracy] [--fill K[,K...]] [--eval] [--every M[,M...]]
 
 (i) pgtt_elevation (one launch); (ii) the same six steps as torch ops (scatter_reduce_ with amax) - what (i) replaces, the yardstick; (iii) the
 camera tick; (iv) the student's two launches; (v) the env step (no camera).
@@ -12,11 +12,16 @@ est against perceive.scan_target over the known points, per band, and the known 
 --accuracy the env fills with the first of them, and the RMSE of filled_est is reported over the covered points (dist != 255) per band and per
 bucket of dist (0 = measured, 1-4, 5-8, 9+ = the pass that filled the cell).
 --eval: evaluate.py's rollout of policy177 on level4, 1000 envs, full domain randomisation, one deterministic episode - on the true observation, on
-the depth-fused and the LiDAR-fused map, and on each of the two filled (--elevation_fill, 16 passes), with the known and the covered share."""
+the depth-fused and the LiDAR-fused map, and on each of the two filled (--elevation_fill, 16 passes), with the known and the covered share.
+--every 1,2,3,5: (vii) pgtt_elevation_follow behind a camera of each period M, in the same job as (i) and (iii): a hold call and a
+fresh call alone (the sensor's counter held where the call is the one or the other), and camera tick + map call in the camera's own schedule, in
+windows of 30 steps (a whole number of periods), which is the mean cost of perception per control step; with --eval, evaluate.py --elevation
+--sensor_every M for each M, with and without --elevation_fill, next to the same command without the flag."""
 import argparse
 import math
 import os
 import sys
+import types
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -198,13 +203,45 @@ def accuracy(terrain, steps_warm=50, steps=200, n=1000, fill=0):
     return lines
 
 
-def evaluation(n=1000):
+def follow_rows(env, periods):
+    """(vii): per period M a camera of its own on the env's buffers and a map that follows it"""
+    from phase_guided_terrain_traversal_amd import depth
+    rows = []
+    for m in periods:
+        cam = depth.DepthCamera(env, **depth.settings(dict(every=m)))
+        shim = types.SimpleNamespace(depth=cam.image, depth_camera=cam, buffers=env.buffers, device=env.device, num_envs=env.num_envs,
+                                     observation_size=env.observation_size, config=env.config, method=env.method)
+        fm = elevation.ElevationMap(shim, follow_sensor=True, **elevation.DEFAULTS)
+        cam.tick(force=True); fm.tick(clear_all=True, force=True)
+
+        def step():
+            cam.tick(); fm.tick()
+        cam.counter.fill_(1)                                              # c = 0: every call is fresh
+        rows.append((f"(vii) M = {m}: pgtt_elevation_follow, a fresh call (two launches)", window_us(fm.tick)))
+        if m > 1:
+            cam.counter.fill_(2)                                          # c = 1: every call is a hold
+            rows.append((f"(vii) M = {m}: pgtt_elevation_follow, a hold call (two launches)", window_us(fm.tick)))
+        cam.counter.zero_()
+        rows.append((f"(vii) M = {m}: camera tick alone in its schedule, mean per step", window_us(cam.tick, calls=30)))
+        cam.counter.zero_()
+        rows.append((f"(vii) M = {m}: camera tick + follow in the camera's schedule, mean per step", window_us(step, calls=30)))
+        fm.close(); cam.close()
+    return rows
+
+
+def evaluation(n=1000, periods=()):
     import evaluate
     base = ["--policy", "policy177", "--terrain_file", "level4"]
     lines = [f"evaluate.py: policy177, level4, {n} envs, full DR, one deterministic episode"]
     lidar = ["--elevation", "--elevation_source", "lidar"]
-    for name, extra in (("true observation", []), ("depth-fused map", ["--elevation"]), ("depth-fused map, filled", ["--elevation", "--elevation_fill"]),
-                        ("LiDAR-fused map", lidar), ("LiDAR-fused map, filled", lidar + ["--elevation_fill"])):
+    cases = [("true observation", []), ("depth-fused map", ["--elevation"]), ("depth-fused map, filled", ["--elevation", "--elevation_fill"]),
+             ("LiDAR-fused map", lidar), ("LiDAR-fused map, filled", lidar + ["--elevation_fill"])]
+    if periods:                                                           # the follow study: the depth-fused map alone, and the command without the flag
+        cases = cases[:3]
+    for m in periods:
+        cases += [(f"depth map, sensor_every {m}", ["--elevation", "--sensor_every", str(m)]),
+                  (f"  the same (M = {m}), filled", ["--elevation", "--elevation_fill", "--sensor_every", str(m)])]
+    for name, extra in cases:
         r = evaluate.run_evaluation(evaluate.make_parser().parse_args(base + extra), num_eval_envs=n, verbose=False)
         shares = (f", known scan points {r['known_share']:.3f}" if "known_share" in r else "") + (f", covered {r['covered_share']:.3f}" if "covered_share" in r else "")
         lines.append(f"  {name:24s} survivors {r['survivors']} / {n}, reward {r['episode_reward']:.2f}, length {r['avg_episode_length']:.1f}, "
@@ -219,7 +256,9 @@ def main():
     ap.add_argument("--accuracy", action="store_true")
     ap.add_argument("--fill", type=str, default=None, metavar="K[,K...]", help="time pgtt_elevation_fill with these numbers of passes; --accuracy fills with the first")
     ap.add_argument("--eval", action="store_true")
+    ap.add_argument("--every", type=str, default=None, metavar="M[,M...]", help="time pgtt_elevation_follow behind a camera of these periods; --eval evaluates with them")
     args = ap.parse_args()
+    periods = [int(m) for m in args.every.split(",")] if args.every else []
     passes = [int(k) for k in args.fill.split(",")] if args.fill else []
     n = args.num_envs
     terrain = np.load(os.path.join(ROOT, "phase_guided_terrain_traversal_amd", "assets", "terrains", "level4.npy"))
@@ -258,6 +297,7 @@ def main():
         share = float((fm.filled_dist != elevation.DIST_UNKNOWN).float().mean())
         rows.append((f"(vi)  pgtt_elevation_fill, {k} passes (covers {share:.3f} of the scan points; the map knows {float((em.known > 0).float().mean()):.3f})", us))
         fm.close()
+    rows += follow_rows(env, periods)
     c = em.config
     traffic = n * (2 * 4 * c.grid ** 2 + 4 * c.width * c.height + 2 * 4 * c.obs_dim + 5 * abi.NSCAN)
     lines = [f"{n} envs, level4, {c.width}x{c.height}, G = {c.grid}, res = {c.res:.3f}, alpha = {c.alpha}; us per call, median [min, max] of 11 windows of 20 calls",
@@ -270,7 +310,7 @@ def main():
     if args.accuracy:
         lines += accuracy(terrain, fill=passes[0] if passes else 0)
     if args.eval:
-        lines += evaluation()
+        lines += evaluation(periods=periods)
     text = "\n".join(lines)
     print(text)
     if args.out:
