@@ -14,7 +14,8 @@ is built.  The policy comes from `--checkpoint_folder` (the newest `<env_steps>.
 whose scan rows the student perception module estimated from the onboard depth image, with `--elevation [grid,res,alpha]` on the observation whose
 scan rows are sampled from the depth-fused elevation map (elevation.py; nothing to train; `--elevation_source lidar` fuses it from the onboard
 LiDAR's points instead, lidar.py; `--elevation_fill [K]` closes the map's holes first and the policy acts on the filled scan; `--sensor_every M`
-runs that sensor at one control step in M and lets the map follow it); the remaining flags of the reference's CLI are accepted and ignored.
+runs that sensor at one control step in M and lets the map follow it; `--elevation_variance [sigma0,sigma_rel,process,gate,band]` fuses the map by
+the variance-weighted update; `--sensor_noise SIGMA[,DROPOUT]` gives the sensor that feeds the map or the student range noise); the remaining flags of the reference's CLI are accepted and ignored.
 """
 import argparse
 import os
@@ -142,11 +143,18 @@ def run_evaluation(args, num_eval_envs=NUM_EVAL_ENVS, seed=0, verbose=True):
     push = configs.push_from_args(args)                           # --push_*: random kicks of the torso (off unless one is given)
     if push is not None:
         kw["push"] = push
+    # --sensor_noise SIGMA[,DROPOUT]: the sensor that feeds the student or the map reads noisy ranges (the sensors' noise=dict(sigma, dropout):
+    # relative range noise and the probability of a `far` reading); without it they are exact
+    noisy = sensor_noise(getattr(args, "sensor_noise", None))
     if getattr(args, "student", None):
         # --student: the policy acts on env.student_obs - the observation whose scan rows a perceive.ScanEstimator estimated from the onboard
         # depth image (the camera of depth.DEFAULTS) - instead of the privileged scan
-        kw.update(depth={}, student=args.student)
+        kw.update(depth=dict(noisy), student=args.student)
     elev = getattr(args, "elevation", None)
+    if noisy and elev is None and not getattr(args, "student", None):
+        raise SystemExit("--sensor_noise is the noise of the sensor that feeds --elevation's map or --student: give one of them too")
+    if getattr(args, "elevation_variance", None) is not None and elev is None:
+        raise SystemExit("--elevation_variance says how --elevation's map is fused: give --elevation too")
     if elev is not None:
         # --elevation [grid,res,alpha]: the policy acts on env.elevation_obs - the observation whose scan rows are sampled from the elevation map
         # fused from the onboard depth image (the camera of depth.DEFAULTS; elevation.DEFAULTS where a value is not given)
@@ -172,9 +180,16 @@ def run_evaluation(args, num_eval_envs=NUM_EVAL_ENVS, seed=0, verbose=True):
         every = int(getattr(args, "sensor_every", 1))
         if every < 1:
             raise SystemExit(f"--sensor_every {every}: the sensor's period must be >= 1")
-        sensor = {} if every == 1 else dict(every=every)
+        sensor = dict(noisy) if every == 1 else dict(noisy, every=every)
         if every > 1:
             given = dict({} if given is True else given, follow_sensor=True)
+        variance = elevation_variance(getattr(args, "elevation_variance", None))
+        if variance is not None:
+            # --elevation_variance [sigma0,sigma_rel,process,gate,band]: the map is fused by the variance-weighted update (elevation.VARIANCE_DEFAULTS
+            # where a value is not given) instead of the maximum and alpha
+            if every > 1:
+                raise SystemExit("--elevation_variance behind a slower sensor (--sensor_every > 1) is not built yet")
+            given = dict({} if given is True else given, variance=variance)
         if source == "lidar":
             # --elevation_source lidar: the map is fused from the world points of the onboard LiDAR (lidar.DEFAULTS), as the deployed mapping stack's is
             kw.update(lidar=sensor, elevation=dict({} if given is True else given, source="lidar"))
@@ -244,6 +259,34 @@ def run_training(args):
     return run_evaluation(args)["survivors"]
 
 
+def sensor_noise(text):
+    """--sensor_noise SIGMA[,DROPOUT] -> {} (not given) or dict(noise=dict(sigma=..., dropout=...)), the sensors' keyword"""
+    if text is None:
+        return {}
+    vals = [v for v in str(text).split(",") if v]
+    try:
+        nums = [float(v) for v in vals]
+    except ValueError:
+        nums = []
+    if not 1 <= len(nums) <= 2 or nums[0] < 0 or not 0 <= (nums[1] if len(nums) > 1 else 0.0) < 1:
+        raise SystemExit(f"--sensor_noise {text}: give SIGMA[,DROPOUT] with SIGMA >= 0 and 0 <= DROPOUT < 1")
+    return dict(noise=dict(sigma=nums[0], dropout=nums[1] if len(nums) > 1 else 0.0))
+
+
+def elevation_variance(text):
+    """--elevation_variance [sigma0,sigma_rel,process,gate,band] -> None (not given), True (the flag alone) or a dict of the values given"""
+    if text is None:
+        return None
+    vals = [v for v in str(text).split(",") if v]
+    names = ("sigma0", "sigma_rel", "process", "gate", "band")
+    if len(vals) > len(names):
+        raise SystemExit("--elevation_variance takes at most sigma0,sigma_rel,process,gate,band")
+    try:
+        return dict(zip(names, (float(v) for v in vals))) if vals else True
+    except ValueError:
+        raise SystemExit(f"--elevation_variance {text}: the values must be numbers")
+
+
 def fill_passes(text):
     """--elevation_fill K: an integer in [1, 95] (elevation.MAX_FILL); the flag without a value is True, elevation.FILL_PASSES"""
     try:
@@ -283,6 +326,10 @@ def make_parser():
                     help="with --elevation: fuse the map from the depth camera's image (default) or from the onboard LiDAR's points (lidar.py)")
     ap.add_argument("--elevation_fill", type=fill_passes, nargs="?", const=True, default=None, metavar="K",
                     help="with --elevation: close the map's holes with K passes (16 unless given) behind every tick; the policy acts on the filled scan")
+    ap.add_argument("--elevation_variance", type=str, nargs="?", const="", default=None, metavar="SIGMA0,SIGMA_REL,PROCESS,GATE,BAND",
+                    help="with --elevation: fuse the map by the variance-weighted (Kalman) update instead of the maximum and alpha; optional settings")
+    ap.add_argument("--sensor_noise", type=str, default=None, metavar="SIGMA[,DROPOUT]",
+                    help="with --elevation or --student: relative range noise and dropout probability of the sensor that feeds it")
     ap.add_argument("--sensor_every", type=int, default=1, metavar="M",
                     help="with --elevation: the sensor that feeds the map runs at one control step in M; for M > 1 the map follows it, holding in between")
     configs.add_push_args(ap)

@@ -119,6 +119,40 @@
  * An env's outputs depend on its own rows only.  pgtt_elevation_fill() is what it was: it reads `map`, `origin` and `state` as they stand, so behind
  * a hold call it fills and samples the held window at the current pose.  Not covered: an image fused later than it was taken (that needs the pose
  * of its capture), sensor phases per env, latency.
+ *
+ * Variance-weighted fusion: a Kalman layer.  Steps 3 and 4 above suit noise-free data: the maximum of n noisy samples is biased upwards, and alpha
+ * is one gain for every distance.  pgtt_elevation_var() and pgtt_elevation_var_points() are ticks that keep, next to `map`, a second persistent
+ * layer `var`: device [N][G][G] fp32 in the slot layout of `map`, the variance of each height in m^2, NaN exactly where `map` is NaN; and that write
+ * one more output per tick, est_var [N][117].  The settings, the two buffers and their ranges are PgttElevationVar's (pgtt_elevation_bind_var).  Per
+ * env, in this order; `alpha` is not read:
+ *  1. Clear.     Step 1 above, on `map` and `var` together.
+ *  2. Recentre.  Step 2 above, on `map` and `var` together.
+ *  3. Tick maximum.  Step 3 above for the image (pgtt_elevation_var) or for the points (pgtt_elevation_var_points), unchanged: validity,
+ *     unprojection, self filter, window test, and zmax[cell] by the LDS atomic maximum on the order-preserving key.
+ *  4. Band sums.  A second pass over the same pixels or points.  A pixel that step 3 admitted into `cell` contributes when zmax[cell] - z <= band,
+ *     with q = rint((zmax[cell] - z) * 2^18), an integer (PGTT_ELEVATION_BAND_SCALE).  Per cell n = the number of contributors and S = the sum of
+ *     their q; the pixel that is the maximum always contributes, with q = 0.  Both are integer sums (LDS integer atomics): the result does not
+ *     depend on the order of the lanes, or of the points in `points`.
+ *  5. Measurement, per touched cell.
+ *         m    = zmax - (S / n) * 2^-18:   the mean of the upper-surface band; with n = 1, m is zmax bit for bit
+ *         rho2 = (cx - bx)^2 + (cy - by)^2 + (m - bz)^2,   (cx, cy) = ((ix + 0.5) res, (iy + 0.5) res) the centre of the world cell, b the BASE
+ *                position - for both sources: the points call knows no sensor mount, and these are settings, not facts about a sensor
+ *         r    = (sigma0^2 + sigma_rel^2 rho2) / min(n, max_count)
+ *  6. Predict.  Every cell that is not NaN, touched or not: v = min(v + process, var_max).
+ *  7. Update, per touched cell.
+ *         the cell is NaN:                     h = m, v = min(r, var_max)
+ *         (m - h)^2 <= gate^2 (v + r):         k = v / (v + r), h += k (m - h), v = v r / (v + r)
+ *         the gate fails and m > h:            h = m, v = min(r, var_max): the map is an upper-surface map, as the maximum made it
+ *         the gate fails and m < h:            the measurement is ignored.  With process > 0 the cell's variance grows tick by tick until a
+ *                                              persistent lower measurement passes the gate; with process = 0 it never does.
+ *  8. Sample.   Step 5 above on `map`: est and known as there.  est_var[i] = v of the cell that contains scan point i, var_max at an unknown point.
+ *  9. Assemble. Step 6 above.
+ * An env's outputs depend on its own rows only.  One launch, one workgroup of 256 lanes per env; LDS holds a key word and a 64-bit (n, S) word per
+ * slot, 12 G G bytes, and this entry keeps that under the 64 KB a launch gets without an attribute: G <= PGTT_ELEVATION_VAR_MAX_GRID = 64;
+ * pgtt_elevation_bind_var refuses a handle with a larger grid (PGTT_E_ARG).
+ * pgtt_elevation_fill() is unchanged: it reads `map` as it stands, so it works behind a variance tick; filled cells have no variance.
+ * `var` is maintained by these two calls alone, and a caller uses ONE kind of tick on a handle: pgtt_elevation(), pgtt_elevation_points() and
+ * pgtt_elevation_follow() on a handle with a variance bound do what they always did and leave `var` stale.
  */
 #ifndef PGTT_ELEVATION_H_
 #define PGTT_ELEVATION_H_
@@ -205,6 +239,36 @@ int pgtt_elevation_bind_rate(pgtt_elevation_handle h, const int64_t* counter, in
 /* Called BEHIND the sensor's call of the same step, with the `force` that call was given.  PGTT_E_STATE before a bind of the buffers or before
  * pgtt_elevation_bind_rate.  The image or the points are used, by which bind was made last (as pgtt_elevation / pgtt_elevation_points). */
 int pgtt_elevation_follow(pgtt_elevation_handle h, const uint8_t* clear_mask, int clear_all, int use_done, int force, void* stream);
+
+#define PGTT_ELEVATION_MAX_BAND 0.5f             /* band <= 0.5 m: q < 2^18, and 65536 pixels of one cell sum below 2^34 */
+#define PGTT_ELEVATION_BAND_SCALE 262144.0f      /* 2^18: the band offsets are summed as integers in units of 2^-18 m */
+#define PGTT_ELEVATION_VAR_MAX_GRID 64           /* 12 * 64 * 64 = 49152 bytes of LDS */
+
+/* the variance layer: its two caller-owned device buffers, sized for N, and its settings (all finite) */
+typedef struct PgttElevationVar {
+  float* var;                            /* [N][G][G], required; NaN where map is NaN */
+  float* est_var;                        /* [N][PGTT_NSCAN], required */
+  float sigma0;                          /* range-independent standard deviation, metres, >= 0 */
+  float sigma_rel;                       /* standard deviation per metre of distance, >= 0, and sigma0 + sigma_rel > 0 */
+  float process;                         /* variance added to every known cell per tick, m^2, >= 0 */
+  float gate;                            /* Mahalanobis gate, > 0 */
+  float band;                            /* thickness of the upper-surface band, metres, 0 <= band <= PGTT_ELEVATION_MAX_BAND */
+  int32_t max_count;                     /* cap on the number of pixels of one cell that count as independent, >= 1 */
+  float var_max;                         /* prior variance and clamp, m^2, > 0 */
+} PgttElevationVar;
+
+/* the settings' ranges alone (the pointers are not looked at): host only, needs no GPU.  PGTT_E_ARG for NULL or a value outside its range. */
+int pgtt_elevation_check_var(const PgttElevationVar* v);
+/* PGTT_E_ARG for a NULL struct, a NULL var or est_var, a value outside its range, or a handle whose grid is above PGTT_ELEVATION_VAR_MAX_GRID.
+ * May be called before or after the buffers are bound and persists across later binds, like pgtt_elevation_bind_fill. */
+int pgtt_elevation_bind_var(pgtt_elevation_handle h, const PgttElevationVar* v);
+/* one variance tick for all N envs from the image: ONE launch on `stream`, no allocation, no synchronisation, no read-back, capturable.
+ * PGTT_E_STATE before the buffers are bound, on a handle bound without a depth image, or before pgtt_elevation_bind_var. */
+int pgtt_elevation_var(pgtt_elevation_handle h, const uint8_t* clear_mask, int clear_all, int use_done, void* stream);
+/* the same from the bound points (the source is whichever bind was made last, as for pgtt_elevation_points): PGTT_E_STATE before
+ * pgtt_elevation_bind_points or before pgtt_elevation_bind_var. */
+int pgtt_elevation_var_points(pgtt_elevation_handle h, const uint8_t* clear_mask, int clear_all, int use_done, void* stream);
+int pgtt_elevation_sizeof_var(void);
 int pgtt_elevation_sizeof_fill(void);
 int pgtt_elevation_sizeof_config(void);
 int pgtt_elevation_sizeof_buffers(void);

@@ -14,6 +14,9 @@
 //   phase F  obs_out = obs with the scan rows replaced.
 // The phases are separated by workgroup barriers.  No global atomics, no scratch; nothing is shared between envs.
 //
+// elevation_var_kernel<POINTS>, the variance tick (pgtt_elevation_var, pgtt_elevation_var_points): the same phases with a second pass over the pixels
+// (integer band sums in a 64-bit LDS word per slot) and a Kalman update per slot while `map` and `var` stream through; described at the kernel.
+//
 // fill_kernel, the hole filling behind a tick: one workgroup of four waves per env again.  LDS holds the window in WINDOW order inside a border of one
 // cell, one key word (key_of the value; kNoKey = a hole or the border) and one byte `D` per cell: 5 (G + 2)^2 bytes, 48020 at G = 96, under the
 // 64 KB that need no launch attribute.  The border makes the window's edges edges and keeps every neighbour's index in range.
@@ -306,6 +309,282 @@ __global__ void __launch_bounds__(kLanes) elevation_kernel(ElevArgs a) {
     sh_est[tid] = es;
     a.est[(long)e * PGTT_NSCAN + tid] = es;
     a.known[(long)e * PGTT_NSCAN + tid] = kn ? 1 : 0;
+  }
+
+  // ---- phase F: obs_out = obs with the scan rows replaced
+  if (a.obs_out) {
+    __syncthreads();
+    assemble(a.obs_out, a.obs, sh_est, e, a.obs_dim, a.scan_row0, tid);
+  }
+}
+
+// the variance tick: the plain tick's arguments (alpha is not read) and the variance layer's
+struct VarArgs {
+  ElevArgs a;
+  float* var; float* est_var;
+  float s0sq, srsq, process, gate2, band, var_max;           // sigma0^2, sigma_rel^2, gate^2
+  int max_count;
+};
+
+constexpr int kCountShift = 40;                   // the (n, S) word: n above bit 40, S below.  n <= 65536 pixels, S < 65536 * 2^17 = 2^33
+static_assert((double)PGTT_ELEVATION_MAX_BAND * PGTT_ELEVATION_BAND_SCALE <= 131072.0 && PGTT_ELEVATION_MAX_DIM * PGTT_ELEVATION_MAX_DIM <= 65536,
+              "S stays below bit 40 for the image; a point cloud of P < 2^23 points does too");
+static_assert(12 * PGTT_ELEVATION_VAR_MAX_GRID * PGTT_ELEVATION_VAR_MAX_GRID + 2048 <= 65536, "the variance tick's LDS needs no launch attribute");
+
+// elevation_var_kernel<POINTS>: the variance tick (include/pgtt_elevation.h, "Variance-weighted fusion"), one workgroup of four waves per env.
+// Dynamic LDS: sh_acc[G G], one 64-bit word (n << 40 | S) per slot, then sh_m[G G], the key word of elevation_kernel.  After phase D sh_m holds the
+// fused heights and the low half of each sh_acc word the slot's variance.
+//   phase A, B  elevation_kernel's; the lanes zero both arrays.
+//   phase C  two passes over the same pixels (or points) by ONE loop body, so that a point and its slot are the same bits in both: pass 0 raises
+//            sh_m[slot] (ds_max_u32 on the key), pass 1 adds (1 << 40 | q) to sh_acc[slot] (ds_add_u64) for the pixels inside the band.  The point is
+//            recomputed in pass 1: a lane holds up to 256 pixels of a 256 x 256 image, which no register file keeps.
+//   phase D  `map` and `var` stream through in 16-byte runs (dwords for an odd G G): stale slots to NaN, predict, measurement and update per slot; a
+//            run of either array is written back only when one of its slots changed there.
+//   phase E, F  elevation_kernel's, with est_var next to est.
+// Integer LDS atomics only; no global atomics, no scratch.
+template <bool POINTS>
+__global__ void __launch_bounds__(kLanes) elevation_var_kernel(VarArgs va) {
+  const ElevArgs& a = va.a;
+  extern __shared__ __attribute__((aligned(16))) unsigned long long sh_acc[];      // [G * G], then the keys
+  __shared__ float sh_p[P_N];
+  __shared__ int sh_i[I_N];
+  __shared__ unsigned char sh_stale[2 * kMaxG];
+  __shared__ float sh_est[PGTT_NSCAN];
+  __shared__ float sh_red[2];
+  const int e = blockIdx.x, tid = threadIdx.x, G = a.G, GG = G * G;
+  const long N = a.N;
+  unsigned* sh_m = reinterpret_cast<unsigned*>(sh_acc + GG);
+
+  // ---- phase A: the poses (lane 0), as in elevation_kernel; the tick maximum and the sums start empty
+  if (tid == 0) {
+    const float* S = a.state + e;
+    const float bx = S[(PGTT_S_QPOS + 0) * N], by = S[(PGTT_S_QPOS + 1) * N], bz = S[(PGTT_S_QPOS + 2) * N];
+    float qw = S[(PGTT_S_QPOS + 3) * N], qx = S[(PGTT_S_QPOS + 4) * N], qy = S[(PGTT_S_QPOS + 5) * N], qz = S[(PGTT_S_QPOS + 6) * N];
+    const float qn = sqrtf(qw * qw + qx * qx + qy * qy + qz * qz);
+    qw /= qn; qx /= qn; qy /= qn; qz /= qn;
+    const float r00 = qw * qw + qx * qx - qy * qy - qz * qz, r01 = 2.f * (qx * qy - qw * qz), r02 = 2.f * (qx * qz + qw * qy);
+    const float r10 = 2.f * (qx * qy + qw * qz), r11 = qw * qw - qx * qx + qy * qy - qz * qz, r12 = 2.f * (qy * qz - qw * qx);
+    const float r20 = 2.f * (qx * qz - qw * qy), r21 = 2.f * (qy * qz + qw * qx), r22 = qw * qw - qx * qx - qy * qy + qz * qz;
+    sh_p[P_BASE + 0] = bx; sh_p[P_BASE + 1] = by; sh_p[P_BASE + 2] = bz;
+    sh_p[P_RB + 0] = r00; sh_p[P_RB + 1] = r01; sh_p[P_RB + 2] = r02; sh_p[P_RB + 3] = r10; sh_p[P_RB + 4] = r11; sh_p[P_RB + 5] = r12;
+    sh_p[P_RB + 6] = r20; sh_p[P_RB + 7] = r21; sh_p[P_RB + 8] = r22;
+    if constexpr (!POINTS) {
+      sh_p[P_CAM + 0] = bx + r00 * a.mpos[0] + r01 * a.mpos[1] + r02 * a.mpos[2];
+      sh_p[P_CAM + 1] = by + r10 * a.mpos[0] + r11 * a.mpos[1] + r12 * a.mpos[2];
+      sh_p[P_CAM + 2] = bz + r20 * a.mpos[0] + r21 * a.mpos[1] + r22 * a.mpos[2];
+      const float mw = a.mquat[0], mx = a.mquat[1], my = a.mquat[2], mz = a.mquat[3];
+      const float cw = qw * mw - qx * mx - qy * my - qz * mz, cx = qw * mx + qx * mw + qy * mz - qz * my;
+      const float cyq = qw * my - qx * mz + qy * mw + qz * mx, cz = qw * mz + qx * my - qy * mx + qz * mw;
+      const float fx = cw * cw + cx * cx - cyq * cyq - cz * cz, fy = 2.f * (cx * cyq + cw * cz), fz = 2.f * (cx * cz - cw * cyq);
+      const float ux = 2.f * (cx * cz + cw * cyq), uy = 2.f * (cyq * cz - cw * cx), uz = cw * cw - cx * cx - cyq * cyq + cz * cz;
+      sh_p[P_FWD + 0] = fx; sh_p[P_FWD + 1] = fy; sh_p[P_FWD + 2] = fz;
+      sh_p[P_UP + 0] = ux; sh_p[P_UP + 1] = uy; sh_p[P_UP + 2] = uz;
+      sh_p[P_RIGHT + 0] = fy * uz - fz * uy; sh_p[P_RIGHT + 1] = fz * ux - fx * uz; sh_p[P_RIGHT + 2] = fx * uy - fy * ux;
+    }
+    float sy, cy; yaw_sincos(qw, qx, qy, qz, sy, cy);
+    sh_p[P_SY] = sy; sh_p[P_CY] = cy;
+    const bool clear = a.clear_all || (a.clear_mask && a.clear_mask[e]) || (a.use_done && a.done && a.done[e] != 0.f);
+    const int ox = cell_of(bx, a.res), oy = cell_of(by, a.res);
+    const int lox = ox - G / 2, loy = oy - G / 2;
+    sh_i[I_LOX] = lox; sh_i[I_LOY] = loy; sh_i[I_LMX] = floor_mod(lox, G); sh_i[I_LMY] = floor_mod(loy, G);
+    const int px = a.origin[2 * (long)e], py = a.origin[2 * (long)e + 1];
+    const bool sane = px >= -(1 << 30) && px <= (1 << 30) && py >= -(1 << 30) && py <= (1 << 30);
+    sh_i[I_OLDX] = px - G / 2; sh_i[I_OLDY] = py - G / 2; sh_i[I_CLEAR] = (clear || !sane) ? 1 : 0;
+    a.origin[2 * (long)e] = ox; a.origin[2 * (long)e + 1] = oy;
+  }
+  for (int s = tid; s < GG; s += kLanes) { sh_acc[s] = 0ull; sh_m[s] = 0u; }
+  __syncthreads();
+
+  // ---- phase B: per axis, the slots whose world cell moved
+  if (tid < 2 * G) {
+    const int ax = tid >= G, s = tid - ax * G;
+    const int lo_new = sh_i[I_LOX + ax], lo_old = sh_i[I_OLDX + ax];
+    unsigned char st = 1;
+    if (!sh_i[I_CLEAR]) st = (lo_new + floor_mod(s - lo_new, G)) != (lo_old + floor_mod(s - lo_old, G));
+    sh_stale[tid] = st;
+  }
+
+  // ---- phase C: pass 0 the tick maximum, pass 1 the band sums.  `admit` is what both do with a point that step 3 admits into `slot`
+  const float bpx = uni(sh_p[P_BASE + 0]), bpy = uni(sh_p[P_BASE + 1]), bpz = uni(sh_p[P_BASE + 2]);
+  const int lox = sh_i[I_LOX], loy = sh_i[I_LOY], lmx = sh_i[I_LMX], lmy = sh_i[I_LMY];
+  {
+    const float b00 = uni(sh_p[P_RB + 0]), b01 = uni(sh_p[P_RB + 1]), b02 = uni(sh_p[P_RB + 2]), b10 = uni(sh_p[P_RB + 3]), b11 = uni(sh_p[P_RB + 4]);
+    const float b12 = uni(sh_p[P_RB + 5]), b20 = uni(sh_p[P_RB + 6]), b21 = uni(sh_p[P_RB + 7]), b22 = uni(sh_p[P_RB + 8]);
+    const float band = va.band;
+    auto admit = [&](int pass, int slot, float pz) {
+      if (pass == 0) {
+        atomicMax(&sh_m[slot], key_of(pz));
+      } else {
+        const float dz = value_of(sh_m[slot]) - pz;                   // >= 0: the maximum was taken over these bits
+        if (dz <= band) atomicAdd(&sh_acc[slot], (1ull << kCountShift) | (unsigned long long)(unsigned)rintf(dz * PGTT_ELEVATION_BAND_SCALE));
+      }
+    };
+    if constexpr (POINTS) {
+      const float* pts = a.points + (long)e * a.P * 3;
+#pragma nounroll
+      for (int pass = 0; pass < 2; pass++) {
+        for (int k = tid; k < a.P; k += kLanes) {
+          const float px = pts[3 * k], py = pts[3 * k + 1], pz = pts[3 * k + 2];
+          if (!(fabsf(px) < INFINITY && fabsf(py) < INFINITY && fabsf(pz) < INFINITY)) continue;
+          if (a.self_on) {
+            const float dx = px - bpx, dy = py - bpy, dz = pz - bpz;
+            const float lx = b00 * dx + b10 * dy + b20 * dz, ly = b01 * dx + b11 * dy + b21 * dz, lz = b02 * dx + b12 * dy + b22 * dz;
+            if (fabsf(lx) <= a.self_half[0] && fabsf(ly) <= a.self_half[1] && fabsf(lz) <= a.self_half[2]) continue;
+          }
+          const int relx = cell_of(px, a.res) - lox, rely = cell_of(py, a.res) - loy;
+          if ((unsigned)relx >= (unsigned)G || (unsigned)rely >= (unsigned)G) continue;
+          int sx = relx + lmx, sy = rely + lmy;
+          sx -= sx >= G ? G : 0; sy -= sy >= G ? G : 0;
+          admit(pass, sx * G + sy, pz);
+        }
+        __syncthreads();
+      }
+    } else {
+      const float cpx = sh_p[P_CAM + 0], cpy = sh_p[P_CAM + 1], cpz = sh_p[P_CAM + 2];
+      const float fx = sh_p[P_FWD + 0], fy = sh_p[P_FWD + 1], fz = sh_p[P_FWD + 2];
+      const float rx = sh_p[P_RIGHT + 0], ry = sh_p[P_RIGHT + 1], rz = sh_p[P_RIGHT + 2];
+      const float ux = sh_p[P_UP + 0], uy = sh_p[P_UP + 1], uz = sh_p[P_UP + 2];
+      const int W = a.W, npix = a.W * a.H;
+      const float* img = a.depth + (long)e * npix;
+      auto pixel = [&](int pass, float d, int i, int j) {
+        if (!(d > a.near_m && d < a.far_m)) return;
+        const float u = (2.f * ((float)j + 0.5f) / (float)W - 1.f) * a.tu, v = (1.f - 2.f * ((float)i + 0.5f) / (float)a.H) * a.tv;
+        const float px = cpx + d * (fx + u * rx + v * ux), py = cpy + d * (fy + u * ry + v * uy), pz = cpz + d * (fz + u * rz + v * uz);
+        if (a.self_on) {
+          const float dx = px - bpx, dy = py - bpy, dz = pz - bpz;
+          const float lx = b00 * dx + b10 * dy + b20 * dz, ly = b01 * dx + b11 * dy + b21 * dz, lz = b02 * dx + b12 * dy + b22 * dz;
+          if (fabsf(lx) <= a.self_half[0] && fabsf(ly) <= a.self_half[1] && fabsf(lz) <= a.self_half[2]) return;
+        }
+        const int relx = cell_of(px, a.res) - lox, rely = cell_of(py, a.res) - loy;
+        if ((unsigned)relx >= (unsigned)G || (unsigned)rely >= (unsigned)G || !(pz == pz)) return;
+        int sx = relx + lmx, sy = rely + lmy;
+        sx -= sx >= G ? G : 0; sy -= sy >= G ? G : 0;
+        admit(pass, sx * G + sy, pz);
+      };
+#pragma nounroll
+      for (int pass = 0; pass < 2; pass++) {
+        if (a.vec_img) {
+          for (int p = 4 * tid; p < npix; p += 4 * kLanes) {
+            const float4 d = *reinterpret_cast<const float4*>(img + p);
+            int i = p / W, j = p - i * W;
+            const float dv[4] = {d.x, d.y, d.z, d.w};
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+              pixel(pass, dv[k], i, j);
+              j++;
+              if (j == W) { j = 0; i++; }
+            }
+          }
+        } else {
+          for (int p = tid; p < npix; p += kLanes) { const int i = p / W; pixel(pass, img[p], i, p - i * W); }
+        }
+        __syncthreads();
+      }
+    }
+  }
+
+  // ---- phase D: map and var stream through; sh_m takes the fused heights, the low half of sh_acc the variances
+  {
+    float* mp = a.map + (long)e * GG;
+    float* vp = va.var + (long)e * GG;
+    float* sh_v = reinterpret_cast<float*>(sh_acc);                    // slot s: sh_v[2 s]
+    const float nanv = __uint_as_float(0x7fc00000u);
+    const float res = a.res, process = va.process, var_max = va.var_max, gate2 = va.gate2, s0sq = va.s0sq, srsq = va.srsq;
+    const int max_count = va.max_count;
+    // one slot: h and v in and out; ch / cv when the stored height / variance has to be written
+    auto slot = [&](float& h, float& v, unsigned key, unsigned long long acc, int sx, int sy, bool& ch, bool& cv) {
+      if (sh_stale[sx] | sh_stale[G + sy]) { h = nanv; v = nanv; ch = true; cv = true; }
+      if (h == h) {                                                    // predict
+        const float v1 = fminf(v + process, var_max);
+        cv |= __float_as_uint(v1) != __float_as_uint(v);
+        v = v1;
+      }
+      if (!key) return;
+      int n = (int)(acc >> kCountShift);
+      const unsigned long long S = acc & ((1ull << kCountShift) - 1);
+      const float zmax = value_of(key);
+      float m = zmax;
+      if (n < 1) n = 1;                                                // a non-finite maximum has no band: it stands alone
+      else if (S) m = zmax - ((float)S / (float)n) * (1.0f / PGTT_ELEVATION_BAND_SCALE);
+      int wa = sx - lmx, wb = sy - lmy;                                // the slot's world cell: lo + ((s - lo) mod G)
+      wa += wa < 0 ? G : 0; wb += wb < 0 ? G : 0;
+      const float dx = ((float)(lox + wa) + 0.5f) * res - bpx, dy = ((float)(loy + wb) + 0.5f) * res - bpy, dz = m - bpz;
+      const float rho2 = dx * dx + dy * dy + dz * dz;
+      const float r = (s0sq + srsq * rho2) / (float)min(n, max_count);
+      if (h != h) {
+        h = m; v = fminf(r, var_max); ch = true; cv = true;
+      } else {
+        const float d = m - h, den = v + r;
+        if (d * d <= gate2 * den) {
+          const float k = den > 0.f ? v / den : 0.f;
+          h += k * d; v = den > 0.f ? v * r / den : 0.f; ch = true; cv = true;
+        } else if (m > h) {
+          h = m; v = fminf(r, var_max); ch = true; cv = true;
+        }
+      }
+    };
+    if (a.vec_map) {
+      for (int s = 4 * tid; s < GG; s += 4 * kLanes) {
+        const float4 hv = *reinterpret_cast<const float4*>(mp + s);
+        const float4 vv = *reinterpret_cast<const float4*>(vp + s);
+        const uint4 kv = *reinterpret_cast<const uint4*>(sh_m + s);
+        const ulonglong2 a01 = *reinterpret_cast<const ulonglong2*>(sh_acc + s), a23 = *reinterpret_cast<const ulonglong2*>(sh_acc + s + 2);
+        int sx = s / G, sy = s - sx * G;
+        float h[4] = {hv.x, hv.y, hv.z, hv.w}, v[4] = {vv.x, vv.y, vv.z, vv.w};
+        const unsigned k4[4] = {kv.x, kv.y, kv.z, kv.w};
+        const unsigned long long a4[4] = {a01.x, a01.y, a23.x, a23.y};
+        bool ch = false, cv = false;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+          slot(h[k], v[k], k4[k], a4[k], sx, sy, ch, cv);
+          sy++;
+          if (sy == G) { sy = 0; sx++; }
+        }
+        const float4 out = make_float4(h[0], h[1], h[2], h[3]);
+        if (ch) *reinterpret_cast<float4*>(mp + s) = out;
+        if (cv) *reinterpret_cast<float4*>(vp + s) = make_float4(v[0], v[1], v[2], v[3]);
+        *reinterpret_cast<float4*>(sh_m + s) = out;
+#pragma unroll
+        for (int k = 0; k < 4; k++) sh_v[2 * (s + k)] = v[k];
+      }
+    } else {
+      for (int s = tid; s < GG; s += kLanes) {
+        const int sx = s / G;
+        bool ch = false, cv = false;
+        float h = mp[s], v = vp[s];
+        slot(h, v, sh_m[s], sh_acc[s], sx, s - sx * G, ch, cv);
+        if (ch) mp[s] = h;
+        if (cv) vp[s] = v;
+        sh_m[s] = __float_as_uint(h);
+        sh_v[2 * s] = v;
+      }
+    }
+  }
+  __syncthreads();
+
+  // ---- phase E: the scan, with the variance of each point's cell
+  float z = 0.f, zv = va.var_max;
+  bool kn = false;
+  if (tid < PGTT_NSCAN) {
+    const int slot = scan_slot(tid, sh_p, sh_i, a.sdx, a.sdy, a.res, G);
+    if (slot >= 0) {
+      z = __uint_as_float(sh_m[slot]);
+      kn = z == z;
+      if (kn) zv = reinterpret_cast<const float*>(sh_acc)[2 * slot];
+    }
+  }
+  float zmin = kn ? z : INFINITY;
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) zmin = fminf(zmin, __shfl_xor(zmin, off, 64));
+  if (tid < 128 && (tid & 63) == 0) sh_red[tid >> 6] = zmin;
+  __syncthreads();
+  zmin = fminf(sh_red[0], sh_red[1]);
+  if (tid < PGTT_NSCAN) {
+    const float es = (kn && zmin < INFINITY) ? z - zmin : 0.f;
+    sh_est[tid] = es;
+    a.est[(long)e * PGTT_NSCAN + tid] = es;
+    a.known[(long)e * PGTT_NSCAN + tid] = kn ? 1 : 0;
+    va.est_var[(long)e * PGTT_NSCAN + tid] = zv;
   }
 
   // ---- phase F: obs_out = obs with the scan rows replaced
@@ -614,6 +893,8 @@ struct pgtt_elevation_map {
   int passes = 0;                        // 0 = no fill bound
   const int64_t* counter = nullptr;      // pgtt_elevation_bind_rate; kept by the other binds
   int every = 0;                         // 0 = no rate bound
+  PgttElevationVar var{};                // pgtt_elevation_bind_var; kept by the other binds
+  bool has_var = false;
 };
 
 namespace {
@@ -626,10 +907,8 @@ int check_buffers(const PgttElevationBuffers* bufs, const char* who) {
   return PGTT_OK;
 }
 
-// one tick from the image (points = false) or from the bound points; follow: the gated tick and the hold behind the sensor's counter, `force` as
-// the sensor's call was given
-int launch(pgtt_elevation_map* h, bool points, const uint8_t* clear_mask, int clear_all, int use_done, void* stream, bool follow = false, int force = 0) {
-  HIP_TRY(hipSetDevice(h->device));
+// the kernel arguments of one tick on the handle's config and buffers
+ElevArgs tick_args(const pgtt_elevation_map* h, const uint8_t* clear_mask, int clear_all, int use_done) {
   const PgttElevationConfig& c = h->cfg;
   const PgttElevationBuffers& b = h->buf;
   ElevArgs a{};
@@ -647,6 +926,16 @@ int launch(pgtt_elevation_map* h, bool points, const uint8_t* clear_mask, int cl
   for (int i = 0; i < 3; i++) { a.mpos[i] = c.mount_pos[i]; a.self_half[i] = c.self_half[i]; }
   for (int i = 0; i < 4; i++) a.mquat[i] = c.mount_quat[i];
   a.points = h->points; a.P = h->P;
+  return a;
+}
+
+// one tick from the image (points = false) or from the bound points; follow: the gated tick and the hold behind the sensor's counter, `force` as
+// the sensor's call was given
+int launch(pgtt_elevation_map* h, bool points, const uint8_t* clear_mask, int clear_all, int use_done, void* stream, bool follow = false, int force = 0) {
+  HIP_TRY(hipSetDevice(h->device));
+  const PgttElevationConfig& c = h->cfg;
+  const PgttElevationBuffers& b = h->buf;
+  ElevArgs a = tick_args(h, clear_mask, clear_all, use_done);
   const size_t lds = (size_t)c.grid * c.grid * sizeof(unsigned);
   if (follow) {
     a.counter = h->counter; a.every = h->every; a.force = force ? 1 : 0;
@@ -669,11 +958,76 @@ int launch(pgtt_elevation_map* h, bool points, const uint8_t* clear_mask, int cl
   return PGTT_OK;
 }
 
+// the variance settings' ranges; `who` prefixes the message
+int resolve_var(const PgttElevationVar* v, const char* who) {
+  const std::string p = std::string(who) + ": ";
+  if (!v) return fail(PGTT_E_ARG, p + "null settings");
+  const float f[6] = {v->sigma0, v->sigma_rel, v->process, v->gate, v->band, v->var_max};
+  for (int i = 0; i < 6; i++)
+    if (!std::isfinite(f[i])) return fail(PGTT_E_ARG, p + "sigma0, sigma_rel, process, gate, band and var_max must be finite");
+  if (!(v->sigma0 >= 0.f) || !(v->sigma_rel >= 0.f) || !(v->sigma0 + v->sigma_rel > 0.f))
+    return fail(PGTT_E_ARG, p + "need sigma0 >= 0, sigma_rel >= 0 and sigma0 + sigma_rel > 0");
+  if (!(v->process >= 0.f)) return fail(PGTT_E_ARG, p + "process must be >= 0");
+  if (!(v->gate > 0.f)) return fail(PGTT_E_ARG, p + "gate must be > 0");
+  if (!(v->band >= 0.f && v->band <= PGTT_ELEVATION_MAX_BAND)) return fail(PGTT_E_ARG, p + "band must be in [0, PGTT_ELEVATION_MAX_BAND = 0.5]");
+  if (v->max_count < 1) return fail(PGTT_E_ARG, p + "max_count must be >= 1");
+  if (!(v->var_max > 0.f)) return fail(PGTT_E_ARG, p + "var_max must be > 0");
+  return PGTT_OK;
+}
+
+// one variance tick from the image (points = false) or from the bound points: one launch
+int launch_var(pgtt_elevation_map* h, bool points, const uint8_t* clear_mask, int clear_all, int use_done, void* stream) {
+  HIP_TRY(hipSetDevice(h->device));
+  const PgttElevationConfig& c = h->cfg;
+  const PgttElevationVar& v = h->var;
+  VarArgs va{};
+  va.a = tick_args(h, clear_mask, clear_all, use_done);
+  // map and var stream together: 16-byte runs need both to start on a 16-byte boundary
+  if (((uintptr_t)v.var & 15) != 0) va.a.vec_map = 0;
+  va.var = v.var; va.est_var = v.est_var;
+  va.s0sq = (float)((double)v.sigma0 * v.sigma0); va.srsq = (float)((double)v.sigma_rel * v.sigma_rel); va.gate2 = (float)((double)v.gate * v.gate);
+  va.process = v.process; va.band = v.band; va.var_max = v.var_max; va.max_count = v.max_count;
+  const size_t lds = (size_t)c.grid * c.grid * (sizeof(unsigned long long) + sizeof(unsigned));
+  if (points) hipLaunchKernelGGL(elevation_var_kernel<true>, dim3(h->num_envs), dim3(kLanes), lds, (hipStream_t)stream, va);
+  else hipLaunchKernelGGL(elevation_var_kernel<false>, dim3(h->num_envs), dim3(kLanes), lds, (hipStream_t)stream, va);
+  HIP_TRY(hipGetLastError());
+  return PGTT_OK;
+}
+
 }  // namespace
 
 extern "C" {
 
 PGTT_SIDE_EXPORTS(elevation, ELEVATION)
+int pgtt_elevation_sizeof_var(void) { return (int)sizeof(PgttElevationVar); }
+
+int pgtt_elevation_check_var(const PgttElevationVar* v) { return resolve_var(v, "pgtt_elevation_check_var"); }
+
+int pgtt_elevation_bind_var(pgtt_elevation_handle h, const PgttElevationVar* v) {
+  if (!h || !v) return fail(PGTT_E_ARG, "pgtt_elevation_bind_var: null argument");
+  if (!v->var || !v->est_var) return fail(PGTT_E_ARG, "pgtt_elevation_bind_var: var and est_var are required");
+  if (int rc = resolve_var(v, "pgtt_elevation_bind_var")) return rc;
+  if (h->cfg.grid > PGTT_ELEVATION_VAR_MAX_GRID)
+    return fail(PGTT_E_ARG, "pgtt_elevation_bind_var: the variance tick supports grid <= PGTT_ELEVATION_VAR_MAX_GRID = 64 (12 bytes of LDS per slot)");
+  h->var = *v;
+  h->has_var = true;
+  return PGTT_OK;
+}
+
+int pgtt_elevation_var(pgtt_elevation_handle h, const uint8_t* clear_mask, int clear_all, int use_done, void* stream) {
+  if (!h) return fail(PGTT_E_ARG, "pgtt_elevation_var: null handle");
+  if (!h->bound) return fail(PGTT_E_STATE, "pgtt_elevation_var: no buffers bound (pgtt_elevation_bind first)");
+  if (!h->buf.depth) return fail(PGTT_E_STATE, "pgtt_elevation_var: the handle was bound without a depth image (pgtt_elevation_bind_points with depth == NULL)");
+  if (!h->has_var) return fail(PGTT_E_STATE, "pgtt_elevation_var: no variance bound (pgtt_elevation_bind_var first)");
+  return launch_var(h, false, clear_mask, clear_all, use_done, stream);
+}
+
+int pgtt_elevation_var_points(pgtt_elevation_handle h, const uint8_t* clear_mask, int clear_all, int use_done, void* stream) {
+  if (!h) return fail(PGTT_E_ARG, "pgtt_elevation_var_points: null handle");
+  if (!h->points) return fail(PGTT_E_STATE, "pgtt_elevation_var_points: no points bound (pgtt_elevation_bind_points first)");
+  if (!h->has_var) return fail(PGTT_E_STATE, "pgtt_elevation_var_points: no variance bound (pgtt_elevation_bind_var first)");
+  return launch_var(h, true, clear_mask, clear_all, use_done, stream);
+}
 int pgtt_elevation_sizeof_config(void) { return (int)sizeof(PgttElevationConfig); }
 int pgtt_elevation_sizeof_buffers(void) { return (int)sizeof(PgttElevationBuffers); }
 int pgtt_elevation_sizeof_fill(void) { return (int)sizeof(PgttElevationFill); }

@@ -74,7 +74,11 @@ class Joystick:
         or lidar=dict(every=3) with source="lidar"; the camera still sits on the torso).  The map then fuses on the steps on which that sensor takes
         new data - reset() forces one - and on the steps in between it is left as it is, but for the clears, while elevation_obs, elevation_known and
         the filled outputs are sampled from it at the current pose on every step (pgtt_elevation_follow).  With every=1 the bits are those of an env
-        without the flag."""
+        without the flag.
+        elevation=dict(variance=True | dict(sigma0=..., sigma_rel=..., process=..., gate=..., band=..., max_count=..., var_max=...), ...) replaces the
+        maximum-and-alpha fusion by a variance-weighted (Kalman) update per cell (pgtt_elevation_var; elevation.VARIANCE_DEFAULTS): the map keeps a
+        variance layer `env.elevation_map.var`, and `env.elevation_var` [N, 117] is the variance at the scan points.  Not with follow_sensor; grid <= 64.
+        obs, state, reward, done, the image and the LiDAR's outputs are what they are without it."""
         if student is not None and depth is None:
             raise ValueError("Joystick(student=...) needs depth=dict(...): the student reads the onboard depth image")
         wants_map = elevation is not None and elevation is not False
@@ -92,6 +96,12 @@ class Joystick:
         if wants_map and map_source == "depth" and ((int(dict(depth).get("every", 1)) != 1 and not follows) or int(dict(depth).get("mount_body", 0)) != 0):
             raise ValueError("Joystick(elevation=...) needs a camera on the torso (mount_body=0) with every=1: a stale image under a moved pose "
                              "would be unprojected wrongly")
+        variance = dict(elevation).get("variance") if wants_map and elevation is not True else None
+        if variance is not None and variance is not False:
+            if follows:
+                raise ValueError("Joystick(elevation=dict(variance=..., follow_sensor=True)): variance behind a slower sensor is not built yet")
+            if variance is not True and not isinstance(variance, dict):
+                raise ValueError(f"Joystick(elevation=dict(variance=...)): variance must be True or a dict of settings, not {variance!r}")
         self.level_start = None
         if isinstance(terrain, (list, tuple)):
             terrain, self.level_start = _curriculum.stack_levels(terrain)
@@ -323,6 +333,11 @@ class Joystick:
         """[N, 117] uint8: 0 where the scan point's cell was measured, p where pass p filled it, 255 where it is unknown; None without a map that fills"""
         return getattr(self.elevation_map, "filled_dist", None)
 
+    @property
+    def elevation_var(self) -> Optional[torch.Tensor]:
+        """[N, 117] float32: the variance (m^2) of the elevation map at the scan points, var_max at an unknown one; None without a variance map"""
+        return getattr(self.elevation_map, "est_var", None)
+
     def push_step(self) -> None:
         """the push scheduler alone (pgtt_push): what step() runs first when pushes are on; for callers of physics() / observe()"""
         native.check(self._lib.pgtt_push(self._h, self._stream()))
@@ -363,6 +378,8 @@ class Joystick:
             self.lidar_scanner.set_terrain(t)
         if getattr(self, "elevation_map", None) is not None:
             self.elevation_map.map.fill_(float("nan"))                # heights of the old terrain: the next tick starts from an empty map
+            if getattr(self.elevation_map, "var", None) is not None:
+                self.elevation_map.var.fill_(float("nan"))            # the variance layer is NaN where the map is
 
     def _stream(self) -> int:
         return torch.cuda.current_stream(self.device).cuda_stream
