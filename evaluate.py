@@ -122,27 +122,10 @@ class VideoRecorder:
         return out
 
 
-def run_evaluation(args, num_eval_envs=NUM_EVAL_ENVS, seed=0, verbose=True):
-    """-> dict(survivors, num_eval_envs, episode_reward, avg_episode_length, tracking_lin_vel, tracking_ang_vel)"""
-    if args.method not in ("pgtt", "baseline"):
-        raise SystemExit("--method must be pgtt (go2/joystick_pgtt.py) or baseline (go2/joystick.py)")
-    cfg = configs.evaluation_config(args.method)          # training/evaluate.py:127-129: commands within +-[0.4, 0.4, 0.7]
-    model = mjcf.load_model(args.task_name)
-    terrain = load_terrain(args.terrain_file) if args.task_name == "stairs" else None
-    n = num_eval_envs
-    level_start = None
-    if args.task_name == "stairs" and getattr(args, "terrain_files", None):
-        # the stacked table of a curriculum run, evaluated on ONE fixed level of it (--level), the curriculum off
-        from phase_guided_terrain_traversal_amd.curriculum import stack_levels
-        terrain, level_start = stack_levels([load_terrain(f) for f in args.terrain_files.split(",")])
-    dr = domain_randomize(model, n, seed=seed, terrain=terrain, level_start=level_start,      # the evaluator's env gets the same randomization_fn
-                          init_level=int(getattr(args, "level", 0)))
-    kw = {"params": torch.from_numpy(dr["params"])}
-    if terrain is not None:
-        kw.update(variant=torch.from_numpy(dr["variant"]), box_friction=torch.from_numpy(dr["box_friction"]))
-    push = configs.push_from_args(args)                           # --push_*: random kicks of the torso (off unless one is given)
-    if push is not None:
-        kw["push"] = push
+def sensor_kwargs(args):
+    """the Joystick keywords of the sensor flags (--student, --elevation and what goes with it, --sensor_noise, --sensor_every): what the policy
+    is to act on and the sensors that deliver it; {} when none is given.  train_distill.py builds its env from the same flags"""
+    kw = {}
     # --sensor_noise SIGMA[,DROPOUT]: the sensor that feeds the student or the map reads noisy ranges (the sensors' noise=dict(sigma, dropout):
     # relative range noise and the probability of a `far` reading); without it they are exact
     noisy = sensor_noise(getattr(args, "sensor_noise", None))
@@ -201,6 +184,31 @@ def run_evaluation(args, num_eval_envs=NUM_EVAL_ENVS, seed=0, verbose=True):
         raise SystemExit("--elevation_fill fills the holes of --elevation's map: give --elevation too")
     elif int(getattr(args, "sensor_every", 1)) != 1:
         raise SystemExit("--sensor_every is the period of the sensor that feeds --elevation's map: give --elevation too")
+    return kw
+
+
+def run_evaluation(args, num_eval_envs=NUM_EVAL_ENVS, seed=0, verbose=True):
+    """-> dict(survivors, num_eval_envs, episode_reward, avg_episode_length, tracking_lin_vel, tracking_ang_vel)"""
+    if args.method not in ("pgtt", "baseline"):
+        raise SystemExit("--method must be pgtt (go2/joystick_pgtt.py) or baseline (go2/joystick.py)")
+    cfg = configs.evaluation_config(args.method)          # training/evaluate.py:127-129: commands within +-[0.4, 0.4, 0.7]
+    model = mjcf.load_model(args.task_name)
+    terrain = load_terrain(args.terrain_file) if args.task_name == "stairs" else None
+    n = num_eval_envs
+    level_start = None
+    if args.task_name == "stairs" and getattr(args, "terrain_files", None):
+        # the stacked table of a curriculum run, evaluated on ONE fixed level of it (--level), the curriculum off
+        from phase_guided_terrain_traversal_amd.curriculum import stack_levels
+        terrain, level_start = stack_levels([load_terrain(f) for f in args.terrain_files.split(",")])
+    dr = domain_randomize(model, n, seed=seed, terrain=terrain, level_start=level_start,      # the evaluator's env gets the same randomization_fn
+                          init_level=int(getattr(args, "level", 0)))
+    kw = {"params": torch.from_numpy(dr["params"])}
+    if terrain is not None:
+        kw.update(variant=torch.from_numpy(dr["variant"]), box_friction=torch.from_numpy(dr["box_friction"]))
+    push = configs.push_from_args(args)                           # --push_*: random kicks of the torso (off unless one is given)
+    if push is not None:
+        kw["push"] = push
+    kw.update(sensor_kwargs(args))
     env = Joystick(args.task_name, cfg, num_envs=n, terrain=terrain, device=DEVICE, autoreset=True, **kw)
     if env.elevation_filled_obs is not None:
         acts_on = env.elevation_filled_obs
@@ -298,6 +306,23 @@ def fill_passes(text):
     return k
 
 
+def add_sensor_args(ap):
+    """the flags sensor_kwargs reads"""
+    ap.add_argument("--student", type=str, default=None, help="a student.npz of train_student.py: the policy acts on the depth camera's estimate of the scan rows")
+    ap.add_argument("--elevation", type=str, nargs="?", const="", default=None, metavar="GRID,RES,ALPHA",
+                    help="the policy acts on the scan rows sampled from the depth-fused elevation map (elevation.py); optional grid[,res[,alpha]]")
+    ap.add_argument("--elevation_source", type=str, default="depth", choices=("depth", "lidar"),
+                    help="with --elevation: fuse the map from the depth camera's image (default) or from the onboard LiDAR's points (lidar.py)")
+    ap.add_argument("--elevation_fill", type=fill_passes, nargs="?", const=True, default=None, metavar="K",
+                    help="with --elevation: close the map's holes with K passes (16 unless given) behind every tick; the policy acts on the filled scan")
+    ap.add_argument("--elevation_variance", type=str, nargs="?", const="", default=None, metavar="SIGMA0,SIGMA_REL,PROCESS,GATE,BAND",
+                    help="with --elevation: fuse the map by the variance-weighted (Kalman) update instead of the maximum and alpha; optional settings")
+    ap.add_argument("--sensor_noise", type=str, default=None, metavar="SIGMA[,DROPOUT]",
+                    help="with --elevation or --student: relative range noise and dropout probability of the sensor that feeds it")
+    ap.add_argument("--sensor_every", type=int, default=1, metavar="M",
+                    help="with --elevation: the sensor that feeds the map runs at one control step in M; for M > 1 the map follows it, holding in between")
+
+
 def make_parser():
     ap = argparse.ArgumentParser(description="Evaluate a trained policy on one terrain file (MI355X-native PGTT env)")
     ap.add_argument("--method", type=str, default="pgtt")
@@ -319,19 +344,7 @@ def make_parser():
     ap.add_argument("--video_every", type=int, default=2, help="one frame every n control steps")
     ap.add_argument("--video_scan", action="store_true", help="overlay the 117 height-scan hits as marker spheres")
     ap.add_argument("--video_depth", action="store_true", help="tile each video env's onboard depth image (grey, near = white) under its RGB tile")
-    ap.add_argument("--student", type=str, default=None, help="a student.npz of train_student.py: the policy acts on the depth camera's estimate of the scan rows")
-    ap.add_argument("--elevation", type=str, nargs="?", const="", default=None, metavar="GRID,RES,ALPHA",
-                    help="the policy acts on the scan rows sampled from the depth-fused elevation map (elevation.py); optional grid[,res[,alpha]]")
-    ap.add_argument("--elevation_source", type=str, default="depth", choices=("depth", "lidar"),
-                    help="with --elevation: fuse the map from the depth camera's image (default) or from the onboard LiDAR's points (lidar.py)")
-    ap.add_argument("--elevation_fill", type=fill_passes, nargs="?", const=True, default=None, metavar="K",
-                    help="with --elevation: close the map's holes with K passes (16 unless given) behind every tick; the policy acts on the filled scan")
-    ap.add_argument("--elevation_variance", type=str, nargs="?", const="", default=None, metavar="SIGMA0,SIGMA_REL,PROCESS,GATE,BAND",
-                    help="with --elevation: fuse the map by the variance-weighted (Kalman) update instead of the maximum and alpha; optional settings")
-    ap.add_argument("--sensor_noise", type=str, default=None, metavar="SIGMA[,DROPOUT]",
-                    help="with --elevation or --student: relative range noise and dropout probability of the sensor that feeds it")
-    ap.add_argument("--sensor_every", type=int, default=1, metavar="M",
-                    help="with --elevation: the sensor that feeds the map runs at one control step in M; for M > 1 the map follows it, holding in between")
+    add_sensor_args(ap)
     configs.add_push_args(ap)
     ap.add_argument("--terrain_files", type=str, default=None, help="comma-separated level files stacked into one table (as train.py --terrain_files); evaluated on --level")
     ap.add_argument("--level", type=int, default=0, help="with --terrain_files: the level every evaluation env stands on (no curriculum at evaluation)")

@@ -2,7 +2,8 @@
  * pgtt_learn.h - libpgtt_learn.so: the pieces of one PPO minibatch update that pgtt_train.h does not have, so that the whole update of
  * phase_guided_terrain_traversal_amd/learn.py::NativeLearner is hand-written HIP (gfx950) on ONE stream: the minibatch gather with the
  * observation and advantage normalisation, the Linear layers forward (bias, SiLU) and their data gradient on fp32 MFMA, the value loss,
- * the global-norm clip with Adam over one flat parameter buffer, and generalised advantage estimation.  The policy loss and the weight /
+ * the global-norm clip with Adam over one flat parameter buffer, and generalised advantage estimation; and, for the policy distillation of
+ * distill.py, which composes the same pieces, the imitation loss between two policy heads and a gather of (observation, label) rows.  The policy loss and the weight /
  * bias gradients stay pgtt_ppo_policy_loss / pgtt_ppo_linear_backward of libpgtt.so (pgtt_train.h).  Like pgtt_train.h these replace no
  * entry point of the reference (its PPO is Brax's, configured at training/train.py:135-161); the arithmetic they restate is that of
  * phase_guided_terrain_traversal_amd/ppo.py, held to the fp64 statement in tests/ppo_reference.py.
@@ -91,6 +92,28 @@ int pgtt_learn_adam_partials(int64_t P);
  * One lane per env, one backward loop over T, one launch. */
 int pgtt_learn_gae(const float* trunc_TxN, const float* done_TxN, const float* rew_TxN, const float* val_TxN, const float* boot_N,
                    int T, int N, float lambda, float gamma, float* adv_TxN, float* vs_TxN, void* stream);
+
+/* Policy distillation (phase_guided_terrain_traversal_amd/distill.py): the imitation loss between two heads and its gradient, held to the fp64
+ * statement in tests/distill_reference.py.  Both heads are in the trainer's layout (loc | raw), [B][2A], sigma = softplus(raw) + 1e-3 with
+ * softplus(r) = max(r, 0) + log1p(exp(-|r|)) (finite for every finite r).  Per row i and dimension a, with d = loc_t - loc_s and
+ * q = (sigma_t^2 + d^2) / sigma_s^2:
+ *   KL = log(sigma_s / sigma_t) + 0.5 (q - 1)            KL(teacher || student) of the two diagonal Gaussians of the pre-tanh variable,
+ *   dL/dloc_s = -d / sigma_s^2 / B,   dL/draw_s = (1 - q) / sigma_s * sigmoid(raw_s) / B,
+ *   loss_2[0] = (1 / B) sum_i sum_a KL,   loss_2[1] = (1 / (B A)) sum_i sum_a (tanh loc_s - tanh loc_t)^2   (the error of the deterministic action:
+ *   logged, no gradient),   grad = d loss_2[0] / d student head, [B][2A] in the layout of the head.
+ * Every division is correctly rounded and 1 - q is formed before the division by sigma_s: a student head that has the teacher's bits gives
+ * loss_2 = (0, 0) and an all-zero gradient exactly.  Two launches: one lane per row in workgroups of 64, the two sums of a workgroup added in lane
+ * order into partial[2 block], partial[2 block + 1]; then one wave adds the partials in block order.  partial holds 2 ceil(B / 64) floats (the layout of
+ * pgtt_ppo_policy_loss).  Any A >= 1. */
+int pgtt_learn_distill_loss(const float* student_Bx2A, const float* teacher_Bx2A, int B, int A, float* partial_2xceilB64, float* loss_2,
+                            float* grad_Bx2A, void* stream);
+
+/* One minibatch of (observation, label) pairs out of [rows]: for i < B, r = idx[i] (clamped into [0, rows): an index outside reads no foreign memory),
+ *   x[i][:] = (obs[r][:] - mean) / std   (one subtraction, one correctly rounded division: the bits of x_s above),
+ *   y[i][:] = target[r][:]               (a copy, equal bits; tgt_dim wide).
+ * One launch, one workgroup per row. */
+int pgtt_learn_gather_rows(const int64_t* idx_B, const float* obs, const float* target, const float* mean, const float* std,
+                           int B, int rows, int obs_dim, int tgt_dim, float* x, float* y, void* stream);
 
 int pgtt_learn_sizeof_gather_args(void);
 int pgtt_learn_sizeof_adam_args(void);

@@ -10,6 +10,9 @@
 //   value_loss_kernel                        one workgroup
 //   adam_norm_kernel / adam_apply_kernel     partial sums of g^2 (and t + 1), then clip coefficient + Adam in every workgroup alike
 //   gae_kernel                               one lane per env, one backward loop over T
+//   distill_loss_kernel / distill_loss_finish   policy distillation (distill.py): one lane per row, KL(teacher || student) of the two heads with its gradient
+//                                            and the error of the deterministic action, summed per workgroup in lane order, then in block order
+//   gather_rows_kernel                       one workgroup per minibatch row: the normalised observation and its label row
 // No atomics, no scratch, no LDS beyond the reductions' 16 words; nothing allocates or synchronises.
 #include <hip/hip_runtime.h>
 
@@ -339,6 +342,70 @@ __global__ __launch_bounds__(256) void gae_kernel(const float* __restrict__ trun
   }
 }
 
+// ------------------------------------------------------------------ distillation: KL(teacher || student) of two heads, its gradient; the row gather
+// finite for every finite r: exp never sees a positive argument
+__device__ __forceinline__ float softplus_stable(float r) { return fmaxf(r, 0.f) + log1pf(expf(-fabsf(r))); }
+__device__ __forceinline__ float sigmoid_stable(float r) {
+  const float e = expf(-fabsf(r));
+  return r >= 0.f ? 1.0f / (1.0f + e) : e / (1.0f + e);
+}
+
+// the sum of v over the wave in lane order 0, 1, .. 63, the same bits in every lane
+__device__ __forceinline__ float lane_order_sum(float v) {
+  float s = 0.f;
+  for (int l = 0; l < 64; l++) s += __shfl(v, l);
+  return s;
+}
+
+__global__ __launch_bounds__(64) void distill_loss_kernel(const float* __restrict__ student, const float* __restrict__ teacher, int B, int A,
+                                                          float* __restrict__ partial, float* __restrict__ grad) {
+  const long i = (long)blockIdx.x * 64 + threadIdx.x;
+  const bool on = i < B;
+  const float fB = (float)B;
+  float kl = 0.f, act = 0.f;
+  if (on) {
+    const float* s = student + i * 2 * A;
+    const float* t = teacher + i * 2 * A;
+    float* g = grad + i * 2 * A;
+    for (int a = 0; a < A; a++) {
+      const float ls = s[a], rs = s[A + a], lt = t[a], rt = t[A + a];
+      const float ss = softplus_stable(rs) + 1e-3f, st = softplus_stable(rt) + 1e-3f;
+      const float e = ls - lt;                               // -d
+      const float ss2 = ss * ss;
+      const float q = (st * st + e * e) / ss2;               // exactly 1 where the student has the teacher's bits
+      kl += logf(ss / st) + 0.5f * (q - 1.0f);
+      const float dt = tanhf(ls) - tanhf(lt);
+      act += dt * dt;
+      g[a] = e / ss2 / fB;
+      g[A + a] = (1.0f - q) / ss * sigmoid_stable(rs) / fB;
+    }
+  }
+  const float v0 = lane_order_sum(kl), v1 = lane_order_sum(act);
+  if (threadIdx.x == 0) { partial[2 * blockIdx.x] = v0; partial[2 * blockIdx.x + 1] = v1; }
+}
+
+// one wave: 64 partials at a time, each run added in block order onto the running sums
+__global__ __launch_bounds__(64) void distill_loss_finish(const float* __restrict__ partial, int nblocks, int B, int A, float* __restrict__ loss) {
+  float v0 = 0.f, v1 = 0.f;
+  for (int b0 = 0; b0 < nblocks; b0 += 64) {
+    const int b = b0 + threadIdx.x;
+    const float p0 = b < nblocks ? partial[2 * b] : 0.f, p1 = b < nblocks ? partial[2 * b + 1] : 0.f;
+    const int n = nblocks - b0 < 64 ? nblocks - b0 : 64;
+    for (int l = 0; l < n; l++) { v0 += __shfl(p0, l); v1 += __shfl(p1, l); }
+  }
+  if (threadIdx.x == 0) { loss[0] = v0 / (float)B; loss[1] = v1 / ((float)B * (float)A); }
+}
+
+__global__ __launch_bounds__(256) void gather_rows_kernel(const int64_t* __restrict__ idx, const float* __restrict__ obs, const float* __restrict__ target,
+                                                          const float* __restrict__ mean, const float* __restrict__ std, int rows, int obs_dim, int tgt_dim,
+                                                          float* __restrict__ x, float* __restrict__ y) {
+  const int i = blockIdx.x, tid = threadIdx.x;
+  long r = idx[i];
+  r = r < 0 ? 0 : (r >= rows ? (long)rows - 1 : r);
+  for (int k = tid; k < obs_dim; k += 256) x[(long)i * obs_dim + k] = (obs[r * obs_dim + k] - mean[k]) / std[k];
+  for (int k = tid; k < tgt_dim; k += 256) y[(long)i * tgt_dim + k] = target[r * tgt_dim + k];
+}
+
 }  // namespace
 
 extern "C" {
@@ -408,6 +475,24 @@ int pgtt_learn_gae(const float* trunc, const float* done, const float* rew, cons
   if (T <= 0 || N <= 0) return fail(PGTT_E_ARG, "pgtt_learn_gae: T and N must be positive");
   hipLaunchKernelGGL(gae_kernel, dim3((N + 255) / 256), dim3(256), 0, (hipStream_t)stream, trunc, done, rew, val, boot, T, N, lambda, gamma, adv, vs);
   return launched("pgtt_learn_gae");
+}
+
+int pgtt_learn_distill_loss(const float* student, const float* teacher, int B, int A, float* partial, float* loss, float* grad, void* stream) {
+  if (!student || !teacher || !partial || !loss || !grad) return fail(PGTT_E_ARG, "pgtt_learn_distill_loss: null pointer");
+  if (B <= 0 || A <= 0) return fail(PGTT_E_ARG, "pgtt_learn_distill_loss: B and A must be positive");
+  const int nb = (B + 63) / 64;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(distill_loss_kernel, dim3(nb), dim3(64), 0, st, student, teacher, B, A, partial, grad);
+  hipLaunchKernelGGL(distill_loss_finish, dim3(1), dim3(64), 0, st, partial, nb, B, A, loss);
+  return launched("pgtt_learn_distill_loss");
+}
+
+int pgtt_learn_gather_rows(const int64_t* idx, const float* obs, const float* target, const float* mean, const float* std, int B, int rows, int obs_dim,
+                           int tgt_dim, float* x, float* y, void* stream) {
+  if (!idx || !obs || !target || !mean || !std || !x || !y) return fail(PGTT_E_ARG, "pgtt_learn_gather_rows: null pointer");
+  if (B <= 0 || rows <= 0 || obs_dim <= 0 || tgt_dim <= 0) return fail(PGTT_E_ARG, "pgtt_learn_gather_rows: B, rows, obs_dim and tgt_dim must be positive");
+  hipLaunchKernelGGL(gather_rows_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, idx, obs, target, mean, std, rows, obs_dim, tgt_dim, x, y);
+  return launched("pgtt_learn_gather_rows");
 }
 
 }  // extern "C"

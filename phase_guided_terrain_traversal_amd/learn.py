@@ -50,6 +50,8 @@ SIDE = _sidelib.SideLib("learn", LearnError, {
     "pgtt_learn_clip_adam": (None, [C.POINTER(PgttLearnAdamArgs), vp]),
     "pgtt_learn_adam_partials": (None, [C.c_int64]),
     "pgtt_learn_gae": (None, [vp, vp, vp, vp, vp, ci, ci, cf, cf, vp, vp, vp]),
+    "pgtt_learn_distill_loss": (None, [vp, vp, ci, ci, vp, vp, vp, vp]),                       # the two entries of distill.py
+    "pgtt_learn_gather_rows": (None, [vp, vp, vp, vp, vp, ci, ci, ci, ci, vp, vp, vp]),
 }, {"pgtt_learn_sizeof_gather_args": PgttLearnGatherArgs, "pgtt_learn_sizeof_adam_args": PgttLearnAdamArgs})
 LIB_PATH, EXPORTS, lib, check, build_info = SIDE.path, SIDE.exports, SIDE.lib, SIDE.check, SIDE.build_info
 
