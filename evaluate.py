@@ -15,7 +15,8 @@ whose scan rows the student perception module estimated from the onboard depth i
 scan rows are sampled from the depth-fused elevation map (elevation.py; nothing to train; `--elevation_source lidar` fuses it from the onboard
 LiDAR's points instead, lidar.py; `--elevation_fill [K]` closes the map's holes first and the policy acts on the filled scan; `--sensor_every M`
 runs that sensor at one control step in M and lets the map follow it; `--elevation_variance [sigma0,sigma_rel,process,gate,band]` fuses the map by
-the variance-weighted update; `--sensor_noise SIGMA[,DROPOUT]` gives the sensor that feeds the map or the student range noise); the remaining flags of the reference's CLI are accepted and ignored.
+the variance-weighted update; `--sensor_noise SIGMA[,DROPOUT]` gives the sensor that feeds the map or the student range noise); a `--policy` file that holds a recurrent policy
+(train_distill.py --memory, recurrent_policy.py) is stepped with a memory per env, cleared where the previous step ended an episode; the remaining flags of the reference's CLI are accepted and ignored.
 """
 import argparse
 import os
@@ -39,10 +40,19 @@ def load_terrain(spec):
     return np.load(p)
 
 
+def recurrent_file(path):
+    """does the .npz hold a recurrent policy (train_distill.py --memory: gru_w_ih next to the feed-forward keys)?"""
+    with np.load(path) as d:
+        return "gru_w_ih" in d.files
+
+
 def load_policy_from_args(args, tmp_dir):
-    """-> PolicyMLP on DEVICE"""
+    """-> PolicyMLP on DEVICE (a recurrent_policy.RecurrentPolicy for a file that holds one)"""
     if args.policy:
         p = args.policy if os.path.exists(args.policy) else os.path.join(POLICY_DIR, args.policy.replace(".npz", "") + ".npz")
+        if recurrent_file(p):
+            from phase_guided_terrain_traversal_amd.recurrent_policy import RecurrentPolicy
+            return RecurrentPolicy.load(p).to(DEVICE)
         return PolicyMLP(p).to(DEVICE)
     if not args.checkpoint_folder:
         raise SystemExit("give --checkpoint_folder (a train.py checkpoint directory) or --policy")
@@ -231,6 +241,11 @@ def run_evaluation(args, num_eval_envs=NUM_EVAL_ENVS, seed=0, verbose=True):
     known = torch.zeros(n, device=dev)                                            # with a map: the scan points it knew, summed over the first episode
     covered = torch.zeros(n, device=dev)                                          # with a fill: the scan points it knew or filled
     video = VideoRecorder(args, env, L) if getattr(args, "video", None) else None
+    recurrent = hasattr(pi, "gru_w_ih")
+    if recurrent:
+        # a recurrent policy: a [n, R] memory that starts at zero and is cleared for the envs whose previous step ended an episode
+        memory, ended = torch.zeros(n, pi.memory, device=dev), torch.zeros(n, dtype=torch.bool, device=dev)
+        pi.requires_grad_(False)
     for t in range(L):
         if video is not None:
             video.capture(t)
@@ -238,7 +253,12 @@ def run_evaluation(args, num_eval_envs=NUM_EVAL_ENVS, seed=0, verbose=True):
             known += env.elevation_known.float().mean(1) * first.float()
         if env.elevation_dist is not None:
             covered += (env.elevation_dist != 255).float().mean(1) * first.float()
-        _, reward, done, info = env.step(pi(acts_on))
+        if recurrent:
+            action, _, memory = pi.step(acts_on, memory, ended)
+            _, reward, done, info = env.step(action)
+            ended = done > 0
+        else:
+            _, reward, done, info = env.step(pi(acts_on))
         w = first.float()
         ret += reward * w; length += w; terms += info["metrics"] * w
         d = done > 0

@@ -13,7 +13,10 @@
 //   distill_loss_kernel / distill_loss_finish   policy distillation (distill.py): one lane per row, KL(teacher || student) of the two heads with its gradient
 //                                            and the error of the deterministic action, summed per workgroup in lane order, then in block order
 //   gather_rows_kernel                       one workgroup per minibatch row: the normalised observation and its label row
-// No atomics, no scratch, no LDS beyond the reductions' 16 words; nothing allocates or synchronises.
+//   normalise_kernel / recurrent_tail_kernel the recurrent policy's acting step (recurrent_policy.py): the normalising copy in front of three linear_forward
+//                                            launches, then per 16 envs the GRU cell on MFMA (gates lane-local), m1, the head over h3 and m1, tanh, stores
+//   gru_clear_rows / gru_cell_forward / gru_cell_backward / add_rows    the point-wise pieces of BPTT over that cell, one lane per (row, memory value)
+// No atomics, no scratch, no LDS beyond the reductions' 16 words and recurrent_tail_kernel's two [16][R + 4] memory tiles; nothing allocates or synchronises.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -406,6 +409,176 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const int64_t* __restr
   for (int k = tid; k < tgt_dim; k += 256) y[(long)i * tgt_dim + k] = target[r * tgt_dim + k];
 }
 
+// ------------------------------------------------------------------ the recurrent policy: the acting step from h3 on, and the point-wise pieces of BPTT
+// no overflow at any v: exp never sees a positive argument
+__device__ __forceinline__ float tanh_stable(float v) {
+  const float t = expf(-2.0f * fabsf(v));
+  return copysignf((1.0f - t) / (1.0f + t), v);
+}
+
+__global__ __launch_bounds__(256) void normalise_kernel(const float* __restrict__ obs, const float* __restrict__ mean, const float* __restrict__ std, int od,
+                                                        float* __restrict__ x, float* __restrict__ store_obs) {
+  const long e = blockIdx.x;
+  for (int k = threadIdx.x; k < od; k += 256) {
+    const float o = obs[e * od + k];
+    x[e * od + k] = (o - mean[k]) / std[k];
+    if (store_obs) store_obs[e * od + k] = o;
+  }
+}
+
+// one step of a chain over 16 k: s outer (the four MFMAs), g inner (the four k of one MFMA)
+__device__ __forceinline__ f32x4 mfma16(const F4& a, const F4& b, f32x4 acc) {
+  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, b.x, acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, b.y, acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, b.z, acc, 0, 0, 0);
+  return __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, b.w, acc, 0, 0, 0);
+}
+
+struct RecurrentK {
+  const float *h3, *w_ih, *w_hh, *b_ih, *b_hh, *w3, *b3, *w_m, *done;
+  const uint8_t* clear_mask;
+  float *mem, *action, *head, *store_mem0;         // the two store pointers are those of row t
+  uint8_t* store_clear;
+  int N, H, R, clear_all, use_done;
+};
+
+constexpr int kHead = 24, kAct = 12;
+
+// One workgroup of four waves per 16 envs.  LDS: m0 and m1 of the 16 envs, [16][R + 4] floats each (the rows 16 bytes apart from a multiple of the
+// 32 banks).  A wave owns the memory values 16 ct .. 16 ct + 15 for ct = wave, wave + 4, ..: four accumulators (r, u, gi_n, gh_n) in the C layout of the
+// 16x16x4 form - register q of lane l is env 4 (l >> 4) + q, memory value 16 ct + (l & 15) - so the gates and m1 are lane-local.  Then the head:
+// waves 0 and 1 take its columns 0..15 and 16..23.  Rows past N repeat env N - 1's h3, count as cleared and are not stored.
+__global__ __launch_bounds__(256) void recurrent_tail_kernel(RecurrentK a) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  __shared__ int scl[16];
+  const int R = a.R, H = a.H, LS = R + 4;
+  float* sm0 = lds;
+  float* sm1 = lds + 16 * LS;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = lane & 15, g = lane >> 4;
+  const long e0 = (long)blockIdx.x * 16;
+  if (tid < 16) {
+    const long e = e0 + tid;
+    int c = 1;
+    if (e < a.N) {
+      c = a.clear_all != 0 || (a.clear_mask && a.clear_mask[e] != 0) || (a.use_done && a.done && a.done[e] != 0.f);
+      if (a.store_clear) a.store_clear[e] = (uint8_t)c;
+    }
+    scl[tid] = c;
+  }
+  __syncthreads();
+  for (int k = tid; k < 16 * R; k += 256) {
+    const int i = k / R, j = k - i * R;
+    const long e = e0 + i;
+    const float v = scl[i] ? 0.f : a.mem[e * R + j];          // a cleared env's row is not read
+    sm0[i * LS + j] = v;
+    if (a.store_mem0 && e < a.N) a.store_mem0[e * R + j] = v;
+  }
+  __syncthreads();
+  const long er = e0 + li < a.N ? e0 + li : (long)a.N - 1;
+  const float* xa = a.h3 + er * H + 4 * g;
+  const float* ma = sm0 + li * LS + 4 * g;
+  for (int ct = wave; ct < R / 16; ct += 4) {
+    const int j = ct * 16 + li;
+    f32x4 ar = {0.f, 0.f, 0.f, 0.f}, au = ar, an = ar, ahn = ar;
+    const float* wr = a.w_ih + (long)j * H + 4 * g;
+    const float* wu = wr + (long)R * H;
+    const float* wn = wu + (long)R * H;
+    for (int kb = 0; kb < H; kb += 16) {
+      const F4 x = ld4(xa + kb);
+      ar = mfma16(x, ld4(wr + kb), ar);
+      au = mfma16(x, ld4(wu + kb), au);
+      an = mfma16(x, ld4(wn + kb), an);
+    }
+    const float* vr = a.w_hh + (long)j * R + 4 * g;
+    const float* vu = vr + (long)R * R;
+    const float* vn = vu + (long)R * R;
+    for (int kb = 0; kb < R; kb += 16) {
+      const F4 x = ld4(ma + kb);
+      ar = mfma16(x, ld4(vr + kb), ar);
+      au = mfma16(x, ld4(vu + kb), au);
+      ahn = mfma16(x, ld4(vn + kb), ahn);
+    }
+    const float bir = a.b_ih[j], biu = a.b_ih[R + j], bin = a.b_ih[2 * R + j];
+    const float bhr = a.b_hh[j], bhu = a.b_hh[R + j], bhn = a.b_hh[2 * R + j];
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+      const int i = 4 * g + q;
+      const float r = sigmoid_stable((ar[q] + bir) + bhr), u = sigmoid_stable((au[q] + biu) + bhu);
+      const float n = tanh_stable((an[q] + bin) + r * (ahn[q] + bhn));
+      const float m1 = (1.0f - u) * n + u * sm0[i * LS + j];
+      sm1[i * LS + j] = m1;
+      if (e0 + i < a.N) a.mem[(e0 + i) * R + j] = m1;
+    }
+  }
+  __syncthreads();
+  if (wave < 2) {
+    const int c = wave * 16 + li, cr = c < kHead ? c : kHead - 1;        // a column past the head repeats the last one and is not stored
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    const float* w3 = a.w3 + (long)cr * H + 4 * g;
+    for (int kb = 0; kb < H; kb += 16) acc = mfma16(ld4(xa + kb), ld4(w3 + kb), acc);
+    const float* wm = a.w_m + (long)cr * R + 4 * g;
+    const float* mb = sm1 + li * LS + 4 * g;
+    for (int kb = 0; kb < R; kb += 16) acc = mfma16(ld4(mb + kb), ld4(wm + kb), acc);
+    if (c < kHead) {
+      const float b = a.b3[c];
+#pragma unroll
+      for (int q = 0; q < 4; q++) {
+        const long e = e0 + 4 * g + q;
+        if (e >= a.N) continue;
+        const float v = acc[q] + b;
+        if (a.head) a.head[e * kHead + c] = v;
+        if (c < kAct) a.action[e * kAct + c] = tanh_stable(v);
+      }
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void gru_clear_rows_kernel(const float* __restrict__ m, const uint8_t* __restrict__ clear, long n, int R, float* __restrict__ m0) {
+  const long k = (long)blockIdx.x * 256 + threadIdx.x;
+  if (k >= n) return;
+  m0[k] = clear[k / R] ? 0.f : m[k];
+}
+
+__global__ __launch_bounds__(256) void gru_cell_forward_kernel(const float* __restrict__ gi, const float* __restrict__ gh, const float* __restrict__ m0,
+                                                               const uint8_t* __restrict__ clear_next, long n, int R, float* __restrict__ gates,
+                                                               float* __restrict__ m1, float* __restrict__ m0_next) {
+  const long k = (long)blockIdx.x * 256 + threadIdx.x;
+  if (k >= n) return;
+  const long i = k / R, b = i * 3 * R + (k - i * R);
+  const float r = sigmoid_stable(gi[b] + gh[b]), u = sigmoid_stable(gi[b + R] + gh[b + R]);
+  const float nn = tanh_stable(gi[b + 2 * R] + r * gh[b + 2 * R]);
+  const float v = (1.0f - u) * nn + u * m0[k];
+  gates[b] = r; gates[b + R] = u; gates[b + 2 * R] = nn;
+  m1[k] = v;
+  if (m0_next) m0_next[k] = (clear_next && clear_next[i]) ? 0.f : v;
+}
+
+__global__ __launch_bounds__(256) void gru_cell_backward_kernel(const float* __restrict__ gates, const float* __restrict__ gh, const float* __restrict__ m0,
+                                                                const float* __restrict__ dm1_head, const float* __restrict__ dm0_next,
+                                                                const uint8_t* __restrict__ clear_next, long n, int R, float* __restrict__ dgi,
+                                                                float* __restrict__ dgh, float* __restrict__ dm0_direct) {
+  const long k = (long)blockIdx.x * 256 + threadIdx.x;
+  if (k >= n) return;
+  const long i = k / R, b = i * 3 * R + (k - i * R);
+  float dm1 = dm1_head[k];
+  if (dm0_next && !(clear_next && clear_next[i])) dm1 += dm0_next[k];
+  const float r = gates[b], u = gates[b + R], nn = gates[b + 2 * R];
+  const float dn = dm1 * (1.0f - u), du = dm1 * (m0[k] - nn);
+  const float dpn = dn * (1.0f - nn * nn), dpu = du * (u * (1.0f - u));
+  const float dr = gh[b + 2 * R] * dpn, dpr = dr * (r * (1.0f - r));
+  dgi[b] = dpr; dgi[b + R] = dpu; dgi[b + 2 * R] = dpn;
+  dgh[b] = dpr; dgh[b + R] = dpu; dgh[b + 2 * R] = r * dpn;
+  dm0_direct[k] = u * dm1;
+}
+
+__global__ __launch_bounds__(256) void add_rows_kernel(const float* a, const float* b, long n, float* out) {
+  const long k = (long)blockIdx.x * 256 + threadIdx.x;
+  if (k < n) out[k] = a[k] + b[k];
+}
+
+bool memory_ok(int R) { return R >= 16 && R <= PGTT_LEARN_MAX_MEMORY && R % 16 == 0; }
+unsigned blocks256(long n) { return (unsigned)((n + 255) / 256); }
+
 }  // namespace
 
 extern "C" {
@@ -493,6 +666,85 @@ int pgtt_learn_gather_rows(const int64_t* idx, const float* obs, const float* ta
   if (B <= 0 || rows <= 0 || obs_dim <= 0 || tgt_dim <= 0) return fail(PGTT_E_ARG, "pgtt_learn_gather_rows: B, rows, obs_dim and tgt_dim must be positive");
   hipLaunchKernelGGL(gather_rows_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, idx, obs, target, mean, std, rows, obs_dim, tgt_dim, x, y);
   return launched("pgtt_learn_gather_rows");
+}
+
+int pgtt_learn_sizeof_recurrent_act_args(void) { return (int)sizeof(PgttLearnRecurrentActArgs); }
+
+int64_t pgtt_learn_recurrent_act_work_floats(int N, int od, int h1, int h2, int h3) {
+  if (N <= 0 || od <= 0 || h1 <= 0 || h2 <= 0 || h3 <= 0) return 0;
+  const int64_t hz = h1 > h2 ? (h1 > h3 ? h1 : h3) : (h2 > h3 ? h2 : h3);
+  return (int64_t)N * ((int64_t)od + h1 + h2 + h3 + hz);
+}
+
+int pgtt_learn_recurrent_act(const PgttLearnRecurrentActArgs* a, void* stream) {
+  const char* who = "pgtt_learn_recurrent_act";
+  if (!a) return fail(PGTT_E_ARG, std::string(who) + ": null args");
+  if (!a->obs || !a->mean || !a->std || !a->w0 || !a->w1 || !a->w2 || !a->w3 || !a->b0 || !a->b1 || !a->b2 || !a->b3 || !a->w_ih || !a->w_hh ||
+      !a->b_ih || !a->b_hh || !a->w_m || !a->mem || !a->action || !a->work)
+    return fail(PGTT_E_ARG, std::string(who) + ": null pointer");
+  if (a->num_envs <= 0 || a->obs_dim <= 0 || a->h1 <= 0 || a->h2 <= 0 || a->h3 <= 0)
+    return fail(PGTT_E_ARG, std::string(who) + ": num_envs, obs_dim, h1, h2 and h3 must be positive");
+  if (a->h3 % 16 != 0) return fail(PGTT_E_ARG, std::string(who) + ": h3 must be a multiple of 16");
+  if (!memory_ok(a->memory)) return fail(PGTT_E_ARG, std::string(who) + ": memory must be a multiple of 16 in [16, 256]");
+  const bool stores = a->store_obs || a->store_mem0 || a->store_clear;
+  if (stores && (a->store_rows <= 0 || a->t < 0 || a->t >= a->store_rows))
+    return fail(PGTT_E_ARG, std::string(who) + ": the storage row t must be in [0, store_rows)");
+  hipStream_t st = (hipStream_t)stream;
+  const long N = a->num_envs, od = a->obs_dim, R = a->memory;
+  float* x = a->work;
+  float* y1 = x + N * od;
+  float* y2 = y1 + N * a->h1;
+  float* y3 = y2 + N * a->h2;
+  float* z = y3 + N * a->h3;                                  // the pre-activations: nobody reads them here
+  const long row = (long)a->t * N;
+  hipLaunchKernelGGL(normalise_kernel, dim3((unsigned)N), dim3(256), 0, st, a->obs, a->mean, a->std, (int)od, x,
+                     a->store_obs ? a->store_obs + row * od : nullptr);
+  int rc = pgtt_learn_linear_forward(x, a->w0, a->b0, (int)N, (int)od, a->h1, 1, y1, z, stream);
+  if (rc == PGTT_OK) rc = pgtt_learn_linear_forward(y1, a->w1, a->b1, (int)N, a->h1, a->h2, 1, y2, z, stream);
+  if (rc == PGTT_OK) rc = pgtt_learn_linear_forward(y2, a->w2, a->b2, (int)N, a->h2, a->h3, 1, y3, z, stream);
+  if (rc != PGTT_OK) return rc;
+  RecurrentK k{y3, a->w_ih, a->w_hh, a->b_ih, a->b_hh, a->w3, a->b3, a->w_m, a->done, a->clear_mask, a->mem, a->action, a->head,
+               a->store_mem0 ? a->store_mem0 + row * R : nullptr, a->store_clear ? a->store_clear + row : nullptr,
+               (int)N, a->h3, (int)R, a->clear_all, a->use_done};
+  hipLaunchKernelGGL(recurrent_tail_kernel, dim3((unsigned)((N + 15) / 16)), dim3(256), (size_t)(2 * 16 * (R + 4)) * sizeof(float), st, k);
+  return launched(who);
+}
+
+int pgtt_learn_gru_clear_rows(const float* m, const uint8_t* clear, int B, int R, float* m0, void* stream) {
+  if (!m || !clear || !m0) return fail(PGTT_E_ARG, "pgtt_learn_gru_clear_rows: null pointer");
+  if (B <= 0) return fail(PGTT_E_ARG, "pgtt_learn_gru_clear_rows: B must be positive");
+  if (!memory_ok(R)) return fail(PGTT_E_ARG, "pgtt_learn_gru_clear_rows: R must be a multiple of 16 in [16, 256]");
+  const long n = (long)B * R;
+  hipLaunchKernelGGL(gru_clear_rows_kernel, dim3(blocks256(n)), dim3(256), 0, (hipStream_t)stream, m, clear, n, R, m0);
+  return launched("pgtt_learn_gru_clear_rows");
+}
+
+int pgtt_learn_gru_cell_forward(const float* gi, const float* gh, const float* m0, const uint8_t* clear_next, int B, int R, float* gates, float* m1,
+                                float* m0_next, void* stream) {
+  if (!gi || !gh || !m0 || !gates || !m1) return fail(PGTT_E_ARG, "pgtt_learn_gru_cell_forward: null pointer");
+  if (B <= 0) return fail(PGTT_E_ARG, "pgtt_learn_gru_cell_forward: B must be positive");
+  if (!memory_ok(R)) return fail(PGTT_E_ARG, "pgtt_learn_gru_cell_forward: R must be a multiple of 16 in [16, 256]");
+  const long n = (long)B * R;
+  hipLaunchKernelGGL(gru_cell_forward_kernel, dim3(blocks256(n)), dim3(256), 0, (hipStream_t)stream, gi, gh, m0, clear_next, n, R, gates, m1, m0_next);
+  return launched("pgtt_learn_gru_cell_forward");
+}
+
+int pgtt_learn_gru_cell_backward(const float* gates, const float* gh, const float* m0, const float* dm1_head, const float* dm0_next,
+                                 const uint8_t* clear_next, int B, int R, float* dgi, float* dgh, float* dm0_direct, void* stream) {
+  if (!gates || !gh || !m0 || !dm1_head || !dgi || !dgh || !dm0_direct) return fail(PGTT_E_ARG, "pgtt_learn_gru_cell_backward: null pointer");
+  if (B <= 0) return fail(PGTT_E_ARG, "pgtt_learn_gru_cell_backward: B must be positive");
+  if (!memory_ok(R)) return fail(PGTT_E_ARG, "pgtt_learn_gru_cell_backward: R must be a multiple of 16 in [16, 256]");
+  const long n = (long)B * R;
+  hipLaunchKernelGGL(gru_cell_backward_kernel, dim3(blocks256(n)), dim3(256), 0, (hipStream_t)stream, gates, gh, m0, dm1_head, dm0_next, clear_next, n, R,
+                     dgi, dgh, dm0_direct);
+  return launched("pgtt_learn_gru_cell_backward");
+}
+
+int pgtt_learn_add_rows(const float* a, const float* b, int64_t n, float* out, void* stream) {
+  if (!a || !b || !out) return fail(PGTT_E_ARG, "pgtt_learn_add_rows: null pointer");
+  if (n <= 0) return fail(PGTT_E_ARG, "pgtt_learn_add_rows: n must be positive");
+  hipLaunchKernelGGL(add_rows_kernel, dim3(blocks256((long)n)), dim3(256), 0, (hipStream_t)stream, a, b, (long)n, out);
+  return launched("pgtt_learn_add_rows");
 }
 
 }  // extern "C"

@@ -10,6 +10,10 @@ the label; the student on the perceived one) around env.step; one update is hand
 pgtt_learn_linear_forward, pgtt_learn_distill_loss (KL(teacher || student) of the two heads and its gradient), per layer pgtt_ppo_linear_backward
 and pgtt_learn_linear_backward_data, pgtt_learn_clip_adam - replayed from one graph after two eager calls.  The student keeps the teacher's
 normaliser.  GPU only, one process: there is no CPU form, no fall-back to PyTorch ops and no data parallel.
+
+With DistillConfig(memory=R), R > 0, the student is a recurrent_policy.RecurrentPolicy - the teacher's layers, a GRU memory of R
+values per env and a read-out of it added to the head - acted by recurrent_policy.RecurrentActor (pgtt_learn_recurrent_act) and trained by
+recurrent_policy.SequenceLearner (truncated BPTT over whole unrolls); save() then writes the recurrent layout.  memory = 0 is the path above.
 """
 from __future__ import annotations
 
@@ -46,6 +50,19 @@ class DistillConfig:
     beta: Tuple[float, float] = (1.0, 0.0)   # share of the envs the teacher drives in the first and the last iteration, linear in between
     student_noise: bool = False              # False: the student acts on its mean
     seed: int = 0
+    memory: int = 0                          # R > 0: the student is a recurrent_policy.RecurrentPolicy with a GRU memory of R values
+
+    def __post_init__(self):
+        _check_memory(self)
+
+
+def _check_memory(cfg) -> None:
+    if cfg.memory == 0:
+        return
+    if not (isinstance(cfg.memory, int) and 16 <= cfg.memory <= 256 and cfg.memory % 16 == 0):
+        raise DistillError(f"memory must be 0 (a feed-forward student) or a multiple of 16 in [16, 256], not {cfg.memory!r}")
+    if cfg.student_noise:
+        raise DistillError("student_noise=True with a memory is not built: the recurrent actor is deterministic (no draws, no log-probabilities)")
 
 
 def _refuse(env) -> None:
@@ -95,16 +112,22 @@ class Rollout:
     "obs" rows record what it saw), the env gets the teacher's tanh(loc) where `mask` is set and the student's action elsewhere, the student
     records.  No host read-back.  The steps are plain launches: the sensors' ticks inside env.step are not pinned under graph capture."""
 
-    def __init__(self, env, teacher: PolicyMLP, obs: torch.Tensor, T: int, seed: int = 0, student_noise: bool = False):
+    def __init__(self, env, teacher: PolicyMLP, obs: torch.Tensor, T: int, seed: int = 0, student_noise: bool = False, memory: int = 0):
+        """memory = R > 0: the student is a recurrent_policy.RecurrentActor (the caller loads its weights); its storage has "obs", "mem0" and
+        "clear" rows, written at the host's step index, and the labels go to the same row"""
         from .acting import FusedActor
         _refuse(env)
-        self.env, self.T, self.noise = env, int(T), bool(student_noise)
+        self.env, self.T, self.noise, self.memory = env, int(T), bool(student_noise), int(memory)
         dev, n = env.device, env.num_envs
         self.teacher = FusedActor(env, 1, seed=seed)
-        self.student = FusedActor(env, self.T, seed=seed + 1, obs=obs)
         layers = [(m.weight, m.bias) for m in teacher.layers]
         self.teacher.load(layers, teacher.mean, teacher.std)
-        self.student.load(layers, teacher.mean, teacher.std)
+        if self.memory:
+            from .recurrent_policy import RecurrentActor
+            self.student = RecurrentActor(env, self.T, self.memory, obs=obs)
+        else:
+            self.student = FusedActor(env, self.T, seed=seed + 1, obs=obs)
+            self.student.load(layers, teacher.mean, teacher.std)
         self.head = torch.zeros(n, 2 * abi.NU, device=dev)
         self.labels = torch.zeros(self.T, n, 2 * abi.NU, device=dev)
         self.mask = torch.ones(n, dtype=torch.bool, device=dev)
@@ -132,8 +155,22 @@ class Rollout:
         env.step(self.action)
         self.student.record()
 
+    @torch.no_grad()
+    def step_recurrent(self, t: int) -> None:
+        """step() under a recurrent student: row t of the labels and of the student's storage by the host's index; the student's memory follows
+        every env, whoever drives it"""
+        self.teacher.act(deterministic=True, head=self.head, store=False)
+        self.labels[t].copy_(self.head)
+        self.student.act(t)
+        torch.where(self.mask[:, None], self.teacher.action, self.student.action, out=self.action)
+        self.env.step(self.action)
+
     def rollout(self) -> Tuple[torch.Tensor, torch.Tensor]:
         """-> (what the student saw [T, N, obs_dim], the teacher's heads [T, N, 24]): the storage itself, overwritten by the next roll-out"""
+        if self.memory:
+            for t in range(self.T):
+                self.step_recurrent(t)
+            return self.student.storage["obs"], self.labels
         self.student.rewind()
         for _ in range(self.T):
             self.step()
@@ -232,10 +269,15 @@ class DistillLearner:
 
 class Distilled:
     """what distill() returns: the student's arrays in the layout of ppo.export_policy_npz (mean, std, w{i} as [in, out], b{i}), the live
-    network, and the per-iteration history"""
+    network, and the per-iteration history; with a memory, the recurrent layout (recurrent_policy.RecurrentPolicy.arrays) and `actor`, the live
+    RecurrentActor with the final weights loaded"""
+    actor = None
 
-    def __init__(self, net: nn.Sequential, mean: torch.Tensor, std: torch.Tensor, history: List[Dict[str, float]]):
+    def __init__(self, net: nn.Module, mean: torch.Tensor, std: torch.Tensor, history: List[Dict[str, float]]):
         self.net, self.history = net, history
+        if hasattr(net, "gru_w_ih"):            # a recurrent_policy.RecurrentPolicy: its own layout, the feed-forward keys plus gru_* and mem_w
+            self.arrays: Dict[str, np.ndarray] = net.arrays()
+            return
         self.arrays: Dict[str, np.ndarray] = {"mean": mean.detach().float().cpu().numpy(), "std": std.detach().float().cpu().numpy()}
         for i, lin in enumerate(m for m in net if isinstance(m, nn.Linear)):
             self.arrays[f"w{i}"] = lin.weight.detach().float().cpu().numpy().T.copy()
@@ -250,6 +292,7 @@ def distill(env, teacher: Union[PolicyMLP, str], cfg: DistillConfig, obs: Union[
     """DAgger from `teacher` into a student that reads `obs`; the env is stepped from the state it is in (reset it first).  Per iteration:
     the drive mask is redrawn, T steps are rolled out, `epochs` passes of minibatch updates run over the T N rows, the new weights are packed
     into the student's acting kernel.  progress_fn(iteration, metrics) is called once per iteration; a true return stops the run."""
+    _check_memory(cfg)
     _refuse(env)
     dev = env.device
     teacher = load_teacher(teacher, dev)
@@ -257,6 +300,8 @@ def distill(env, teacher: Union[PolicyMLP, str], cfg: DistillConfig, obs: Union[
         raise DistillError(f"the teacher reads {teacher.mean.shape[0]} observations, the env gives {env.observation_size['state']}")
     seen = perceived(env, obs)
     T, n = int(cfg.unroll_length), env.num_envs
+    if cfg.memory:
+        return _distill_recurrent(env, teacher, cfg, seen, progress_fn)
     roll = Rollout(env, teacher, seen, T, seed=cfg.seed, student_noise=cfg.student_noise)
     net = student_net(teacher, dev)
     flat = FlatParams(net)
@@ -290,3 +335,47 @@ def distill(env, teacher: Union[PolicyMLP, str], cfg: DistillConfig, obs: Union[
         if progress_fn is not None and progress_fn(it, m):
             break
     return Distilled(net, mean, std, history)
+
+
+def _distill_recurrent(env, teacher: PolicyMLP, cfg: DistillConfig, seen: torch.Tensor, progress_fn) -> Distilled:
+    """distill() with cfg.memory = R > 0: the student is a RecurrentPolicy that starts as the teacher (W_m = 0), acts through a RecurrentActor and
+    learns by SequenceLearner over minibatches of max(1, batch_size // T) whole unrolls.  Its memory is cleared here once and by `done` afterwards;
+    it carries across iterations: an unroll's m_init is the roll-out's stored mem0 of row 0."""
+    from .recurrent_policy import RecurrentPolicy, SequenceLearner
+    dev, T, n = env.device, int(cfg.unroll_length), env.num_envs
+    roll = Rollout(env, teacher, seen, T, seed=cfg.seed, memory=cfg.memory)
+    policy = RecurrentPolicy.from_teacher(teacher, cfg.memory, cfg.seed).to(dev)
+    flat = FlatParams(policy)
+    roll.student.load(policy)
+    roll.student.reset_memory()
+    S = roll.student.storage
+    b_env = min(n, max(1, int(cfg.batch_size) // T))
+    learner = SequenceLearner(policy, flat, S["obs"], roll.labels, S["mem0"], S["clear"], b_env, cfg)
+    gen = torch.Generator(device=dev).manual_seed(int(cfg.seed))
+    b0, b1 = (float(v) for v in cfg.beta)
+    acc = torch.zeros(2, device=dev)
+    history: List[Dict[str, float]] = []
+    t_start = time.time()
+    for it in range(int(cfg.iterations)):
+        t0 = time.time()
+        beta = b0 + (b1 - b0) * (it / max(1, int(cfg.iterations) - 1))
+        share = roll.draw_mask(beta, gen)
+        roll.rollout()
+        acc.zero_()
+        updates = 0
+        for _ in range(int(cfg.epochs)):
+            perm = torch.randperm(n, device=dev, generator=gen)
+            for k in range(n // b_env):
+                acc += learner.update(perm[k * b_env:(k + 1) * b_env])
+                updates += 1
+        roll.student.load(policy)
+        kl, act = (acc / max(1, updates)).tolist()                            # the iteration's one host read
+        dt = time.time() - t0
+        m = {"kl": kl, "action_error": act, "drive_share": share, "beta": beta, "updates": float(updates), "grad_norm": float(learner.norm),
+             "env_steps_per_s": T * n / dt, "seconds": time.time() - t_start}
+        history.append(m)
+        if progress_fn is not None and progress_fn(it, m):
+            break
+    out = Distilled(policy, policy.mean, policy.std, history)
+    out.actor = roll.student
+    return out

@@ -34,7 +34,14 @@ class PgttLearnAdamArgs(C.Structure):
                [(k, C.c_double) for k in ("lr", "beta1", "beta2", "eps")] + [("max_norm", C.c_float), ("grad_scale", C.c_float)]
 
 
-assert C.sizeof(PgttLearnGatherArgs) == 160 and C.sizeof(PgttLearnAdamArgs) == 104
+class PgttLearnRecurrentActArgs(C.Structure):
+    """the acting step of the recurrent policy (recurrent_policy.RecurrentActor)"""
+    _fields_ = [(k, vp) for k in ("obs", "mean", "std", "w0", "w1", "w2", "w3", "b0", "b1", "b2", "b3", "w_ih", "w_hh", "b_ih", "b_hh", "w_m",
+                                  "done", "clear_mask", "mem", "action", "head", "store_obs", "store_mem0", "store_clear", "work")] + \
+               [(k, i32) for k in ("num_envs", "obs_dim", "h1", "h2", "h3", "memory", "t", "store_rows", "clear_all", "use_done")]
+
+
+assert C.sizeof(PgttLearnGatherArgs) == 160 and C.sizeof(PgttLearnAdamArgs) == 104 and C.sizeof(PgttLearnRecurrentActArgs) == 240
 
 
 class LearnError(RuntimeError):
@@ -52,7 +59,14 @@ SIDE = _sidelib.SideLib("learn", LearnError, {
     "pgtt_learn_gae": (None, [vp, vp, vp, vp, vp, ci, ci, cf, cf, vp, vp, vp]),
     "pgtt_learn_distill_loss": (None, [vp, vp, ci, ci, vp, vp, vp, vp]),                       # the two entries of distill.py
     "pgtt_learn_gather_rows": (None, [vp, vp, vp, vp, vp, ci, ci, ci, ci, vp, vp, vp]),
-}, {"pgtt_learn_sizeof_gather_args": PgttLearnGatherArgs, "pgtt_learn_sizeof_adam_args": PgttLearnAdamArgs})
+    "pgtt_learn_recurrent_act": (None, [C.POINTER(PgttLearnRecurrentActArgs), vp]),             # the entries of recurrent_policy.py
+    "pgtt_learn_recurrent_act_work_floats": (C.c_int64, [ci, ci, ci, ci, ci]),
+    "pgtt_learn_gru_clear_rows": (None, [vp, vp, ci, ci, vp, vp]),
+    "pgtt_learn_gru_cell_forward": (None, [vp, vp, vp, vp, ci, ci, vp, vp, vp, vp]),
+    "pgtt_learn_gru_cell_backward": (None, [vp, vp, vp, vp, vp, vp, ci, ci, vp, vp, vp, vp]),
+    "pgtt_learn_add_rows": (None, [vp, vp, C.c_int64, vp, vp]),
+}, {"pgtt_learn_sizeof_gather_args": PgttLearnGatherArgs, "pgtt_learn_sizeof_adam_args": PgttLearnAdamArgs,
+    "pgtt_learn_sizeof_recurrent_act_args": PgttLearnRecurrentActArgs})
 LIB_PATH, EXPORTS, lib, check, build_info = SIDE.path, SIDE.exports, SIDE.lib, SIDE.check, SIDE.build_info
 
 

@@ -46,7 +46,7 @@ def run(args):
     env = make_env(args)
     env.reset(args.seed)
     cfg = distill.DistillConfig(iterations=args.iters, unroll_length=args.horizon, epochs=args.epochs, batch_size=args.batch_size,
-                                learning_rate=args.learning_rate, beta=(b0, b1), seed=args.seed)
+                                learning_rate=args.learning_rate, beta=(b0, b1), seed=args.seed, memory=args.memory)
     t0 = time.time()
 
     def progress(it, m):
@@ -77,6 +77,8 @@ def make_parser():
     ap.add_argument("--batch_size", type=int, default=1024)
     ap.add_argument("--learning_rate", type=float, default=1e-4)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--memory", type=int, default=0, metavar="R",
+                    help="R > 0: the student is a recurrent policy with a GRU memory of R values (a multiple of 16 in [16, 256]); 0: feed-forward")
     ap.add_argument("--obs", type=str, default="elevation", choices=sorted(distill.OBS_NAMES), help="the perceived observation the student reads")
     evaluate.add_sensor_args(ap)
     ap.add_argument("--max_seconds", type=float, default=0.0, help="stop after the iteration that passes this wall time (0 = never)")
