@@ -177,6 +177,37 @@ typedef struct PgttLearnRecurrentActArgs {
 int pgtt_learn_recurrent_act(const PgttLearnRecurrentActArgs* args, void* stream);
 int64_t pgtt_learn_recurrent_act_work_floats(int num_envs, int obs_dim, int h1, int h2, int h3);
 
+/* The sampled acting step: the step above with the tanh-normal head of pgtt_policy_act (pgtt_train.h) behind it, still five launches - the sampling is
+ * the end of the fifth.  head, mem, store_obs, store_mem0 and store_clear are those of pgtt_learn_recurrent_act, bit for bit: the sample does not feed
+ * the memory.  Per env e and actuator j < 12, with loc = head[j], raw = head[12 + j], all in fp32 and in exactly the forms of policy_act_kernel:
+ *   sc   = softplus_t(raw) + 1e-3f                        softplus_t(x) = x > 20 ? x : log1pf(expf(x))   (torch's threshold 20)
+ *   eps  = eps[e][j] when eps is given, else the in-kernel draw of pgtt_train.h: actuators 2k and 2k + 1 share ONE Philox4x32-10 block, key
+ *          (seed & 0xffffffff, seed >> 32), counter ((uint32)(env_id_offset + e), draw & 0xffffffff, (draw >> 32) ^ 0x50475454, k) with
+ *          draw = counters[1] (0 when counters == NULL; counters[0] is not read: the storage row is act.t), words w0 .. w3 (w2, w3 unused);
+ *          u1 = ((float)(w0 >> 8) + 0.5f) 2^-24,  u2 = (float)(w1 >> 8) 2^-24,  r = sqrtf(-2 logf(u1)),  theta = 6.28318530717958648f * u2,
+ *          eps = r cosf(theta) for even j, r sinf(theta) for odd j
+ *   u    = deterministic ? loc : loc + sc * eps           the pre-tanh sample
+ *   z    = (u - loc) / sc
+ *   lp_j = -0.5f z z - logf(sc) - 0.91893853320467274f - 2.0f (0.69314718055994531f - u - softplus_t(-2.0f u))
+ *   act.action[e][j] = tanh(u)                            the overflow-free form above: deterministic != 0 gives pgtt_learn_recurrent_act's action bits
+ *   logp[e] = ((..(0 + lp_0) + lp_1) + ..) + lp_11        one lane per env adds the 12 terms out of LDS, j ascending from 0
+ * With store pointers given, row act.t (0 <= t < store_rows, PGTT_E_ARG otherwise) receives store_u[t][e][:] = u and store_logp[t][e] = logp[e].
+ * Rows past num_envs are neither drawn for nor stored.  An env's u, logp and action depend on its own row and on its global id env_id_offset + e only:
+ * the same bits in any batch, at any position.  No atomics, no scratch; on top of the two memory tiles the kernel holds 2304 bytes of static LDS (the
+ * [16][24] head values of its 16 envs and their [16][12] terms lp_j).  Refused with PGTT_E_ARG, nothing written: a NULL args, everything
+ * pgtt_learn_recurrent_act refuses of `act`, and store_u or store_logp given with store_rows <= 0 or t outside [0, store_rows). */
+typedef struct PgttLearnRecurrentSampleArgs {
+  PgttLearnRecurrentActArgs act;  /* every field with the meaning it has above; act.action receives tanh(u) */
+  const float* eps;               /* [N][12] standard-normal draws, or NULL: drawn in the kernel */
+  const int64_t* counters;        /* device int64[2] or NULL: draw = counters[1] (0 when NULL); counters[0] is not read, the row is act.t */
+  float* store_u;                 /* [store_rows][N][12] or NULL: the pre-tanh sample, row act.t */
+  float* store_logp;              /* [store_rows][N] or NULL */
+  uint64_t seed;
+  int64_t env_id_offset;
+  int32_t deterministic;          /* non-zero: u = loc */
+} PgttLearnRecurrentSampleArgs;
+int pgtt_learn_recurrent_act_sample(const PgttLearnRecurrentSampleArgs* args, void* stream);
+
 /* The point-wise pieces of back-propagation through time over the same cell; the products around them are pgtt_learn_linear_forward (act = 0, a zero
  * bias where none exists), pgtt_learn_linear_backward_data and pgtt_ppo_linear_backward.  Rows [B][.], gates in the order r | u | n, clear flags uint8.
  *   clear_rows:    m0[i][:] = clear[i] ? 0 : m[i][:]          (a cleared row of m is not read).  One launch.
@@ -198,6 +229,7 @@ int pgtt_learn_gru_cell_backward(const float* gates_Bx3R, const float* gh_Bx3R, 
 int pgtt_learn_add_rows(const float* a_n, const float* b_n, int64_t n, float* out_n, void* stream);
 
 int pgtt_learn_sizeof_recurrent_act_args(void);
+int pgtt_learn_sizeof_recurrent_sample_args(void);
 int pgtt_learn_sizeof_gather_args(void);
 int pgtt_learn_sizeof_adam_args(void);
 const char* pgtt_learn_build_info(void);      /* "src=<srchash.side_sha256("learn")>;flavor=product" */

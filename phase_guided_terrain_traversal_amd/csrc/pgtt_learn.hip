@@ -14,9 +14,12 @@
 //                                            and the error of the deterministic action, summed per workgroup in lane order, then in block order
 //   gather_rows_kernel                       one workgroup per minibatch row: the normalised observation and its label row
 //   normalise_kernel / recurrent_tail_kernel the recurrent policy's acting step (recurrent_policy.py): the normalising copy in front of three linear_forward
-//                                            launches, then per 16 envs the GRU cell on MFMA (gates lane-local), m1, the head over h3 and m1, tanh, stores
+//                                            launches, then per 16 envs the GRU cell on MFMA (gates lane-local), m1, the head over h3 and m1, tanh, stores;
+//                                            recurrent_tail_kernel<true> (pgtt_learn_recurrent_act_sample) ends in the tanh-normal head of policy_act_kernel
+//                                            instead: the 16 x 24 head values through LDS, one lane per (env, actuator), Philox draws, u, logp, tanh(u)
 //   gru_clear_rows / gru_cell_forward / gru_cell_backward / add_rows    the point-wise pieces of BPTT over that cell, one lane per (row, memory value)
-// No atomics, no scratch, no LDS beyond the reductions' 16 words and recurrent_tail_kernel's two [16][R + 4] memory tiles; nothing allocates or synchronises.
+// No atomics, no scratch, no LDS beyond the reductions' 16 words, recurrent_tail_kernel's two [16][R + 4] memory tiles and, in its sampled form, 2304 static
+// bytes (the [16][24] head tile and the [16][12] log-probability terms); nothing allocates or synchronises.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -442,13 +445,48 @@ struct RecurrentK {
   int N, H, R, clear_all, use_done;
 };
 
+// what the sampled tail needs on top: the tanh-normal head of policy_act_kernel (pgtt_policy.hip), its forms and its draws
+struct SampleK {
+  const float* eps;
+  const int64_t* counters;
+  float *store_u, *store_logp;                     // those of row t
+  unsigned long long seed;
+  long env_id_offset;
+  int deterministic;
+};
+template <bool SAMPLE> struct TailK : RecurrentK { SampleK s; };
+template <> struct TailK<false> : RecurrentK {};
+
+__device__ __forceinline__ float softplus_t(float x) { return x > 20.f ? x : log1pf(expf(x)); }      // torch F.softplus (threshold 20)
+
+__device__ __forceinline__ void philox4x32_10(unsigned k0, unsigned k1, unsigned& c0, unsigned& c1, unsigned& c2, unsigned& c3) {
+#pragma unroll
+  for (int r = 0; r < 10; r++) {
+    const unsigned h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
+    const unsigned h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
+    const unsigned n0 = h1 ^ c1 ^ k0, n2 = h0 ^ c3 ^ k1;
+    c0 = n0; c1 = l1; c2 = n2; c3 = l0;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+}
+
 constexpr int kHead = 24, kAct = 12;
+
+// the sampled tail's static LDS, 1536 + 768 bytes; only the kernel that calls these owns them.  With scl's 64 bytes the statics stay a multiple of 16, so
+// the dynamic memory tiles behind them keep their 16-byte alignment (their rows are read as 128-bit runs)
+__device__ __forceinline__ float* sampled_head_tile() { __shared__ float t[16 * kHead]; return t; }
+__device__ __forceinline__ float* sampled_logp_tile() { __shared__ float t[16 * kAct]; return t; }
 
 // One workgroup of four waves per 16 envs.  LDS: m0 and m1 of the 16 envs, [16][R + 4] floats each (the rows 16 bytes apart from a multiple of the
 // 32 banks).  A wave owns the memory values 16 ct .. 16 ct + 15 for ct = wave, wave + 4, ..: four accumulators (r, u, gi_n, gh_n) in the C layout of the
 // 16x16x4 form - register q of lane l is env 4 (l >> 4) + q, memory value 16 ct + (l & 15) - so the gates and m1 are lane-local.  Then the head:
 // waves 0 and 1 take its columns 0..15 and 16..23.  Rows past N repeat env N - 1's h3, count as cleared and are not stored.
-__global__ __launch_bounds__(256) void recurrent_tail_kernel(RecurrentK a) {
+// SAMPLE: loc[j] and raw[j] of an actuator sit in different lanes (and, for j >= 4, waves), so waves 0 and 1 leave the 16 x 24 head values in a static
+// LDS tile (1536 bytes) and, after one barrier, lane tid < 16 * 12 takes one (env, actuator): scale, the draw, u, its log-probability term (into a
+// second static tile, 768 bytes: 2304 bytes in all), tanh(u); after a second barrier one lane per env adds the 12 terms, j ascending.  Rows past N
+// are neither drawn for nor stored.
+template <bool SAMPLE>
+__global__ __launch_bounds__(256) void recurrent_tail_kernel(TailK<SAMPLE> a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   __shared__ int scl[16];
   const int R = a.R, H = a.H, LS = R + 4;
@@ -456,6 +494,8 @@ __global__ __launch_bounds__(256) void recurrent_tail_kernel(RecurrentK a) {
   float* sm1 = lds + 16 * LS;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = lane & 15, g = lane >> 4;
   const long e0 = (long)blockIdx.x * 16;
+  float *shead = nullptr, *slp = nullptr;
+  if constexpr (SAMPLE) { shead = sampled_head_tile(); slp = sampled_logp_tile(); }
   if (tid < 16) {
     const long e = e0 + tid;
     int c = 1;
@@ -524,11 +564,52 @@ __global__ __launch_bounds__(256) void recurrent_tail_kernel(RecurrentK a) {
 #pragma unroll
       for (int q = 0; q < 4; q++) {
         const long e = e0 + 4 * g + q;
+        if constexpr (SAMPLE) shead[(4 * g + q) * kHead + c] = acc[q] + b;      // rows past N too: finite, and nobody reads them
         if (e >= a.N) continue;
         const float v = acc[q] + b;
         if (a.head) a.head[e * kHead + c] = v;
-        if (c < kAct) a.action[e * kAct + c] = tanh_stable(v);
+        if constexpr (!SAMPLE) {
+          if (c < kAct) a.action[e * kAct + c] = tanh_stable(v);
+        }
       }
+    }
+  }
+  if constexpr (SAMPLE) {
+    __syncthreads();
+    if (tid < 16 * kAct) {
+      const int env = tid / kAct, j = tid - env * kAct;
+      const long e = e0 + env;
+      float lp = 0.f;
+      if (e < a.N) {
+        const float loc = shead[env * kHead + j], raw = shead[env * kHead + kAct + j];
+        const float sc = softplus_t(raw) + 1e-3f;
+        float eps;
+        if (a.s.eps) eps = a.s.eps[e * kAct + j];
+        else {
+          // one Philox block per (env, draw, actuator pair): Box-Muller on two of its four words (pgtt_train.h)
+          const unsigned long long draw = a.s.counters ? (unsigned long long)a.s.counters[1] : 0ull;
+          unsigned c0 = (unsigned)(a.s.env_id_offset + e), c1 = (unsigned)draw, c2 = (unsigned)(draw >> 32) ^ 0x50475454u, c3 = (unsigned)(j >> 1);
+          philox4x32_10((unsigned)a.s.seed, (unsigned)(a.s.seed >> 32), c0, c1, c2, c3);
+          const float u1 = ((float)(c0 >> 8) + 0.5f) * (1.0f / 16777216.0f), u2 = (float)(c1 >> 8) * (1.0f / 16777216.0f);
+          const float r = sqrtf(-2.0f * logf(u1));
+          float sn, cs; sincosf(6.28318530717958648f * u2, &sn, &cs);
+          eps = (j & 1) ? r * sn : r * cs;
+        }
+        const float u = a.s.deterministic ? loc : loc + sc * eps;
+        const float z = (u - loc) / sc;
+        const float kHalfLog2Pi = 0.91893853320467274f, kLog2 = 0.69314718055994531f;
+        lp = -0.5f * z * z - logf(sc) - kHalfLog2Pi - 2.0f * (kLog2 - u - softplus_t(-2.0f * u));
+        a.action[e * kAct + j] = tanh_stable(u);
+        if (a.s.store_u) a.s.store_u[e * kAct + j] = u;
+      }
+      slp[tid] = lp;
+    }
+    __syncthreads();
+    if (tid < 16 && e0 + tid < a.N && a.s.store_logp) {
+      float lp = 0.f;
+#pragma unroll
+      for (int j = 0; j < kAct; j++) lp += slp[tid * kAct + j];
+      a.s.store_logp[e0 + tid] = lp;
     }
   }
 }
@@ -676,9 +757,12 @@ int64_t pgtt_learn_recurrent_act_work_floats(int N, int od, int h1, int h2, int 
   return (int64_t)N * ((int64_t)od + h1 + h2 + h3 + hz);
 }
 
-int pgtt_learn_recurrent_act(const PgttLearnRecurrentActArgs* a, void* stream) {
-  const char* who = "pgtt_learn_recurrent_act";
-  if (!a) return fail(PGTT_E_ARG, std::string(who) + ": null args");
+}  // extern "C"
+
+namespace {
+
+// both acting entries: every check, then the five launches; `s` given = the sampled tail
+int recurrent_act(const PgttLearnRecurrentActArgs* a, const PgttLearnRecurrentSampleArgs* s, void* stream, const char* who) {
   if (!a->obs || !a->mean || !a->std || !a->w0 || !a->w1 || !a->w2 || !a->w3 || !a->b0 || !a->b1 || !a->b2 || !a->b3 || !a->w_ih || !a->w_hh ||
       !a->b_ih || !a->b_hh || !a->w_m || !a->mem || !a->action || !a->work)
     return fail(PGTT_E_ARG, std::string(who) + ": null pointer");
@@ -689,6 +773,8 @@ int pgtt_learn_recurrent_act(const PgttLearnRecurrentActArgs* a, void* stream) {
   const bool stores = a->store_obs || a->store_mem0 || a->store_clear;
   if (stores && (a->store_rows <= 0 || a->t < 0 || a->t >= a->store_rows))
     return fail(PGTT_E_ARG, std::string(who) + ": the storage row t must be in [0, store_rows)");
+  if (s && (s->store_u || s->store_logp) && (a->store_rows <= 0 || a->t < 0 || a->t >= a->store_rows))
+    return fail(PGTT_E_ARG, std::string(who) + ": the storage row t of store_u / store_logp must be in [0, store_rows)");
   hipStream_t st = (hipStream_t)stream;
   const long N = a->num_envs, od = a->obs_dim, R = a->memory;
   float* x = a->work;
@@ -706,8 +792,36 @@ int pgtt_learn_recurrent_act(const PgttLearnRecurrentActArgs* a, void* stream) {
   RecurrentK k{y3, a->w_ih, a->w_hh, a->b_ih, a->b_hh, a->w3, a->b3, a->w_m, a->done, a->clear_mask, a->mem, a->action, a->head,
                a->store_mem0 ? a->store_mem0 + row * R : nullptr, a->store_clear ? a->store_clear + row : nullptr,
                (int)N, a->h3, (int)R, a->clear_all, a->use_done};
-  hipLaunchKernelGGL(recurrent_tail_kernel, dim3((unsigned)((N + 15) / 16)), dim3(256), (size_t)(2 * 16 * (R + 4)) * sizeof(float), st, k);
+  const dim3 grid((unsigned)((N + 15) / 16));
+  const size_t lds = (size_t)(2 * 16 * (R + 4)) * sizeof(float);
+  if (!s) {
+    TailK<false> kd;
+    static_cast<RecurrentK&>(kd) = k;
+    hipLaunchKernelGGL(recurrent_tail_kernel<false>, grid, dim3(256), lds, st, kd);
+  } else {
+    TailK<true> ks;
+    static_cast<RecurrentK&>(ks) = k;
+    ks.s = SampleK{s->eps, s->counters, s->store_u ? s->store_u + row * kAct : nullptr, s->store_logp ? s->store_logp + row : nullptr,
+                   (unsigned long long)s->seed, (long)s->env_id_offset, s->deterministic};
+    hipLaunchKernelGGL(recurrent_tail_kernel<true>, grid, dim3(256), lds, st, ks);
+  }
   return launched(who);
+}
+
+}  // namespace
+
+extern "C" {
+
+int pgtt_learn_sizeof_recurrent_sample_args(void) { return (int)sizeof(PgttLearnRecurrentSampleArgs); }
+
+int pgtt_learn_recurrent_act(const PgttLearnRecurrentActArgs* a, void* stream) {
+  if (!a) return fail(PGTT_E_ARG, "pgtt_learn_recurrent_act: null args");
+  return recurrent_act(a, nullptr, stream, "pgtt_learn_recurrent_act");
+}
+
+int pgtt_learn_recurrent_act_sample(const PgttLearnRecurrentSampleArgs* s, void* stream) {
+  if (!s) return fail(PGTT_E_ARG, "pgtt_learn_recurrent_act_sample: null args");
+  return recurrent_act(&s->act, s, stream, "pgtt_learn_recurrent_act_sample");
 }
 
 int pgtt_learn_gru_clear_rows(const float* m, const uint8_t* clear, int B, int R, float* m0, void* stream) {

@@ -41,7 +41,14 @@ class PgttLearnRecurrentActArgs(C.Structure):
                [(k, i32) for k in ("num_envs", "obs_dim", "h1", "h2", "h3", "memory", "t", "store_rows", "clear_all", "use_done")]
 
 
+class PgttLearnRecurrentSampleArgs(C.Structure):
+    """the sampled acting step (recurrent_policy.RecurrentActor.act(t, sample=True)): the struct above, embedded, and the sampling fields"""
+    _fields_ = [("act", PgttLearnRecurrentActArgs)] + [(k, vp) for k in ("eps", "counters", "store_u", "store_logp")] + \
+               [("seed", C.c_uint64), ("env_id_offset", C.c_int64), ("deterministic", i32)]
+
+
 assert C.sizeof(PgttLearnGatherArgs) == 160 and C.sizeof(PgttLearnAdamArgs) == 104 and C.sizeof(PgttLearnRecurrentActArgs) == 240
+assert C.sizeof(PgttLearnRecurrentSampleArgs) == 296
 
 
 class LearnError(RuntimeError):
@@ -61,12 +68,14 @@ SIDE = _sidelib.SideLib("learn", LearnError, {
     "pgtt_learn_gather_rows": (None, [vp, vp, vp, vp, vp, ci, ci, ci, ci, vp, vp, vp]),
     "pgtt_learn_recurrent_act": (None, [C.POINTER(PgttLearnRecurrentActArgs), vp]),             # the entries of recurrent_policy.py
     "pgtt_learn_recurrent_act_work_floats": (C.c_int64, [ci, ci, ci, ci, ci]),
+    "pgtt_learn_recurrent_act_sample": (None, [C.POINTER(PgttLearnRecurrentSampleArgs), vp]),
     "pgtt_learn_gru_clear_rows": (None, [vp, vp, ci, ci, vp, vp]),
     "pgtt_learn_gru_cell_forward": (None, [vp, vp, vp, vp, ci, ci, vp, vp, vp, vp]),
     "pgtt_learn_gru_cell_backward": (None, [vp, vp, vp, vp, vp, vp, ci, ci, vp, vp, vp, vp]),
     "pgtt_learn_add_rows": (None, [vp, vp, C.c_int64, vp, vp]),
 }, {"pgtt_learn_sizeof_gather_args": PgttLearnGatherArgs, "pgtt_learn_sizeof_adam_args": PgttLearnAdamArgs,
-    "pgtt_learn_sizeof_recurrent_act_args": PgttLearnRecurrentActArgs})
+    "pgtt_learn_sizeof_recurrent_act_args": PgttLearnRecurrentActArgs,
+    "pgtt_learn_sizeof_recurrent_sample_args": PgttLearnRecurrentSampleArgs})
 LIB_PATH, EXPORTS, lib, check, build_info = SIDE.path, SIDE.exports, SIDE.lib, SIDE.check, SIDE.build_info
 
 

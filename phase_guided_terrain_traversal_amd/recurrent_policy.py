@@ -6,6 +6,7 @@ last hidden layer and its head, head = W3 h3 + b3 + W_m m1.  With W_m = 0 it is 
     heads = policy.sequence(obs_TxBxod, m_init, clear_TxB)                       # the autograd form of a whole unroll
     actor = RecurrentActor(env, T, memory=64, obs=env.elevation_obs); actor.load(policy)
     actor.act(t)                                                                 # pgtt_learn_recurrent_act: hand-written HIP, storage row t
+    actor.act(t, sample=True)                                                    # pgtt_learn_recurrent_act_sample: a draw, its u and logp rows
     learner = SequenceLearner(policy, FlatParams(policy), ...); learner.update(env_idx)      # one BPTT update, hand-written HIP on one stream
 
 The file format is that of ppo.export_policy_npz (mean, std, w{i} as [in, out], b{i}) plus gru_w_ih [3R, 128], gru_w_hh [3R, R], gru_b_ih, gru_b_hh
@@ -24,7 +25,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import abi, learn, native
-from .learn import FlatParams, PgttLearnAdamArgs, PgttLearnRecurrentActArgs, _stream
+from .learn import FlatParams, PgttLearnAdamArgs, PgttLearnRecurrentActArgs, PgttLearnRecurrentSampleArgs, _stream
 
 MAX_MEMORY = 256
 GRU_KEYS = ("gru_w_ih", "gru_w_hh", "gru_b_ih", "gru_b_hh", "mem_w")
@@ -139,9 +140,12 @@ class RecurrentPolicy(nn.Module):
 class RecurrentActor:
     """The acting step of a roll-out under a RecurrentPolicy: pgtt_learn_recurrent_act on the env's observation (or `obs`), the memory [N, R] kept
     here and cleared by the env's `done` of the step before (use_done) and, on the first call and after reset_memory(), for every env.
-    storage["obs" | "mem0" | "clear"] are [T, N, .] rows written by act(t)."""
+    storage["obs" | "mem0" | "clear"] are [T, N, .] rows written by act(t).  act(t, sample=True) is pgtt_learn_recurrent_act_sample: the action is
+    tanh(u) of a draw from the tanh-normal head (Philox, keyed by `seed`, the env's global id and counters[1]), and storage["u" | "logp"] receive the
+    pre-tanh sample and its log-probability.  `counters` is the device int64[2] {storage row, draw counter} that pgtt_rollout_record advances; the
+    acting step reads the draw counter only - its row is the `t` it is given."""
 
-    def __init__(self, env, T: int, memory: int = 64, obs: Optional[torch.Tensor] = None):
+    def __init__(self, env, T: int, memory: int = 64, obs: Optional[torch.Tensor] = None, seed: int = 0, counters: Optional[torch.Tensor] = None):
         if torch.device(env.device).type != "cuda":
             raise learn.LearnError("RecurrentActor needs a Joystick on a ROCm device; there is no CPU path")
         if not memory_ok(memory):
@@ -172,6 +176,15 @@ class RecurrentActor:
         a.mem, a.action, a.work = self.mem.data_ptr(), self.action.data_ptr(), self.work.data_ptr()
         a.num_envs, a.obs_dim, a.h1, a.h2, a.h3, a.memory, a.store_rows, a.use_done = n, od, d[1], d[2], d[3], R, self.T, 1
         self._args = a
+        # the sampled step: its own copy of the struct above (embedded, refreshed by act), the draw counter and the two rows it adds
+        self.storage["u"], self.storage["logp"] = z(self.T, n, abi.NU), z(self.T, n)
+        self.counters = torch.zeros(2, dtype=torch.int64, device=dev) if counters is None else counters
+        if not (self.counters.dtype == torch.int64 and self.counters.numel() == 2 and self.counters.is_contiguous()
+                and self.counters.device == self.mem.device):
+            raise ValueError(f"RecurrentActor: `counters` must be two contiguous int64 values on {dev}")
+        s = PgttLearnRecurrentSampleArgs()
+        s.counters, s.seed, s.env_id_offset = self.counters.data_ptr(), int(seed) & 0xFFFFFFFFFFFFFFFF, int(getattr(env, "env_id_offset", 0))
+        self._sample_args = s
 
     @torch.no_grad()
     def load(self, policy: RecurrentPolicy) -> None:
@@ -187,17 +200,30 @@ class RecurrentActor:
         """the next act() starts every env from a zero memory (clear_all)"""
         self._clear_all = True
 
-    def act(self, t: Optional[int] = None, head: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def act(self, t: Optional[int] = None, head: Optional[torch.Tensor] = None, sample: bool = False, eps: Optional[torch.Tensor] = None,
+            deterministic: bool = False) -> torch.Tensor:
         """the deterministic action tanh(loc) for the current observation -> self.action; with t, row t of the storage is written; `head` [N, 24]
-        receives the raw head"""
+        receives the raw head.  sample=True: the action is tanh(u), u = loc + scale eps with eps drawn in the kernel (or `eps` [N, 12]; deterministic:
+        u = loc), and with t the rows "u" and "logp" are written too"""
         a, S = self._args, self.storage
+        if not sample and (eps is not None or deterministic):
+            raise ValueError("RecurrentActor.act: `eps` and `deterministic` belong to sample=True")
         a.clear_all, self._clear_all = int(self._clear_all), False
         if head is not None:
             assert head.is_contiguous() and head.dtype == torch.float32 and tuple(head.shape) == (self.env.num_envs, self.dims[4])
         a.head = None if head is None else head.data_ptr()
         a.t = 0 if t is None else int(t)
         a.store_obs, a.store_mem0, a.store_clear = (None, None, None) if t is None else (S["obs"].data_ptr(), S["mem0"].data_ptr(), S["clear"].data_ptr())
-        learn.check(self._L.pgtt_learn_recurrent_act(C.byref(a), _stream(self.env.device)))
+        if not sample:
+            learn.check(self._L.pgtt_learn_recurrent_act(C.byref(a), _stream(self.env.device)))
+            return self.action
+        s = self._sample_args
+        if eps is not None:
+            assert eps.is_contiguous() and eps.dtype == torch.float32 and tuple(eps.shape) == (self.env.num_envs, abi.NU) and eps.device == self.mem.device
+        s.act = a                                   # a copy of the struct as it stands now
+        s.eps, s.deterministic = None if eps is None else eps.data_ptr(), int(bool(deterministic))
+        s.store_u, s.store_logp = (None, None) if t is None else (S["u"].data_ptr(), S["logp"].data_ptr())
+        learn.check(self._L.pgtt_learn_recurrent_act_sample(C.byref(s), _stream(self.env.device)))
         return self.action
 
 
@@ -217,7 +243,7 @@ class SequenceLearner:
         T, N, od = obs_store.shape
         R, d = policy.memory, policy.dims
         assert obs_store.is_contiguous() and label_store.is_contiguous() and mem0_store.is_contiguous() and clear_store.is_contiguous()
-        assert tuple(label_store.shape) == (T, N, d[4]) and tuple(mem0_store.shape)[1:] == (N, R) and tuple(clear_store.shape) == (T, N)
+        assert tuple(label_store.shape) == (T, N, self._label_dim(d)) and tuple(mem0_store.shape)[1:] == (N, R) and tuple(clear_store.shape) == (T, N)
         assert clear_store.dtype == torch.uint8 and od == d[0] and policy.mean.is_contiguous() and policy.std.is_contiguous()
         self.policy, self.flat, self.cfg, self.dev = policy, flat, cfg, dev
         self.obs_store, self.label_store, self.mem0_store, self.clear_store = obs_store, label_store, mem0_store, clear_store
@@ -229,7 +255,7 @@ class SequenceLearner:
         self.idx = torch.zeros(TB, dtype=torch.long, device=dev)
         self._t_off = (torch.arange(T, device=dev) * N)[:, None]
         self.m_init, self.clear = z(B, R), torch.zeros(T, B, dtype=torch.uint8, device=dev)
-        self.x, self.y = z(TB, od), z(TB, d[4])
+        self.x, self.y = z(TB, od), z(TB, self._label_dim(d))
         self.h = [z(TB, d[i + 1]) for i in range(3)]
         self.zs = [z(TB, d[i + 1]) for i in range(3)]
         self.dz = [z(TB, d[i + 1]) for i in range(3)]
@@ -260,12 +286,23 @@ class SequenceLearner:
             scratch = max(scratch, S * (Nn * M + Nn))
         self.lb_partial = z(scratch)
 
+    @staticmethod
+    def _label_dim(d) -> int:
+        """the width of the rows of `label_store` that the gather copies into self.y next to the normalised observation"""
+        return d[4]
+
+    def _loss(self) -> None:
+        """self.head [T B, 24] and self.y -> dL/dhead into self.dhead: the one call a subclass replaces (recurrent_ppo.SequencePPOLearner)"""
+        learn.check(self.lib.pgtt_learn_distill_loss(C.c_void_p(self.head.data_ptr()), C.c_void_p(self.y.data_ptr()), self.rows, self.dims[4] // 2,
+                                                     C.c_void_p(self.partial.data_ptr()), C.c_void_p(self.loss2.data_ptr()),
+                                                     C.c_void_p(self.dhead.data_ptr()), _stream(self.dev)))
+
     def _forward_backward(self):
         L, P, st, p, check = self.lib, self.plib, _stream(self.dev), (lambda t: None if t is None else C.c_void_p(t.data_ptr())), learn.check
         pi, T, B, TB, R, d = self.policy, self.T, self.B, self.rows, self.R, self.dims
         lin = pi.layers
-        check(L.pgtt_learn_gather_rows(p(self.idx), p(self.obs_store), p(self.label_store), p(pi.mean), p(pi.std), TB, self.T * self.N, d[0], d[4],
-                                       p(self.x), p(self.y), st))
+        check(L.pgtt_learn_gather_rows(p(self.idx), p(self.obs_store), p(self.label_store), p(pi.mean), p(pi.std), TB, self.T * self.N, d[0],
+                                       self.y.shape[1], p(self.x), p(self.y), st))
         x = self.x
         for i in range(3):
             check(L.pgtt_learn_linear_forward(p(x), p(lin[i].weight), p(lin[i].bias), TB, d[i], d[i + 1], 1, p(self.h[i]), p(self.zs[i]), st))
@@ -282,7 +319,7 @@ class SequenceLearner:
         check(L.pgtt_learn_linear_forward(p(h3), p(lin[3].weight), p(lin[3].bias), TB, d[3], d[4], 0, p(self.head_h), None, st))
         check(L.pgtt_learn_linear_forward(p(self.m1), p(pi.mem_w), p(self.zero_bias), TB, R, d[4], 0, p(self.head_m), None, st))
         check(L.pgtt_learn_add_rows(p(self.head_h), p(self.head_m), TB * d[4], p(self.head), st))
-        check(L.pgtt_learn_distill_loss(p(self.head), p(self.y), TB, d[4] // 2, p(self.partial), p(self.loss2), p(self.dhead), st))
+        self._loss()
         # the backward recurrence
         check(L.pgtt_learn_linear_backward_data(p(self.dhead), p(pi.mem_w), None, TB, R, d[4], p(self.dm1_head), st))
         for t in range(T - 1, -1, -1):

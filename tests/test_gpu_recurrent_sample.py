@@ -1,0 +1,331 @@
+"""pgtt_learn_recurrent_act_sample through the bare C ABI (include/pgtt_learn.h): the recurrent acting step with the tanh-normal head of
+policy_act_kernel fused into its tail.  Held (a) to pgtt_learn_recurrent_act, bit for bit, for everything the sampling must not touch, (b) to the fp64
+head of tests/acting_reference.py for u, action and logp, evaluated from the kernel's own fp32 head taken as exact, (c) to the reference Philox draws.
+Every output is a view into a larger allocation of sentinels at an odd float offset, as in test_gpu_recurrent_kernels.py (whose Guarded, Act and
+policies this file uses).
+
+The bars are those test_gpu_acting_edges.py::check_head derives for the same quantities of policy_act_kernel, with U = 2^-24, none fitted to a kernel:
+
+  u       loc and raw are the kernel's own fp32 head, eps is given exactly.  scale = softplus_t(raw) + 1e-3f is off its fp64 value by at most 4 U scale
+          (log1pf(expf(.)) 2 ulp, the addition, the constant 1e-3f), the product scale eps and the sum are one or two roundings (fused or not):
+              |u - (loc + scale64 eps)| <= 2 U (|loc| + |scale64 eps|) + 4 U |eps| scale64  [+ scale64 eps_err where eps is only known to eps_err].
+          deterministic: u == loc as bits.
+  action  tanh(u) in the library's overflow-free form, sign(u) (1 - t) / (1 + t) with t = expf(-2 |u|), from the exact fp32 u: the bar of
+          test_gpu_recurrent_kernels.py with dv = 0, 2 U (1 - n^2) + 3 U |n| + TINY (it replaces the 4 U of tanhf there); for |u| >= 20, t < 2^-57 and
+          1 - t = 1 + t = 1 in fp32: the action is exactly +-1.
+  logp    |logp - logp64| <= ppo_reference.logp_error(mag) = 8 U mag, mag the sum of the absolute values of the terms (ppo_reference.log_prob).
+  draws   with loc = 0 and raw_j = 24 + j (past the softplus switch) scale_j = float32(raw_j) + float32(1e-3) exactly, so u / scale_j is the kernel's
+          own eps: |eps - eps64| <= DRAW_ULPS 2^-24 r, DRAW_ULPS = 8 (logf, sqrtf, sincosf 2 ulp, two products and a third of slack: derived at
+          test_gpu_acting_edges.py::test_in_kernel_draws_are_the_reference_draws), r the pair's Box-Muller radius.
+"""
+import ctypes as C
+import os
+import sys
+
+import numpy as np
+import pytest
+
+torch = pytest.importorskip("torch")
+pytestmark = pytest.mark.gpu
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import acting_reference as ref  # noqa: E402
+import ppo_reference  # noqa: E402
+import test_gpu_recurrent_kernels as rk  # noqa: E402
+
+from phase_guided_terrain_traversal_amd import learn  # noqa: E402
+from phase_guided_terrain_traversal_amd.learn import PgttLearnRecurrentSampleArgs  # noqa: E402
+
+U, TINY, SENT, E_ARG = rk.U, rk.TINY, rk.SENT, rk.E_ARG
+Guarded = rk.Guarded
+SEED = 0x9E3779B97F4A7C15
+DRAW_ULPS = 8
+T_ROWS = 3
+
+
+class Sample(rk.Act):
+    """one call of pgtt_learn_recurrent_act_sample (or, sample=False, of the deterministic entry on the same buffers) with guarded outputs"""
+
+    def __init__(self, pi, N, T=T_ROWS, head=True, stores=True, sample_stores=True):
+        super().__init__(pi, N, T=T, head=head, stores=stores)
+        self.s_u = Guarded(T, N, 12, front=23, back=19) if sample_stores else None
+        self.s_logp = Guarded(T, N, front=17, back=21) if sample_stores else None
+
+    def sample_args(self, obs, eps=None, counters=None, seed=0, offset=0, det=0, **kw):
+        s = PgttLearnRecurrentSampleArgs()
+        s.act = self.args(obs, **kw)
+        s.eps, s.counters = rk._p(eps), rk._p(counters)
+        s.store_u, s.store_logp = rk._p(self.s_u), rk._p(self.s_logp)
+        s.seed, s.env_id_offset, s.deterministic = seed, offset, det
+        return s
+
+    def run_sample(self, obs, mem, eps=None, counters=None, **kw):
+        self.mem.view.copy_(mem)
+        self._obs = obs.cuda().contiguous()
+        self._eps = None if eps is None else torch.as_tensor(np.asarray(eps, np.float32)).cuda().contiguous()
+        self._cnt = None if counters is None else torch.tensor([int(c) for c in counters], dtype=torch.int64, device="cuda")
+        self._kw = {k: (v.cuda() if torch.is_tensor(v) else v) for k, v in kw.items()}
+        rc = learn.lib().pgtt_learn_recurrent_act_sample(C.byref(self.sample_args(self._obs, self._eps, self._cnt, **self._kw)), rk._st())
+        assert rc == 0, rk._msg()
+        torch.cuda.synchronize()
+        if self._cnt is not None:
+            assert self._cnt.tolist() == [int(c) for c in counters]              # the acting step only reads them
+        return self
+
+    def row(self, t):
+        """(head, u, action, logp) of storage row t as numpy"""
+        return (self.head.view.cpu().numpy(), self.s_u.view[t].cpu().numpy(), self.action.view.cpu().numpy(), self.s_logp.view[t].cpu().numpy())
+
+
+def bits(x):
+    return (x if isinstance(x, np.ndarray) else x.cpu().numpy()).view(np.int32)
+
+
+def check_sample(head, u32, act, logp, eps=None, eps_err=None, det=False):
+    """the bars of the docstring from what the kernel reports -> worst error / bar of (u, action, logp)"""
+    loc, raw = head[:, :12].astype(np.float64), head[:, 12:].astype(np.float64)
+    u = u32.astype(np.float64)
+    assert np.isfinite(u).all() and np.isfinite(logp).all() and np.isfinite(act).all()
+    ru = 0.0
+    if det:
+        assert np.array_equal(bits(u32), bits(np.ascontiguousarray(head[:, :12])))
+    elif eps is not None:
+        sc = ref.scale_of(raw)
+        bar = 2 * U * (np.abs(loc) + np.abs(sc * eps)) + 4 * U * np.abs(eps) * sc + (0.0 if eps_err is None else sc * eps_err)
+        err = np.abs(u - (loc + sc * eps))
+        assert (err <= bar).all(), float((err / np.maximum(bar, 1e-300)).max())
+        ru = float((err[bar > 0] / bar[bar > 0]).max()) if (bar > 0).any() else 0.0
+    n = np.tanh(u)
+    bar_a = 2 * U * (1 - n * n) + 3 * U * np.abs(n) + TINY
+    ea = np.abs(act.astype(np.float64) - n)
+    assert (ea <= bar_a).all(), float((ea / bar_a).max())
+    big = np.abs(u) >= 20
+    assert np.array_equal(act[big], np.sign(u32[big]))
+    logp64, mag = ref.head_logp(loc, raw, u)
+    el, bar_l = np.abs(logp.astype(np.float64) - logp64), ppo_reference.logp_error(torch.as_tensor(mag)).numpy()
+    assert (el <= bar_l).all(), float((el / bar_l).max())
+    return ru, float((ea / bar_a).max()), float((el / bar_l).max())
+
+
+def _eps(N, seed):
+    return torch.randn(N, 12, generator=torch.Generator().manual_seed(seed)).numpy()
+
+
+def _old_entry(pi, N, obs, mem, **kw):
+    return Sample(pi, N, sample_stores=False).run(obs, mem, **kw)
+
+
+OLD = ("mem", "action", "head", "s_obs", "s_mem0", "s_clear")
+
+
+# ------------------------------------------------------------------ against the old entry, and a given eps against fp64
+@pytest.mark.parametrize("R", [16, 64])
+@pytest.mark.parametrize("N", [1, 15, 16, 17, 33])
+def test_sampled_step_against_the_old_entry_and_fp64(N, R):
+    pi = rk._policy(R)
+    obs, mem = rk._inputs(pi, N, 10 * N + R)
+    clear = torch.zeros(N, dtype=torch.uint8)
+    clear[N // 2] = 1
+    old = _old_entry(pi, N, obs, mem, t=1, clear_mask=clear)
+    eps = _eps(N, N + R)
+    # deterministic = 1: every output of the old entry has its bits, u == loc, and logp is that of z = 0
+    det = Sample(pi, N).run_sample(obs, mem, eps=eps, det=1, t=1, clear_mask=clear)
+    for k in OLD:
+        assert torch.equal(getattr(det, k).big, getattr(old, k).big), k                  # guard bands and untouched rows included
+    head, u, act, logp = det.row(1)
+    r_det = check_sample(head, u, act, logp, det=True)
+    # deterministic = 0: the sample does not feed the memory - head, mem and the three old rows keep their bits; the action is tanh(u)
+    s = Sample(pi, N).run_sample(obs, mem, eps=eps, t=1, clear_mask=clear)
+    for k in OLD:
+        if k != "action":
+            assert torch.equal(getattr(s, k).big, getattr(old, k).big), k
+    assert s.action.written() and not torch.equal(s.action.view, old.action.view)
+    head, u, act, logp = s.row(1)
+    r = check_sample(head, u, act, logp, eps=eps.astype(np.float64))
+    print(f"sampled act N={N} R={R}: u, action, logp error / bar = {r}; deterministic {r_det}")
+    # the two new rows: row 1 written, rows 0 and 2 and the guard bands untouched; two calls give equal bits
+    for g in (s.s_u, s.s_logp):
+        assert g.guards_intact() and bool((g.view[1] != SENT).all()) and bool((g.view[0] == SENT).all()) and bool((g.view[2] == SENT).all())
+    again = Sample(pi, N).run_sample(obs, mem, eps=eps, t=1, clear_mask=clear)
+    for k in OLD + ("s_u", "s_logp"):
+        assert torch.equal(getattr(again, k).big, getattr(s, k).big), k
+
+
+# ------------------------------------------------------------------ the head around its switches: a last layer that is a bias only
+F32 = np.float32
+RAWS = np.array([-100.0, -20.0, 0.0, np.nextafter(F32(20), F32(0)), 20.0, np.nextafter(F32(20), F32(40)), 25.0, 80.0], np.float64)
+LOCS = np.array([0.0, 0.5, -0.5, 9.0, -9.0, 20.0, -20.0])
+EPSS = np.array([0.0, 1e-3, -1e-3, 1.0, -1.0, 5.88, -5.88])
+
+
+def _bias_head(R, loc, raw):
+    """the policy of rk._policy(R) with W3 = 0, W_m = 0 and b3 = (loc | raw): the head chain is 0 + .. + b3, exactly the bias"""
+    import copy
+    pi = copy.deepcopy(rk._policy(R))
+    with torch.no_grad():
+        pi.layers[3].weight.zero_(); pi.mem_w.zero_()
+        pi.layers[3].bias.copy_(torch.tensor(np.concatenate([loc, raw]).astype(np.float32)))
+    return pi
+
+
+def _edge_launches():
+    """(loc [12], raw [12], eps [n, 12]) grids.  0, 1: the twelve actuators walk RAWS (raw = -100: scale = 1e-3; -20 and 20 -+ 1 ulp: both sides of
+    the softplus switch) and LOCS at two phases, every actuator meets every value of EPSS, eps = 0 among them.  2: eps per element so that u lands on
+    +-10 (1 + k 2^-23) and +-20 (1 + k 2^-23), k = -3 .. 3 (-2 u on either side of the switch at 20 inside the tanh correction; tanh saturated), and on
+    +-44 and +-100, from every loc and the six raws with scale >= 0.69"""
+    out = []
+    j = np.arange(12)
+    for phase in (0, 1):
+        loc, raw = LOCS[(j + 3 * phase) % 7], RAWS[(5 * j + phase) % 8] if phase else RAWS[j % 8]
+        e, jj = np.meshgrid(np.arange(28), j, indexing="ij")
+        out.append((loc, raw, EPSS[(e + jj) % 7]))
+    loc, raw = LOCS[j % 7], RAWS[2 + (j % 6)]
+    scale = ref.scale_of(raw.astype(np.float32))
+    targets = np.array([s * m * (1 + k * 2.0 ** -23) for m in (10.0, 20.0) for s in (1, -1) for k in range(-3, 4)] + [44.0, -44.0, 100.0, -100.0])
+    out.append((loc, raw, (targets[:, None] - loc[None, :]) / scale[None, :]))
+    return out
+
+
+@pytest.mark.parametrize("det", [0, 1])
+@pytest.mark.parametrize("launch", [0, 1, 2])
+def test_head_edges(launch, det):
+    loc, raw, eps = _edge_launches()[launch]
+    n = eps.shape[0]
+    assert n <= 40
+    pi = _bias_head(16, loc, raw)
+    obs, mem = rk._inputs(pi, n, 4 + launch)
+    s = Sample(pi, n, T=2).run_sample(obs, mem, eps=eps, det=det, t=1)
+    head, u32, act, logp = s.row(1)
+    assert np.array_equal(head, np.tile(np.concatenate([loc, raw]).astype(np.float32), (n, 1)))
+    eps32 = eps.astype(np.float32).astype(np.float64)
+    res = check_sample(head, u32, act, logp, eps=eps32, det=bool(det))
+    print(f"head edges launch {launch} det {det}: u, action, logp error / bar = {res}")
+    if det:
+        return
+    u = u32.astype(np.float64)
+    if launch == 2:                    # the launch covers what it is for
+        for s_ in (1.0, -1.0):
+            for m in (10.0, 20.0):
+                near = np.abs(u - m * s_) <= 8 * 2.0 ** -19
+                assert (s_ * u[near] < m).any() and (s_ * u[near] > m).any()
+            assert (np.abs(u - 44.0 * s_) <= 4 * 2.0 ** -18).any() and (np.abs(u - 100.0 * s_) <= 4 * 2.0 ** -17).any()
+    else:
+        assert set(np.unique(raw)) == set(RAWS) and set(np.unique(loc)) == set(LOCS)
+        zero = eps32 == 0
+        assert zero.any() and np.array_equal(bits(u32)[zero], bits(np.ascontiguousarray(head[:, :12]))[zero])      # eps = 0: u is loc
+
+
+# ------------------------------------------------------------------ the in-kernel draws
+RAW_A = 24.0 + np.arange(12)
+
+
+def _drawn_eps(u32):
+    scale = (RAW_A.astype(np.float32) + np.float32(1e-3)).astype(np.float64)
+    return u32.astype(np.float64) / scale
+
+
+@pytest.mark.parametrize("draw", [0, 1, 2 ** 32 - 1, 2 ** 32, 2 ** 40 + 3])
+def test_in_kernel_draws_are_the_reference_draws(draw):
+    n = 24
+    pi = _bias_head(16, np.zeros(12), RAW_A)
+    obs, mem = rk._inputs(pi, n, 3)
+    us = {}
+    for offset in (0, 1000003, 2 ** 31 + 5):
+        for seed in (SEED, SEED & 0xFFFFFFFF):
+            s = Sample(pi, n, T=1).run_sample(obs, mem, counters=(77, draw), seed=seed, offset=offset, t=0)
+            head, u32, act, logp = s.row(0)
+            assert np.array_equal(head[:, :12], np.zeros((n, 12), np.float32)) and np.array_equal(head[:, 12:], np.tile(RAW_A, (n, 1)).astype(np.float32))
+            eps64, r = ref.draws(seed, offset, draw, n)
+            err, bar = np.abs(_drawn_eps(u32) - eps64), DRAW_ULPS * U * r
+            assert (err <= bar).all(), float((err[bar > 0] / bar[bar > 0]).max())
+            print(f"draws offset {offset} counter {draw} seed {seed:#x}: worst |eps - eps64| / (8 2^-24 r) = {float((err[bar > 0] / bar[bar > 0]).max()):.3f}")
+            check_sample(head, u32, act, logp, eps=eps64, eps_err=bar)
+            us[(offset, seed)] = u32
+    assert (us[(0, SEED)] != us[(0, SEED & 0xFFFFFFFF)]).all()                       # the seed's high word is part of the key
+    assert (us[(0, SEED)] != us[(1000003, SEED)]).all()                              # and the env's global id of the counter
+
+
+def test_draws_depend_on_seed_global_id_and_draw_only():
+    pi = rk._policy(16)
+    N = 33
+    obs, mem = rk._inputs(pi, N, 5)
+    draw = 2 ** 32 + 9
+    full = Sample(pi, N).run_sample(obs, mem, counters=(0, draw), seed=SEED, t=0)
+    for k in (0, 20, 32):                    # an env alone with env_id_offset = k has the bits it has as env k of 33 with offset 0
+        one = Sample(pi, 1).run_sample(obs[k:k + 1], mem[k:k + 1], counters=(5, draw), seed=SEED, offset=k, t=0)
+        for name in ("s_u", "s_logp", "action", "head", "mem"):
+            a, b = getattr(one, name).view, getattr(full, name).view
+            a, b = (a[0, 0], b[0, k]) if name.startswith("s_") else (a[0], b[k])
+            assert torch.equal(a, b), (k, name)
+    nxt = Sample(pi, N).run_sample(obs, mem, counters=(0, draw + 1), seed=SEED, t=0)
+    low = Sample(pi, N).run_sample(obs, mem, counters=(0, 9), seed=SEED, t=0)          # the same low word: draw >= 2^32 reaches the third counter word
+    assert bool((nxt.s_u.view[0] != full.s_u.view[0]).all()) and bool((low.s_u.view[0] != full.s_u.view[0]).all())
+    assert torch.equal(nxt.head.view, full.head.view) and torch.equal(nxt.mem.view, full.mem.view)
+    zero = Sample(pi, N).run_sample(obs, mem, counters=(3, 0), seed=SEED, t=0)
+    null = Sample(pi, N).run_sample(obs, mem, counters=None, seed=SEED, t=0)            # counters == NULL is draw 0
+    for name in ("s_u", "s_logp", "action"):
+        assert torch.equal(getattr(zero, name).big, getattr(null, name).big), name
+    head, u32, act, logp = full.row(0)
+    eps64, r = ref.draws(SEED, 0, draw, N)
+    print("random heads, in-kernel draws: u, action, logp error / bar =", check_sample(head, u32, act, logp, eps=eps64, eps_err=DRAW_ULPS * U * r))
+
+
+# ------------------------------------------------------------------ stores
+@pytest.mark.parametrize("N", [1, 17])
+def test_stores_land_in_their_row_only(N):
+    pi = rk._policy(16)
+    obs, mem = rk._inputs(pi, N, 40 + N)
+    eps = _eps(N, 1)
+    first = None
+    for t in (0, T_ROWS - 1):
+        s = Sample(pi, N).run_sample(obs, mem, eps=eps, t=t)
+        for g in (s.s_u, s.s_logp, s.s_obs, s.s_mem0):
+            assert g.guards_intact()
+            for row in range(T_ROWS):
+                assert bool(((g.view[row] != SENT) if row == t else (g.view[row] == SENT)).all()), (t, row)
+        assert s.s_clear.guards_intact() and bool((s.s_clear.view[[r for r in range(T_ROWS) if r != t]] == 7).all())
+        if first is not None:
+            assert torch.equal(s.s_u.view[t], first.s_u.view[0]) and torch.equal(s.s_logp.view[t], first.s_logp.view[0])
+        first = first or s
+    # every store NULL (t is then not looked at), and head == NULL: action and mem as before, nothing else written
+    bare = Sample(pi, N, head=False, stores=False, sample_stores=False).run_sample(obs, mem, eps=eps, t=99)
+    assert torch.equal(bare.action.big, first.action.big) and torch.equal(bare.mem.big, first.mem.big)
+    only_old = Sample(pi, N, head=False, sample_stores=False).run_sample(obs, mem, eps=eps, t=0)
+    assert torch.equal(only_old.action.big, first.action.big) and torch.equal(only_old.s_obs.big, first.s_obs.big)
+    only_new = Sample(pi, N, stores=False).run_sample(obs, mem, eps=eps, t=0)
+    assert torch.equal(only_new.s_u.big, first.s_u.big) and torch.equal(only_new.s_logp.big, first.s_logp.big)
+
+
+# ------------------------------------------------------------------ refusals
+def test_refusals_write_nothing():
+    pi = rk._policy(16)
+    N = 5
+    obs, mem = rk._inputs(pi, N, 1)
+    dobs = obs.cuda()
+    lib = learn.lib()
+    a = Sample(pi, N)
+    a.mem.view.fill_(SENT)
+    required = ["obs", "mean", "std", "w0", "w1", "w2", "w3", "b0", "b1", "b2", "b3", "w_ih", "w_hh", "b_ih", "b_hh", "w_m", "mem", "action", "work"]
+    cases = [(k, None) for k in required] + [("memory", v) for v in (0, 8, 272)] + [("t", -1), ("t", T_ROWS), ("store_rows", 0)]
+    cases += [(k, v) for k in ("num_envs", "obs_dim", "h1", "h2", "h3") for v in (0, -1)] + [("h3", 120)]
+    for k, v in cases:
+        s = a.sample_args(dobs, t=0)
+        setattr(s.act, k, v)
+        assert lib.pgtt_learn_recurrent_act_sample(C.byref(s), rk._st()) == E_ARG, (k, v)
+        assert rk._msg().startswith("pgtt_learn_recurrent_act_sample"), (k, v)
+    # t outside the storage with only the new rows given: the old stores are NULL, so only the new check can refuse
+    b = Sample(pi, N, stores=False)
+    b.mem.view.fill_(SENT)
+    for t, rows in ((-1, T_ROWS), (T_ROWS, T_ROWS), (0, 0)):
+        for keep in ("store_u", "store_logp"):
+            s = b.sample_args(dobs, t=t)
+            s.act.store_rows = rows
+            setattr(s, "store_logp" if keep == "store_u" else "store_u", None)
+            assert lib.pgtt_learn_recurrent_act_sample(C.byref(s), rk._st()) == E_ARG, (t, rows, keep)
+            assert "store_u / store_logp" in rk._msg()
+    assert lib.pgtt_learn_recurrent_act_sample(None, rk._st()) == E_ARG and rk._msg().startswith("pgtt_learn_recurrent_act_sample")
+    torch.cuda.synchronize()
+    for x in (a, b):
+        for g in (x.mem, x.action, x.head, x.s_obs, x.s_mem0, x.s_clear, x.s_u, x.s_logp):
+            assert g is None or g.untouched()
+    assert lib.pgtt_learn_sizeof_recurrent_sample_args() == C.sizeof(PgttLearnRecurrentSampleArgs) == 296
