@@ -25,7 +25,7 @@ int pgtt_ppo_policy_loss(const float* out_Bx2A, const float* u_BxA, const float*
                          float* partial_2xceilB64, float* loss_3, float* grad_Bx2A, void* stream);
 /* Weight and bias gradient of a Linear layer over a long batch, dW[n][m] = sum_k dY[k][n] X[k][m],
  * db[n] = sum_k dY[k][n] (X [K][M], dY [K][N], dW in torch's [N][M] layout), K split over S workgroups per 64x64 tile on
- * fp32 MFMA, summed in a fixed order.  partial holds S * (N * M + N) floats of scratch.  Device pointers, caller's stream.
+ * fp32 MFMA, summed in a fixed order; db's column sums are carried in fp64 and rounded to fp32 once per plane and once at the end.  partial holds S * (N * M + N) floats of scratch.  Device pointers, caller's stream.
  * The chunk height is ceil(K / S) rounded up to an even number, so only Sused = ceil(K / chunk) <= S planes are written and summed
  * (Sused < S whenever S > K / 2) - but the column-sum planes start at partial + S * N * M, so the scratch must have room for all S planes
  * whatever Sused is.  Refused with PGTT_E_ARG, nothing written: a NULL pointer, K, M, N or S <= 0. */

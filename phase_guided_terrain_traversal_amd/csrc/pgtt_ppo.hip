@@ -94,6 +94,8 @@ extern "C" int pgtt_ppo_policy_loss(const float* out_Bx2A, const float* u_BxA, c
 // workgroups (34 us whatever M x N) and the bias gradient is a second 15 us reduction.  Here K is split over S workgroups per
 // 64x64 output tile (one wave each, 2x2 v_mfma_f32_32x32x2_f32 blocks, exact fp32), the column sums of dY ride along, and a
 // second launch adds the S partial planes in a fixed order (deterministic; no atomics).
+// The column sums are carried in fp64 and rounded once per plane and once at the end: db of a narrow head (N = 1: the value net's last bias) is ONE
+// number summed from K terms of both signs, and an fp32 chain over them costs a few ulp times its condition number.
 namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -108,7 +110,7 @@ __global__ __launch_bounds__(64) void linear_bwd_partial_kernel(const float* __r
   const float fna = na < N ? 1.f : 0.f, fnb = nb < N ? 1.f : 0.f, fma_ = ma < M ? 1.f : 0.f, fmb = mb < M ? 1.f : 0.f;
   const int cna = na < N ? na : N - 1, cnb = nb < N ? nb : N - 1, cma = ma < M ? ma : M - 1, cmb = mb < M ? mb : M - 1;
   f32x16 acc00 = {0}, acc01 = {0}, acc10 = {0}, acc11 = {0};
-  float sa = 0.f, sb = 0.f;
+  double sa = 0.0, sb = 0.0;
   // wave-uniform trip count (an MFMA needs both half-waves); eight k-pairs per trip, all 32 operand loads issued before the
   // 32 MFMAs (scheduling fence) so that one memory latency is paid per trip, not per pair
   constexpr int T = 8;
@@ -130,7 +132,7 @@ __global__ __launch_bounds__(64) void linear_bwd_partial_kernel(const float* __r
       acc01 = __builtin_amdgcn_mfma_f32_32x32x2f32(x0, y1, acc01, 0, 0, 0);
       acc10 = __builtin_amdgcn_mfma_f32_32x32x2f32(x1, y0, acc10, 0, 0, 0);
       acc11 = __builtin_amdgcn_mfma_f32_32x32x2f32(x1, y1, acc11, 0, 0, 0);
-      sa += x0; sb += x1;
+      sa += (double)x0; sb += (double)x1;
     }
     __builtin_amdgcn_sched_barrier(0);
   }
@@ -145,7 +147,7 @@ __global__ __launch_bounds__(64) void linear_bwd_partial_kernel(const float* __r
   put(acc00, n0, m0); put(acc01, n0, m0 + 32); put(acc10, n0 + 32, m0); put(acc11, n0 + 32, m0 + 32);
   if (blockIdx.x == 0) {                       // column sums of dY: the two half-waves hold the even / odd rows
     sa += __shfl_xor(sa, 32); sb += __shfl_xor(sb, 32);
-    if (half == 0) { if (na < N) Pb[(long)s * N + na] = sa; if (nb < N) Pb[(long)s * N + nb] = sb; }
+    if (half == 0) { if (na < N) Pb[(long)s * N + na] = (float)sa; if (nb < N) Pb[(long)s * N + nb] = (float)sb; }
   }
 }
 
@@ -165,7 +167,7 @@ __global__ __launch_bounds__(256) void linear_bwd_reduce_kernel(const float* __r
     for (; s < S; s++) v += Pw[(long)s * NM + i];
     dW[i] = v;
   }
-  if (i < N) { float v = 0.f; for (int s = 0; s < S; s++) v += Pb[(long)s * N + i]; db[i] = v; }
+  if (i < N) { double v = 0.0; for (int s = 0; s < S; s++) v += (double)Pb[(long)s * N + i]; db[i] = (float)v; }
 }
 
 }  // namespace

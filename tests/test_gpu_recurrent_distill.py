@@ -15,6 +15,7 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import recurrent_policy_reference as rref  # noqa: E402
+import recurrent_update_cases as cases  # noqa: E402
 
 from phase_guided_terrain_traversal_amd import configs, distill, learn  # noqa: E402
 from phase_guided_terrain_traversal_amd.policy import PolicyMLP, _DIR as POLICY_DIR  # noqa: E402
@@ -75,22 +76,33 @@ def _kl_torch(head, labels):
     return (torch.log(ss / st) + 0.5 * ((st * st + d * d) / (ss * ss) - 1.0)).sum(-1).mean()
 
 
-def test_update_gradients_against_fp64_and_the_op_form():
-    """one update over T = 3 steps of 5 envs (R = 16, the full trunk), a clear at t = 1 in two of them: the loss within 2e-5 of fp64, every tensor's
+@pytest.mark.parametrize("case", cases.IDS)
+def test_update_gradients_against_fp64_and_the_op_form(case, monkeypatch):
+    """one update at each shape of recurrent_update_cases.py (the full trunk; "small" is T = 3 steps of 5 envs, R = 16, a clear at t = 1 in two of
+    them; "shipped" is 51 envs x 20 steps at R = 64, where the split-K factors are those of a real run): the loss within 2e-5 of fp64, every tensor's
     gradient in relative L2 against fp64 next to the torch-autograd fp32 form of the same update; the native error is at most 4 times the op form's
-    per tensor (the margin of DESIGN.md 17 and 23)"""
-    T, N, B, R = 3, 9, 5, 16
+    per tensor (the margin of DESIGN.md 17 and 23).  In "one_step" m0 is zero everywhere: W_hh's gradient is exactly 0 in fp64 and on the device, and
+    that one tensor has no relative error to compare."""
+    monkeypatch.delenv("PGTT_PPO_SPLITK", raising=False)
+    T, N, B, R, env_list, clears = cases.minibatch(case)
     pi = _policy(21, R)
-    envs = torch.tensor([7, 0, 3, 8, 2], device="cuda")
-    stores = _stores(pi, 21, T, N, clears=[(1, 0), (1, 8), (2, 4)])               # envs 0 and 8 are in the minibatch, env 4 is not
+    envs = torch.tensor(env_list, device="cuda")
+    stores = _stores(pi, 21, T, N, clears=clears)
     obs, labels, mem0, clear = stores
     op = copy.deepcopy(pi)
     before = [p.detach().clone() for p in pi.tensors()]
     learner, flat = _learner(pi, stores, B, lr=0.0, use_graph=False)
+    cases.check_split_k(case, learner.S)
     loss2 = learner.update(envs).clone()
     torch.cuda.synchronize()
     ob, lb, mb, cb = obs[:, envs], labels[:, envs], mem0[0, envs], clear[:, envs]
-    assert int(cb.sum()) == 2 and int(cb[1].sum()) == 2
+    assert int(cb.sum()) == cases.clears_inside(env_list, clears) and int(clear.sum()) == len(set(clears))
+    if case == "small":
+        assert int(cb.sum()) == 2 and int(cb[1].sum()) == 2
+    if case in ("shipped", "wide"):
+        assert int(cb[0].sum()) == 2 and int(cb[T - 1].sum()) == 2 and int(cb.all(0).sum()) == 1 and int(clear.sum()) > int(cb.sum())
+    if case in ("one_step", "cut"):
+        assert bool(cb[T - 1].all()) and int(cb.sum()) == B
     want = rref.update(_P(op), ob, mb, cb, lb)
     heads = op.sequence(ob, mb, cb)
     op_loss = _kl_torch(heads.reshape(T * B, 24), lb.reshape(T * B, 24))
@@ -102,8 +114,12 @@ def test_update_gradients_against_fp64_and_the_op_form():
     own = float(rref.f64(flat.grad).norm())
     assert abs(float(learner.norm) - own) <= (flat.numel / 64 + 70) * rref.U32 * own and abs(own - want["grad_norm"]) <= 1e-4 * own
     bad = []
-    print("sequence update, 3 steps x 5 envs: gradient error against fp64, relative L2")
+    print(f"sequence update [{case}], {T} steps x {B} envs, R = {R}, S = {learner.S}: gradient error against fp64, relative L2")
     for name, p, g64, gop in zip(NAMES, pi.tensors(), want["grads"], op_grads):
+        if case == "one_step" and name == "gru_w_hh":                              # m0 = 0 in every row: exactly zero on both sides, no ratio
+            assert bool((g64 == 0).all()) and bool((flat.grad_of(p) == 0).all())
+            print(f"  {name:9s}: exactly 0 in fp64 and on the device")
+            continue
         e_na = float((rref.f64(flat.grad_of(p)) - g64).norm() / g64.norm())
         e_op = float((rref.f64(gop) - g64).norm() / g64.norm())
         print(f"  {name:9s}: op form {e_op:.2e}   native {e_na:.2e}   native / op {e_na / max(e_op, 1e-300):.2f}")
@@ -160,6 +176,31 @@ def test_graph_replay_gives_the_bits_of_eager_calls():
         for x, y in zip(a, b):
             assert torch.equal(x, y), k
     assert not torch.equal(runs[0][0][2], runs[0][4][2]) and all(bool(torch.isfinite(x).all()) for rec in runs[0] for x in rec)
+
+
+def test_graph_replay_gives_the_bits_of_eager_calls_at_the_shipped_shape(monkeypatch):
+    """the same at 51 envs x 20 steps, R = 64 - 24 + 5 T = 124 launches in one graph, the split-K factors of a real run - over four updates on
+    changing minibatches, captured at the third: loss, gradient, norm and parameters have equal bits"""
+    monkeypatch.delenv("PGTT_PPO_SPLITK", raising=False)
+    T, N, B, R, _, clears = cases.minibatch("shipped")
+    runs = []
+    for use_graph in (True, False):
+        pi = _policy(24, R)
+        stores = _stores(pi, 24, T, N, noise=(0.3, 0.5), clears=clears)
+        learner, flat = _learner(pi, stores, B, lr=1e-3, use_graph=use_graph)
+        cases.check_split_k("shipped", learner.S)
+        perm = torch.randperm(N, device="cuda", generator=torch.Generator(device="cuda").manual_seed(3))
+        rec = []
+        for k in range(4):
+            l2 = learner.update(perm.roll(7 * k)[:B]).clone()
+            torch.cuda.synchronize()
+            rec.append((l2, flat.grad.clone(), flat.flat.clone(), learner.norm.clone()))
+        assert (learner.graph is not None) == use_graph and flat.t.tolist() == [4]
+        runs.append(rec)
+    for k, (a, b) in enumerate(zip(*runs)):
+        for x, y in zip(a, b):
+            assert torch.equal(x, y), k
+    assert not torch.equal(runs[0][0][2], runs[0][3][2]) and all(bool(torch.isfinite(x).all()) for rec in runs[0] for x in rec)
 
 
 # ------------------------------------------------------------------ a task only a memory can solve

@@ -1,6 +1,7 @@
 """The recurrent policy's entries of libpgtt_learn.so through the bare C ABI (include/pgtt_learn.h): the point-wise GRU cell forward and backward,
 the clear, the add, and pgtt_learn_recurrent_act, against the fp64 statement in tests/recurrent_policy_reference.py.  Every output is a view into
-a larger allocation of sentinels at an odd float offset, as in test_gpu_learn_kernels.py.
+a larger allocation of sentinels at an odd float offset, as in test_gpu_learn_kernels.py.  The acting step runs at every trip count of its tile loop
+(R = 16, 32, 48, 64, 80, 256) on policy177's trunk and, through the bare ABI, on three small trunks (ACT_CASES).
 
 The bars, first order in u = 2^-24, none fitted to the kernel.  expf is taken at 2 ulp = 4 u, every other operation at u; TINY = 2^-126 is added where
 an expf result can be denormal (its relative accuracy is lost there).  A bar X_bar is an absolute bound of |X - X64|.
@@ -266,18 +267,33 @@ def test_add_rows_and_the_refusals_of_the_pieces():
 
 # ------------------------------------------------------------------ pgtt_learn_recurrent_act
 OD, DIMS = 171, (171, 512, 256, 128, 24)
+TRUNK = DIMS[:4]                                                                    # (od, h1, h2, h3) of policy177
+SMALL = [((5, 16, 16, 16), 16, 17), ((171, 64, 32, 48), 80, 33), ((20, 32, 48, 144), 256, 17)]       # (od, h1, h2, h3), R, N: one kb trip; h3 no power of two
 _CACHE = {}
 
 
-def _policy(R):
-    """policy177's layers, seeded GRU tensors, a non-zero W_m; built once per R"""
-    if R not in _CACHE:
-        pi = RecurrentPolicy.from_teacher(PolicyMLP(os.path.join(POLICY_DIR, "policy177.npz")), R, seed=7)
-        with torch.no_grad():
-            pi.mem_w.copy_(torch.randn(24, R, generator=torch.Generator().manual_seed(R)) * 0.2)
+def _policy(R, trunk=TRUNK):
+    """policy177's layers, seeded GRU tensors, a non-zero W_m; for another trunk (od, h1, h2, h3) a seeded RecurrentPolicy as
+    test_gpu_recurrent_distill._policy builds it, with statistics away from (0, 1); built once per (R, trunk)"""
+    trunk = tuple(trunk)
+    if (R, trunk) not in _CACHE:
+        if trunk == TRUNK:
+            pi = RecurrentPolicy.from_teacher(PolicyMLP(os.path.join(POLICY_DIR, "policy177.npz")), R, seed=7)
+            with torch.no_grad():
+                pi.mem_w.copy_(torch.randn(24, R, generator=torch.Generator().manual_seed(R)) * 0.2)
+        else:
+            with torch.random.fork_rng(devices=[]):
+                torch.manual_seed(1000 * R + sum(trunk))
+                pi = RecurrentPolicy(trunk + (24,), R)
+                cell = torch.nn.GRUCell(trunk[3], R)
+                with torch.no_grad():
+                    pi.gru_w_ih.copy_(cell.weight_ih); pi.gru_w_hh.copy_(cell.weight_hh); pi.gru_b_ih.copy_(cell.bias_ih); pi.gru_b_hh.copy_(cell.bias_hh)
+                    pi.mem_w.copy_(torch.randn(24, R) * 0.3)
+                    pi.layers[3].weight.mul_(3.0); pi.layers[3].bias.add_(torch.randn(24) * 0.3)
+                    pi.mean.copy_(torch.randn(trunk[0]) * 2 + 0.5); pi.std.copy_(torch.rand(trunk[0]) * 2 + 0.1)
         pi.requires_grad_(False)
-        _CACHE[R] = pi
-    return _CACHE[R]
+        _CACHE[(R, trunk)] = pi
+    return _CACHE[(R, trunk)]
 
 
 def _P(pi):
@@ -287,15 +303,17 @@ def _P(pi):
 
 def _inputs(pi, N, seed):
     g = torch.Generator().manual_seed(seed)
-    obs = (pi.mean + pi.std * torch.randn(N, OD, generator=g)).contiguous()
+    obs = (pi.mean + pi.std * torch.randn(N, pi.dims[0], generator=g)).contiguous()
     return obs, torch.randn(N, pi.memory, generator=g).contiguous()
 
 
 class Act:
-    """one call of pgtt_learn_recurrent_act with guarded outputs; the weights live on the device once per policy"""
+    """one call of pgtt_learn_recurrent_act with guarded outputs; the weights live on the device once per policy.  The trunk (od, h1, h2, h3) is the
+    policy's: the scratch is sized for it by pgtt_learn_recurrent_act_work_floats and sits between guard bands like every output"""
 
     def __init__(self, pi, N, T=3, head=True, stores=True):
         R = pi.memory
+        OD, H1, H2, H3 = self.trunk = tuple(pi.dims[:4])
         self.pi, self.N, self.R, self.T = pi, N, R, T
         self.dev = {k: (v.cuda().contiguous() if torch.is_tensor(v) else [t.cuda().contiguous() for t in v]) for k, v in _P(pi).items()}
         self.mem, self.action = Guarded(N, R), Guarded(N, 12, front=21, back=17)
@@ -303,7 +321,16 @@ class Act:
         self.s_obs = Guarded(T, N, OD) if stores else None
         self.s_mem0 = Guarded(T, N, R, front=21, back=17) if stores else None
         self.s_clear = Guarded(T, N, dtype=torch.uint8, fill=7, front=5, back=3) if stores else None
-        self.work = torch.zeros(int(learn.lib().pgtt_learn_recurrent_act_work_floats(N, OD, 512, 256, 128)), device="cuda")
+        floats = int(learn.lib().pgtt_learn_recurrent_act_work_floats(N, OD, H1, H2, H3))
+        assert floats == N * (OD + H1 + H2 + H3 + max(H1, H2, H3))                    # x, h1, h2, h3 in this order, then the pre-activations
+        self.work_guarded = Guarded(floats, front=20, back=23)                         # 80 bytes in front: the scratch keeps torch's 16-byte alignment
+        self.work = self.work_guarded.view
+
+    def h3(self):
+        """the trunk's output [N, h3] as the last call left it in the scratch"""
+        OD, H1, H2, H3 = self.trunk
+        lo = self.N * (OD + H1 + H2)
+        return self.work[lo:lo + self.N * H3].view(self.N, H3)
 
     def args(self, obs, t=0, clear_all=0, clear_mask=None, done=None, use_done=0):
         a, d = PgttLearnRecurrentActArgs(), self.dev
@@ -314,7 +341,8 @@ class Act:
         a.done, a.clear_mask = _p(done), _p(clear_mask)
         a.mem, a.action, a.head, a.work = self.mem.ptr(), self.action.ptr(), _p(self.head), self.work.data_ptr()
         a.store_obs, a.store_mem0, a.store_clear = _p(self.s_obs), _p(self.s_mem0), _p(self.s_clear)
-        a.num_envs, a.obs_dim, a.h1, a.h2, a.h3, a.memory = self.N, OD, 512, 256, 128, self.R
+        a.num_envs, a.memory = self.N, self.R
+        a.obs_dim, a.h1, a.h2, a.h3 = self.trunk
         a.t, a.store_rows, a.clear_all, a.use_done = t, self.T, clear_all, use_done
         return a
 
@@ -365,24 +393,32 @@ def _act_bars(pi, obs, mem, clear, h3=None):
     return s, {"head": head_bar, "action": act_bar, "mem": mem_bar}
 
 
-@pytest.mark.parametrize("R", [16, 64])
-@pytest.mark.parametrize("N", [1, 15, 16, 17, 65])
-def test_recurrent_act_against_fp64(N, R):
-    pi = _policy(R)
+# The tail walks the memory tiles with ct = wave, wave + 4, .. < R / 16.  R = 16: wave 0 alone; 32, 48: whole waves reach the barrier without a tile;
+# 64: one tile per wave; 80: wave 0 makes a second trip, the others one; 256: four trips per wave and the largest LDS (33,280 bytes dynamic).
+# The first ten ids are the cases this test had before the others were added.
+ACT_CASES = [pytest.param(N, R, TRUNK, id=f"{N}-{R}") for R in (16, 64) for N in (1, 15, 16, 17, 65)]
+ACT_CASES += [pytest.param(N, R, TRUNK, id=f"{N}-{R}") for R, N in ((32, 17), (48, 1), (48, 33), (80, 17), (80, 33), (256, 1), (256, 17), (256, 33))]
+ACT_CASES += [pytest.param(N, R, trunk, id=f"{N}-{R}-" + "x".join(str(d) for d in trunk)) for trunk, R, N in SMALL]
+
+
+@pytest.mark.parametrize("N,R,trunk", ACT_CASES)
+def test_recurrent_act_against_fp64(N, R, trunk):
+    pi = _policy(R, trunk)
+    assert tuple(pi.dims[:4]) == tuple(trunk) and pi.memory == R
     obs, mem = _inputs(pi, N, 10 * N + R)
     clear = torch.zeros(N, dtype=torch.bool)
     clear[N // 2] = True
     a = Act(pi, N).run(obs, mem, t=1, clear_mask=clear.to(torch.uint8))
-    assert a.mem.written() and a.action.written() and a.head.written()
+    assert a.mem.written() and a.action.written() and a.head.written() and a.work_guarded.guards_intact()
     want, bars = _act_bars(pi, obs, mem, clear)
     worst = {k: float(((getattr(a, k).f64() - want[k]).abs() / bars[k]).max()) for k in ("head", "action", "mem")}
-    print(f"recurrent act N={N} R={R}: worst / bar " + "  ".join(f"{k} {v:.2e}" for k, v in worst.items()))
+    print(f"recurrent act N={N} R={R} trunk={trunk}: worst / bar " + "  ".join(f"{k} {v:.2e}" for k, v in worst.items()))
     assert all(v <= 1.0 for v in worst.values()), worst
     # the new kernel alone: from the h3 the trunk left in `work` (x, h1, h2, h3 in this order), taken as exact
-    h3 = a.work[N * (OD + 512 + 256):N * (OD + 512 + 256 + 128)].view(N, 128)
+    h3 = a.h3()
     want3, bars3 = _act_bars(pi, obs, mem, clear, h3=h3)
     worst3 = {k: float(((getattr(a, k).f64() - want3[k]).abs() / bars3[k]).max()) for k in ("head", "action", "mem")}
-    print(f"recurrent act N={N} R={R} from the kernel's h3: worst / bar " + "  ".join(f"{k} {v:.2e}" for k, v in worst3.items()))
+    print(f"recurrent act N={N} R={R} trunk={trunk} from the kernel's h3: worst / bar " + "  ".join(f"{k} {v:.2e}" for k, v in worst3.items()))
     assert all(v <= 1.0 for v in worst3.values()), worst3
     # the stored rows: row t = 1 holds the inputs' bits, rows 0 and 2 and every guard band are untouched
     od = obs.cuda()
@@ -401,7 +437,7 @@ def test_recurrent_act_against_fp64(N, R):
     assert torch.equal(b.mem.view, first[0]) and torch.equal(b.action.view, first[1]) and b.action.guards_intact() and b.mem.guards_intact()
 
 
-@pytest.mark.parametrize("R", [16, 64])
+@pytest.mark.parametrize("R", [16, 64, 80, 256])
 def test_recurrent_act_rows_do_not_depend_on_the_batch(R):
     pi = _policy(R)
     obs, mem = _inputs(pi, 65, 3 + R)
@@ -422,7 +458,12 @@ def test_recurrent_act_rows_do_not_depend_on_the_batch(R):
 
 
 def test_recurrent_act_clears_exactly_the_envs_named():
-    pi = _policy(16)
+    for R in (16, 80):                                                              # one tile in wave 0; unequal trip counts among the waves
+        _clears_exactly_the_envs_named(R)
+
+
+def _clears_exactly_the_envs_named(R):
+    pi = _policy(R)
     N = 33
     obs, mem = _inputs(pi, N, 77)
     named = torch.zeros(N, dtype=torch.bool); named[[0, 7, 16, 32]] = True
@@ -440,9 +481,9 @@ def test_recurrent_act_clears_exactly_the_envs_named():
     for name, kw, mem_in, want, flags in cases:
         a = Act(pi, N).run(obs, mem_in, t=0, **kw)
         for k in ("mem", "action", "head"):
-            assert torch.equal(getattr(a, k).view, getattr(want, k).view), (name, k)
-        assert torch.equal(a.s_clear.view[0].cpu(), flags), name
-        assert bool((a.s_mem0.view[0][flags.bool().cuda()] == 0).all()), name
+            assert torch.equal(getattr(a, k).view, getattr(want, k).view), (R, name, k)
+        assert torch.equal(a.s_clear.view[0].cpu(), flags), (R, name)
+        assert bool((a.s_mem0.view[0][flags.bool().cuda()] == 0).all()), (R, name)
 
 
 def test_recurrent_act_refusals():

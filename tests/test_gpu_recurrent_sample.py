@@ -119,8 +119,13 @@ OLD = ("mem", "action", "head", "s_obs", "s_mem0", "s_clear")
 
 
 # ------------------------------------------------------------------ against the old entry, and a given eps against fp64
-@pytest.mark.parametrize("R", [16, 64])
-@pytest.mark.parametrize("N", [1, 15, 16, 17, 33])
+# The sampled tail is an instantiation of its own with 2304 bytes of static LDS in front of the dynamic memory tiles: R = 48 leaves a wave without a tile
+# before the barrier, 80 gives the waves unequal trip counts, 256 is four trips per wave and the largest LDS.  The first ten ids are the earlier cases.
+SAMPLED_CASES = [pytest.param(N, R, id=f"{N}-{R}") for R in (16, 64) for N in (1, 15, 16, 17, 33)]
+SAMPLED_CASES += [pytest.param(N, R, id=f"{N}-{R}") for R in (48, 80, 256) for N in (1, 17, 33)]
+
+
+@pytest.mark.parametrize("N,R", SAMPLED_CASES)
 def test_sampled_step_against_the_old_entry_and_fp64(N, R):
     pi = rk._policy(R)
     obs, mem = rk._inputs(pi, N, 10 * N + R)
@@ -271,9 +276,9 @@ def test_draws_depend_on_seed_global_id_and_draw_only():
 
 
 # ------------------------------------------------------------------ stores
-@pytest.mark.parametrize("N", [1, 17])
-def test_stores_land_in_their_row_only(N):
-    pi = rk._policy(16)
+@pytest.mark.parametrize("N,R", [pytest.param(1, 16, id="1"), pytest.param(17, 16, id="17"), pytest.param(1, 256, id="1-256"), pytest.param(17, 256, id="17-256")])
+def test_stores_land_in_their_row_only(N, R):
+    pi = rk._policy(R)
     obs, mem = rk._inputs(pi, N, 40 + N)
     eps = _eps(N, 1)
     first = None

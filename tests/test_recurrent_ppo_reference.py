@@ -115,6 +115,65 @@ def test_gradients_are_the_central_differences_of_the_total_loss():
             assert abs(fd - float(gf[k])) <= 1e-6 * scale, (name, k, fd, float(gf[k]))
 
 
+# the shapes at which the GPU tests lean on this reference: a long unroll at the largest memory, no recurrence at all, a cut at the last step
+SHAPES = {"T20_B7_R256": (20, 7, 256), "T1_all_cleared": (1, 6, 48), "T2_all_cleared_at_1": (2, 5, 80)}
+
+
+def _shape_clears(shape, T, B):
+    if shape == "T20_B7_R256":                                                         # at t = 0, in the last row, at every step of one env, the rest never
+        return [(0, 0), (T - 1, 1)] + [(t, 2) for t in range(T)]
+    return [(0 if shape == "T1_all_cleared" else 1, e) for e in range(B)]
+
+
+@pytest.mark.parametrize("shape", list(SHAPES))
+def test_update_is_the_hand_written_bptt_at_the_shapes_the_gpu_tests_use(shape):
+    """update()'s gradients are autograd's through rref.sequence; rref.bptt is the recurrence by hand.  Fed update()'s own d total / d heads, the two agree
+    on the thirteen policy tensors to the 1e-9 that test_recurrent_policy_reference.py asks of bptt, and the heads to 1e-12."""
+    T, B, R_ = SHAPES[shape]
+    dims = (11, 16, 16, 16, 24)
+    P, V = _params(dims, R_, 21), _value(PD, (8, 8, 8), 22)
+    mb = _minibatch(P, T, B, R_, PD, 23, clears=_shape_clears(shape, T, B))
+    out = ref.update(P, V, mb)
+    by_hand = rref.bptt(P, mb["obs"], mb["m_init"], mb["clear"], out["dhead"].reshape(T, B, 24))
+    assert float((by_hand["heads"].reshape(T * B, 24) - out["heads"]).abs().max()) <= 1e-12
+    for name, a, g in zip(ref.POLICY_NAMES, rref.flat_grads(by_hand), out["grads"][:13]):
+        assert a.shape == g.shape and float((a - g).norm()) <= 1e-9 * float(g.norm()), name
+        if shape == "T1_all_cleared" and name == "w_hh":                                # m0 = 0 in every row: exactly zero, by hand and by autograd
+            assert bool((a == 0).all()) and bool((g == 0).all())
+        else:
+            assert float(g.norm()) > 1e-4, name
+    assert all(float(g.norm()) > 1e-4 for g in out["grads"][13:]) and len(out["grads"]) == 21
+
+
+@pytest.mark.parametrize("shape", ["T1_all_cleared", "T2_all_cleared_at_1"])
+def test_gradients_are_the_central_differences_where_every_env_is_cleared(shape):
+    """the check of test_gradients_are_the_central_differences_of_the_total_loss, 10 seeded entries per tensor, at the two shapes with an all-cleared step;
+    W_hh at T = 1 has a zero gradient and a zero difference"""
+    T, B, R_ = SHAPES[shape]
+    P, V = _params(DIMS, R_, 31), _value(PD, (8, 8, 8), 32)
+    mb = _minibatch(P, T, B, R_, PD, 33, clears=_shape_clears(shape, T, B))
+    out = ref.update(P, V, mb)
+    assert float(torch.minimum((out["ratio"] - 0.7).abs(), (out["ratio"] - 1.3).abs()).min()) > 1e-3
+    tensors = ref.policy_tensors(P) + [t for wb in V for t in wb]
+
+    def total():
+        return float(ref.losses(ref.with_tensors(P, tensors[:13]), [(tensors[13 + 2 * i], tensors[14 + 2 * i]) for i in range(4)], mb)["total"])
+    h = 1e-5
+    gen = torch.Generator().manual_seed(34)
+    for name, t, g in zip(ref.POLICY_NAMES + ref.VALUE_NAMES, tensors, out["grads"]):
+        flat, gf = t.view(-1), g.reshape(-1)
+        scale = float(gf.abs().max())
+        assert (scale == 0) == (shape == "T1_all_cleared" and name == "w_hh"), name
+        for k in torch.randint(0, flat.numel(), (10,), generator=gen).tolist():
+            keep = float(flat[k])
+            flat[k] = keep + h
+            up = total()
+            flat[k] = keep - h
+            down = total()
+            flat[k] = keep
+            assert abs((up - down) / (2 * h) - float(gf[k])) <= 1e-6 * scale, (name, k)
+
+
 def test_a_cleared_step_cuts_the_gradient_to_earlier_steps_exactly():
     P = _params(DIMS, R, 11)
     mb = _minibatch(P, 3, 4, R, PD, 12, clears=[(2, 1), (1, 3)])
