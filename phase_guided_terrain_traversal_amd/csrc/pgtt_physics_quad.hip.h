@@ -1675,22 +1675,49 @@ struct QSolver {
     LSPoint p0, lo0;
     { const float a0 = 0.f; ls_points<1>(&a0, jv_lim, jv0, qg0, qg1, qg2, &p0); }
     { const float a1 = p0.alpha - div_normal(p0.d0, p0.d1); ls_points<1, false>(&a1, jv_lim, jv0, qg0, qg1, qg2, &lo0); }
-    bool lesser = lo0.d0 < p0.d0;
-    LSPoint hi = lesser ? p0 : lo0, lo = lesser ? lo0 : p0;
-    bool swap = true; int it = 0;
-    for (;;) {
-      bool done = it >= m->ls_iterations || !swap || ((lo.d0 < 0.f) && (lo.d0 > -gtol)) || ((hi.d0 > 0.f) && (hi.d0 < gtol));
-      if (__ballot(!done) == 0ull) break;
-      const float al3[3] = {lo.alpha - div_normal(lo.d0, lo.d1), hi.alpha - div_normal(hi.d0, hi.d1), 0.5f * (lo.alpha + hi.alpha)};
+    const bool lesser = lo0.d0 < p0.d0;
+    // The two bracket ends go through the same code on mirrored inputs (Newton step, tighten, tolerance test), and all lanes of an env would
+    // run both with identical operands.  Each lane of a PAIR (lane, lane ^ 1: one env in every layout - the sub-lane bit in hex and oct, leg
+    // bit 0 in quad) carries ONE end instead: role 0 `lo`, role 1 `hi`, and the pair trades what the other half needs by quad_perm [1,0,3,2].
+    // What enters the row sums (al3) and what leaves the search (lo / hi.alpha) is replicated again first: a role-held value never meets a
+    // butterfly or a store.  Selects only, every exchange with all 64 lanes active.
+    const bool role = (threadIdx.x & 1) != 0;
+    const float rsign = role ? 1.0f : -1.0f;
+    LSPoint own = role == lesser ? p0 : lo0;         // hi = lesser ? p0 : lo0, lo = lesser ? lo0 : p0
+    // Exit test of the own end on d0 * rsign (exact): `lo.d0 < 0 && lo.d0 > -gtol` is `0 < -lo.d0 < gtol`, the `hi` test on the negated value.
+    // One number per lane - 4: within tolerance, 1: the end moved, 0: neither - OR-ed with the partner's is 1 exactly while the env goes on:
+    // done = cap || !swap || tol with swap = (v & 1), tol = (v & 4).  A lane in tolerance does not report its move: the env is done either way,
+    // moves nothing from then on (threshold 0) and keeps its d0, so it stays done as it does through !swap.
+    auto vote = [&](bool moved) {
+      const float t = own.d0 * rsign;
+      const bool tol = (t > 0.f) & (t < gtol);
+      const int v = tol ? 4 : (moved ? 1 : 0);
+      return v | dpp_i<0xB1>(v);
+    };
+    int v = vote(true);
+    // the cap is the model's, the same in every lane (`it >= ls_iterations` finishes every env of the wave at once): read into an SGPR once, it bounds
+    // the loop instead of entering every lane's `done`; the ballot takes the compare's mask as it is (no 0 / 1 value and a second compare in between)
+    // (oct keeps the per-lane form of the cap: with the scalar loop its two DR + terrain kernels, at 256 + 256 registers, spill 8 B per lane)
+    const int cap = kSubs == 2 ? 0 : __builtin_amdgcn_readfirstlane(m->ls_iterations);
+    for (int it = 0; kSubs == 2 || it < cap; it++) {
+      const bool done = (kSubs == 2 && it >= m->ls_iterations) | (v != 1);
+      if (__builtin_amdgcn_ballot_w64(!done) == 0ull) break;
+      const float st = own.alpha - div_normal(own.d0, own.d1), st_p = dpp_f<0xB1>(st), al_p = dpp_f<0xB1>(own.alpha);
+      // the replicated trial steps, in the order they always had: {lo's Newton step, hi's Newton step, midpoint (a + b = b + a, same bits)}
+      const float al3[3] = {role ? st_p : st, role ? st : st_p, 0.5f * (own.alpha + al_p)};
       LSPoint pt[3];
       ls_points<3, false>(al3, jv_lim, jv0, qg0, qg1, qg2, pt);
-      bool ml, mh;
-      lo = tighten(lo, pt[0], pt[2], pt[1], done, ml);
-      hi = tighten(hi, pt[1], pt[2], pt[0], done, mh);
-      // a finished env moves nothing, so swap turns false and keeps it finished (`done` is sticky through !swap); its count may run on
-      swap = ml | mh; it++;
+      // candidates in the order of both ends: the point of the own step, the midpoint, the point of the partner's step
+      const LSPoint mine_pt = role ? pt[1] : pt[0], other_pt = role ? pt[0] : pt[1];
+      bool moved;
+      own = tighten(own, mine_pt, pt[2], other_pt, done, moved);
+      // a finished env moves nothing (threshold 0), so its vote is never 1 again: `done` is sticky
+      v = vote(moved);
     }
-    {   // costs of the two points the bracket ended with
+    LSPoint lo, hi;
+    {   // both ends' alpha in every lane again (also when no round ran), then the costs of the two points the bracket ended with
+      const float al_p = dpp_f<0xB1>(own.alpha);
+      lo.alpha = role ? al_p : own.alpha; hi.alpha = role ? own.alpha : al_p;
       const float al2[2] = {lo.alpha, hi.alpha};
       LSPoint fin[2];
       ls_points<2, true>(al2, jv_lim, jv0, qg0, qg1, qg2, fin);
