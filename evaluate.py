@@ -14,7 +14,8 @@ is built.  The policy comes from `--checkpoint_folder` (the newest `<env_steps>.
 whose scan rows the student perception module estimated from the onboard depth image, with `--elevation [grid,res,alpha]` on the observation whose
 scan rows are sampled from the depth-fused elevation map (elevation.py; nothing to train; `--elevation_source lidar` fuses it from the onboard
 LiDAR's points instead, lidar.py; `--elevation_fill [K]` closes the map's holes first and the policy acts on the filled scan; `--sensor_every M`
-runs that sensor at one control step in M and lets the map follow it; `--elevation_variance [sigma0,sigma_rel,process,gate,band]` fuses the map by
+runs that sensor at one control step in M and lets the map follow it; `--odometry_drift [sigma_xy,sigma_z,sigma_yaw,yaw_bias,scale]` registers the map
+with a dead-reckoned pose that drifts, and adds a line with the drift at the end; `--elevation_variance [sigma0,sigma_rel,process,gate,band]` fuses the map by
 the variance-weighted update; `--sensor_noise SIGMA[,DROPOUT]` gives the sensor that feeds the map or the student range noise); a `--policy` file that holds a recurrent policy
 (train_distill.py --memory, recurrent_policy.py) is stepped with a memory per env, cleared where the previous step ended an episode; the remaining flags of the reference's CLI are accepted and ignored.
 """
@@ -148,6 +149,8 @@ def sensor_kwargs(args):
         raise SystemExit("--sensor_noise is the noise of the sensor that feeds --elevation's map or --student: give one of them too")
     if getattr(args, "elevation_variance", None) is not None and elev is None:
         raise SystemExit("--elevation_variance says how --elevation's map is fused: give --elevation too")
+    if getattr(args, "odometry_drift", None) is not None and elev is None:
+        raise SystemExit("--odometry_drift is the drift of the pose --elevation's map is registered with: give --elevation too")
     if elev is not None:
         # --elevation [grid,res,alpha]: the policy acts on env.elevation_obs - the observation whose scan rows are sampled from the elevation map
         # fused from the onboard depth image (the camera of depth.DEFAULTS; elevation.DEFAULTS where a value is not given)
@@ -183,6 +186,11 @@ def sensor_kwargs(args):
             if every > 1:
                 raise SystemExit("--elevation_variance behind a slower sensor (--sensor_every > 1) is not built yet")
             given = dict({} if given is True else given, variance=variance)
+        drift = odometry_drift(getattr(args, "odometry_drift", None))
+        if drift is not None:
+            # --odometry_drift [sigma_xy,sigma_z,sigma_yaw,yaw_bias,scale]: the map is registered with a dead-reckoned pose that drifts
+            # (elevation.ODOMETRY_DEFAULTS where a value is not given) instead of the simulator's exact one
+            given = dict({} if given is True else given, odometry=drift)
         if source == "lidar":
             # --elevation_source lidar: the map is fused from the world points of the onboard LiDAR (lidar.DEFAULTS), as the deployed mapping stack's is
             kw.update(lidar=sensor, elevation=dict({} if given is True else given, source="lidar"))
@@ -240,6 +248,7 @@ def run_evaluation(args, num_eval_envs=NUM_EVAL_ENVS, seed=0, verbose=True):
     terms = torch.zeros(abi.NMETRIC, n, device=dev)
     known = torch.zeros(n, device=dev)                                            # with a map: the scan points it knew, summed over the first episode
     covered = torch.zeros(n, device=dev)                                          # with a fill: the scan points it knew or filled
+    drift = torch.zeros(n, 4, device=dev)                                         # with odometry drift: the error when the first episode ended
     video = VideoRecorder(args, env, L) if getattr(args, "video", None) else None
     recurrent = hasattr(pi, "gru_w_ih")
     if recurrent:
@@ -253,6 +262,9 @@ def run_evaluation(args, num_eval_envs=NUM_EVAL_ENVS, seed=0, verbose=True):
             known += env.elevation_known.float().mean(1) * first.float()
         if env.elevation_dist is not None:
             covered += (env.elevation_dist != 255).float().mean(1) * first.float()
+        if env.odometry_error is not None:
+            # the step that ends an episode clears the env's estimate: keep the error as it stood before that step
+            drift = torch.where(first[:, None], env.odometry_error, drift)
         if recurrent:
             action, _, memory = pi.step(acts_on, memory, ended)
             _, reward, done, info = env.step(action)
@@ -273,12 +285,16 @@ def run_evaluation(args, num_eval_envs=NUM_EVAL_ENVS, seed=0, verbose=True):
         out["known_share"] = float((known / length.clamp(min=1)).mean())          # mean share of the 117 scan points the map knew when the policy acted
     if env.elevation_dist is not None:
         out["covered_share"] = float((covered / length.clamp(min=1)).mean())      # ... that the map knew or the fill reached (dist != 255)
+    if env.odometry_error is not None:                                             # at the end of the run: of each env's first episode, before its last step
+        out["odometry_e_xy"], out["odometry_psi"] = float(drift[:, :2].norm(dim=1).mean()), float(drift[:, 3].abs().mean())
     if video is not None:
         out["video"] = video.write(verbose)
     env.close()
     if verbose:                                                                    # training/evaluate.py:212,226
         print(out["episode_reward"])
         print([survivors])
+        if "odometry_e_xy" in out:
+            print(f"odometry drift at the end: mean |e_xy| = {out['odometry_e_xy']:.4f} m, mean |psi| = {out['odometry_psi']:.4f} rad")
     return out
 
 
@@ -315,6 +331,20 @@ def elevation_variance(text):
         raise SystemExit(f"--elevation_variance {text}: the values must be numbers")
 
 
+def odometry_drift(text):
+    """--odometry_drift [sigma_xy,sigma_z,sigma_yaw,yaw_bias,scale] -> None (not given), True (the flag alone) or a dict of the values given"""
+    if text is None:
+        return None
+    vals = [v for v in str(text).split(",") if v]
+    names = ("sigma_xy", "sigma_z", "sigma_yaw", "yaw_bias", "scale")
+    if len(vals) > len(names):
+        raise SystemExit("--odometry_drift takes at most sigma_xy,sigma_z,sigma_yaw,yaw_bias,scale")
+    try:
+        return dict(zip(names, (float(v) for v in vals))) if vals else True
+    except ValueError:
+        raise SystemExit(f"--odometry_drift {text}: the values must be numbers")
+
+
 def fill_passes(text):
     """--elevation_fill K: an integer in [1, 95] (elevation.MAX_FILL); the flag without a value is True, elevation.FILL_PASSES"""
     try:
@@ -337,6 +367,8 @@ def add_sensor_args(ap):
                     help="with --elevation: close the map's holes with K passes (16 unless given) behind every tick; the policy acts on the filled scan")
     ap.add_argument("--elevation_variance", type=str, nargs="?", const="", default=None, metavar="SIGMA0,SIGMA_REL,PROCESS,GATE,BAND",
                     help="with --elevation: fuse the map by the variance-weighted (Kalman) update instead of the maximum and alpha; optional settings")
+    ap.add_argument("--odometry_drift", type=str, nargs="?", const="", default=None, metavar="SIGMA_XY,SIGMA_Z,SIGMA_YAW,YAW_BIAS,SCALE",
+                    help="with --elevation: register the map with a dead-reckoned pose that drifts in x, y, z and yaw, not with the exact one; optional settings")
     ap.add_argument("--sensor_noise", type=str, default=None, metavar="SIGMA[,DROPOUT]",
                     help="with --elevation or --student: relative range noise and dropout probability of the sensor that feeds it")
     ap.add_argument("--sensor_every", type=int, default=1, metavar="M",

@@ -153,6 +153,47 @@
  * pgtt_elevation_fill() is unchanged: it reads `map` as it stands, so it works behind a variance tick; filled cells have no variance.
  * `var` is maintained by these two calls alone, and a caller uses ONE kind of tick on a handle: pgtt_elevation(), pgtt_elevation_points() and
  * pgtt_elevation_follow() on a handle with a variance bound do what they always did and leave `var` stale.
+ *
+ * Odometry drift: the map on an estimated pose.  Everything above registers the image or the points with the simulator's exact base pose.  A robot
+ * dead-reckons its pose from leg odometry and a gyro, and the estimate walks away from the truth in x, y and yaw.  pgtt_elevation_odometry() writes
+ * such an estimate, pose_est [7][N], and - when points are bound - the world points re-registered at it, points_est [N][P][3].  A promise makes them
+ * usable: EVERY entry of this library reads rows PGTT_S_QPOS + 0..6 of `state` (PGTT_S_QPOS is 0) and no other row, so a [7][N] buffer is a legal
+ * `state` for pgtt_elevation_bind, pgtt_elevation_bind_points and all the calls behind them.  The caller binds PgttElevationBuffers.state = pose_est
+ * and points = points_est itself; the odometry call uses the handle for N and the device only and neither reads nor rebinds the handle's buffers.
+ * The model is an error-state dead reckoning, per env, in fp32, in the fixed order below; in the error-state form all-zero settings return the true
+ * pose BY VALUE (x + 0), which a re-integration of increments would not.  The settings (PgttElevationOdometry) are settings, not facts about a robot.
+ * Persistent per env is odo[e][PGTT_ELEVATION_ODO_WORDS = 12]:
+ *     0..2  e_x, e_y, e_z            the position error, metres
+ *     3     psi                      the yaw error, radians, not wrapped
+ *     4..6  prev_x, prev_y, prev_z   the TRUE base position at the last call
+ *     7, 8  scale_e, bias_e          the episode's odometry scale error and gyro bias (rad/s), drawn once per episode
+ *     9..11 reserved, written as 0
+ * With b = rows 0..2 and q = rows 3..6 of the true `state` (q raw, not normalised), gid = env_id_offset + e, c = counter[0] as it stands before the
+ * call, and u_k = the top 24 bits of word k of a Philox block times 2^-24 (the convention of pgtt_depth.h; key = (seed lo, seed hi)):
+ *  Clear.  An env is cleared when clear_all != 0, or clear_mask[e] != 0, or use_done != 0 and done[e] != 0 - the map's own rule; a NULL done clears
+ *     nothing.  e = 0, psi = 0, prev = b; with the block (gid, (uint32) c, PGTT_RS_ODOMETRY, 1):
+ *         scale_e = scale (2 u_0 - 1),   bias_e = yaw_bias (2 u_1 - 1).
+ *     No step is made on this call.
+ *  Step (an env that is not cleared).  D = b - prev, L = sqrtf(Dx^2 + Dy^2 + Dz^2); with the block (gid, (uint32) c, PGTT_RS_ODOMETRY, 0):
+ *         (n_x, n_y)   = sqrtf(-2 logf(1 - u_0)) * (cos, sin)(2 pi u_1),    (n_z, n_psi) the same on (u_2, u_3)
+ *         D'   = (1 + scale_e) D
+ *         e_x += (cos psi D'x - sin psi D'y) - Dx + sigma_xy sqrtf(L) n_x          with the OLD psi
+ *         e_y += (sin psi D'x + cos psi D'y) - Dy + sigma_xy sqrtf(L) n_y
+ *         e_z += (D'z - Dz) + sigma_z sqrtf(L) n_z
+ *         psi += bias_e dt + sigma_yaw sqrtf(dt) n_psi,    prev = b
+ *     Position noise grows with the distance walked (sigma_xy, sigma_z in m / sqrt(m)), yaw noise with time (sigma_yaw in rad / sqrt(s), yaw_bias in
+ *     rad / s).  Roll and pitch stay true: gravity is observable.  The cosine and sine of 2 pi u are taken of the exact product (the half-turn
+ *     forms, on 2 u), so the draw carries no rounding of the angle.
+ *  Outputs.  pose_est[0..2][e] = b + e;  pose_est[3..6][e] = qz(psi) (x) q, the quaternion product with qz(psi) = (cos psi/2, 0, 0, sin psi/2), not
+ *     normalised - the map normalises, as it does for `state`.
+ *  Points.  When points are bound, for every k < P, with p the world point and r = p - b:
+ *         points_est = p + ((Rz(psi) r) - r) + e              with the NEW psi and e
+ *     which is T_est o T_true^-1, written so that zero error returns p by value.  A point with a coordinate that is not finite is written as
+ *     three NaNs.
+ *  counter[0] advances by one per call, in a launch of its own behind the update: no workgroup reads a counter another has advanced.
+ * An env's outputs depend on its own rows and its global id only: the same bits at any batch position, at any N, with or without points.
+ * Not covered: loop closure or any correction of the drift, roll or pitch error, latency between capture and fusion, drift on the
+ * proprioceptive rows of the observation.
  */
 #ifndef PGTT_ELEVATION_H_
 #define PGTT_ELEVATION_H_
@@ -268,6 +309,39 @@ int pgtt_elevation_var(pgtt_elevation_handle h, const uint8_t* clear_mask, int c
 /* the same from the bound points (the source is whichever bind was made last, as for pgtt_elevation_points): PGTT_E_STATE before
  * pgtt_elevation_bind_points or before pgtt_elevation_bind_var. */
 int pgtt_elevation_var_points(pgtt_elevation_handle h, const uint8_t* clear_mask, int clear_all, int use_done, void* stream);
+
+#define PGTT_RS_ODOMETRY 34                      /* Philox stream id of the odometry draws (pgtt.h uses ids below 32, the depth camera 32, the LiDAR 33) */
+#define PGTT_ELEVATION_ODO_WORDS 12              /* floats of persistent odometry state per env */
+
+/* the odometry call's device buffers, caller-owned and sized for N, and its settings (all finite) */
+typedef struct PgttElevationOdometry {
+  const float* state;                    /* the TRUE state: [PGTT_NSTATE][N] (PgttBuffers.state) or any [>= 7][N]; rows 0..6 are read; required */
+  const float* done;                     /* [N] 0 / 1 or NULL: use_done then clears nothing */
+  const float* points;                   /* [N][P][3] world points registered at the true pose, or NULL */
+  float* points_est;                     /* [N][P][3], required with points and NULL without */
+  int32_t P;                             /* >= 1 with points */
+  float* pose_est;                       /* [7][N], required: a legal `state` of every entry of this library */
+  float* odo;                            /* [N][PGTT_ELEVATION_ODO_WORDS], required; the first call clears it (clear_all) */
+  int64_t* counter;                      /* [1], required: the epoch of the draws, advanced by one per call */
+  uint64_t seed;                         /* key of the Philox draws */
+  int64_t env_id_offset;                 /* global id of env 0 */
+  float dt;                              /* seconds between two calls (the control step), > 0 */
+  float sigma_xy, sigma_z;               /* position random walk per sqrt(metre walked), >= 0 */
+  float sigma_yaw;                       /* yaw random walk, rad / sqrt(s), >= 0 */
+  float yaw_bias;                        /* bound of the episode's gyro bias, rad / s, >= 0 */
+  float scale;                           /* bound of the episode's odometry scale error, 0 <= scale < 1 */
+} PgttElevationOdometry;
+
+/* the settings' ranges alone (the pointers and P are not looked at): host only, needs no GPU.  PGTT_E_ARG for NULL or a value outside its range. */
+int pgtt_elevation_check_odometry(const PgttElevationOdometry* o);
+/* PGTT_E_ARG for a NULL struct, a NULL state, pose_est, odo or counter, points without points_est or the other way round, points with P < 1, or
+ * a setting outside its range.  May be called before or after the buffers are bound and persists across later binds, like pgtt_elevation_bind_fill. */
+int pgtt_elevation_bind_odometry(pgtt_elevation_handle h, const PgttElevationOdometry* o);
+/* one odometry update for all N envs, called BEFORE the tick that reads pose_est: two launches on `stream` (the update; the counter), no allocation,
+ * no synchronisation, no read-back, capturable.  Without points one lane per env, with points one workgroup of 256 lanes per env.
+ * PGTT_E_STATE before pgtt_elevation_bind_odometry. */
+int pgtt_elevation_odometry(pgtt_elevation_handle h, const uint8_t* clear_mask, int clear_all, int use_done, void* stream);
+int pgtt_elevation_sizeof_odometry(void);
 int pgtt_elevation_sizeof_var(void);
 int pgtt_elevation_sizeof_fill(void);
 int pgtt_elevation_sizeof_config(void);

@@ -37,6 +37,10 @@
 //            needs 117 of its cells, gathered from global memory.  Lane 0 of each env stages the pose and the window (and writes the origin of a
 //            cleared env); a cleared env's map goes out as NaN in 16-byte runs; the minimum is phase E's wave reduction and LDS exchange; est,
 //            known, obs_out.  No atomics.
+//
+// Odometry drift (pgtt_elevation_odometry): odometry_kernel<POINTS> writes the estimated pose [7][N] the map may be bound to in place of `state`, and
+// with POINTS the world points re-registered at it; odometry_advance_kernel behind it advances the draws' epoch.  Described at the kernel.  It reads
+// and writes nothing of the handle's buffers, and no kernel above knows of it.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -856,6 +860,131 @@ __global__ void __launch_bounds__(kLanes) fill_kernel(FillArgs a) {
   }
 }
 
+// ---------------------------------------------------------------- odometry drift (pgtt_elevation_odometry): the estimated pose the map is bound to
+struct OdoArgs {
+  const float* state; const float* done; const uint8_t* clear_mask; const float* points; float* points_est;
+  float* pose_est; float* odo; const int64_t* counter;
+  int N, P, clear_all, use_done;
+  unsigned k0, k1, gid0;                                       // the Philox key (seed lo, seed hi); (uint32) env_id_offset
+  float dt, sigma_xy, sigma_z, sigma_yaw, yaw_bias, scale;
+};
+
+// Philox4x32-10, the env's generator (pgtt.h); this library's own copy, as pgtt_depth.hip and pgtt_lidar.hip have theirs
+__device__ __forceinline__ void philox4x32_10(unsigned k0, unsigned k1, unsigned& c0, unsigned& c1, unsigned& c2, unsigned& c3) {
+#pragma unroll
+  for (int r = 0; r < 10; r++) {
+    const unsigned h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
+    const unsigned h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
+    const unsigned n0 = h1 ^ c1 ^ k0, n2 = h0 ^ c3 ^ k1;
+    c0 = n0; c1 = l1; c2 = n2; c3 = l0;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+}
+
+// the transform of an env's points, T_est o T_true^-1: the cosine and sine of the new psi, the true base position, the new position error
+enum { T_COS = 0, T_SIN = 1, T_B = 2, T_E = 5, T_N = 8 };
+constexpr int kOdoTile = 3 * kLanes;                           // floats of one tile of points: one point per lane
+
+// env e's update in the header's order: reads its rows of `state` and `odo`, writes `odo` and its column of pose_est, leaves the transform in t
+__device__ __forceinline__ void odo_update(const OdoArgs& a, int e, float* t) {
+  const long N = a.N;
+  const float* S = a.state + e;
+  const float bx = S[(PGTT_S_QPOS + 0) * N], by = S[(PGTT_S_QPOS + 1) * N], bz = S[(PGTT_S_QPOS + 2) * N];
+  const float qw = S[(PGTT_S_QPOS + 3) * N], qx = S[(PGTT_S_QPOS + 4) * N], qy = S[(PGTT_S_QPOS + 5) * N], qz = S[(PGTT_S_QPOS + 6) * N];
+  float* o = a.odo + (size_t)e * PGTT_ELEVATION_ODO_WORDS;
+  const bool clear = a.clear_all || (a.clear_mask && a.clear_mask[e]) || (a.use_done && a.done && a.done[e] != 0.f);
+  unsigned w0 = a.gid0 + (unsigned)e, w1 = (unsigned)a.counter[0], w2 = PGTT_RS_ODOMETRY, w3 = clear ? 1u : 0u;
+  philox4x32_10(a.k0, a.k1, w0, w1, w2, w3);
+  const float k24 = 1.0f / 16777216.0f;
+  const float u0 = (float)(w0 >> 8) * k24, u1 = (float)(w1 >> 8) * k24, u2 = (float)(w2 >> 8) * k24, u3 = (float)(w3 >> 8) * k24;
+  float ex = 0.f, ey = 0.f, ez = 0.f, psi = 0.f, se, be;
+  if (clear) {
+    se = a.scale * (2.f * u0 - 1.f);
+    be = a.yaw_bias * (2.f * u1 - 1.f);
+  } else {
+    ex = o[0]; ey = o[1]; ez = o[2]; psi = o[3]; se = o[7]; be = o[8];
+    const float Dx = bx - o[4], Dy = by - o[5], Dz = bz - o[6];
+    const float sl = sqrtf(sqrtf(Dx * Dx + Dy * Dy + Dz * Dz));
+    // 2 pi u as half turns: 2 u is exact
+    float s01, c01, s23, c23, sp, cp;
+    sincospif(2.f * u1, &s01, &c01);
+    sincospif(2.f * u3, &s23, &c23);
+    const float r01 = sqrtf(-2.f * logf(1.f - u0)), r23 = sqrtf(-2.f * logf(1.f - u2));
+    const float nx = r01 * c01, ny = r01 * s01, nz = r23 * c23, npsi = r23 * s23;
+    sincosf(psi, &sp, &cp);                                    // the OLD psi
+    const float g = 1.f + se, Px = g * Dx, Py = g * Dy, Pz = g * Dz;
+    ex += ((cp * Px - sp * Py) - Dx) + (a.sigma_xy * sl) * nx;
+    ey += ((sp * Px + cp * Py) - Dy) + (a.sigma_xy * sl) * ny;
+    ez += (Pz - Dz) + (a.sigma_z * sl) * nz;
+    psi += be * a.dt + (a.sigma_yaw * sqrtf(a.dt)) * npsi;
+  }
+  o[0] = ex; o[1] = ey; o[2] = ez; o[3] = psi; o[4] = bx; o[5] = by; o[6] = bz; o[7] = se; o[8] = be; o[9] = 0.f; o[10] = 0.f; o[11] = 0.f;
+  float sh, ch;
+  sincosf(0.5f * psi, &sh, &ch);
+  float* E = a.pose_est + e;
+  E[0 * N] = bx + ex; E[1 * N] = by + ey; E[2 * N] = bz + ez;
+  // qz(psi) (x) q, qz = (ch, 0, 0, sh)
+  E[3 * N] = ch * qw - sh * qz; E[4 * N] = ch * qx - sh * qy; E[5 * N] = ch * qy + sh * qx; E[6 * N] = ch * qz + sh * qw;
+  sincosf(psi, &t[T_SIN], &t[T_COS]);                          // the NEW psi
+  t[T_B + 0] = bx; t[T_B + 1] = by; t[T_B + 2] = bz; t[T_E + 0] = ex; t[T_E + 1] = ey; t[T_E + 2] = ez;
+}
+
+// POINTS = false: one lane per env; state, pose_est rows are read and written coalesced.
+// POINTS = true: one workgroup per env.  Lane 0 makes the env's update once and leaves the transform in LDS; then the env's 3 P floats stream
+// through in tiles of 256 points: coalesced dword loads into LDS, one point per lane there (12-byte rows: a stride of 3 banks, no conflict),
+// coalesced dword stores.  Every lane loads and stores the same LDS words of a tile, so two barriers per tile order everything.  No atomics.
+template <bool POINTS>
+__global__ void __launch_bounds__(kLanes) odometry_kernel(OdoArgs a) {
+  const int tid = threadIdx.x;
+  if constexpr (!POINTS) {
+    const long e = (long)blockIdx.x * kLanes + tid;
+    float t[T_N];
+    if (e < a.N) odo_update(a, (int)e, t);
+  } else {
+    __shared__ float sh_t[T_N];
+    __shared__ float sh_pts[kOdoTile];
+    const int e = blockIdx.x;
+    if (tid == 0) odo_update(a, e, sh_t);
+    __syncthreads();
+    const float c = sh_t[T_COS], s = sh_t[T_SIN];
+    const float bx = sh_t[T_B + 0], by = sh_t[T_B + 1], ex = sh_t[T_E + 0], ey = sh_t[T_E + 1], ez = sh_t[T_E + 2];
+    const long F = 3L * a.P;
+    const float* src = a.points + (size_t)e * (size_t)F;
+    float* dst = a.points_est + (size_t)e * (size_t)F;
+    for (long f0 = 0; f0 < F; f0 += kOdoTile) {
+#pragma unroll
+      for (int j = 0; j < 3; j++) {
+        const long i = f0 + j * kLanes + tid;
+        if (i < F) sh_pts[j * kLanes + tid] = src[i];
+      }
+      __syncthreads();
+      if (f0 + 3 * tid < F) {                                  // F is a multiple of 3: the lane's point is whole
+        float* p = sh_pts + 3 * tid;
+        const float x = p[0], y = p[1], z = p[2];
+        if (isfinite(x) && isfinite(y) && isfinite(z)) {
+          const float rx = x - bx, ry = y - by;
+          p[0] = (x + ((c * rx - s * ry) - rx)) + ex;
+          p[1] = (y + ((s * rx + c * ry) - ry)) + ey;
+          p[2] = z + ez;                                       // Rz leaves z alone: (Rz r - r).z is 0
+        } else {
+          p[0] = p[1] = p[2] = __uint_as_float(0x7fc00000u);
+        }
+      }
+      __syncthreads();
+#pragma unroll
+      for (int j = 0; j < 3; j++) {
+        const long i = f0 + j * kLanes + tid;
+        if (i < F) dst[i] = sh_pts[j * kLanes + tid];
+      }
+    }
+  }
+}
+
+// behind the update: the epoch of the next call's draws
+__global__ void __launch_bounds__(64) odometry_advance_kernel(int64_t* counter) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) counter[0] = counter[0] + 1;
+}
+
 // the config's checks; `who` prefixes the message
 int resolve(const PgttElevationConfig* c, const char* who) {
   const std::string p = std::string(who) + ": ";
@@ -895,6 +1024,8 @@ struct pgtt_elevation_map {
   int every = 0;                         // 0 = no rate bound
   PgttElevationVar var{};                // pgtt_elevation_bind_var; kept by the other binds
   bool has_var = false;
+  PgttElevationOdometry odo{};           // pgtt_elevation_bind_odometry; kept by the other binds
+  bool has_odo = false;
 };
 
 namespace {
@@ -994,11 +1125,59 @@ int launch_var(pgtt_elevation_map* h, bool points, const uint8_t* clear_mask, in
   return PGTT_OK;
 }
 
+// the odometry settings' ranges; `who` prefixes the message
+int resolve_odometry(const PgttElevationOdometry* o, const char* who) {
+  const std::string p = std::string(who) + ": ";
+  if (!o) return fail(PGTT_E_ARG, p + "null settings");
+  const float f[6] = {o->dt, o->sigma_xy, o->sigma_z, o->sigma_yaw, o->yaw_bias, o->scale};
+  for (int i = 0; i < 6; i++)
+    if (!std::isfinite(f[i])) return fail(PGTT_E_ARG, p + "dt, sigma_xy, sigma_z, sigma_yaw, yaw_bias and scale must be finite");
+  if (!(o->dt > 0.f)) return fail(PGTT_E_ARG, p + "dt must be > 0");
+  if (!(o->sigma_xy >= 0.f) || !(o->sigma_z >= 0.f) || !(o->sigma_yaw >= 0.f) || !(o->yaw_bias >= 0.f))
+    return fail(PGTT_E_ARG, p + "sigma_xy, sigma_z, sigma_yaw and yaw_bias must be >= 0");
+  if (!(o->scale >= 0.f && o->scale < 1.f)) return fail(PGTT_E_ARG, p + "scale must be in [0, 1)");
+  return PGTT_OK;
+}
+
 }  // namespace
 
 extern "C" {
 
 PGTT_SIDE_EXPORTS(elevation, ELEVATION)
+int pgtt_elevation_sizeof_odometry(void) { return (int)sizeof(PgttElevationOdometry); }
+
+int pgtt_elevation_check_odometry(const PgttElevationOdometry* o) { return resolve_odometry(o, "pgtt_elevation_check_odometry"); }
+
+int pgtt_elevation_bind_odometry(pgtt_elevation_handle h, const PgttElevationOdometry* o) {
+  if (!h || !o) return fail(PGTT_E_ARG, "pgtt_elevation_bind_odometry: null argument");
+  if (!o->state || !o->pose_est || !o->odo || !o->counter) return fail(PGTT_E_ARG, "pgtt_elevation_bind_odometry: state, pose_est, odo and counter are required");
+  if ((o->points != nullptr) != (o->points_est != nullptr)) return fail(PGTT_E_ARG, "pgtt_elevation_bind_odometry: points and points_est come together");
+  if (o->points && o->P < 1) return fail(PGTT_E_ARG, "pgtt_elevation_bind_odometry: points need P >= 1");
+  if (int rc = resolve_odometry(o, "pgtt_elevation_bind_odometry")) return rc;
+  h->odo = *o;
+  h->has_odo = true;
+  return PGTT_OK;
+}
+
+int pgtt_elevation_odometry(pgtt_elevation_handle h, const uint8_t* clear_mask, int clear_all, int use_done, void* stream) {
+  if (!h) return fail(PGTT_E_ARG, "pgtt_elevation_odometry: null handle");
+  if (!h->has_odo) return fail(PGTT_E_STATE, "pgtt_elevation_odometry: no odometry bound (pgtt_elevation_bind_odometry first)");
+  HIP_TRY(hipSetDevice(h->device));
+  const PgttElevationOdometry& o = h->odo;
+  OdoArgs a{};
+  a.state = o.state; a.done = o.done; a.clear_mask = clear_mask; a.points = o.points; a.points_est = o.points_est;
+  a.pose_est = o.pose_est; a.odo = o.odo; a.counter = o.counter;
+  a.N = h->num_envs; a.P = o.P; a.clear_all = clear_all ? 1 : 0; a.use_done = use_done ? 1 : 0;
+  a.k0 = (unsigned)o.seed; a.k1 = (unsigned)(o.seed >> 32); a.gid0 = (unsigned)o.env_id_offset;
+  a.dt = o.dt; a.sigma_xy = o.sigma_xy; a.sigma_z = o.sigma_z; a.sigma_yaw = o.sigma_yaw; a.yaw_bias = o.yaw_bias; a.scale = o.scale;
+  if (o.points) hipLaunchKernelGGL(odometry_kernel<true>, dim3(h->num_envs), dim3(kLanes), 0, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL(odometry_kernel<false>, dim3((h->num_envs + kLanes - 1) / kLanes), dim3(kLanes), 0, (hipStream_t)stream, a);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(odometry_advance_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, o.counter);
+  HIP_TRY(hipGetLastError());
+  return PGTT_OK;
+}
+
 int pgtt_elevation_sizeof_var(void) { return (int)sizeof(PgttElevationVar); }
 
 int pgtt_elevation_check_var(const PgttElevationVar* v) { return resolve_var(v, "pgtt_elevation_check_var"); }

@@ -16,6 +16,9 @@ points of the env's LiDAR (lidar.py) instead: the sensor such a stack reads on t
     em = ElevationMap(env, variance=True)                    # variance-weighted (Kalman) fusion in place of the maximum and alpha: a measurement
     em.var, em.est_var                                       # noise per cell from its distance, [N, G, G] variances (m^2) and [N, 117] at the scan
 
+    em = ElevationMap(env, odometry=True)                    # the map is registered with a dead-reckoned pose that drifts in x, y, z and yaw
+    em.pose_est, em.odo                                      # (ODOMETRY_DEFAULTS), not with the simulator's: [7, N] and [N, 12] (e_xyz, psi, ...)
+
 `Joystick(..., depth=dict(...), elevation=dict(...) | True)` owns one and ticks it behind the camera (env.elevation_obs);
 `Joystick(..., lidar=dict(...), elevation=dict(source="lidar"))` one that is ticked behind the LiDAR.  The module is not imported by env.py unless
 an elevation map is asked for.
@@ -47,6 +50,10 @@ PLACEHOLDER_CAMERA = dict(width=1, height=1, fovy=90.0, near=0.1, far=1.0)
 # of a cell's pixels taken as one surface, at most 4 of them counted as independent, and a prior of 1 m^2 - settings, not measured facts about a sensor
 VARIANCE_DEFAULTS = dict(sigma0=0.005, sigma_rel=0.01, process=1e-6, gate=3.0, band=0.03, max_count=4, var_max=1.0)
 MAX_BAND, VAR_MAX_GRID = 0.5, 64                   # PGTT_ELEVATION_MAX_BAND, PGTT_ELEVATION_VAR_MAX_GRID
+# odometry=True: 2 cm of horizontal and 1 cm of vertical random walk per sqrt(metre walked), 0.01 rad / sqrt(s) of yaw random walk, a gyro bias of up
+# to 0.005 rad / s and an odometry scale error of up to 2 %, both drawn once per episode - settings, not measured facts about a robot
+ODOMETRY_DEFAULTS = dict(sigma_xy=0.02, sigma_z=0.01, sigma_yaw=0.01, yaw_bias=0.005, scale=0.02, seed=0)
+RS_ODOMETRY, ODO_WORDS = 34, 12                    # PGTT_RS_ODOMETRY, PGTT_ELEVATION_ODO_WORDS
 
 f, i32 = C.c_float, C.c_int32
 
@@ -72,7 +79,13 @@ class PgttElevationVar(C.Structure):
 
 
 assert C.sizeof(PgttElevationConfig) == 92 and C.sizeof(PgttElevationBuffers) == 72 and C.sizeof(PgttElevationFill) == 40
-assert C.sizeof(PgttElevationVar) == 48
+class PgttElevationOdometry(C.Structure):
+    _fields_ = [("state", C.c_void_p), ("done", C.c_void_p), ("points", C.c_void_p), ("points_est", C.c_void_p), ("P", i32),
+                ("pose_est", C.c_void_p), ("odo", C.c_void_p), ("counter", C.c_void_p), ("seed", C.c_uint64), ("env_id_offset", C.c_int64),
+                ("dt", f), ("sigma_xy", f), ("sigma_z", f), ("sigma_yaw", f), ("yaw_bias", f), ("scale", f)]
+
+
+assert C.sizeof(PgttElevationVar) == 48 and C.sizeof(PgttElevationOdometry) == 104
 
 
 class ElevationError(RuntimeError):
@@ -90,8 +103,11 @@ SIDE = _sidelib.SideLib("elevation", ElevationError, {
     "pgtt_elevation_bind_rate": (None, [vp, vp, C.c_int]), "pgtt_elevation_follow": (None, [vp, vp, C.c_int, C.c_int, C.c_int, vp]),
     "pgtt_elevation_check_var": (None, [C.POINTER(PgttElevationVar)]), "pgtt_elevation_bind_var": (None, [vp, C.POINTER(PgttElevationVar)]),
     "pgtt_elevation_var": (None, [vp, vp, C.c_int, C.c_int, vp]), "pgtt_elevation_var_points": (None, [vp, vp, C.c_int, C.c_int, vp]),
+    "pgtt_elevation_check_odometry": (None, [C.POINTER(PgttElevationOdometry)]),
+    "pgtt_elevation_bind_odometry": (None, [vp, C.POINTER(PgttElevationOdometry)]), "pgtt_elevation_odometry": (None, [vp, vp, C.c_int, C.c_int, vp]),
 }, {"pgtt_elevation_sizeof_config": PgttElevationConfig, "pgtt_elevation_sizeof_buffers": PgttElevationBuffers,
-    "pgtt_elevation_sizeof_fill": PgttElevationFill, "pgtt_elevation_sizeof_var": PgttElevationVar})
+    "pgtt_elevation_sizeof_fill": PgttElevationFill, "pgtt_elevation_sizeof_var": PgttElevationVar,
+    "pgtt_elevation_sizeof_odometry": PgttElevationOdometry})
 LIB_PATH, EXPORTS, lib, check, build_info = SIDE.path, SIDE.exports, SIDE.lib, SIDE.check, SIDE.build_info
 
 
@@ -119,6 +135,32 @@ def variance_struct(sigma0=0.005, sigma_rel=0.01, process=1e-6, gate=3.0, band=0
     v.sigma0, v.sigma_rel, v.process, v.gate, v.band, v.max_count, v.var_max = (float(sigma0), float(sigma_rel), float(process), float(gate),
                                                                                  float(band), int(max_count), float(var_max))
     return v
+
+
+def odometry_settings(odometry=None) -> Optional[Dict]:
+    """ElevationMap's `odometry` argument as a full dict: None / False -> None (the map is registered with the true pose), True ->
+    ODOMETRY_DEFAULTS, a dict -> the defaults with it on top.  ValueError for a key that is no setting or for anything else."""
+    if odometry is None or odometry is False:
+        return None
+    if odometry is not True and not isinstance(odometry, dict):
+        raise ValueError(f"ElevationMap(odometry=...): odometry must be True or a dict of settings, not {odometry!r}")
+    over = {} if odometry is True else dict(odometry)
+    unknown = sorted(set(over) - set(ODOMETRY_DEFAULTS))
+    if unknown:
+        raise ValueError(f"ElevationMap(odometry=...): unknown setting(s) {unknown}; the settings are {sorted(ODOMETRY_DEFAULTS)}")
+    return {**ODOMETRY_DEFAULTS, **over}
+
+
+def odometry_struct(dt, sigma_xy=0.02, sigma_z=0.01, sigma_yaw=0.01, yaw_bias=0.005, scale=0.02, seed=0, env_id_offset=0, state=None, done=None,
+                    points=None, points_est=None, P=0, pose_est=None, odo=None, counter=None) -> PgttElevationOdometry:
+    """no checks: the library makes its own (pgtt_elevation_check_odometry)"""
+    o = PgttElevationOdometry()
+    o.state, o.done, o.points, o.points_est, o.P = state, done, points, points_est, int(P)
+    o.pose_est, o.odo, o.counter = pose_est, odo, counter
+    o.seed, o.env_id_offset = int(seed) & (2 ** 64 - 1), int(env_id_offset)
+    o.dt, o.sigma_xy, o.sigma_z, o.sigma_yaw, o.yaw_bias, o.scale = (float(dt), float(sigma_xy), float(sigma_z), float(sigma_yaw), float(yaw_bias),
+                                                                    float(scale))
+    return o
 
 
 def config_struct(width, height, fovy, near, far, mount_pos=(0.0, 0.0, 0.0), mount_quat=(1.0, 0.0, 0.0, 0.0), mount_body=0, grid=64, res=0.04,
@@ -155,13 +197,20 @@ class ElevationMap(_sidelib.Handle):
     cell's pixels as the measurement, a Mahalanobis gate and `process` noise per tick; alpha is not read.  `var` [N, G, G] is the variance layer (m^2,
     NaN where `map` is) and `est_var` [N, 117] the variance at the scan points (var_max at an unknown one).  It needs grid <= 64 and is not built for
     follow_sensor yet.  variance=None, the default: nothing of this is allocated or called.
+    odometry = True (ODOMETRY_DEFAULTS) or a dict over them: the map is registered with a dead-reckoned pose, not with the simulator's.  tick()
+    first enqueues pgtt_elevation_odometry with the same clear arguments - the pose estimate `pose_est` [7, N] walks away from the env's true pose in
+    x, y, z and yaw (`odo` [N, 12]: the position error, the yaw error psi, ...; include/pgtt_elevation.h), and for source="lidar" the LiDAR's world
+    points are re-registered at it (`points_est` [N, P, 3]) - and the map is bound to those in place of the env's state and the LiDAR's points.  dt is
+    the env's control step, the draws are keyed by `seed` and env.env_id_offset.  Works with fill, variance and follow_sensor; nothing is corrected
+    (no loop closure).  The defaults are settings, not facts about a robot.  odometry=None, the default: nothing of this is allocated or called.
     Runs on the env's device and current stream; reads env.depth or the LiDAR's points, env.buffers["state" | "obs_state" | "done"] and writes nothing
     but its own tensors."""
     _prefix, _check = "pgtt_elevation", staticmethod(check)
 
     def __init__(self, env, grid: int = 64, res: float = 0.04, alpha: float = 1.0, self_half: Sequence[float] = (0.45, 0.25, 0.45),
-                 source: str = "depth", fill: int = 0, dense: bool = False, follow_sensor: bool = False, variance=None):
+                 source: str = "depth", fill: int = 0, dense: bool = False, follow_sensor: bool = False, variance=None, odometry=None):
         self.variance = variance_settings(variance)
+        self.odometry = odometry_settings(odometry)
         if self.variance is not None:
             if follow_sensor:
                 raise ValueError("ElevationMap: variance with follow_sensor=True is not built yet (the hold call would have to leave var alone)")
@@ -219,6 +268,12 @@ class ElevationMap(_sidelib.Handle):
         if self.variance is not None:
             self.var = torch.full((n, self.grid, self.grid), float("nan"), dtype=torch.float32, device=dev)
             self.est_var = torch.full((n, NSCAN), float(self.variance["var_max"]), dtype=torch.float32, device=dev)
+        if self.odometry is not None:
+            self.pose_est = torch.zeros((7, n), dtype=torch.float32, device=dev)
+            self.odo = torch.zeros((n, ODO_WORDS), dtype=torch.float32, device=dev)
+            self.odo_counter = torch.zeros(1, dtype=torch.int64, device=dev)
+            if source == "lidar":
+                self.points_est = torch.full_like(env.lidar_scanner.points, float("nan"))
         if self.follow_sensor:
             sensor = env.lidar_scanner if source == "lidar" else env.depth_camera
             self.sensor_counter, self.sensor_every = sensor.counter, int(sensor.config.every)
@@ -226,15 +281,17 @@ class ElevationMap(_sidelib.Handle):
         self.bind()
 
     def bind(self) -> None:
-        """(re)bind: the env's state, image or points, observation and done flags, this object's outputs"""
+        """(re)bind: the env's state (with odometry: the pose estimate), image or points, observation and done flags, this object's outputs"""
         b = PgttElevationBuffers()
         eb = self.env.buffers
         b.state, b.obs = eb["state"].data_ptr(), eb["obs_state"].data_ptr()
+        if self.odometry is not None:
+            b.state = self.pose_est.data_ptr()                  # rows 0..6 are all the library reads of `state`
         b.done = eb["done"].data_ptr() if eb.get("done") is not None else None
         b.map, b.origin, b.est, b.known, b.obs_out = (t.data_ptr() for t in (self.map, self.origin, self.est, self.known, self.obs))
         if self.source == "lidar":
             pts = self.env.lidar_scanner.points
-            check(self._lib.pgtt_elevation_bind_points(self._h, C.byref(b), pts.data_ptr(), pts.shape[1]))
+            check(self._lib.pgtt_elevation_bind_points(self._h, C.byref(b), (pts if self.odometry is None else self.points_est).data_ptr(), pts.shape[1]))
         else:
             b.depth = self.env.depth.data_ptr()
             check(self._lib.pgtt_elevation_bind(self._h, C.byref(b)))
@@ -247,6 +304,13 @@ class ElevationMap(_sidelib.Handle):
         if self.variance is not None:
             v = variance_struct(**self.variance, var=self.var.data_ptr(), est_var=self.est_var.data_ptr())
             check(self._lib.pgtt_elevation_bind_var(self._h, C.byref(v)))
+        if self.odometry is not None:
+            lidar = self.source == "lidar"
+            o = odometry_struct(self.env.dt, **self.odometry, env_id_offset=self.env.env_id_offset, state=eb["state"].data_ptr(), done=b.done,
+                                points=self.env.lidar_scanner.points.data_ptr() if lidar else None,
+                                points_est=self.points_est.data_ptr() if lidar else None, P=self.points_est.shape[1] if lidar else 0,
+                                pose_est=self.pose_est.data_ptr(), odo=self.odo.data_ptr(), counter=self.odo_counter.data_ptr())
+            check(self._lib.pgtt_elevation_bind_odometry(self._h, C.byref(o)))
 
     def tick(self, clear_mask: Optional[torch.Tensor] = None, clear_all: bool = False, use_done: bool = False, force: bool = False) -> torch.Tensor:
         """integrate the env's current image (or LiDAR points) under its current pose and sample the scan: one launch on the env's current stream,
@@ -254,13 +318,17 @@ class ElevationMap(_sidelib.Handle):
         the envs whose done flag is set (use_done) are cleared.  With fill > 0 the hole filling is enqueued behind it.
         With follow_sensor (two launches, one of which returns at once) this is so on the calls behind a sensor tick that took new data - `force`
         is what that sensor tick was given; on the others the clears are made, nothing else of the map changes and the scan is sampled from it at
-        the current pose.  `force` is not read without follow_sensor."""
+        the current pose.  `force` is not read without follow_sensor.
+        With odometry the pose estimate is updated first (two small launches), with the same clear arguments: a cleared env's estimate is the
+        truth again and its episode's scale error and gyro bias are drawn anew."""
         mp = None
         if clear_mask is not None:
             self._mask = clear_mask.to(self.env.device, torch.uint8).contiguous()      # kept alive until the next tick: the launch is asynchronous
             assert self._mask.shape == (self.env.num_envs,)
             mp = self._mask.data_ptr()
         stream = torch.cuda.current_stream(self.env.device).cuda_stream
+        if self.odometry is not None:
+            check(self._lib.pgtt_elevation_odometry(self._h, mp, int(bool(clear_all)), int(bool(use_done)), stream))
         if self.follow_sensor:
             check(self._lib.pgtt_elevation_follow(self._h, mp, int(bool(clear_all)), int(bool(use_done)), int(bool(force)), stream))
         elif self.variance is not None:

@@ -78,6 +78,10 @@ class Joystick:
         elevation=dict(variance=True | dict(sigma0=..., sigma_rel=..., process=..., gate=..., band=..., max_count=..., var_max=...), ...) replaces the
         maximum-and-alpha fusion by a variance-weighted (Kalman) update per cell (pgtt_elevation_var; elevation.VARIANCE_DEFAULTS): the map keeps a
         variance layer `env.elevation_map.var`, and `env.elevation_var` [N, 117] is the variance at the scan points.  Not with follow_sensor; grid <= 64.
+        elevation=dict(odometry=True | dict(sigma_xy=..., sigma_z=..., sigma_yaw=..., yaw_bias=..., scale=..., seed=...), ...) registers the map with a
+        dead-reckoned pose that drifts in x, y, z and yaw instead of the simulator's (pgtt_elevation_odometry; elevation.ODOMETRY_DEFAULTS, settings and
+        not facts about a robot): `env.odometry_pose` [7, N] is the estimate, `env.odometry_error` [N, 4] its position and yaw error (e_x, e_y, e_z,
+        psi), zero after reset() and for an env whose episode just ended.  Works with fill, variance, follow_sensor and both sources.
         obs, state, reward, done, the image and the LiDAR's outputs are what they are without it."""
         if student is not None and depth is None:
             raise ValueError("Joystick(student=...) needs depth=dict(...): the student reads the onboard depth image")
@@ -337,6 +341,17 @@ class Joystick:
     def elevation_var(self) -> Optional[torch.Tensor]:
         """[N, 117] float32: the variance (m^2) of the elevation map at the scan points, var_max at an unknown one; None without a variance map"""
         return getattr(self.elevation_map, "est_var", None)
+
+    @property
+    def odometry_error(self) -> Optional[torch.Tensor]:
+        """[N, 4] float32, a view: the error (e_x, e_y, e_z, psi) of the pose the elevation map is registered with; None without odometry drift"""
+        odo = getattr(self.elevation_map, "odo", None)
+        return None if odo is None else odo[:, :4]
+
+    @property
+    def odometry_pose(self) -> Optional[torch.Tensor]:
+        """[7, N] float32: the dead-reckoned base pose (position, quaternion wxyz) the elevation map is registered with; None without odometry drift"""
+        return getattr(self.elevation_map, "pose_est", None)
 
     def push_step(self) -> None:
         """the push scheduler alone (pgtt_push): what step() runs first when pushes are on; for callers of physics() / observe()"""
