@@ -307,7 +307,14 @@ int pgtt_create(const PgttConfig* cfg, const PgttModel* model, int device, int n
 int pgtt_destroy(pgtt_handle h);
 
 /* terrain: T variants x B(<=100) boxes x [pos xyz, quat wxyz, half-size xyz] (terrains/level*.npy layout,
- * terrain/generator.py:368-391). HOST pointer, copied once into a resident device table. T = 0 => plane only. */
+ * terrain/generator.py:368-391). HOST pointer, copied once into a resident device table. T = 0 => plane only.
+ * Range: the collision pass culls through a 16 x 16 grid of box sets over [-E, E]^2 (E = the reach of the boxes with |x|, |y| < 50 m, at least 1 m;
+ * border cells reach to infinity, so feet and boxes may lie anywhere outside it).  Each set is built from the box's world AABB grown by the foot radius
+ * + 1.1e-4 m, and that slack has to cover the fp32 rounding of the AABB's bounds: it does while |x|, |y| of every box face stay below about 500 m
+ * (a conservative figure: one fp32 ulp at 512 m is 6.1e-5 m, the point from which a full ulp approaches the slack; the two half-ulp roundings of
+ * p +- h +- grow stay under it up to about 1000 m) - the reference's parked placeholders, at most about 200 m out, are well inside.  A table with boxes farther out
+ * is accepted, but a foot within a rounding of such a box's grown AABB may miss it.  tests/test_gpu_collision_edges.py holds the contact set to the
+ * brute-force oracle on grid lines, on the border, on placeholders up to 198 m and on boxes that E ignores. */
 int pgtt_set_terrain(pgtt_handle h, const float* boxes_TxBx10, int T, int B);
 
 int pgtt_bind(pgtt_handle h, const PgttBuffers* bufs);
