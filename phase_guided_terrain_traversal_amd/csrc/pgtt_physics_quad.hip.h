@@ -76,6 +76,26 @@ PG_INL float sub_sum(float x) {
 #endif
   return x;
 }
+// quad_sum(sub_sum(.)) of two values that the lanes of a pair (lane, lane ^ 1: one env in every layout) hold in OPPOSITE slots - x0 of a lane is the
+// partial of what its partner keeps in x1 (the line search's role-held trial steps).  The first step, quad_perm [1,0,3,2], is the one that pairs the
+// two lanes: taken crossed, it adds the same two partials the replicated form added (in either order: IEEE addition commutes), and s0 / s1 come out
+// for (the own, the partner's) value.  Every later step pairs lanes of equal bit 0, which hold the same s0 and the same s1.
+PG_INL void pair_sum2(float x0, float x1, float& s0, float& s1) {
+#pragma clang fp contract(off)
+  s0 = x0 + dpp_f<0xB1>(x1);
+  s1 = x1 + dpp_f<0xB1>(x0);
+#if PG_SUBS == 1
+  s0 = s0 + dpp_f<kLegStep2>(s0);
+  s1 = s1 + dpp_f<kLegStep2>(s1);
+#else
+#if PG_SUBS == 4
+  s0 = s0 + dpp_f<0x4E>(s0);
+  s1 = s1 + dpp_f<0x4E>(s1);
+#endif
+  s0 = quad_sum(s0);
+  s1 = quad_sum(s1);
+#endif
+}
 PG_INL int sub_sum_i(int x) {
 #if PG_SUBS >= 2
   x += dpp_i<0xB1>(x);
@@ -1469,8 +1489,15 @@ struct QSolver {
   PG_INL static void ls_row2(f2 ja, f2 jv, float D, const float* al, f2 (*q)[3]) { ls_row2d<NA, COST>(ja, jv, f2{D, D}, al, q); }
   // COST = false: the derivatives alone (the bracketing rounds only look at d0 / d1; the costs of the two points the search
   // ends with are evaluated once, afterwards - same function of alpha, same bits)
-  template <int NA, bool COST = true>
+  // PAIRED (the bracketing rounds; NA = 3, no costs): the lane holds its trial steps in ROLE order - al = {own Newton step, the pair partner's,
+  // midpoint} - so al[0] / al[1] differ between the lanes of a pair (lane, lane ^ 1) while al[0] of one is al[1] of the other, bit for bit.  The row pass
+  // is the same; the sums of slots 0 and 1 take their first butterfly step, the one that pairs the two roles, crossed (pair_sum2): out[0] is the point
+  // of the own step, out[1] that of the partner's - what the replicated form held in slots `role` and `1 - role` - and out[2] the midpoint, as ever.
+  // PAIR (hex): 1 / 0 - the caller has asked nslots > 2 already, for all its rounds; -1 - asked here
+  template <int V> struct PairTag { static constexpr int value = V; };
+  template <int NA, bool COST = true, bool PAIRED = false, int PAIR = -1>
   PG_INL void ls_points(const float* al, const float* jv_lim, const float* jv0, float qg0, float qg1, float qg2, LSPoint* out) const {
+    static_assert(!PAIRED || (NA == 3 && !COST), "the paired form is the bracketing round's: two role-held steps and the midpoint, derivatives only");
     f2 q[NA][3];
 #pragma unroll
     for (int a = 0; a < NA; a++) { q[a][0] = f2{0.f, 0.f}; q[a][1] = f2{0.f, 0.f}; q[a][2] = f2{0.f, 0.f}; }
@@ -1511,11 +1538,21 @@ struct QSolver {
       // zeros and add exact zeros) - a not-taken branch costs a one-wave SIMD ~10 cycles, and a round has a dozen instructions per pair
       if (kTerrainTU || any_lim || any_con0) ls_row2d<NA, COST>(hx_ja, hx_jv, hx_D, al, q);       // own (limit row, plane row), picked once per search
       if (kTerrainTU || nslots > 0) ls_row2d<NA, COST>(ls_ja[0], ls_jv[0], ls_D[0], al, q);
-      if (__builtin_expect(nslots > 2, 0)) ls_row2d<NA, COST>(ls_ja[1], ls_jv[1], ls_D[1], al, q);      // three or four box contacts on one foot: rare, out of line
+      if (PAIR > 0 || (PAIR < 0 && __builtin_expect(nslots > 2, 0))) ls_row2d<NA, COST>(ls_ja[1], ls_jv[1], ls_D[1], al, q);      // three or four box contacts on one foot: rare, out of line
+    }
+    float x1[NA], x2[NA];
+#pragma unroll
+    for (int a = 0; a < NA; a++) { x1[a] = q[a][1].x + q[a][1].y; x2[a] = q[a][2].x + q[a][2].y; }
+    if constexpr (PAIRED) {
+      pair_sum2(x1[0], x1[1], x1[0], x1[1]); pair_sum2(x2[0], x2[1], x2[0], x2[1]);
+      x1[2] = quad_sum(sub_sum(x1[2])); x2[2] = quad_sum(sub_sum(x2[2]));
+    } else {
+#pragma unroll
+      for (int a = 0; a < NA; a++) { x1[a] = quad_sum(sub_sum(x1[a])); x2[a] = quad_sum(sub_sum(x2[a])); }
     }
 #pragma unroll
     for (int a = 0; a < NA; a++) {
-      const float q1 = quad_sum(sub_sum(q[a][1].x + q[a][1].y)) + qg1, q2 = quad_sum(sub_sum(q[a][2].x + q[a][2].y)) + qg2;
+      const float q1 = x1[a] + qg1, q2 = x2[a] + qg2;
       const float alpha = al[a];
       out[a].alpha = alpha;
       if (COST) {
@@ -1549,6 +1586,13 @@ struct QSolver {
   PG_INL static float div_normal(float a, float b) {
 #pragma clang fp contract(off)
     return a * __builtin_amdgcn_rcpf(b);
+  }
+
+  // searching != 0 ? left - 1 : 0 for a wave-uniform count, on the scalar side (written as `?:` it is compiled to a counter in a VGPR, a borrow
+  // mask and two more mask operations: the hand-overs this loop is rid of)
+  PG_INL static int rounds_left(int left, unsigned long long searching) {
+    asm("s_sub_u32 %0, %0, 1\n\ts_cmp_lg_u64 %1, 0\n\ts_cselect_b32 %0, %0, 0" : "+s"(left) : "s"(searching) : "scc");
+    return left;
   }
 
   PG_INL void linesearch(bool frozen) {
@@ -1679,8 +1723,9 @@ struct QSolver {
     // The two bracket ends go through the same code on mirrored inputs (Newton step, tighten, tolerance test), and all lanes of an env would
     // run both with identical operands.  Each lane of a PAIR (lane, lane ^ 1: one env in every layout - the sub-lane bit in hex and oct, leg
     // bit 0 in quad) carries ONE end instead: role 0 `lo`, role 1 `hi`, and the pair trades what the other half needs by quad_perm [1,0,3,2].
-    // What enters the row sums (al3) and what leaves the search (lo / hi.alpha) is replicated again first: a role-held value never meets a
-    // butterfly or a store.  Selects only, every exchange with all 64 lanes active.
+    // A role-held value enters a butterfly step only where that step pairs lanes of the SAME role (every step but the first, which the round's row sums
+    // take crossed: pair_sum2); what leaves the search (lo / hi.alpha) is replicated again first, and no role-held value meets a store.  Selects only,
+    // every exchange with all 64 lanes active.
     const bool role = (threadIdx.x & 1) != 0;
     const float rsign = role ? 1.0f : -1.0f;
     LSPoint own = role == lesser ? p0 : lo0;         // hi = lesser ? p0 : lo0, lo = lesser ? lo0 : p0
@@ -1695,24 +1740,43 @@ struct QSolver {
       return v | dpp_i<0xB1>(v);
     };
     int v = vote(true);
-    // the cap is the model's, the same in every lane (`it >= ls_iterations` finishes every env of the wave at once): read into an SGPR once, it bounds
-    // the loop instead of entering every lane's `done`; the ballot takes the compare's mask as it is (no 0 / 1 value and a second compare in between)
-    // (oct keeps the per-lane form of the cap: with the scalar loop its two DR + terrain kernels, at 256 + 256 registers, spill 8 B per lane)
-    const int cap = kSubs == 2 ? 0 : __builtin_amdgcn_readfirstlane(m->ls_iterations);
-    for (int it = 0; kSubs == 2 || it < cap; it++) {
-      const bool done = (kSubs == 2 && it >= m->ls_iterations) | (v != 1);
-      if (__builtin_amdgcn_ballot_w64(!done) == 0ull) break;
+    // one bracketing round; `pair` (a PairTag) says whether hex's (slot 2, slot 3) row pair is in it: 1 / 0 - the caller knows - or -1: asked in place
+    auto round = [&](bool done, auto pair) {
       const float st = own.alpha - div_normal(own.d0, own.d1), st_p = dpp_f<0xB1>(st), al_p = dpp_f<0xB1>(own.alpha);
-      // the replicated trial steps, in the order they always had: {lo's Newton step, hi's Newton step, midpoint (a + b = b + a, same bits)}
-      const float al3[3] = {role ? st_p : st, role ? st : st_p, 0.5f * (own.alpha + al_p)};
+      // the trial steps in ROLE order: {own Newton step, the partner's, midpoint (a + b = b + a, same bits)}.  The first two are role-held: the row sums
+      // trade them in their first butterfly step (ls_points' paired form), so no select puts them into end order and none takes the points back out
+      const float al3[3] = {st, st_p, 0.5f * (own.alpha + al_p)};
       LSPoint pt[3];
-      ls_points<3, false>(al3, jv_lim, jv0, qg0, qg1, qg2, pt);
+      ls_points<3, false, true, decltype(pair)::value>(al3, jv_lim, jv0, qg0, qg1, qg2, pt);
       // candidates in the order of both ends: the point of the own step, the midpoint, the point of the partner's step
-      const LSPoint mine_pt = role ? pt[1] : pt[0], other_pt = role ? pt[0] : pt[1];
       bool moved;
-      own = tighten(own, mine_pt, pt[2], other_pt, done, moved);
+      own = tighten(own, pt[0], pt[2], pt[1], done, moved);
       // a finished env moves nothing (threshold 0), so its vote is never 1 again: `done` is sticky
       v = vote(moved);
+    };
+    // the cap is the model's, the same in every lane (`it >= ls_iterations` finishes every env of the wave at once)
+    if constexpr (kSubs == 2) {
+      // oct keeps the per-lane form of the cap: with a scalar loop its two DR + terrain kernels, at 256 + 256 registers, spill 8 B per lane
+      for (int it = 0;; it++) {
+        const bool done = (it >= m->ls_iterations) | (v != 1);
+        if (__builtin_amdgcn_ballot_w64(!done) == 0ull) break;
+        round(done, PairTag<-1>{});
+      }
+    } else {
+      // The cap is read into an SGPR once and bounds the loop instead of entering every lane's `done`.  One question per round, asked once, at the bottom,
+      // of ONE scalar: `left` counts the rounds down in an SGPR and drops to 0 with the wave's last searching env, so "any env still searching, and the cap not reached" is one compare's mask handed to the scalar side and one loop branch.
+      // In hex the whole loop exists twice, picked by nslots before it (wave-uniform, fixed for the search): the common one holds no (slot 2, slot 3)
+      // row pair and no branch round it - the row pass falls through into the sums - and the crowded wave's loop sits behind it.
+      const int cap = __builtin_amdgcn_readfirstlane(m->ls_iterations);
+      auto rounds = [&](auto pair) {
+        int left = __builtin_amdgcn_ballot_w64(v == 1) != 0ull ? cap : 0;
+        while (left > 0) {
+          round(v != 1, pair);
+          left = rounds_left(left, __builtin_amdgcn_ballot_w64(v == 1));
+        }
+      };
+      if (kSubs == 4 && nslots > 2) rounds(PairTag<1>{});
+      else rounds(PairTag<(kSubs == 4 ? 0 : -1)>{});
     }
     LSPoint lo, hi;
     {   // both ends' alpha in every lane again (also when no round ran), then the costs of the two points the bracket ended with
