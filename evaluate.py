@@ -15,7 +15,8 @@ whose scan rows the student perception module estimated from the onboard depth i
 scan rows are sampled from the depth-fused elevation map (elevation.py; nothing to train; `--elevation_source lidar` fuses it from the onboard
 LiDAR's points instead, lidar.py; `--elevation_fill [K]` closes the map's holes first and the policy acts on the filled scan; `--sensor_every M`
 runs that sensor at one control step in M and lets the map follow it; `--odometry_drift [sigma_xy,sigma_z,sigma_yaw,yaw_bias,scale]` registers the map
-with a dead-reckoned pose that drifts, and adds a line with the drift at the end; `--elevation_variance [sigma0,sigma_rel,process,gate,band]` fuses the map by
+with a dead-reckoned pose that drifts, and adds a line with the drift at the end; `--elevation_visibility [margin,end_guard,stride]` cleans the map by
+visibility in front of every tick and adds a line with the cells forgotten per step; `--elevation_variance [sigma0,sigma_rel,process,gate,band]` fuses the map by
 the variance-weighted update; `--sensor_noise SIGMA[,DROPOUT]` gives the sensor that feeds the map or the student range noise); a `--policy` file that holds a recurrent policy
 (train_distill.py --memory, recurrent_policy.py) is stepped with a memory per env, cleared where the previous step ended an episode; the remaining flags of the reference's CLI are accepted and ignored.
 """
@@ -151,6 +152,8 @@ def sensor_kwargs(args):
         raise SystemExit("--elevation_variance says how --elevation's map is fused: give --elevation too")
     if getattr(args, "odometry_drift", None) is not None and elev is None:
         raise SystemExit("--odometry_drift is the drift of the pose --elevation's map is registered with: give --elevation too")
+    if getattr(args, "elevation_visibility", None) is not None and elev is None:
+        raise SystemExit("--elevation_visibility cleans --elevation's map: give --elevation too")
     if elev is not None:
         # --elevation [grid,res,alpha]: the policy acts on env.elevation_obs - the observation whose scan rows are sampled from the elevation map
         # fused from the onboard depth image (the camera of depth.DEFAULTS; elevation.DEFAULTS where a value is not given)
@@ -191,6 +194,13 @@ def sensor_kwargs(args):
             # --odometry_drift [sigma_xy,sigma_z,sigma_yaw,yaw_bias,scale]: the map is registered with a dead-reckoned pose that drifts
             # (elevation.ODOMETRY_DEFAULTS where a value is not given) instead of the simulator's exact one
             given = dict({} if given is True else given, odometry=drift)
+        vis = elevation_visibility(getattr(args, "elevation_visibility", None))
+        if vis is not None:
+            # --elevation_visibility [margin,end_guard,stride]: the map is cleaned by visibility in front of every tick
+            # (elevation.VISIBILITY_DEFAULTS where a value is not given)
+            if every > 1:
+                raise SystemExit("--elevation_visibility behind a slower sensor (--sensor_every > 1) is not built: a hold step must not clean with a stale image")
+            given = dict({} if given is True else given, visibility=vis)
         if source == "lidar":
             # --elevation_source lidar: the map is fused from the world points of the onboard LiDAR (lidar.DEFAULTS), as the deployed mapping stack's is
             kw.update(lidar=sensor, elevation=dict({} if given is True else given, source="lidar"))
@@ -249,6 +259,7 @@ def run_evaluation(args, num_eval_envs=NUM_EVAL_ENVS, seed=0, verbose=True):
     known = torch.zeros(n, device=dev)                                            # with a map: the scan points it knew, summed over the first episode
     covered = torch.zeros(n, device=dev)                                          # with a fill: the scan points it knew or filled
     drift = torch.zeros(n, 4, device=dev)                                         # with odometry drift: the error when the first episode ended
+    forgot = torch.zeros(n, device=dev)                                           # with visibility clean-up: the cells forgotten, summed over the first episode
     video = VideoRecorder(args, env, L) if getattr(args, "video", None) else None
     recurrent = hasattr(pi, "gru_w_ih")
     if recurrent:
@@ -262,6 +273,8 @@ def run_evaluation(args, num_eval_envs=NUM_EVAL_ENVS, seed=0, verbose=True):
             known += env.elevation_known.float().mean(1) * first.float()
         if env.elevation_dist is not None:
             covered += (env.elevation_dist != 255).float().mean(1) * first.float()
+        if env.elevation_cleared is not None:
+            forgot += env.elevation_cleared.float() * first.float()
         if env.odometry_error is not None:
             # the step that ends an episode clears the env's estimate: keep the error as it stood before that step
             drift = torch.where(first[:, None], env.odometry_error, drift)
@@ -287,6 +300,8 @@ def run_evaluation(args, num_eval_envs=NUM_EVAL_ENVS, seed=0, verbose=True):
         out["covered_share"] = float((covered / length.clamp(min=1)).mean())      # ... that the map knew or the fill reached (dist != 255)
     if env.odometry_error is not None:                                             # at the end of the run: of each env's first episode, before its last step
         out["odometry_e_xy"], out["odometry_psi"] = float(drift[:, :2].norm(dim=1).mean()), float(drift[:, 3].abs().mean())
+    if env.elevation_cleared is not None:                                          # cells the clean-up forgot per env and step of the first episode
+        out["visibility_cleared_per_step"] = float((forgot / length.clamp(min=1)).mean())
     if video is not None:
         out["video"] = video.write(verbose)
     env.close()
@@ -295,6 +310,8 @@ def run_evaluation(args, num_eval_envs=NUM_EVAL_ENVS, seed=0, verbose=True):
         print([survivors])
         if "odometry_e_xy" in out:
             print(f"odometry drift at the end: mean |e_xy| = {out['odometry_e_xy']:.4f} m, mean |psi| = {out['odometry_psi']:.4f} rad")
+        if "visibility_cleared_per_step" in out:
+            print(f"visibility clean-up: {out['visibility_cleared_per_step']:.3f} cells forgotten per env and step")
     return out
 
 
@@ -345,6 +362,19 @@ def odometry_drift(text):
         raise SystemExit(f"--odometry_drift {text}: the values must be numbers")
 
 
+def elevation_visibility(text):
+    """--elevation_visibility [margin,end_guard,stride] -> None (not given), True (the flag alone) or a dict of the values given"""
+    if text is None:
+        return None
+    vals = [v for v in str(text).split(",") if v]
+    if len(vals) > 3:
+        raise SystemExit("--elevation_visibility takes at most margin,end_guard,stride")
+    try:
+        return dict(zip(("margin", "end_guard", "stride"), [float(v) for v in vals[:2]] + [int(v) for v in vals[2:]])) if vals else True
+    except ValueError:
+        raise SystemExit(f"--elevation_visibility {text}: margin and end_guard must be numbers, stride an integer")
+
+
 def fill_passes(text):
     """--elevation_fill K: an integer in [1, 95] (elevation.MAX_FILL); the flag without a value is True, elevation.FILL_PASSES"""
     try:
@@ -369,6 +399,8 @@ def add_sensor_args(ap):
                     help="with --elevation: fuse the map by the variance-weighted (Kalman) update instead of the maximum and alpha; optional settings")
     ap.add_argument("--odometry_drift", type=str, nargs="?", const="", default=None, metavar="SIGMA_XY,SIGMA_Z,SIGMA_YAW,YAW_BIAS,SCALE",
                     help="with --elevation: register the map with a dead-reckoned pose that drifts in x, y, z and yaw, not with the exact one; optional settings")
+    ap.add_argument("--elevation_visibility", type=str, nargs="?", const="", default=None, metavar="MARGIN,END_GUARD,STRIDE",
+                    help="with --elevation: clean the map by visibility in front of every tick (a cell a ray passed below is forgotten); optional settings")
     ap.add_argument("--sensor_noise", type=str, default=None, metavar="SIGMA[,DROPOUT]",
                     help="with --elevation or --student: relative range noise and dropout probability of the sensor that feeds it")
     ap.add_argument("--sensor_every", type=int, default=1, metavar="M",

@@ -194,6 +194,38 @@
  * An env's outputs depend on its own rows and its global id only: the same bits at any batch position, at any N, with or without points.
  * Not covered: loop closure or any correction of the drift, roll or pitch error, latency between capture and fusion, drift on the
  * proprioceptive rows of the observation.
+ *
+ * Visibility clean-up.  The ticks above only ever add heights: a cell keeps what was fused into it until the window leaves it or a later measurement
+ * lands in it.  Under a drifting pose a stair edge fused some centimetres ago stays as a ghost next to the real one.  pgtt_elevation_visibility() is
+ * a launch of its own, called behind the sensor's call (and behind pgtt_elevation_odometry where that is used) and BEFORE the tick of the same step,
+ * with the clear arguments that tick will be given.  A ray that reached its end point while passing below a cell's recorded height contradicts that
+ * cell, and the cell is forgotten (NaN).  The source is the image or the points, by which bind was made last.  It reads rows PGTT_S_QPOS + 0..6 of
+ * `state` and no other, so the promise of the odometry block holds.  The settings and outputs are PgttElevationVisibility's.  Per env, in fp32, in
+ * this order:
+ *  1. Skip.  An env the tick behind this call will clear (clear_all != 0, or clear_mask[e] != 0, or use_done != 0 and done[e] != 0) is not looked
+ *     at: cleared[e] = 0 and its bound_out is NaN everywhere.  The window is the one origin[e] describes, as the last tick left it; an origin outside
+ *     +-2^30 is taken as +-2^30, as pgtt_elevation_fill does.  There is no recentring and `origin` is not written.
+ *  2. Rays.  The sensor position s: for the image the camera position of the tick (base + R_base mount_pos); for the points base + R_base sensor_pos.
+ *     The end point p: the unprojected pixel of step 3 of the tick (near < d < far, the same formula) or the world point.  A ray whose p the tick
+ *     would drop for validity (NaN, not finite, outside near .. far) or by the self filter is not cast; a p outside the window is fine, the ray still
+ *     crosses the window.  Only the pixels with i mod stride == 0 and j mod stride == 0, or the points with k mod stride == 0, cast a ray.
+ *  3. Samples.  With Lh = hypot(px - sx, py - sy), sample k = 0, 1, ... lies at the horizontal distance r_k = (k + 0.5) res from s:
+ *         (x_k, y_k) = (sx, sy) + r_k (px - sx, py - sy) / Lh,      z_k = sz + (pz - sz) r_k / Lh
+ *     A sample is made while r_k <= Lh - end_guard and k < 2 G.  Lh == 0, or Lh - end_guard below the first sample, gives no samples and no division
+ *     (one reciprocal of Lh per ray otherwise).  The cell of a sample is (floor(x_k * (1 / res)), floor(y_k * (1 / res))) with the reciprocal formed
+ *     once, in fp32 - NOT the tick's floor(x / res): a sample within a rounding error of a cell border may fall on the other side of it than the
+ *     tick would put it.  The indices are clamped to +-1e9 before the window test, as in the tick, so no coordinate can index outside the map.  A
+ *     sample whose cell is outside the window, or whose z_k is NaN, is dropped; otherwise bound[cell] = min(bound[cell], z_k), an LDS atomic minimum
+ *     on the tick's order-preserving integer key: the result does not depend on the order of the lanes, pixels or points.  This is a definition
+ *     by sampling, not a cell traversal: a ray may clip a cell's corner without sampling it, which errs on the side of keeping cells.
+ *  4. Clean.  For every slot with a bound whose height h is not NaN: without a variance layer the cell becomes NaN when h > bound + margin; with
+ *     one bound (pgtt_elevation_bind_var) the test is h - sigmas * sqrtf(v) > bound + margin and `var` becomes NaN with `map`.  cleared[e] = the
+ *     number of such cells, an integer sum.  bound_out, when bound, is the bound layer in the slot layout of `map`, NaN where no sample fell.
+ *  5. Nothing else is written: est, known, obs_out and origin are the tick's outputs and stay as they were.  The tick that follows sees the
+ *     cleaned map and does what it always did.
+ * An env's outputs depend on its own rows only.  One launch, one workgroup of 256 lanes per env, one key word per slot in LDS (4 G G bytes, every
+ * G the map allows), LDS integer atomics only, no global atomics.  Not covered: a hold step behind pgtt_elevation_follow (a stale image must not
+ * clean), lowering a cell instead of forgetting it, the rays of pixels that hit nothing.
  */
 #ifndef PGTT_ELEVATION_H_
 #define PGTT_ELEVATION_H_
@@ -346,6 +378,28 @@ int pgtt_elevation_sizeof_var(void);
 int pgtt_elevation_sizeof_fill(void);
 int pgtt_elevation_sizeof_config(void);
 int pgtt_elevation_sizeof_buffers(void);
+
+/* Visibility clean-up: its settings (all finite) and its two caller-owned device outputs, sized for N */
+typedef struct PgttElevationVisibility {
+  float margin;                          /* metres, > 0: a cell is contradicted when h (see sigmas) > bound + margin */
+  float end_guard;                       /* metres, >= 0: samples closer than this (horizontally) to the ray's end point are not made */
+  int32_t stride;                        /* >= 1: image pixels with i % stride == 0 and j % stride == 0 cast a ray; points with k % stride == 0 */
+  float sigmas;                          /* >= 0, read only with a variance layer bound: h is replaced by h - sigmas * sqrtf(v) in the test */
+  float sensor_pos[3];                   /* points source only: the sensor's position in the BASE frame (the image source uses cfg.mount_pos) */
+  int32_t* cleared;                      /* [N], required: cells set to NaN by this call */
+  float* bound_out;                      /* [N][G][G] or NULL: the bound layer in the slot layout of `map`, NaN = no sample fell into the cell */
+} PgttElevationVisibility;
+
+/* the settings' ranges alone (the pointers are not looked at): host only, needs no GPU.  PGTT_E_ARG for NULL or a value outside its range. */
+int pgtt_elevation_check_visibility(const PgttElevationVisibility* v);
+/* PGTT_E_ARG for a NULL struct, a NULL cleared or a setting outside its range.  May be called before or after the buffers are bound and persists
+ * across later binds, like pgtt_elevation_bind_fill. */
+int pgtt_elevation_bind_visibility(pgtt_elevation_handle h, const PgttElevationVisibility* v);
+/* the clean-up for all N envs, called BEFORE the tick of the same step with that tick's clear arguments: ONE launch on `stream`, no allocation, no
+ * synchronisation, no read-back, capturable.  PGTT_E_STATE before the buffers are bound (either kind of bind) or before
+ * pgtt_elevation_bind_visibility. */
+int pgtt_elevation_visibility(pgtt_elevation_handle h, const uint8_t* clear_mask, int clear_all, int use_done, void* stream);
+int pgtt_elevation_sizeof_visibility(void);
 /* "src=<SHA-256 of pgtt_elevation.hip and the files it includes>;flavor=product" */
 const char* pgtt_elevation_build_info(void);
 const char* pgtt_elevation_last_error(void);

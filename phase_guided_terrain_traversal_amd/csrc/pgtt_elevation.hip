@@ -41,6 +41,10 @@
 // Odometry drift (pgtt_elevation_odometry): odometry_kernel<POINTS> writes the estimated pose [7][N] the map may be bound to in place of `state`, and
 // with POINTS the world points re-registered at it; odometry_advance_kernel behind it advances the draws' epoch.  Described at the kernel.  It reads
 // and writes nothing of the handle's buffers, and no kernel above knows of it.
+//
+// Visibility clean-up (pgtt_elevation_visibility): visibility_kernel<POINTS>, a launch of its own in front of a tick.  The rays of the image or of the
+// points lower a bound per slot in LDS, and a cell that stands above its bound by more than the margin is forgotten.  Described at the kernel.  It
+// writes `map` (and `var`) and its own two outputs, and no kernel above knows of it.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -985,6 +989,205 @@ __global__ void __launch_bounds__(64) odometry_advance_kernel(int64_t* counter) 
   if (threadIdx.x == 0 && blockIdx.x == 0) counter[0] = counter[0] + 1;
 }
 
+// ---------------------------------------------------------------- visibility clean-up (pgtt_elevation_visibility): rays forget contradicted cells
+struct VisArgs {
+  const float* state; const float* depth; const float* done; const uint8_t* clear_mask; const float* points; const int32_t* origin;
+  float* map; float* var; int32_t* cleared; float* bound_out;
+  int N, W, H, G, P, stride, clear_all, use_done, self_on, vec_map, vec_out;
+  float near_m, far_m, res, tu, tv, margin, end_guard, sigmas;
+  float mpos[3], mquat[4], self_half[3], spos[3];
+};
+
+// visibility_kernel<POINTS>: one workgroup of four waves per env, in the phases of the tick.  Dynamic LDS: sh_b[G G], the bound of every slot as the
+// tick's order-preserving key, kNoKey = no sample fell into the slot (above the key of every value a sample can have: a NaN z is not a sample).
+//   skip     every lane reads the env's clear flags alike: an env the tick will clear writes cleared = 0 and a NaN bound_out, and returns before any
+//            barrier.
+//   phase A  lane 0 stages the base pose, the sensor position, the camera basis (the image) and the window of the stored origin; the others set the
+//            keys to kNoKey.
+//   phase B  a per-lane ray loop, ray r = tid + 256 n of the strided pixels in row-major order (or of the strided points): the 64 lanes of a wave
+//            hold neighbours of one image row, whose rays are about as long as each other, so a wave's lanes leave the sample loop together; the four
+//            waves take the image's rows in turn, so each gets far rows and near rows alike.  Per ray one reciprocal of Lh; per sample two FMAs for
+//            x and y, one for z, the cell, the window test and one ds_min_u32.
+//   phase C  `map` (and `var`) stream through in 16-byte runs (dwords when G G is no multiple of 4), a run is written back only when one of its
+//            slots was forgotten; bound_out streams out; the count is a wave reduction and one LDS exchange.
+// LDS integer atomics only; no global atomics, no scratch.
+template <bool POINTS>
+__global__ void __launch_bounds__(kLanes) visibility_kernel(VisArgs a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned sh_b[];      // [G * G]
+  __shared__ float sh_p[P_N];
+  __shared__ int sh_i[I_N];
+  __shared__ int sh_cnt[kLanes / 64];
+  const int e = blockIdx.x, tid = threadIdx.x, G = a.G, GG = G * G;
+  const long N = a.N;
+  const float nanv = __uint_as_float(0x7fc00000u);
+
+  // ---- skip: the tick behind this call will clear the env
+  if (a.clear_all || (a.clear_mask && a.clear_mask[e]) || (a.use_done && a.done && a.done[e] != 0.f)) {
+    if (tid == 0) a.cleared[e] = 0;
+    if (a.bound_out) {
+      float* bo = a.bound_out + (long)e * GG;
+      for (int s = tid; s < GG; s += kLanes) bo[s] = nanv;
+    }
+    return;
+  }
+
+  // ---- phase A: the pose, the sensor and the window (lane 0); the bounds start empty
+  if (tid == 0) {
+    const float* S = a.state + e;
+    const float bx = S[(PGTT_S_QPOS + 0) * N], by = S[(PGTT_S_QPOS + 1) * N], bz = S[(PGTT_S_QPOS + 2) * N];
+    float qw = S[(PGTT_S_QPOS + 3) * N], qx = S[(PGTT_S_QPOS + 4) * N], qy = S[(PGTT_S_QPOS + 5) * N], qz = S[(PGTT_S_QPOS + 6) * N];
+    const float qn = sqrtf(qw * qw + qx * qx + qy * qy + qz * qz);
+    qw /= qn; qx /= qn; qy /= qn; qz /= qn;
+    const float r00 = qw * qw + qx * qx - qy * qy - qz * qz, r01 = 2.f * (qx * qy - qw * qz), r02 = 2.f * (qx * qz + qw * qy);
+    const float r10 = 2.f * (qx * qy + qw * qz), r11 = qw * qw - qx * qx + qy * qy - qz * qz, r12 = 2.f * (qy * qz - qw * qx);
+    const float r20 = 2.f * (qx * qz - qw * qy), r21 = 2.f * (qy * qz + qw * qx), r22 = qw * qw - qx * qx - qy * qy + qz * qz;
+    sh_p[P_BASE + 0] = bx; sh_p[P_BASE + 1] = by; sh_p[P_BASE + 2] = bz;
+    sh_p[P_RB + 0] = r00; sh_p[P_RB + 1] = r01; sh_p[P_RB + 2] = r02; sh_p[P_RB + 3] = r10; sh_p[P_RB + 4] = r11; sh_p[P_RB + 5] = r12;
+    sh_p[P_RB + 6] = r20; sh_p[P_RB + 7] = r21; sh_p[P_RB + 8] = r22;
+    // the sensor: the tick's camera position, or the points' sensor_pos, both in the base frame
+    const float* mp = POINTS ? a.spos : a.mpos;
+    sh_p[P_CAM + 0] = bx + r00 * mp[0] + r01 * mp[1] + r02 * mp[2];
+    sh_p[P_CAM + 1] = by + r10 * mp[0] + r11 * mp[1] + r12 * mp[2];
+    sh_p[P_CAM + 2] = bz + r20 * mp[0] + r21 * mp[1] + r22 * mp[2];
+    if constexpr (!POINTS) {
+      const float mw = a.mquat[0], mx = a.mquat[1], my = a.mquat[2], mz = a.mquat[3];
+      const float cw = qw * mw - qx * mx - qy * my - qz * mz, cx = qw * mx + qx * mw + qy * mz - qz * my;
+      const float cyq = qw * my - qx * mz + qy * mw + qz * mx, cz = qw * mz + qx * my - qy * mx + qz * mw;
+      const float fx = cw * cw + cx * cx - cyq * cyq - cz * cz, fy = 2.f * (cx * cyq + cw * cz), fz = 2.f * (cx * cz - cw * cyq);
+      const float ux = 2.f * (cx * cz + cw * cyq), uy = 2.f * (cyq * cz - cw * cx), uz = cw * cw - cx * cx - cyq * cyq + cz * cz;
+      sh_p[P_FWD + 0] = fx; sh_p[P_FWD + 1] = fy; sh_p[P_FWD + 2] = fz;
+      sh_p[P_UP + 0] = ux; sh_p[P_UP + 1] = uy; sh_p[P_UP + 2] = uz;
+      sh_p[P_RIGHT + 0] = fy * uz - fz * uy; sh_p[P_RIGHT + 1] = fz * ux - fx * uz; sh_p[P_RIGHT + 2] = fx * uy - fy * ux;
+    }
+    // the origin as the last tick left it; one outside the tick's clamp (a map never ticked) is as far away as the clamp (fill_kernel's rule)
+    const int ox = min(max(a.origin[2 * (long)e], -(1 << 30)), 1 << 30), oy = min(max(a.origin[2 * (long)e + 1], -(1 << 30)), 1 << 30);
+    const int lox = ox - G / 2, loy = oy - G / 2;
+    sh_i[I_LOX] = lox; sh_i[I_LOY] = loy; sh_i[I_LMX] = floor_mod(lox, G); sh_i[I_LMY] = floor_mod(loy, G);
+  }
+  for (int s = tid; s < GG; s += kLanes) sh_b[s] = kNoKey;
+  __syncthreads();
+
+  // ---- phase B: the rays
+  {
+    const float sx = sh_p[P_CAM + 0], sy = sh_p[P_CAM + 1], sz = sh_p[P_CAM + 2];
+    const float bpx = uni(sh_p[P_BASE + 0]), bpy = uni(sh_p[P_BASE + 1]), bpz = uni(sh_p[P_BASE + 2]);
+    const float b00 = uni(sh_p[P_RB + 0]), b01 = uni(sh_p[P_RB + 1]), b02 = uni(sh_p[P_RB + 2]), b10 = uni(sh_p[P_RB + 3]), b11 = uni(sh_p[P_RB + 4]);
+    const float b12 = uni(sh_p[P_RB + 5]), b20 = uni(sh_p[P_RB + 6]), b21 = uni(sh_p[P_RB + 7]), b22 = uni(sh_p[P_RB + 8]);
+    const int lox = sh_i[I_LOX], loy = sh_i[I_LOY], lmx = sh_i[I_LMX], lmy = sh_i[I_LMY];
+    const float res = a.res, ires = 1.0f / a.res, end_guard = a.end_guard;
+    const int kmax = 2 * G;
+    // one ray from the sensor to the admitted end point p
+    auto ray = [&](float px, float py, float pz) {
+      if (a.self_on) {
+        const float dx = px - bpx, dy = py - bpy, dz = pz - bpz;             // R^T (p - base): the tick's self filter
+        const float lx = b00 * dx + b10 * dy + b20 * dz, ly = b01 * dx + b11 * dy + b21 * dz, lz = b02 * dx + b12 * dy + b22 * dz;
+        if (fabsf(lx) <= a.self_half[0] && fabsf(ly) <= a.self_half[1] && fabsf(lz) <= a.self_half[2]) return;
+      }
+      const float dx = px - sx, dy = py - sy;
+      const float Lh = hypotf(dx, dy), lim = Lh - end_guard;
+      if (!(0.5f * res <= lim)) return;                                 // no sample, no division: Lh == 0, a NaN, a ray shorter than the first sample
+      const float inv = 1.0f / Lh;
+      const float ux = dx * inv, uy = dy * inv, uz = (pz - sz) * inv;
+      for (int k = 0; k < kmax; k++) {
+        const float rk = ((float)k + 0.5f) * res;
+        if (!(rk <= lim)) break;
+        const float x = fmaf(rk, ux, sx), y = fmaf(rk, uy, sy), z = fmaf(rk, uz, sz);
+        const int relx = (int)fminf(fmaxf(floorf(x * ires), -kCellClamp), kCellClamp) - lox;
+        const int rely = (int)fminf(fmaxf(floorf(y * ires), -kCellClamp), kCellClamp) - loy;
+        if ((unsigned)relx >= (unsigned)G || (unsigned)rely >= (unsigned)G || !(z == z)) continue;
+        int cx = relx + lmx, cy = rely + lmy;                           // (lo + rel) mod G
+        cx -= cx >= G ? G : 0; cy -= cy >= G ? G : 0;
+        atomicMin(&sh_b[cx * G + cy], key_of(z));
+      }
+    };
+    const int stride = a.stride;
+    if constexpr (POINTS) {
+      const float* pts = a.points + (long)e * a.P * 3;
+      const int nray = (a.P + stride - 1) / stride;
+      for (int r = tid; r < nray; r += kLanes) {
+        const long k = (long)r * stride;
+        const float px = pts[3 * k], py = pts[3 * k + 1], pz = pts[3 * k + 2];
+        if (!(fabsf(px) < INFINITY && fabsf(py) < INFINITY && fabsf(pz) < INFINITY)) continue;      // the tick's validity test
+        ray(px, py, pz);
+      }
+    } else {
+      const float fx = sh_p[P_FWD + 0], fy = sh_p[P_FWD + 1], fz = sh_p[P_FWD + 2];
+      const float rx = sh_p[P_RIGHT + 0], ry = sh_p[P_RIGHT + 1], rz = sh_p[P_RIGHT + 2];
+      const float ux = sh_p[P_UP + 0], uy = sh_p[P_UP + 1], uz = sh_p[P_UP + 2];
+      const int W = a.W, nw = (a.W + stride - 1) / stride, nray = nw * ((a.H + stride - 1) / stride);
+      const float* img = a.depth + (long)e * a.W * a.H;
+      for (int r = tid; r < nray; r += kLanes) {
+        const int ri = r / nw, i = ri * stride, j = (r - ri * nw) * stride;
+        const float d = img[i * W + j];
+        if (!(d > a.near_m && d < a.far_m)) continue;                  // the tick's validity test and its unprojection
+        const float u = (2.f * ((float)j + 0.5f) / (float)W - 1.f) * a.tu, v = (1.f - 2.f * ((float)i + 0.5f) / (float)a.H) * a.tv;
+        ray(sx + d * (fx + u * rx + v * ux), sy + d * (fy + u * ry + v * uy), sz + d * (fz + u * rz + v * uz));
+      }
+    }
+  }
+  __syncthreads();
+
+  // ---- phase C: the map (and the variance layer) stream through; the bound layer streams out
+  int count = 0;
+  {
+    float* mp = a.map + (long)e * GG;
+    float* vp = a.var ? a.var + (long)e * GG : nullptr;
+    float* bo = a.bound_out ? a.bound_out + (long)e * GG : nullptr;
+    const float margin = a.margin, sigmas = a.sigmas;
+    // one slot: h (and v) in and out; -> true when the cell is forgotten
+    auto slot = [&](float& h, float& v, unsigned key) {
+      if (key == kNoKey || h != h) return false;
+      const float t = vp ? h - sigmas * sqrtf(v) : h;
+      if (!(t > value_of(key) + margin)) return false;
+      h = nanv; v = nanv;
+      return true;
+    };
+    if (a.vec_map) {
+      for (int s = 4 * tid; s < GG; s += 4 * kLanes) {
+        const float4 hv = *reinterpret_cast<const float4*>(mp + s);
+        float4 vv = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (vp) vv = *reinterpret_cast<const float4*>(vp + s);
+        const uint4 kv = *reinterpret_cast<const uint4*>(sh_b + s);
+        float h[4] = {hv.x, hv.y, hv.z, hv.w}, v[4] = {vv.x, vv.y, vv.z, vv.w};
+        const unsigned k4[4] = {kv.x, kv.y, kv.z, kv.w};
+        int n = 0;
+#pragma unroll
+        for (int k = 0; k < 4; k++) n += slot(h[k], v[k], k4[k]) ? 1 : 0;
+        if (n) {
+          *reinterpret_cast<float4*>(mp + s) = make_float4(h[0], h[1], h[2], h[3]);
+          if (vp) *reinterpret_cast<float4*>(vp + s) = make_float4(v[0], v[1], v[2], v[3]);
+          count += n;
+        }
+      }
+    } else {
+      for (int s = tid; s < GG; s += kLanes) {
+        float h = mp[s], v = vp ? vp[s] : 0.f;
+        if (slot(h, v, sh_b[s])) {
+          mp[s] = h;
+          if (vp) vp[s] = v;
+          count++;
+        }
+      }
+    }
+    if (bo) {
+      if (a.vec_out) {
+        for (int s = 4 * tid; s < GG; s += 4 * kLanes) {
+          const uint4 kv = *reinterpret_cast<const uint4*>(sh_b + s);
+          *reinterpret_cast<float4*>(bo + s) = make_float4(kv.x == kNoKey ? nanv : value_of(kv.x), kv.y == kNoKey ? nanv : value_of(kv.y),
+                                                            kv.z == kNoKey ? nanv : value_of(kv.z), kv.w == kNoKey ? nanv : value_of(kv.w));
+        }
+      } else {
+        for (int s = tid; s < GG; s += kLanes) { const unsigned k = sh_b[s]; bo[s] = k == kNoKey ? nanv : value_of(k); }
+      }
+    }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) count += __shfl_xor(count, off, 64);
+  if ((tid & 63) == 0) sh_cnt[tid >> 6] = count;
+  __syncthreads();
+  if (tid == 0) a.cleared[e] = sh_cnt[0] + sh_cnt[1] + sh_cnt[2] + sh_cnt[3];
+}
+
 // the config's checks; `who` prefixes the message
 int resolve(const PgttElevationConfig* c, const char* who) {
   const std::string p = std::string(who) + ": ";
@@ -1026,6 +1229,8 @@ struct pgtt_elevation_map {
   bool has_var = false;
   PgttElevationOdometry odo{};           // pgtt_elevation_bind_odometry; kept by the other binds
   bool has_odo = false;
+  PgttElevationVisibility vis{};         // pgtt_elevation_bind_visibility; kept by the other binds
+  bool has_vis = false;
 };
 
 namespace {
@@ -1139,11 +1344,69 @@ int resolve_odometry(const PgttElevationOdometry* o, const char* who) {
   return PGTT_OK;
 }
 
+// the visibility settings' ranges; `who` prefixes the message
+int resolve_visibility(const PgttElevationVisibility* v, const char* who) {
+  const std::string p = std::string(who) + ": ";
+  if (!v) return fail(PGTT_E_ARG, p + "null settings");
+  const float f[6] = {v->margin, v->end_guard, v->sigmas, v->sensor_pos[0], v->sensor_pos[1], v->sensor_pos[2]};
+  for (int i = 0; i < 6; i++)
+    if (!std::isfinite(f[i])) return fail(PGTT_E_ARG, p + "margin, end_guard, sigmas and sensor_pos must be finite");
+  if (!(v->margin > 0.f)) return fail(PGTT_E_ARG, p + "margin must be > 0");
+  if (!(v->end_guard >= 0.f)) return fail(PGTT_E_ARG, p + "end_guard must be >= 0");
+  if (v->stride < 1) return fail(PGTT_E_ARG, p + "stride must be >= 1");
+  if (!(v->sigmas >= 0.f)) return fail(PGTT_E_ARG, p + "sigmas must be >= 0");
+  return PGTT_OK;
+}
+
 }  // namespace
 
 extern "C" {
 
 PGTT_SIDE_EXPORTS(elevation, ELEVATION)
+int pgtt_elevation_sizeof_visibility(void) { return (int)sizeof(PgttElevationVisibility); }
+
+int pgtt_elevation_check_visibility(const PgttElevationVisibility* v) { return resolve_visibility(v, "pgtt_elevation_check_visibility"); }
+
+int pgtt_elevation_bind_visibility(pgtt_elevation_handle h, const PgttElevationVisibility* v) {
+  if (!h || !v) return fail(PGTT_E_ARG, "pgtt_elevation_bind_visibility: null argument");
+  if (!v->cleared) return fail(PGTT_E_ARG, "pgtt_elevation_bind_visibility: cleared is required");
+  if (int rc = resolve_visibility(v, "pgtt_elevation_bind_visibility")) return rc;
+  h->vis = *v;
+  h->has_vis = true;
+  return PGTT_OK;
+}
+
+int pgtt_elevation_visibility(pgtt_elevation_handle h, const uint8_t* clear_mask, int clear_all, int use_done, void* stream) {
+  if (!h) return fail(PGTT_E_ARG, "pgtt_elevation_visibility: null handle");
+  if (!h->bound) return fail(PGTT_E_STATE, "pgtt_elevation_visibility: no buffers bound (pgtt_elevation_bind or pgtt_elevation_bind_points first)");
+  if (!h->has_vis) return fail(PGTT_E_STATE, "pgtt_elevation_visibility: no visibility bound (pgtt_elevation_bind_visibility first)");
+  HIP_TRY(hipSetDevice(h->device));
+  const PgttElevationConfig& c = h->cfg;
+  const PgttElevationBuffers& b = h->buf;
+  const PgttElevationVisibility& v = h->vis;
+  const bool points = h->points != nullptr;                            // the source: whichever bind was made last
+  VisArgs a{};
+  a.state = b.state; a.depth = b.depth; a.done = b.done; a.clear_mask = clear_mask; a.points = h->points; a.origin = b.origin;
+  a.map = b.map; a.var = h->has_var ? h->var.var : nullptr; a.cleared = v.cleared; a.bound_out = v.bound_out;
+  a.N = h->num_envs; a.W = c.width; a.H = c.height; a.G = c.grid; a.P = h->P; a.stride = v.stride;
+  a.clear_all = clear_all ? 1 : 0; a.use_done = use_done ? 1 : 0;
+  a.self_on = (c.self_half[0] != 0.f || c.self_half[1] != 0.f || c.self_half[2] != 0.f) ? 1 : 0;
+  // 16-byte runs need every env's block to start on a 16-byte boundary: map and var stream together
+  const bool quads = (c.grid * c.grid) % 4 == 0;
+  a.vec_map = (quads && ((uintptr_t)b.map & 15) == 0 && ((uintptr_t)a.var & 15) == 0) ? 1 : 0;
+  a.vec_out = (quads && ((uintptr_t)v.bound_out & 15) == 0) ? 1 : 0;
+  const double th = std::tan(0.5 * (double)c.fovy_deg * 3.14159265358979323846 / 180.0);
+  a.near_m = c.near; a.far_m = c.far; a.res = c.res; a.tu = (float)(th * c.width / c.height); a.tv = (float)th;
+  a.margin = v.margin; a.end_guard = v.end_guard; a.sigmas = v.sigmas;
+  for (int i = 0; i < 3; i++) { a.mpos[i] = c.mount_pos[i]; a.self_half[i] = c.self_half[i]; a.spos[i] = v.sensor_pos[i]; }
+  for (int i = 0; i < 4; i++) a.mquat[i] = c.mount_quat[i];
+  const size_t lds = (size_t)c.grid * c.grid * sizeof(unsigned);
+  if (points) hipLaunchKernelGGL(visibility_kernel<true>, dim3(h->num_envs), dim3(kLanes), lds, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL(visibility_kernel<false>, dim3(h->num_envs), dim3(kLanes), lds, (hipStream_t)stream, a);
+  HIP_TRY(hipGetLastError());
+  return PGTT_OK;
+}
+
 int pgtt_elevation_sizeof_odometry(void) { return (int)sizeof(PgttElevationOdometry); }
 
 int pgtt_elevation_check_odometry(const PgttElevationOdometry* o) { return resolve_odometry(o, "pgtt_elevation_check_odometry"); }

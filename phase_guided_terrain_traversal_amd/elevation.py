@@ -19,6 +19,9 @@ points of the env's LiDAR (lidar.py) instead: the sensor such a stack reads on t
     em = ElevationMap(env, odometry=True)                    # the map is registered with a dead-reckoned pose that drifts in x, y, z and yaw
     em.pose_est, em.odo                                      # (ODOMETRY_DEFAULTS), not with the simulator's: [7, N] and [N, 12] (e_xyz, psi, ...)
 
+    em = ElevationMap(env, visibility=True)                  # visibility clean-up in front of every tick: a ray that passed below a cell's height
+    em.cleared                                               # on its way to the ground forgets the cell (VISIBILITY_DEFAULTS); [N] int32 per call
+
 `Joystick(..., depth=dict(...), elevation=dict(...) | True)` owns one and ticks it behind the camera (env.elevation_obs);
 `Joystick(..., lidar=dict(...), elevation=dict(source="lidar"))` one that is ticked behind the LiDAR.  The module is not imported by env.py unless
 an elevation map is asked for.
@@ -54,6 +57,10 @@ MAX_BAND, VAR_MAX_GRID = 0.5, 64                   # PGTT_ELEVATION_MAX_BAND, PG
 # to 0.005 rad / s and an odometry scale error of up to 2 %, both drawn once per episode - settings, not measured facts about a robot
 ODOMETRY_DEFAULTS = dict(sigma_xy=0.02, sigma_z=0.01, sigma_yaw=0.01, yaw_bias=0.005, scale=0.02, seed=0)
 RS_ODOMETRY, ODO_WORDS = 34, 12                    # PGTT_RS_ODOMETRY, PGTT_ELEVATION_ODO_WORDS
+# visibility=True: a cell is forgotten when it stands more than 5 cm above a ray, no sample within one and a half cells (of DEFAULTS' 4 cm) of the
+# ray's end - the cell that was hit and its neighbour are the tick's business -, every second row and column of the image (every second point)
+# casts a ray, and with a variance layer the height is taken as it stands (sigmas = 0) - settings, not facts; end_guard=None is 1.5 res
+VISIBILITY_DEFAULTS = dict(margin=0.05, end_guard=None, stride=2, sigmas=0.0)
 
 f, i32 = C.c_float, C.c_int32
 
@@ -85,7 +92,12 @@ class PgttElevationOdometry(C.Structure):
                 ("dt", f), ("sigma_xy", f), ("sigma_z", f), ("sigma_yaw", f), ("yaw_bias", f), ("scale", f)]
 
 
-assert C.sizeof(PgttElevationVar) == 48 and C.sizeof(PgttElevationOdometry) == 104
+class PgttElevationVisibility(C.Structure):
+    _fields_ = [("margin", f), ("end_guard", f), ("stride", i32), ("sigmas", f), ("sensor_pos", f * 3), ("cleared", C.c_void_p),
+                ("bound_out", C.c_void_p)]
+
+
+assert C.sizeof(PgttElevationVar) == 48 and C.sizeof(PgttElevationOdometry) == 104 and C.sizeof(PgttElevationVisibility) == 48
 
 
 class ElevationError(RuntimeError):
@@ -105,9 +117,12 @@ SIDE = _sidelib.SideLib("elevation", ElevationError, {
     "pgtt_elevation_var": (None, [vp, vp, C.c_int, C.c_int, vp]), "pgtt_elevation_var_points": (None, [vp, vp, C.c_int, C.c_int, vp]),
     "pgtt_elevation_check_odometry": (None, [C.POINTER(PgttElevationOdometry)]),
     "pgtt_elevation_bind_odometry": (None, [vp, C.POINTER(PgttElevationOdometry)]), "pgtt_elevation_odometry": (None, [vp, vp, C.c_int, C.c_int, vp]),
+    "pgtt_elevation_check_visibility": (None, [C.POINTER(PgttElevationVisibility)]),
+    "pgtt_elevation_bind_visibility": (None, [vp, C.POINTER(PgttElevationVisibility)]),
+    "pgtt_elevation_visibility": (None, [vp, vp, C.c_int, C.c_int, vp]),
 }, {"pgtt_elevation_sizeof_config": PgttElevationConfig, "pgtt_elevation_sizeof_buffers": PgttElevationBuffers,
     "pgtt_elevation_sizeof_fill": PgttElevationFill, "pgtt_elevation_sizeof_var": PgttElevationVar,
-    "pgtt_elevation_sizeof_odometry": PgttElevationOdometry})
+    "pgtt_elevation_sizeof_odometry": PgttElevationOdometry, "pgtt_elevation_sizeof_visibility": PgttElevationVisibility})
 LIB_PATH, EXPORTS, lib, check, build_info = SIDE.path, SIDE.exports, SIDE.lib, SIDE.check, SIDE.build_info
 
 
@@ -163,6 +178,32 @@ def odometry_struct(dt, sigma_xy=0.02, sigma_z=0.01, sigma_yaw=0.01, yaw_bias=0.
     return o
 
 
+def visibility_settings(visibility=None, res=DEFAULTS["res"]) -> Optional[Dict]:
+    """ElevationMap's `visibility` argument as a full dict: None / False -> None (no clean-up), True -> VISIBILITY_DEFAULTS, a dict -> the defaults
+    with it on top; an end_guard of None becomes 1.5 res.  ValueError for a key that is no setting or for anything else."""
+    if visibility is None or visibility is False:
+        return None
+    if visibility is not True and not isinstance(visibility, dict):
+        raise ValueError(f"ElevationMap(visibility=...): visibility must be True or a dict of settings, not {visibility!r}")
+    over = {} if visibility is True else dict(visibility)
+    unknown = sorted(set(over) - set(VISIBILITY_DEFAULTS))
+    if unknown:
+        raise ValueError(f"ElevationMap(visibility=...): unknown setting(s) {unknown}; the settings are {sorted(VISIBILITY_DEFAULTS)}")
+    out = {**VISIBILITY_DEFAULTS, **over}
+    if out["end_guard"] is None:
+        out["end_guard"] = 1.5 * float(res)
+    return out
+
+
+def visibility_struct(margin=0.05, end_guard=0.06, stride=2, sigmas=0.0, sensor_pos=(0.0, 0.0, 0.0), cleared=None, bound_out=None) -> PgttElevationVisibility:
+    """no checks: the library makes its own (pgtt_elevation_check_visibility)"""
+    v = PgttElevationVisibility()
+    v.margin, v.end_guard, v.stride, v.sigmas = float(margin), float(end_guard), int(stride), float(sigmas)
+    v.sensor_pos[:] = [float(x) for x in sensor_pos]
+    v.cleared, v.bound_out = cleared, bound_out
+    return v
+
+
 def config_struct(width, height, fovy, near, far, mount_pos=(0.0, 0.0, 0.0), mount_quat=(1.0, 0.0, 0.0, 0.0), mount_body=0, grid=64, res=0.04,
                   alpha=1.0, self_half=(0.0, 0.0, 0.0), scan_dist_x=0.1, scan_dist_y=0.1, obs_dim=abi.OBS, scan_row0=38) -> PgttElevationConfig:
     """no checks: the library makes its own"""
@@ -203,14 +244,26 @@ class ElevationMap(_sidelib.Handle):
     points are re-registered at it (`points_est` [N, P, 3]) - and the map is bound to those in place of the env's state and the LiDAR's points.  dt is
     the env's control step, the draws are keyed by `seed` and env.env_id_offset.  Works with fill, variance and follow_sensor; nothing is corrected
     (no loop closure).  The defaults are settings, not facts about a robot.  odometry=None, the default: nothing of this is allocated or called.
+    visibility = True (VISIBILITY_DEFAULTS) or a dict over them: tick() enqueues pgtt_elevation_visibility behind the odometry call and in front of
+    the tick, with the same clear arguments - every stride-th ray of the image (or point of the LiDAR, from its mount on the torso) lowers a bound
+    over the cells it passes, and a cell that stands more than `margin` above its bound is forgotten (NaN, in `var` too).  `cleared` [N] int32 is the
+    number of cells the last call forgot; with dense_bound=True `bound` [N, G, G] is the bound layer (NaN = no ray passed).  Not with follow_sensor: a
+    hold step must not clean with a stale image.  visibility=None, the default: nothing of this is allocated or called.
     Runs on the env's device and current stream; reads env.depth or the LiDAR's points, env.buffers["state" | "obs_state" | "done"] and writes nothing
     but its own tensors."""
     _prefix, _check = "pgtt_elevation", staticmethod(check)
 
     def __init__(self, env, grid: int = 64, res: float = 0.04, alpha: float = 1.0, self_half: Sequence[float] = (0.45, 0.25, 0.45),
-                 source: str = "depth", fill: int = 0, dense: bool = False, follow_sensor: bool = False, variance=None, odometry=None):
+                 source: str = "depth", fill: int = 0, dense: bool = False, follow_sensor: bool = False, variance=None, odometry=None,
+                 visibility=None, dense_bound: bool = False):
         self.variance = variance_settings(variance)
         self.odometry = odometry_settings(odometry)
+        self.visibility = visibility_settings(visibility, res)
+        if self.visibility is not None and follow_sensor:
+            raise ValueError("ElevationMap: visibility with follow_sensor=True is not built (a hold step must not clean with a stale image)")
+        if dense_bound and self.visibility is None:
+            raise ValueError("ElevationMap: dense_bound=True asks for the clean-up's bound layer, so it needs visibility")
+        self._sensor_pos = (0.0, 0.0, 0.0)
         if self.variance is not None:
             if follow_sensor:
                 raise ValueError("ElevationMap: variance with follow_sensor=True is not built yet (the hold call would have to leave var alone)")
@@ -230,6 +283,11 @@ class ElevationMap(_sidelib.Handle):
                 raise ValueError("ElevationMap(source='lidar') needs an env with a LiDAR that writes points: Joystick(..., lidar=dict(...))")
             if lid.config.every != 1 and not self.follow_sensor:
                 raise ValueError(f"ElevationMap needs a LiDAR of period 1 (every={lid.config.every}): the map would fuse a stale scan again at every tick")
+            if self.visibility is not None:
+                if lid.config.mount_body != 0:
+                    raise ValueError(f"ElevationMap(visibility=...) supports a LiDAR on the torso only (mount_body == 0), not on body "
+                                     f"{lid.config.mount_body}: the rays start at the mount, which the map knows in the base frame alone")
+                self._sensor_pos = tuple(lid.config.mount_pos)
             od = env.observation_size["state"]
             self.config = config_struct(**PLACEHOLDER_CAMERA, grid=grid, res=res, alpha=alpha, self_half=self_half,
                                         scan_dist_x=env.config["scan_dist_x"], scan_dist_y=env.config["scan_dist_y"], obs_dim=od,
@@ -274,6 +332,11 @@ class ElevationMap(_sidelib.Handle):
             self.odo_counter = torch.zeros(1, dtype=torch.int64, device=dev)
             if source == "lidar":
                 self.points_est = torch.full_like(env.lidar_scanner.points, float("nan"))
+        if self.visibility is not None:
+            self.cleared = torch.zeros(n, dtype=torch.int32, device=dev)
+            if dense_bound:
+                self.bound = torch.full((n, self.grid, self.grid), float("nan"), dtype=torch.float32, device=dev)
+        self.dense_bound = bool(dense_bound)
         if self.follow_sensor:
             sensor = env.lidar_scanner if source == "lidar" else env.depth_camera
             self.sensor_counter, self.sensor_every = sensor.counter, int(sensor.config.every)
@@ -311,6 +374,10 @@ class ElevationMap(_sidelib.Handle):
                                 points_est=self.points_est.data_ptr() if lidar else None, P=self.points_est.shape[1] if lidar else 0,
                                 pose_est=self.pose_est.data_ptr(), odo=self.odo.data_ptr(), counter=self.odo_counter.data_ptr())
             check(self._lib.pgtt_elevation_bind_odometry(self._h, C.byref(o)))
+        if self.visibility is not None:
+            v = visibility_struct(**self.visibility, sensor_pos=self._sensor_pos, cleared=self.cleared.data_ptr(),
+                                  bound_out=self.bound.data_ptr() if self.dense_bound else None)
+            check(self._lib.pgtt_elevation_bind_visibility(self._h, C.byref(v)))
 
     def tick(self, clear_mask: Optional[torch.Tensor] = None, clear_all: bool = False, use_done: bool = False, force: bool = False) -> torch.Tensor:
         """integrate the env's current image (or LiDAR points) under its current pose and sample the scan: one launch on the env's current stream,
@@ -320,7 +387,8 @@ class ElevationMap(_sidelib.Handle):
         is what that sensor tick was given; on the others the clears are made, nothing else of the map changes and the scan is sampled from it at
         the current pose.  `force` is not read without follow_sensor.
         With odometry the pose estimate is updated first (two small launches), with the same clear arguments: a cleared env's estimate is the
-        truth again and its episode's scale error and gyro bias are drawn anew."""
+        truth again and its episode's scale error and gyro bias are drawn anew.
+        With visibility the clean-up is enqueued behind that and in front of the tick (one launch), with the same clear arguments."""
         mp = None
         if clear_mask is not None:
             self._mask = clear_mask.to(self.env.device, torch.uint8).contiguous()      # kept alive until the next tick: the launch is asynchronous
@@ -329,6 +397,8 @@ class ElevationMap(_sidelib.Handle):
         stream = torch.cuda.current_stream(self.env.device).cuda_stream
         if self.odometry is not None:
             check(self._lib.pgtt_elevation_odometry(self._h, mp, int(bool(clear_all)), int(bool(use_done)), stream))
+        if self.visibility is not None:
+            check(self._lib.pgtt_elevation_visibility(self._h, mp, int(bool(clear_all)), int(bool(use_done)), stream))
         if self.follow_sensor:
             check(self._lib.pgtt_elevation_follow(self._h, mp, int(bool(clear_all)), int(bool(use_done)), int(bool(force)), stream))
         elif self.variance is not None:
@@ -348,6 +418,19 @@ class ElevationMap(_sidelib.Handle):
             raise ElevationError("ElevationMap.fill(): this map was made with fill=0")
         check(self._lib.pgtt_elevation_fill(self._h, torch.cuda.current_stream(self.env.device).cuda_stream))
         return self.filled_obs
+
+    def clean(self, clear_mask: Optional[torch.Tensor] = None, clear_all: bool = False, use_done: bool = False) -> torch.Tensor:
+        """the visibility clean-up alone, on `map`, `origin` and the env's pose and image (or points) as they are: one launch on the env's current
+        stream, no synchronisation; the clear arguments are those of the tick that is to follow (an env it will clear is skipped).  -> cleared"""
+        if self.visibility is None:
+            raise ElevationError("ElevationMap.clean(): this map was made without visibility")
+        mp = None
+        if clear_mask is not None:
+            self._mask = clear_mask.to(self.env.device, torch.uint8).contiguous()
+            assert self._mask.shape == (self.env.num_envs,)
+            mp = self._mask.data_ptr()
+        check(self._lib.pgtt_elevation_visibility(self._h, mp, int(bool(clear_all)), int(bool(use_done)), torch.cuda.current_stream(self.env.device).cuda_stream))
+        return self.cleared
 
     def world_cells(self) -> torch.Tensor:
         """[N, G, G, 2] int64: the world cell (ix, iy) each slot of `map` holds under the current window"""

@@ -82,7 +82,11 @@ class Joystick:
         dead-reckoned pose that drifts in x, y, z and yaw instead of the simulator's (pgtt_elevation_odometry; elevation.ODOMETRY_DEFAULTS, settings and
         not facts about a robot): `env.odometry_pose` [7, N] is the estimate, `env.odometry_error` [N, 4] its position and yaw error (e_x, e_y, e_z,
         psi), zero after reset() and for an env whose episode just ended.  Works with fill, variance, follow_sensor and both sources.
-        obs, state, reward, done, the image and the LiDAR's outputs are what they are without it."""
+        obs, state, reward, done, the image and the LiDAR's outputs are what they are without it.
+        elevation=dict(visibility=True | dict(margin=..., end_guard=..., stride=..., sigmas=...), ...) cleans the map by visibility in front of every
+        tick (pgtt_elevation_visibility; elevation.VISIBILITY_DEFAULTS): a cell that a ray passed below on its way to the ground is forgotten, which
+        removes the ghosts a drifting pose leaves.  `env.elevation_cleared` [N] int32 is the number of cells the last step forgot.  With both sources
+        (a LiDAR on the torso); not with follow_sensor.  obs, state, reward, done and the sensors' outputs are what they are without it."""
         if student is not None and depth is None:
             raise ValueError("Joystick(student=...) needs depth=dict(...): the student reads the onboard depth image")
         wants_map = elevation is not None and elevation is not False
@@ -347,6 +351,11 @@ class Joystick:
         """[N, 4] float32, a view: the error (e_x, e_y, e_z, psi) of the pose the elevation map is registered with; None without odometry drift"""
         odo = getattr(self.elevation_map, "odo", None)
         return None if odo is None else odo[:, :4]
+
+    @property
+    def elevation_cleared(self) -> Optional[torch.Tensor]:
+        """[N] int32, a view: the cells the visibility clean-up forgot in front of the last tick of the elevation map; None without the clean-up"""
+        return getattr(self.elevation_map, "cleared", None)
 
     @property
     def odometry_pose(self) -> Optional[torch.Tensor]:

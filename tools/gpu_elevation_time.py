@@ -16,7 +16,11 @@ the depth-fused and the LiDAR-fused map, and on each of the two filled (--elevat
 --every 1,2,3,5: (vii) pgtt_elevation_follow behind a camera of each period M, in the same job as (i) and (iii): a hold call and a
 fresh call alone (the sensor's counter held where the call is the one or the other), and camera tick + map call in the camera's own schedule, in
 windows of 30 steps (a whole number of periods), which is the mean cost of perception per control step; with --eval, evaluate.py --elevation
---sensor_every M for each M, with and without --elevation_fill, next to the same command without the flag."""
+--sensor_every M for each M, with and without --elevation_fill, next to the same command without the flag.
+--visibility 1,2,4: (viii) pgtt_elevation_visibility alone at each stride, on a copy of the map the 41 ticks left, next to (i) in the
+same job; then the same for the LiDAR source (2048 points, an env of its own stepped alike) next to pgtt_elevation_points.  With --accuracy the
+accuracy block is repeated with the clean-up at the defaults, and both again at three times the odometry defaults, with the cells forgotten per env
+and step; with --eval, evaluate.py --elevation --odometry_drift at three times the defaults with and without --elevation_visibility, two seeds."""
 import argparse
 import math
 import os
@@ -148,11 +152,12 @@ class TorchElevation:
 DIST_BUCKETS = (("0", 0, 0), ("1-4", 1, 4), ("5-8", 5, 8), ("9+", 9, 254))
 
 
-def accuracy(terrain, steps_warm=50, steps=200, n=1000, fill=0):
+def accuracy(terrain, steps_warm=50, steps=200, n=1000, fill=0, extra=None, label=""):
     dr = domain_randomize(mjcf.load_model("stairs"), n, seed=0, terrain=terrain)
     kw = dict(params=torch.from_numpy(dr["params"]), variant=torch.from_numpy(dr["variant"]), box_friction=torch.from_numpy(dr["box_friction"]))
     env = Joystick("stairs", configs.evaluation_config("pgtt"), num_envs=n, terrain=terrain, device="cuda:0", autoreset=True, depth={},
-                   elevation=dict(fill=fill) if fill else True, **kw)
+                   elevation=dict(extra or {}, fill=fill) if fill or extra else True, **kw)
+    forgot = 0.0
     pi = load_policy("policy177", "cuda:0")
     env.reset(0)
     fse = {k: 0.0 for k in perceive.BANDS}
@@ -168,6 +173,8 @@ def accuracy(terrain, steps_warm=50, steps=200, n=1000, fill=0):
         for t in range(steps_warm + steps):
             _, _, done, _ = env.step(pi(env.buffers["obs_state"]))
             age = torch.where(done > 0, torch.zeros_like(age), age + 1)
+            if t >= steps_warm and env.elevation_cleared is not None:
+                forgot += float(env.elevation_cleared.sum())
             if t < steps_warm:
                 continue
             # the env's scan_z is the step's; a done env's state rows are the new episode's, so its target is not this pose's: leave it out
@@ -186,12 +193,14 @@ def accuracy(terrain, steps_warm=50, steps=200, n=1000, fill=0):
             young = known & (age < 50)[:, None]
             fresh_se += float((err ** 2 * young).sum()); fresh_cnt += float(young.sum())
     env.close()
-    lines = [f"accuracy: policy177 on the true observation, {n} envs, level4, full DR, steps {steps_warm}..{steps_warm + steps}; est against perceive.scan_target over the known points"]
+    lines = [f"accuracy{label}: policy177 on the true observation, {n} envs, level4, full DR, steps {steps_warm}..{steps_warm + steps}; est against perceive.scan_target over the known points"]
     for k in perceive.BANDS:
         lines.append(f"  {k:7s} rmse {math.sqrt(se[k] / max(cnt[k], 1)):.4f} m, known share {cnt[k] / max(tot[k], 1):.3f}")
     allse, allcnt = sum(se.values()), sum(cnt.values())
     lines.append(f"  all     rmse {math.sqrt(allse / max(allcnt, 1)):.4f} m; within 50 steps of a reset: rmse {math.sqrt(fresh_se / max(fresh_cnt, 1)):.4f} m on {fresh_cnt / max(allcnt, 1):.3f} of the known points; "
                  f"older: rmse {math.sqrt((allse - fresh_se) / max(allcnt - fresh_cnt, 1)):.4f} m")
+    if extra and "visibility" in extra:
+        lines.append(f"  visibility clean-up: {forgot / (n * steps):.3f} cells forgotten per env and step")
     if fill:
         lines.append(f"filled with {fill} passes: filled_est against perceive.scan_target over the covered points (dist != 255)")
         for k in perceive.BANDS:
@@ -229,6 +238,50 @@ def follow_rows(env, periods):
     return rows
 
 
+def visibility_rows(env, em, strides, kw, terrain, n):
+    """(viii): the clean-up alone at each stride on a copy of the ticked map, for the camera and for a LiDAR of 2048 points"""
+    rows = []
+    for s in strides:
+        vm = elevation.ElevationMap(env, **elevation.DEFAULTS, visibility=dict(stride=s))
+        vm.map.copy_(em.map); vm.origin.copy_(em.origin)
+        vm.clean(); torch.cuda.synchronize()
+        first = float(vm.cleared.float().mean())
+        rows.append((f"(viii) pgtt_elevation_visibility, image, stride {s} (first call forgot {first:.2f} cells per env)", window_us(vm.clean)))
+        vm.close()
+    lenv = Joystick("stairs", configs.training_config(), num_envs=n, terrain=terrain, device="cuda:0", lidar={}, **kw)
+    lenv.reset(0)
+    g = torch.Generator().manual_seed(1)
+    lm = elevation.ElevationMap(lenv, **elevation.DEFAULTS, source="lidar")
+    lm.tick(clear_all=True)
+    for _ in range(40):
+        lenv.step((0.2 * torch.randn(n, 12, generator=g)).clamp(-1, 1).cuda())
+        lm.tick()
+    torch.cuda.synchronize()
+    rows.append((f"(i-L) pgtt_elevation_points, {lenv.lidar_scanner.points.shape[1]} points, one launch", window_us(lm.tick)))
+    for s in strides:
+        vm = elevation.ElevationMap(lenv, **elevation.DEFAULTS, source="lidar", visibility=dict(stride=s))
+        vm.map.copy_(lm.map); vm.origin.copy_(lm.origin)
+        vm.clean(); torch.cuda.synchronize()
+        first = float(vm.cleared.float().mean())
+        rows.append((f"(viii) pgtt_elevation_visibility, points, stride {s} (first call forgot {first:.2f} cells per env)", window_us(vm.clean)))
+        vm.close()
+    lm.close(); lenv.close()
+    return rows
+
+
+def drift_evaluation(n=1000):
+    import evaluate
+    d3 = ",".join(str(3 * elevation.ODOMETRY_DEFAULTS[k]) for k in ("sigma_xy", "sigma_z", "sigma_yaw", "yaw_bias", "scale"))
+    base = ["--policy", "policy177", "--terrain_file", "level4", "--elevation", "--odometry_drift", d3]
+    lines = [f"evaluate.py --elevation --odometry_drift {d3} (three times the defaults): policy177, level4, {n} envs, one deterministic episode"]
+    for seed in (0, 1):
+        for name, extra in (("without clean-up", []), ("--elevation_visibility", ["--elevation_visibility"])):
+            r = evaluate.run_evaluation(evaluate.make_parser().parse_args(base + extra), num_eval_envs=n, seed=seed, verbose=False)
+            more = f", forgotten per step {r['visibility_cleared_per_step']:.3f}" if "visibility_cleared_per_step" in r else ""
+            lines.append(f"  seed {seed} {name:24s} survivors {r['survivors']} / {n}, reward {r['episode_reward']:.2f}, known scan points {r['known_share']:.3f}{more}")
+    return lines
+
+
 def evaluation(n=1000, periods=()):
     import evaluate
     base = ["--policy", "policy177", "--terrain_file", "level4"]
@@ -257,7 +310,9 @@ def main():
     ap.add_argument("--fill", type=str, default=None, metavar="K[,K...]", help="time pgtt_elevation_fill with these numbers of passes; --accuracy fills with the first")
     ap.add_argument("--eval", action="store_true")
     ap.add_argument("--every", type=str, default=None, metavar="M[,M...]", help="time pgtt_elevation_follow behind a camera of these periods; --eval evaluates with them")
+    ap.add_argument("--visibility", type=str, default=None, metavar="S[,S...]", help="time pgtt_elevation_visibility at these strides, for both sources")
     args = ap.parse_args()
+    strides = [int(v) for v in args.visibility.split(",")] if args.visibility else []
     periods = [int(m) for m in args.every.split(",")] if args.every else []
     passes = [int(k) for k in args.fill.split(",")] if args.fill else []
     n = args.num_envs
@@ -298,6 +353,8 @@ def main():
         rows.append((f"(vi)  pgtt_elevation_fill, {k} passes (covers {share:.3f} of the scan points; the map knows {float((em.known > 0).float().mean()):.3f})", us))
         fm.close()
     rows += follow_rows(env, periods)
+    if strides:
+        rows += visibility_rows(env, em, strides, kw, terrain, n)
     c = em.config
     traffic = n * (2 * 4 * c.grid ** 2 + 4 * c.width * c.height + 2 * 4 * c.obs_dim + 5 * abi.NSCAN)
     lines = [f"{n} envs, level4, {c.width}x{c.height}, G = {c.grid}, res = {c.res:.3f}, alpha = {c.alpha}; us per call, median [min, max] of 11 windows of 20 calls",
@@ -307,12 +364,21 @@ def main():
                  f"{traffic / rows[0][1][0] / 1e6:.2f} TB/s at the median")
     lines.append(f"torch statement against the kernel after 41 ticks: known flags equal on {same_known:.5f} of the points, max |est difference| where both know = {agree:.2e}")
     env.close(); plain.close()
+    print("\n".join(lines), flush=True)                                   # each block as it is ready: the later ones take minutes
+
+    def more(block):
+        print("\n".join(block), flush=True)
+        lines.extend(block)
     if args.accuracy:
-        lines += accuracy(terrain, fill=passes[0] if passes else 0)
+        more(accuracy(terrain, fill=passes[0] if passes else 0))
+        if strides:
+            d3 = {k: 3 * v for k, v in elevation.ODOMETRY_DEFAULTS.items() if k != "seed"}
+            more(accuracy(terrain, extra=dict(visibility=True), label=", visibility clean-up at the defaults"))
+            more(accuracy(terrain, extra=dict(odometry=d3), label=", three times the odometry defaults"))
+            more(accuracy(terrain, extra=dict(odometry=d3, visibility=True), label=", three times the odometry defaults, visibility clean-up"))
     if args.eval:
-        lines += evaluation(periods=periods)
+        more(drift_evaluation() if strides else evaluation(periods=periods))
     text = "\n".join(lines)
-    print(text)
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         open(args.out, "w").write(text + "\n")
