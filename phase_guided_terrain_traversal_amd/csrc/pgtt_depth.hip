@@ -104,10 +104,13 @@ __device__ __forceinline__ float hit_sphere(V3 oc, V3 d, float r) {
   const float t = -b - sqrtf(disc);
   return t > 0.f ? t : INFINITY;
 }
+// the cylinder's quadratic in its cross-product form; a <= 1e-12 baba, decided before h: the ray runs along the axis (see pgtt_raycast.hip.h)
 __device__ __forceinline__ float hit_capsule(V3 d, V3 c, V3 ax, float r, float hl) {
   const V3 pa = c - hl * ax, ba = (2.f * hl) * ax, oa = -1.f * pa;
-  const float baba = dot(ba, ba), bard = dot(ba, d), baoa = dot(ba, oa), rdoa = dot(d, oa), oaoa = dot(oa, oa);
-  const float a = baba - bard * bard, b = baba * rdoa - baoa * bard, cc = baba * oaoa - baoa * baoa - r * r * baba;
+  const V3 bd = cross(ba, d), bo = cross(ba, oa);
+  const float baba = dot(ba, ba), bard = dot(ba, d), baoa = dot(ba, oa);
+  const float a = dot(bd, bd), b = dot(bd, bo), cc = dot(bo, bo) - r * r * baba;
+  if (!(a > 1e-12f * baba)) return fminf(hit_sphere(oa, d, r), hit_sphere(oa - ba, d, r));
   const float h = b * b - a * cc;
   if (h < 0.f) return INFINITY;
   const float t = (-b - sqrtf(h)) / a, y = baoa + t * bard;

@@ -10,7 +10,9 @@
 //   phase B  rays over lanes, 256 per pass.  Ray r's unit direction in the sensor frame is one 16-byte row of the pattern table, the same for
 //            every env (a coalesced read that L2 serves).  Every lane walks the same list (LDS broadcasts, wave-uniform trip count), takes
 //            the minimum with the plane, clamps, adds the noise, stores the range coalesced and the world point as a 12-byte-per-lane run.
-// Unlike the camera's (u, v, 1) rays a pattern direction may be exactly perpendicular to a box axis: hit_box states that case.
+// A pattern direction may be exactly perpendicular to a box axis, and hit_box states that case.  (So may a camera ray: with an odd width or
+// height the centre column or row of (u, v, 1) has u = 0 or v = 0.  The camera leaves it to rcp(0) = inf, which decides the slab the same way:
+// inside it no constraint, outside it a miss; tests/test_gpu_raycast_edges.py holds both kernels to that.)
 // A tick that the sensor period skips returns at once in every workgroup (the decision reads counter[0] on the device); lidar_advance_kernel,
 // enqueued behind it, adds one to the counter.  Nothing is shared between envs: an env's scan does not depend on the batch.
 #include <hip/hip_runtime.h>
@@ -101,18 +103,18 @@ __device__ __forceinline__ float hit_sphere(V3 oc, V3 d, float r) {
   const float t = -b - sqrtf(disc);
   return t > 0.f ? t : INFINITY;
 }
+// the cylinder's quadratic in its cross-product form; a <= 1e-12 baba, decided before h: the ray runs along the axis (see pgtt_raycast.hip.h)
 __device__ __forceinline__ float hit_capsule(V3 d, V3 c, V3 ax, float r, float hl) {
   const V3 pa = c - hl * ax, ba = (2.f * hl) * ax, oa = -1.f * pa;
-  const float baba = dot(ba, ba), bard = dot(ba, d), baoa = dot(ba, oa), rdoa = dot(d, oa), oaoa = dot(oa, oa);
-  const float a = baba - bard * bard, b = baba * rdoa - baoa * bard, cc = baba * oaoa - baoa * baoa - r * r * baba;
+  const V3 bd = cross(ba, d), bo = cross(ba, oa);
+  const float baba = dot(ba, ba), bard = dot(ba, d), baoa = dot(ba, oa);
+  const float a = dot(bd, bd), b = dot(bd, bo), cc = dot(bo, bo) - r * r * baba;
+  if (!(a > 1e-12f * baba)) return fminf(hit_sphere(oa, d, r), hit_sphere(oa - ba, d, r));
   const float h = b * b - a * cc;
   if (h < 0.f) return INFINITY;
-  if (a > 0.f) {                                                         // a = 0: the ray runs along the axis and can only meet a cap
-    const float t = (-b - sqrtf(h)) / a, y = baoa + t * bard;
-    if (y > 0.f && y < baba) return t > 0.f ? t : INFINITY;
-    return hit_sphere(y <= 0.f ? oa : oa - ba, d, r);
-  }
-  return fminf(hit_sphere(oa, d, r), hit_sphere(oa - ba, d, r));
+  const float t = (-b - sqrtf(h)) / a, y = baoa + t * bard;
+  if (y > 0.f && y < baba) return t > 0.f ? t : INFINITY;
+  return hit_sphere(y <= 0.f ? oa : oa - ba, d, r);
 }
 
 template <bool NOISE>

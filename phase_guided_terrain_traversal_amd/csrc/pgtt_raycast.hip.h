@@ -7,7 +7,17 @@
 // (profiles/r10_ab_raycast_chain.txt); a shared placement and shared hit tests, the depth camera calling the renderer's forms with the ray
 // origin at zero, moved 1.5 % of the pixels of a thigh-mounted camera that sees the robot by up to 7e-6 m (profiles/r10_ab_raycast_hits.txt).
 // So each kernel keeps its own statement of these (the LiDAR's, the third, likewise), and tests/test_gpu_render.py, tests/test_gpu_depth.py and
-// tests/test_gpu_lidar.py hold them against fp64 references.
+// tests/test_gpu_lidar.py hold them against fp64 references on whole scenes; tests/test_gpu_raycast_edges.py holds hit_box, hit_sphere and
+// hit_capsule to fp64 at their edges, on crafted cases.
+// What the three statements of hit_capsule have in common (pa, ba = the segment's start and vector, oa = origin - pa, |d| = 1):
+//   the cylinder's quadratic a t^2 + 2 b t + cc = 0 in its cross-product form (Lagrange's identity),
+//     a = baba - bard^2 = |ba x d|^2,   b = baba rdoa - baoa bard = (ba x d).(ba x oa),   cc = baba oaoa - baoa^2 - r^2 baba = |ba x oa|^2 - r^2 baba.
+//   The dot-product form cancels to rounding noise for a ray within 1e-3 rad of the axis (misses, and hits 2 hl too deep); this one does not.
+//   a <= 1e-12 baba, i.e. the ray within 1e-6 rad of the axis: the ray drifts less than 1e-6 of the capsule's length off the axis over it and
+//   can only meet a cap, so both caps are tried.  Below that scale a is rounding noise: a component of ba x d carries an error of about
+//   6e-8 |ba| (one rounded product), which gives an a of about 1e-14 baba for a ray exactly along the axis, so the threshold has a margin of 100.
+//   It is decided BEFORE h = b^2 - a cc is looked at: the compiler may form ba x d twice, contracted differently, and multiply the two, so
+//   that an a at noise level, and with it h, comes out negative for a ray that meets the capsule.
 // Included by those three translation units only.  It does not include pgtt_common.hip.h (whose qrot(v, q) is the physics kernels' form): that
 // file is inside the physics source hash (srchash.py), and this one is inside the three side hashes only.  For the same reason the Philox copies
 // of pgtt_depth.hip, pgtt_lidar.hip and pgtt_policy.hip stay where they are.

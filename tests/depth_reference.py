@@ -1,10 +1,16 @@
 """fp64 numpy statement of include/pgtt_depth.h: the camera pose from the env's qpos (mjcf.kinematics_np), the ray grid, the plane, boxes,
 spheres and capsules, the clamp, and the Philox noise.  Also the ambiguity mask of an image, computed from this reference alone: a pixel is
 ambiguous when moving its ray by +-0.02 pixel in either image direction changes which primitive is nearest, or when its two nearest candidates
-are within 1e-4 relative of each other.  No GPU, no test module imported."""
+are within 1e-4 relative of each other.  No GPU, no test module imported (raycast_edge_cases.py is numpy alone)."""
+import os
+import sys
+
 import numpy as np
 
-from phase_guided_terrain_traversal_amd import abi, mjcf, render
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import raycast_edge_cases as edge_cases  # noqa: E402
+
+from phase_guided_terrain_traversal_amd import abi, mjcf, render  # noqa: E402
 
 RS_DEPTH = 32                         # include/pgtt_depth.h
 ID_MISS, ID_PLANE, ID_BOX, ID_GEOM = -1, 0, 1, 1000
@@ -106,7 +112,13 @@ def hit_capsule(o, d, c, ax, r, hl):
     tb = np.where(body & (t > 0), t, np.inf)
     o2 = np.broadcast_to(o, d.shape)
     tc = np.where(y <= 0, hit_sphere(o2, d, pa, r), hit_sphere(o2, d, pa + ba, r))
-    return np.where(h < 0, np.inf, np.where(body, tb, tc))
+    out = np.where(h < 0, np.inf, np.where(body, tb, tc))
+    # within 1e-3 rad of the axis a, b and cc cancel, and at a = 0 the quadratic is 0 / 0 and picks the far cap: there the capsule is the union of
+    # three pieces of raycast_edge_cases.py, which shares no expression with the above (tests/test_raycast_edge_cases.py compares the two elsewhere)
+    along = a <= 1e-6 * baba
+    if along.any():
+        out[along] = edge_cases.hit_capsule(o2[along], d[along], c, ax, r, hl)
+    return out
 
 
 def terrain_boxes(tab_v):

@@ -104,7 +104,7 @@ def test_flat_ground_closed_form():
     lid.close(); env.close()
 
 
-# ---------------------------------------------------------------- 2. directions with zero components: the case the camera never meets
+# ---------------------------------------------------------------- 2. directions with zero components (the camera's: test_gpu_raycast_edges.py)
 def test_axis_rays_on_an_axis_aligned_box():
     """one axis-aligned box, the sensor at identity pose: the rays along +-x, +-y and -z have two components that are exactly 0 in the box frame.
     Inside the slabs of those axes they meet the face at the closed-form distance; outside one of them they miss, whatever the third axis says."""

@@ -4,10 +4,14 @@ and the evaluate.py --video path."""
 import ctypes as C
 import math
 import os
+import sys
 
 import numpy as np
 import pytest
 import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import raycast_edge_cases as edge_cases  # noqa: E402
 
 from phase_guided_terrain_traversal_amd import abi, configs, mjcf, render
 from phase_guided_terrain_traversal_amd.env import Joystick
@@ -92,7 +96,13 @@ def _hit_capsule(o, d, c, ax, r, hl):
     cap_a = _hit_sphere(o2, d, pa, r)
     cap_b = _hit_sphere(o2, d, pa + ba, r)
     tc = np.where(y <= 0, cap_a, cap_b)
-    return np.where(h < 0, np.inf, np.where(body, tb, tc))
+    out = np.where(h < 0, np.inf, np.where(body, tb, tc))
+    # within 1e-3 rad of the axis a, b and cc cancel, and at a = 0 the quadratic is 0 / 0 and picks the far cap: there the capsule is the union of
+    # three pieces of raycast_edge_cases.py, which shares no expression with the above
+    along = a <= 1e-6 * baba
+    if along.any():
+        out[along] = edge_cases.hit_capsule(o2[along], d[along], c, ax, r, hl)
+    return out
 
 
 def _geom_hit(o, d, g):
