@@ -87,11 +87,12 @@ LIB_PATH, EXPORTS, lib, check, build_info = SIDE.path, SIDE.exports, SIDE.lib, S
 
 
 def conv_shapes(cfg: Dict) -> List[Tuple[int, int, int]]:
-    """[(channels, height, width)] of the input and of every conv's output; no padding, no dilation"""
+    """[(channels, height, width)] of the input and of every conv's output; no padding, no dilation.  An output is 0 x 0 where the kernel does
+    not fit or the stride is not positive: check_config refuses such a layer"""
     shapes = [(1, int(cfg["height"]), int(cfg["width"]))]
     for co, k, s in cfg["conv"]:
         _, h, w = shapes[-1]
-        shapes.append((int(co), (h - k) // s + 1 if h >= k else 0, (w - k) // s + 1 if w >= k else 0))
+        shapes.append((int(co), (h - k) // s + 1 if h >= k and s > 0 else 0, (w - k) // s + 1 if w >= k and s > 0 else 0))
     return shapes
 
 
