@@ -14,7 +14,8 @@ is built.  The policy comes from `--checkpoint_folder` (the newest `<env_steps>.
 whose scan rows the student perception module estimated from the onboard depth image, with `--elevation [grid,res,alpha]` on the observation whose
 scan rows are sampled from the depth-fused elevation map (elevation.py; nothing to train; `--elevation_source lidar` fuses it from the onboard
 LiDAR's points instead, lidar.py; `--elevation_fill [K]` closes the map's holes first and the policy acts on the filled scan; `--sensor_every M`
-runs that sensor at one control step in M and lets the map follow it; `--odometry_drift [sigma_xy,sigma_z,sigma_yaw,yaw_bias,scale]` registers the map
+runs that sensor at one control step in M and lets the map follow it; `--sensor_latency LO[,HI]` fuses every frame LO steps after it was taken, under
+the pose of its capture (LO,HI: drawn per env per episode); `--odometry_drift [sigma_xy,sigma_z,sigma_yaw,yaw_bias,scale]` registers the map
 with a dead-reckoned pose that drifts, and adds a line with the drift at the end; `--elevation_visibility [margin,end_guard,stride]` cleans the map by
 visibility in front of every tick and adds a line with the cells forgotten per step; `--elevation_variance [sigma0,sigma_rel,process,gate,band]` fuses the map by
 the variance-weighted update; `--sensor_noise SIGMA[,DROPOUT]` gives the sensor that feeds the map or the student range noise); a `--policy` file that holds a recurrent policy
@@ -201,6 +202,14 @@ def sensor_kwargs(args):
             if every > 1:
                 raise SystemExit("--elevation_visibility behind a slower sensor (--sensor_every > 1) is not built: a hold step must not clean with a stale image")
             given = dict({} if given is True else given, visibility=vis)
+        lat = sensor_latency(getattr(args, "sensor_latency", None))
+        if lat is not None:
+            # --sensor_latency LO[,HI]: every frame is fused LO control steps after it was taken, under the pose of its capture; with HI the latency
+            # is drawn per env per episode in [LO, HI]
+            for flag, on in (("--sensor_every > 1", every > 1), ("--elevation_variance", variance is not None), ("--elevation_visibility", vis is not None)):
+                if on:
+                    raise SystemExit(f"--sensor_latency with {flag} is not built")
+            given = dict({} if given is True else given, latency=lat)
         if source == "lidar":
             # --elevation_source lidar: the map is fused from the world points of the onboard LiDAR (lidar.DEFAULTS), as the deployed mapping stack's is
             kw.update(lidar=sensor, elevation=dict({} if given is True else given, source="lidar"))
@@ -212,6 +221,8 @@ def sensor_kwargs(args):
         raise SystemExit("--elevation_fill fills the holes of --elevation's map: give --elevation too")
     elif int(getattr(args, "sensor_every", 1)) != 1:
         raise SystemExit("--sensor_every is the period of the sensor that feeds --elevation's map: give --elevation too")
+    elif getattr(args, "sensor_latency", None) is not None:
+        raise SystemExit("--sensor_latency is the latency of the sensor that feeds --elevation's map: give --elevation too")
     return kw
 
 
@@ -375,6 +386,24 @@ def elevation_visibility(text):
         raise SystemExit(f"--elevation_visibility {text}: margin and end_guard must be numbers, stride an integer")
 
 
+def sensor_latency(text):
+    """--sensor_latency LO[,HI] -> None (not given) or the pair (LO, HI) of control steps, HI = LO unless given, 0 <= LO <= HI <= 8
+    (elevation.MAX_LATENCY)"""
+    if text is None:
+        return None
+    vals = [v for v in str(text).split(",") if v]
+    try:
+        ticks = [int(v) for v in vals]
+    except ValueError:
+        ticks = []
+    if len(ticks) not in (1, 2) or len(ticks) != len(vals):
+        raise SystemExit(f"--sensor_latency {text}: give LO or LO,HI, whole numbers of control steps")
+    lo, hi = ticks[0], ticks[-1]
+    if not 0 <= lo <= hi <= 8:
+        raise SystemExit(f"--sensor_latency {text}: need 0 <= LO <= HI <= 8")
+    return (lo, hi)
+
+
 def fill_passes(text):
     """--elevation_fill K: an integer in [1, 95] (elevation.MAX_FILL); the flag without a value is True, elevation.FILL_PASSES"""
     try:
@@ -405,6 +434,8 @@ def add_sensor_args(ap):
                     help="with --elevation or --student: relative range noise and dropout probability of the sensor that feeds it")
     ap.add_argument("--sensor_every", type=int, default=1, metavar="M",
                     help="with --elevation: the sensor that feeds the map runs at one control step in M; for M > 1 the map follows it, holding in between")
+    ap.add_argument("--sensor_latency", type=str, default=None, metavar="LO[,HI]",
+                    help="with --elevation: a frame is fused LO control steps after it was taken, under the pose of its capture; LO,HI draws it per env per episode")
 
 
 def make_parser():

@@ -118,7 +118,7 @@
  *     4. Assemble.  Step 6 into obs_out.
  * An env's outputs depend on its own rows only.  pgtt_elevation_fill() is what it was: it reads `map`, `origin` and `state` as they stand, so behind
  * a hold call it fills and samples the held window at the current pose.  Not covered: an image fused later than it was taken (that needs the pose
- * of its capture), sensor phases per env, latency.
+ * of its capture; "Sensor latency" below does that for a sensor of period 1), sensor phases per env.
  *
  * Variance-weighted fusion: a Kalman layer.  Steps 3 and 4 above suit noise-free data: the maximum of n noisy samples is biased upwards, and alpha
  * is one gain for every distance.  pgtt_elevation_var() and pgtt_elevation_var_points() are ticks that keep, next to `map`, a second persistent
@@ -192,8 +192,7 @@
  *     three NaNs.
  *  counter[0] advances by one per call, in a launch of its own behind the update: no workgroup reads a counter another has advanced.
  * An env's outputs depend on its own rows and its global id only: the same bits at any batch position, at any N, with or without points.
- * Not covered: loop closure or any correction of the drift, roll or pitch error, latency between capture and fusion, drift on the
- * proprioceptive rows of the observation.
+ * Not covered: loop closure or any correction of the drift, roll or pitch error, drift on the proprioceptive rows of the observation.
  *
  * Visibility clean-up.  The ticks above only ever add heights: a cell keeps what was fused into it until the window leaves it or a later measurement
  * lands in it.  Under a drifting pose a stair edge fused some centimetres ago stays as a ghost next to the real one.  pgtt_elevation_visibility() is
@@ -226,6 +225,32 @@
  * An env's outputs depend on its own rows only.  One launch, one workgroup of 256 lanes per env, one key word per slot in LDS (4 G G bytes, every
  * G the map allows), LDS integer atomics only, no global atomics.  Not covered: a hold step behind pgtt_elevation_follow (a stale image must not
  * clean), lowering a cell instead of forgetting it, the rays of pixels that hit nothing.
+ *
+ * Sensor latency: capture-stamped fusion.  Every tick above unprojects the image under the pose of the same call.  A real depth camera or LiDAR delivers
+ * its frame some calls after the shutter; a mapping stack fuses that frame under the pose it had at CAPTURE and answers the height queries at the pose
+ * it has now.  pgtt_elevation_delayed() is the tick of a handle with a PgttElevationLatency bound (pgtt_elevation_bind_latency): a ring of D frames
+ * and of the poses they were taken at lives on the device, and every env fuses the frame of lat[e] calls ago.  The source is the image or the points,
+ * by which bind was made last.  The latency is fixed (lat_lo == lat_hi) or drawn per env per episode in [lat_lo, lat_hi].  With c = counter[0] as it
+ * stands before the call and gid = env_id_offset + e, per env, in this order:
+ *  1. Clear rule.  The tick's own: clear_all != 0, or clear_mask[e] != 0, or use_done != 0 and done[e] != 0.  A cleared env draws its latency, on
+ *     integers alone:   lat[e] = lat_lo + (int) (((uint64) w0 * (uint64) (lat_hi - lat_lo + 1)) >> 32),
+ *     w0 = word 0 of the Philox block (gid, (uint32) c, PGTT_RS_LATENCY, 0) under the key (seed lo, seed hi); and its age[e] becomes 0.
+ *  2. Push.  Slot w = c mod D (floor-mod on the 64-bit counter): ring_data[w][e] takes the env's current image (or its P points) bit for bit,
+ *     ring_pose[w][0..6][e] rows 0..6 of the bound `state`, raw, and age[e] = min(age[e] + 1, D).  No other slot and no other env's part of slot w
+ *     is written.
+ *  3. Pick.  With L = lat[e]: when L < age[e] the frame is that of slot (c - L) mod D (floor-mod) and fused[e] = 1; otherwise the frame that would be
+ *     due predates the episode, nothing is fused and fused[e] = 0.
+ *  4. Stamped tick.  The six steps of pgtt_elevation() or pgtt_elevation_points() with two poses.  Steps 1, 2, 5 and 6 - clear, recentre and
+ *     `origin`, sample, assemble - use the CURRENT pose (the bound `state`).  Step 3 uses the CAPTURE pose from the ring for the camera pose, the basis
+ *     of the unprojection and the base position and rotation of the self filter; it takes the frame from the ring and tests the cells against the
+ *     NEW window.  Step 4 is unchanged.  Without a frame step 3 admits nothing: the map is cleared or recentred and the scan sampled from what it holds.
+ *  counter[0] advances by one per call, in a launch of its own behind the others: no workgroup reads a counter another has advanced.
+ * With lat_lo = lat_hi = 0 every output (map, origin, est, known, obs_out) has the bits of the plain tick: the capture pose is a copy of the current
+ * rows and the frame a copy of the current image.  An env's outputs, lat included, depend on its own rows and its global id only: the same bits at
+ * any batch position and at any N.  The ring stores whatever `state` and `points` the handle is bound to: with odometry those are pose_est and
+ * points_est, the map is registered with the estimate the robot had at capture, and nothing in the odometry call changes.  pgtt_elevation_fill()
+ * behind it is what it was.  Not covered: the variance tick, visibility and pgtt_elevation_follow behind a latency (a sensor of period 1 is assumed;
+ * the Python layer refuses these combinations), sub-step latencies, latency on the proprioceptive rows of the observation.
  */
 #ifndef PGTT_ELEVATION_H_
 #define PGTT_ELEVATION_H_
@@ -400,6 +425,34 @@ int pgtt_elevation_bind_visibility(pgtt_elevation_handle h, const PgttElevationV
  * pgtt_elevation_bind_visibility. */
 int pgtt_elevation_visibility(pgtt_elevation_handle h, const uint8_t* clear_mask, int clear_all, int use_done, void* stream);
 int pgtt_elevation_sizeof_visibility(void);
+
+#define PGTT_RS_LATENCY 35                       /* Philox stream id of the latency draws (pgtt.h uses ids below 32, the depth camera 32, the LiDAR 33, the odometry 34) */
+#define PGTT_ELEVATION_MAX_LATENCY 8             /* ticks */
+
+/* Sensor latency: the ring, the per-env bookkeeping (device buffers, caller-owned and sized for N) and the range of the draws */
+typedef struct PgttElevationLatency {
+  float* ring_data;                      /* image source: [D][N][H][W]; points source: [D][N][P][3]; required */
+  float* ring_pose;                      /* [D][7][N]: rows 0..6 of the bound `state` at capture, raw; required */
+  int32_t* lat;                          /* [N]: the env's latency of this episode, in calls; required */
+  int32_t* age;                          /* [N]: frames pushed since the env was last cleared, saturating at D; required */
+  uint8_t* fused;                        /* [N] out: 1 when this call fused a frame for the env, else 0; required */
+  int64_t* counter;                      /* [1]: calls so far; advanced by one per call; required */
+  int32_t D;                             /* ring slots, lat_hi + 1 <= D <= PGTT_ELEVATION_MAX_LATENCY + 1 */
+  int32_t lat_lo, lat_hi;                /* 0 <= lat_lo <= lat_hi <= PGTT_ELEVATION_MAX_LATENCY */
+  uint64_t seed;                         /* key of the Philox draws */
+  int64_t env_id_offset;                 /* global id of env 0 */
+} PgttElevationLatency;
+
+/* the ranges alone (the pointers are not looked at): host only, needs no GPU.  PGTT_E_ARG for NULL or a value outside its range. */
+int pgtt_elevation_check_latency(const PgttElevationLatency* l);
+/* PGTT_E_ARG for a NULL struct, a NULL pointer or a value outside its range.  May be called before or after the buffers are bound and persists
+ * across later binds, like pgtt_elevation_bind_fill.  The ring's frames are those of the source bound when pgtt_elevation_delayed is called. */
+int pgtt_elevation_bind_latency(pgtt_elevation_handle h, const PgttElevationLatency* l);
+/* the tick of a handle with a latency bound, from the image or the points, by which bind was made last: at most three launches on `stream` (the
+ * push; the stamped tick; the counter), no allocation, no synchronisation, no read-back, capturable.  PGTT_E_STATE before the buffers are bound
+ * (either kind of bind) or before pgtt_elevation_bind_latency. */
+int pgtt_elevation_delayed(pgtt_elevation_handle h, const uint8_t* clear_mask, int clear_all, int use_done, void* stream);
+int pgtt_elevation_sizeof_latency(void);
 /* "src=<SHA-256 of pgtt_elevation.hip and the files it includes>;flavor=product" */
 const char* pgtt_elevation_build_info(void);
 const char* pgtt_elevation_last_error(void);

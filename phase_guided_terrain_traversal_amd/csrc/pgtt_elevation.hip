@@ -45,6 +45,11 @@
 // Visibility clean-up (pgtt_elevation_visibility): visibility_kernel<POINTS>, a launch of its own in front of a tick.  The rays of the image or of the
 // points lower a bound per slot in LDS, and a cell that stands above its bound by more than the margin is forgotten.  Described at the kernel.  It
 // writes `map` (and `var`) and its own two outputs, and no kernel above knows of it.
+//
+// Sensor latency (pgtt_elevation_delayed): three launches.  latency_push_kernel stores the env's frame and its seven pose rows in slot `counter mod D`
+// of a ring, draws a cleared env's latency and says whether the frame that is due exists; elevation_kernel<POINTS, false, true>, the STAMPED
+// instantiation, is the tick with phase C under the pose of the due frame's capture and on that frame, everything else under the current pose;
+// odometry_advance_kernel advances the counter behind both.  The four older instantiations hold none of this.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -69,16 +74,20 @@ struct ElevArgs {
   float mpos[3], mquat[4], self_half[3];
   const float* points; int P;                                // the points entry: [N][P][3] world points
   const int64_t* counter; int every, force;                  // the gated instantiations alone (pgtt_elevation_follow)
+  // the stamped instantiations alone (pgtt_elevation_delayed): the ring the push kernel has filled, its counter as both kernels find it
+  const float* ring_data; const float* ring_pose; const int32_t* lat; const uint8_t* fused; const int64_t* lat_counter; int D;
 };
 
 // what lane 0 stages for the workgroup
 enum { P_CAM = 0, P_FWD = 3, P_RIGHT = 6, P_UP = 9, P_BASE = 12, P_RB = 15, P_SY = 24, P_CY = 25, P_N = 26 };
-enum { I_LOX = 0, I_LOY = 1, I_LMX = 2, I_LMY = 3, I_OLDX = 4, I_OLDY = 5, I_CLEAR = 6, I_N = 8 };
+enum { P_CBASE = P_N, P_NS = P_N + 3 };           // the stamped tick: the base position at CAPTURE, next to the current one in P_BASE
+enum { I_LOX = 0, I_LOY = 1, I_LMX = 2, I_LMY = 3, I_OLDX = 4, I_OLDY = 5, I_CLEAR = 6, I_FRAME = 7, I_N = 8 };   // I_FRAME: the stamped tick's ring slot, -1 = no frame
 
 __device__ __forceinline__ int cell_of(float x, float res) { return (int)fminf(fmaxf(floorf(x / res), -kCellClamp), kCellClamp); }
 // a value every lane holds alike, moved to a scalar register
 __device__ __forceinline__ float uni(float x) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(x))); }
 __device__ __forceinline__ int floor_mod(int a, int g) { const int r = a % g; return r < 0 ? r + g : r; }
+__device__ __forceinline__ int floor_mod64(long long a, int g) { const int r = (int)(a % g); return r < 0 ? r + g : r; }
 // fp32 -> a key whose unsigned order is the order of the floats; no finite value maps to 0
 __device__ __forceinline__ unsigned key_of(float z) { const unsigned b = __float_as_uint(z); return b ^ ((unsigned)((int)b >> 31) | 0x80000000u); }
 __device__ __forceinline__ float value_of(unsigned k) { return __uint_as_float(k ^ (((k >> 31) - 1u) | 0x80000000u)); }
@@ -117,13 +126,16 @@ __device__ __forceinline__ bool fresh_call(const int64_t* counter, int every, in
   return force || (c >= 0 && (unsigned long long)c % (unsigned)every == 0);
 }
 
-template <bool POINTS, bool GATED = false>
+// STAMPED (pgtt_elevation_delayed): phase C works under the pose of the frame's CAPTURE, read from the ring - the camera, the self filter's rotation
+// and, in P_CBASE, its base position - on the ring's frame; everything else (the clear, the window, the scan) under the current pose, as ever.
+template <bool POINTS, bool GATED = false, bool STAMPED = false>
 __global__ void __launch_bounds__(kLanes) elevation_kernel(ElevArgs a) {
   if constexpr (GATED) {
     if (!fresh_call(a.counter, a.every, a.force)) return;              // a hold call: elevation_hold_kernel's
   }
   extern __shared__ __attribute__((aligned(16))) unsigned sh_m[];      // [G * G]
-  __shared__ float sh_p[P_N];
+  __shared__ float sh_p[STAMPED ? P_NS : P_N];
+  constexpr int P_SELF = STAMPED ? P_CBASE : P_BASE;                   // the base position the self filter reads
   __shared__ int sh_i[I_N];
   __shared__ unsigned char sh_stale[2 * kMaxG];                        // [0, G): slot rows (x), [G, 2G): slot columns (y)
   __shared__ float sh_est[PGTT_NSCAN];
@@ -134,7 +146,14 @@ __global__ void __launch_bounds__(kLanes) elevation_kernel(ElevArgs a) {
   // ---- phase A: the poses (lane 0); the tick maximum starts empty
   if (tid == 0) {
     const float* S = a.state + e;
-    const float bx = S[(PGTT_S_QPOS + 0) * N], by = S[(PGTT_S_QPOS + 1) * N], bz = S[(PGTT_S_QPOS + 2) * N];
+    if constexpr (STAMPED) {
+      // the pose of the frame's capture: rows 0..6 as the push kernel stored them, PGTT_S_QPOS = 0.  Without a frame the slot's rows are read all
+      // the same and what is made of them is not: phase C is skipped
+      const int frame = floor_mod64(a.lat_counter[0] - (long long)a.lat[e], a.D);
+      sh_i[I_FRAME] = a.fused[e] ? frame : -1;
+      S = a.ring_pose + (long)frame * 7 * N + e;
+    }
+    float bx = S[(PGTT_S_QPOS + 0) * N], by = S[(PGTT_S_QPOS + 1) * N], bz = S[(PGTT_S_QPOS + 2) * N];
     float qw = S[(PGTT_S_QPOS + 3) * N], qx = S[(PGTT_S_QPOS + 4) * N], qy = S[(PGTT_S_QPOS + 5) * N], qz = S[(PGTT_S_QPOS + 6) * N];
     const float qn = sqrtf(qw * qw + qx * qx + qy * qy + qz * qz);
     qw /= qn; qx /= qn; qy /= qn; qz /= qn;
@@ -142,7 +161,7 @@ __global__ void __launch_bounds__(kLanes) elevation_kernel(ElevArgs a) {
     const float r00 = qw * qw + qx * qx - qy * qy - qz * qz, r01 = 2.f * (qx * qy - qw * qz), r02 = 2.f * (qx * qz + qw * qy);
     const float r10 = 2.f * (qx * qy + qw * qz), r11 = qw * qw - qx * qx + qy * qy - qz * qz, r12 = 2.f * (qy * qz - qw * qx);
     const float r20 = 2.f * (qx * qz - qw * qy), r21 = 2.f * (qy * qz + qw * qx), r22 = qw * qw - qx * qx - qy * qy + qz * qz;
-    sh_p[P_BASE + 0] = bx; sh_p[P_BASE + 1] = by; sh_p[P_BASE + 2] = bz;
+    sh_p[P_SELF + 0] = bx; sh_p[P_SELF + 1] = by; sh_p[P_SELF + 2] = bz;
     sh_p[P_RB + 0] = r00; sh_p[P_RB + 1] = r01; sh_p[P_RB + 2] = r02; sh_p[P_RB + 3] = r10; sh_p[P_RB + 4] = r11; sh_p[P_RB + 5] = r12;
     sh_p[P_RB + 6] = r20; sh_p[P_RB + 7] = r21; sh_p[P_RB + 8] = r22;
     if constexpr (!POINTS) {
@@ -158,6 +177,16 @@ __global__ void __launch_bounds__(kLanes) elevation_kernel(ElevArgs a) {
       sh_p[P_FWD + 0] = fx; sh_p[P_FWD + 1] = fy; sh_p[P_FWD + 2] = fz;
       sh_p[P_UP + 0] = ux; sh_p[P_UP + 1] = uy; sh_p[P_UP + 2] = uz;
       sh_p[P_RIGHT + 0] = fy * uz - fz * uy; sh_p[P_RIGHT + 1] = fz * ux - fx * uz; sh_p[P_RIGHT + 2] = fx * uy - fy * ux;
+    }
+    if constexpr (STAMPED) {
+      // from here on the CURRENT pose: the yaw, the clear and the window are the plain tick's.  The same operations on the same rows as above when
+      // the latency is 0, so the same bits
+      const float* T = a.state + e;
+      bx = T[(PGTT_S_QPOS + 0) * N]; by = T[(PGTT_S_QPOS + 1) * N]; bz = T[(PGTT_S_QPOS + 2) * N];
+      qw = T[(PGTT_S_QPOS + 3) * N]; qx = T[(PGTT_S_QPOS + 4) * N]; qy = T[(PGTT_S_QPOS + 5) * N]; qz = T[(PGTT_S_QPOS + 6) * N];
+      const float tn = sqrtf(qw * qw + qx * qx + qy * qy + qz * qz);
+      qw /= tn; qx /= tn; qy /= tn; qz /= tn;
+      sh_p[P_BASE + 0] = bx; sh_p[P_BASE + 1] = by; sh_p[P_BASE + 2] = bz;
     }
     float sy, cy; yaw_sincos(qw, qx, qy, qz, sy, cy);
     sh_p[P_SY] = sy; sh_p[P_CY] = cy;
@@ -186,12 +215,18 @@ __global__ void __launch_bounds__(kLanes) elevation_kernel(ElevArgs a) {
 
   // ---- phase C: the tick maximum
   if constexpr (POINTS) {
-    const float bpx = uni(sh_p[P_BASE + 0]), bpy = uni(sh_p[P_BASE + 1]), bpz = uni(sh_p[P_BASE + 2]);
+    const float bpx = uni(sh_p[P_SELF + 0]), bpy = uni(sh_p[P_SELF + 1]), bpz = uni(sh_p[P_SELF + 2]);
     const float b00 = uni(sh_p[P_RB + 0]), b01 = uni(sh_p[P_RB + 1]), b02 = uni(sh_p[P_RB + 2]), b10 = uni(sh_p[P_RB + 3]), b11 = uni(sh_p[P_RB + 4]);
     const float b12 = uni(sh_p[P_RB + 5]), b20 = uni(sh_p[P_RB + 6]), b21 = uni(sh_p[P_RB + 7]), b22 = uni(sh_p[P_RB + 8]);
     const int lox = sh_i[I_LOX], loy = sh_i[I_LOY], lmx = sh_i[I_LMX], lmy = sh_i[I_LMY];
     const float* pts = a.points + (long)e * a.P * 3;
-    for (int k = tid; k < a.P; k += kLanes) {
+    int np = a.P;
+    if constexpr (STAMPED) {                                           // the ring's frame, or none
+      const int frame = sh_i[I_FRAME];
+      pts = a.ring_data + ((long)max(frame, 0) * N + e) * a.P * 3;
+      if (frame < 0) np = 0;
+    }
+    for (int k = tid; k < np; k += kLanes) {
       const float px = pts[3 * k], py = pts[3 * k + 1], pz = pts[3 * k + 2];
       if (!(fabsf(px) < INFINITY && fabsf(py) < INFINITY && fabsf(pz) < INFINITY)) continue;      // a NaN (no return) or a non-finite coordinate
       if (a.self_on) {
@@ -212,12 +247,18 @@ __global__ void __launch_bounds__(kLanes) elevation_kernel(ElevArgs a) {
     const float ux = sh_p[P_UP + 0], uy = sh_p[P_UP + 1], uz = sh_p[P_UP + 2];
     // the self filter's base position and rotation are read once, like the camera basis (the compiler cannot hoist LDS reads over the LDS atomics),
     // and kept in scalar registers: twelve more vector registers would cost the eighth wave per SIMD
-    const float bpx = uni(sh_p[P_BASE + 0]), bpy = uni(sh_p[P_BASE + 1]), bpz = uni(sh_p[P_BASE + 2]);
+    const float bpx = uni(sh_p[P_SELF + 0]), bpy = uni(sh_p[P_SELF + 1]), bpz = uni(sh_p[P_SELF + 2]);
     const float b00 = uni(sh_p[P_RB + 0]), b01 = uni(sh_p[P_RB + 1]), b02 = uni(sh_p[P_RB + 2]), b10 = uni(sh_p[P_RB + 3]), b11 = uni(sh_p[P_RB + 4]);
     const float b12 = uni(sh_p[P_RB + 5]), b20 = uni(sh_p[P_RB + 6]), b21 = uni(sh_p[P_RB + 7]), b22 = uni(sh_p[P_RB + 8]);
     const int lox = sh_i[I_LOX], loy = sh_i[I_LOY], lmx = sh_i[I_LMX], lmy = sh_i[I_LMY];
-    const int W = a.W, npix = a.W * a.H;
+    const int W = a.W;
+    int npix = a.W * a.H;
     const float* img = a.depth + (long)e * npix;
+    if constexpr (STAMPED) {                                           // the ring's frame, or none
+      const int frame = sh_i[I_FRAME];
+      img = a.ring_data + ((long)max(frame, 0) * N + e) * npix;
+      if (frame < 0) npix = 0;
+    }
     auto pixel = [&](float d, int i, int j) {
       if (!(d > a.near_m && d < a.far_m)) return;                     // NaN, a miss, a dropout, below near
       const float u = (2.f * ((float)j + 0.5f) / (float)W - 1.f) * a.tu, v = (1.f - 2.f * ((float)i + 0.5f) / (float)a.H) * a.tv;
@@ -989,6 +1030,51 @@ __global__ void __launch_bounds__(64) odometry_advance_kernel(int64_t* counter) 
   if (threadIdx.x == 0 && blockIdx.x == 0) counter[0] = counter[0] + 1;
 }
 
+// ---------------------------------------------------------------- sensor latency (pgtt_elevation_delayed): the ring of frames and their poses
+struct PushArgs {
+  const float* state; const float* src; const float* done; const uint8_t* clear_mask; const int64_t* counter;
+  float* ring_data; float* ring_pose; int32_t* lat; int32_t* age; uint8_t* fused;
+  int N, D, F, vec, clear_all, use_done, lat_lo, lat_hi;       // F: floats of one env's frame (H W, or 3 P)
+  unsigned k0, k1, gid0;                                       // the Philox key (seed lo, seed hi); (uint32) env_id_offset
+};
+
+// latency_push_kernel: in front of the stamped tick, one workgroup of four waves per env (include/pgtt_elevation.h, "Sensor latency", steps 1 - 3).
+// Lane 0 makes the env's clear and draw, stores the seven pose rows in slot w = counter mod D, counts the frame and says whether the frame that is
+// due exists; the lanes copy the env's frame into its part of slot w, in 16-byte runs when the host found that the frame's size and both addresses
+// allow (vec, the vec_img convention) and in dwords otherwise.  One source serves the image and the points: a frame is F floats.  The counter is
+// only read: odometry_advance_kernel advances it behind the stamped tick.  No atomics, no LDS.
+__global__ void __launch_bounds__(kLanes) latency_push_kernel(PushArgs a) {
+  const int e = blockIdx.x, tid = threadIdx.x;
+  const long N = a.N;
+  const long long c = a.counter[0];
+  const int w = floor_mod64(c, a.D);
+  if (tid == 0) {
+    const bool clear = a.clear_all || (a.clear_mask && a.clear_mask[e]) || (a.use_done && a.done && a.done[e] != 0.f);
+    int L = a.lat[e], age = a.age[e];
+    if (clear) {
+      unsigned w0 = a.gid0 + (unsigned)e, w1 = (unsigned)c, w2 = PGTT_RS_LATENCY, w3 = 0u;
+      philox4x32_10(a.k0, a.k1, w0, w1, w2, w3);
+      L = a.lat_lo + (int)(((unsigned long long)w0 * (unsigned long long)(a.lat_hi - a.lat_lo + 1)) >> 32);      // integers alone
+      age = 0;
+      a.lat[e] = L;
+    }
+    age = min(age + 1, a.D);
+    a.age[e] = age;
+    a.fused[e] = L < age ? 1 : 0;                                 // else the frame that is due predates the episode
+    const float* S = a.state + e;
+    float* R = a.ring_pose + (long)w * 7 * N + e;
+#pragma unroll
+    for (int r = 0; r < 7; r++) R[r * N] = S[(PGTT_S_QPOS + r) * N];
+  }
+  const float* src = a.src + (long)e * a.F;
+  float* dst = a.ring_data + ((long)w * N + e) * a.F;
+  if (a.vec) {
+    for (int i = 4 * tid; i < a.F; i += 4 * kLanes) *reinterpret_cast<float4*>(dst + i) = *reinterpret_cast<const float4*>(src + i);
+  } else {
+    for (int i = tid; i < a.F; i += kLanes) dst[i] = src[i];
+  }
+}
+
 // ---------------------------------------------------------------- visibility clean-up (pgtt_elevation_visibility): rays forget contradicted cells
 struct VisArgs {
   const float* state; const float* depth; const float* done; const uint8_t* clear_mask; const float* points; const int32_t* origin;
@@ -1231,6 +1317,8 @@ struct pgtt_elevation_map {
   bool has_odo = false;
   PgttElevationVisibility vis{};         // pgtt_elevation_bind_visibility; kept by the other binds
   bool has_vis = false;
+  PgttElevationLatency lat{};            // pgtt_elevation_bind_latency; kept by the other binds
+  bool has_lat = false;
 };
 
 namespace {
@@ -1358,9 +1446,64 @@ int resolve_visibility(const PgttElevationVisibility* v, const char* who) {
   return PGTT_OK;
 }
 
+// the latency settings' ranges; `who` prefixes the message
+int resolve_latency(const PgttElevationLatency* l, const char* who) {
+  const std::string p = std::string(who) + ": ";
+  if (!l) return fail(PGTT_E_ARG, p + "null settings");
+  if (l->lat_lo < 0 || l->lat_lo > l->lat_hi || l->lat_hi > PGTT_ELEVATION_MAX_LATENCY)
+    return fail(PGTT_E_ARG, p + "need 0 <= lat_lo <= lat_hi <= PGTT_ELEVATION_MAX_LATENCY = 8");
+  if (l->D < l->lat_hi + 1 || l->D > PGTT_ELEVATION_MAX_LATENCY + 1) return fail(PGTT_E_ARG, p + "D must be in [lat_hi + 1, PGTT_ELEVATION_MAX_LATENCY + 1]");
+  return PGTT_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int pgtt_elevation_sizeof_latency(void) { return (int)sizeof(PgttElevationLatency); }
+
+int pgtt_elevation_check_latency(const PgttElevationLatency* l) { return resolve_latency(l, "pgtt_elevation_check_latency"); }
+
+int pgtt_elevation_bind_latency(pgtt_elevation_handle h, const PgttElevationLatency* l) {
+  if (!h || !l) return fail(PGTT_E_ARG, "pgtt_elevation_bind_latency: null argument");
+  if (!l->ring_data || !l->ring_pose || !l->lat || !l->age || !l->fused || !l->counter)
+    return fail(PGTT_E_ARG, "pgtt_elevation_bind_latency: ring_data, ring_pose, lat, age, fused and counter are required");
+  if (int rc = resolve_latency(l, "pgtt_elevation_bind_latency")) return rc;
+  h->lat = *l;
+  h->has_lat = true;
+  return PGTT_OK;
+}
+
+int pgtt_elevation_delayed(pgtt_elevation_handle h, const uint8_t* clear_mask, int clear_all, int use_done, void* stream) {
+  if (!h) return fail(PGTT_E_ARG, "pgtt_elevation_delayed: null handle");
+  if (!h->bound) return fail(PGTT_E_STATE, "pgtt_elevation_delayed: no buffers bound (pgtt_elevation_bind or pgtt_elevation_bind_points first)");
+  if (!h->has_lat) return fail(PGTT_E_STATE, "pgtt_elevation_delayed: no latency bound (pgtt_elevation_bind_latency first)");
+  HIP_TRY(hipSetDevice(h->device));
+  const PgttElevationConfig& c = h->cfg;
+  const PgttElevationLatency& l = h->lat;
+  const bool points = h->points != nullptr;                            // the source: whichever bind was made last
+  ElevArgs a = tick_args(h, clear_mask, clear_all, use_done);
+  PushArgs p{};
+  p.state = h->buf.state; p.src = points ? h->points : h->buf.depth; p.done = h->buf.done; p.clear_mask = clear_mask; p.counter = l.counter;
+  p.ring_data = l.ring_data; p.ring_pose = l.ring_pose; p.lat = l.lat; p.age = l.age; p.fused = l.fused;
+  p.N = h->num_envs; p.D = l.D; p.F = points ? 3 * h->P : c.width * c.height;
+  p.clear_all = a.clear_all; p.use_done = a.use_done; p.lat_lo = l.lat_lo; p.lat_hi = l.lat_hi;
+  p.k0 = (unsigned)l.seed; p.k1 = (unsigned)(l.seed >> 32); p.gid0 = (unsigned)l.env_id_offset;
+  // 16-byte runs need every env's frame to start on a 16-byte boundary, in the source and in the ring
+  const bool ring16 = p.F % 4 == 0 && ((uintptr_t)l.ring_data & 15) == 0;
+  p.vec = (ring16 && ((uintptr_t)p.src & 15) == 0) ? 1 : 0;
+  hipLaunchKernelGGL(latency_push_kernel, dim3(h->num_envs), dim3(kLanes), 0, (hipStream_t)stream, p);
+  HIP_TRY(hipGetLastError());
+  a.ring_data = l.ring_data; a.ring_pose = l.ring_pose; a.lat = l.lat; a.fused = l.fused; a.lat_counter = l.counter; a.D = l.D;
+  a.vec_img = ring16 ? 1 : 0;                                          // the image is the ring's now
+  const size_t lds = (size_t)c.grid * c.grid * sizeof(unsigned);
+  if (points) hipLaunchKernelGGL((elevation_kernel<true, false, true>), dim3(h->num_envs), dim3(kLanes), lds, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL((elevation_kernel<false, false, true>), dim3(h->num_envs), dim3(kLanes), lds, (hipStream_t)stream, a);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(odometry_advance_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, l.counter);
+  HIP_TRY(hipGetLastError());
+  return PGTT_OK;
+}
 
 PGTT_SIDE_EXPORTS(elevation, ELEVATION)
 int pgtt_elevation_sizeof_visibility(void) { return (int)sizeof(PgttElevationVisibility); }

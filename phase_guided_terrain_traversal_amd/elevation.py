@@ -22,6 +22,9 @@ points of the env's LiDAR (lidar.py) instead: the sensor such a stack reads on t
     em = ElevationMap(env, visibility=True)                  # visibility clean-up in front of every tick: a ray that passed below a cell's height
     em.cleared                                               # on its way to the ground forgets the cell (VISIBILITY_DEFAULTS); [N] int32 per call
 
+    em = ElevationMap(env, latency=2)                        # sensor latency: every frame is fused 2 ticks after it was taken, under the pose of
+    em.latency, em.fused                                     # its capture; latency=(0, 4) draws it per env per episode; [N] int32, [N] uint8
+
 `Joystick(..., depth=dict(...), elevation=dict(...) | True)` owns one and ticks it behind the camera (env.elevation_obs);
 `Joystick(..., lidar=dict(...), elevation=dict(source="lidar"))` one that is ticked behind the LiDAR.  The module is not imported by env.py unless
 an elevation map is asked for.
@@ -61,6 +64,10 @@ RS_ODOMETRY, ODO_WORDS = 34, 12                    # PGTT_RS_ODOMETRY, PGTT_ELEV
 # ray's end - the cell that was hit and its neighbour are the tick's business -, every second row and column of the image (every second point)
 # casts a ray, and with a variance layer the height is taken as it stands (sigmas = 0) - settings, not facts; end_guard=None is 1.5 res
 VISIBILITY_DEFAULTS = dict(margin=0.05, end_guard=None, stride=2, sigmas=0.0)
+# latency=K or (lo, hi): the ticks between a frame's capture and its fusion, fixed or drawn per env per episode in [lo, hi] - a setting; the default
+# of the dict form is no latency at all
+LATENCY_DEFAULTS = dict(ticks=(0, 0), seed=0)
+RS_LATENCY, MAX_LATENCY = 35, 8                    # PGTT_RS_LATENCY, PGTT_ELEVATION_MAX_LATENCY
 
 f, i32 = C.c_float, C.c_int32
 
@@ -97,7 +104,13 @@ class PgttElevationVisibility(C.Structure):
                 ("bound_out", C.c_void_p)]
 
 
+class PgttElevationLatency(C.Structure):
+    _fields_ = [("ring_data", C.c_void_p), ("ring_pose", C.c_void_p), ("lat", C.c_void_p), ("age", C.c_void_p), ("fused", C.c_void_p),
+                ("counter", C.c_void_p), ("D", i32), ("lat_lo", i32), ("lat_hi", i32), ("seed", C.c_uint64), ("env_id_offset", C.c_int64)]
+
+
 assert C.sizeof(PgttElevationVar) == 48 and C.sizeof(PgttElevationOdometry) == 104 and C.sizeof(PgttElevationVisibility) == 48
+assert C.sizeof(PgttElevationLatency) == 80
 
 
 class ElevationError(RuntimeError):
@@ -120,9 +133,13 @@ SIDE = _sidelib.SideLib("elevation", ElevationError, {
     "pgtt_elevation_check_visibility": (None, [C.POINTER(PgttElevationVisibility)]),
     "pgtt_elevation_bind_visibility": (None, [vp, C.POINTER(PgttElevationVisibility)]),
     "pgtt_elevation_visibility": (None, [vp, vp, C.c_int, C.c_int, vp]),
+    "pgtt_elevation_check_latency": (None, [C.POINTER(PgttElevationLatency)]),
+    "pgtt_elevation_bind_latency": (None, [vp, C.POINTER(PgttElevationLatency)]),
+    "pgtt_elevation_delayed": (None, [vp, vp, C.c_int, C.c_int, vp]),
 }, {"pgtt_elevation_sizeof_config": PgttElevationConfig, "pgtt_elevation_sizeof_buffers": PgttElevationBuffers,
     "pgtt_elevation_sizeof_fill": PgttElevationFill, "pgtt_elevation_sizeof_var": PgttElevationVar,
-    "pgtt_elevation_sizeof_odometry": PgttElevationOdometry, "pgtt_elevation_sizeof_visibility": PgttElevationVisibility})
+    "pgtt_elevation_sizeof_odometry": PgttElevationOdometry, "pgtt_elevation_sizeof_visibility": PgttElevationVisibility,
+    "pgtt_elevation_sizeof_latency": PgttElevationLatency})
 LIB_PATH, EXPORTS, lib, check, build_info = SIDE.path, SIDE.exports, SIDE.lib, SIDE.check, SIDE.build_info
 
 
@@ -204,6 +221,43 @@ def visibility_struct(margin=0.05, end_guard=0.06, stride=2, sigmas=0.0, sensor_
     return v
 
 
+def latency_settings(latency=None) -> Optional[Dict]:
+    """ElevationMap's `latency` argument as a full dict: None / False -> None (every frame is fused in the tick it was taken), an int K ->
+    dict(ticks=(K, K), seed=0), a pair (lo, hi) -> that range, drawn per env per episode, a dict -> LATENCY_DEFAULTS with it on top (its `ticks` an
+    int or a pair).  ValueError for a key that is no setting or for anything else; the ranges are the library's to check."""
+    if latency is None or latency is False:
+        return None
+
+    def pair(t):
+        if isinstance(t, int) and not isinstance(t, bool):
+            return (t, t)
+        if isinstance(t, (tuple, list)) and len(t) == 2 and all(isinstance(x, int) and not isinstance(x, bool) for x in t):
+            return (int(t[0]), int(t[1]))
+        raise ValueError(f"ElevationMap(latency=...): the ticks must be an int or a pair (lo, hi) of ints, not {t!r}")
+    if isinstance(latency, dict):
+        unknown = sorted(set(latency) - set(LATENCY_DEFAULTS))
+        if unknown:
+            raise ValueError(f"ElevationMap(latency=...): unknown setting(s) {unknown}; the settings are {sorted(LATENCY_DEFAULTS)}")
+        out = {**LATENCY_DEFAULTS, **latency}
+        if isinstance(out["seed"], bool) or not isinstance(out["seed"], int):
+            raise ValueError(f"ElevationMap(latency=...): seed must be an int, not {out['seed']!r}")
+        return dict(ticks=pair(out["ticks"]), seed=out["seed"])
+    if isinstance(latency, bool):
+        raise ValueError("ElevationMap(latency=...): latency must be an int, a pair (lo, hi) or a dict of settings, not True")
+    return dict(ticks=pair(latency), seed=0)
+
+
+def latency_struct(ticks=(0, 0), seed=0, env_id_offset=0, D=None, ring_data=None, ring_pose=None, lat=None, age=None, fused=None,
+                   counter=None) -> PgttElevationLatency:
+    """no checks: the library makes its own (pgtt_elevation_check_latency).  D=None: hi + 1 slots"""
+    l = PgttElevationLatency()
+    l.ring_data, l.ring_pose, l.lat, l.age, l.fused, l.counter = ring_data, ring_pose, lat, age, fused, counter
+    l.lat_lo, l.lat_hi = int(ticks[0]), int(ticks[1])
+    l.D = int(ticks[1]) + 1 if D is None else int(D)
+    l.seed, l.env_id_offset = int(seed) & (2 ** 64 - 1), int(env_id_offset)
+    return l
+
+
 def config_struct(width, height, fovy, near, far, mount_pos=(0.0, 0.0, 0.0), mount_quat=(1.0, 0.0, 0.0, 0.0), mount_body=0, grid=64, res=0.04,
                   alpha=1.0, self_half=(0.0, 0.0, 0.0), scan_dist_x=0.1, scan_dist_y=0.1, obs_dim=abi.OBS, scan_row0=38) -> PgttElevationConfig:
     """no checks: the library makes its own"""
@@ -249,13 +303,26 @@ class ElevationMap(_sidelib.Handle):
     over the cells it passes, and a cell that stands more than `margin` above its bound is forgotten (NaN, in `var` too).  `cleared` [N] int32 is the
     number of cells the last call forgot; with dense_bound=True `bound` [N, G, G] is the bound layer (NaN = no ray passed).  Not with follow_sensor: a
     hold step must not clean with a stale image.  visibility=None, the default: nothing of this is allocated or called.
+    latency = K, (lo, hi) or a dict over LATENCY_DEFAULTS: tick() is pgtt_elevation_delayed in place of the plain tick - every call pushes the image
+    (or the points) and the pose rows into a ring on the device, and each env fuses the frame of `latency[e]` calls ago under the pose of its
+    CAPTURE, while the window and the scan follow the current pose.  `latency` [N] int32 is the env's latency of this episode, K or drawn in
+    [lo, hi] when the env's map is cleared (keyed by `seed` and env.env_id_offset); `fused` [N] uint8 is 0 while the frame that is due predates the
+    episode - the first latency[e] calls after a clear fuse nothing.  Latency 0 is the plain tick bit for bit.  Odometry goes in front as ever (the
+    ring then stores the pose estimate and the re-registered points) and the fill behind.  The ring costs D N H W 4 bytes with D = hi + 1 (3 P in
+    place of H W for the LiDAR): 252 MB at 4096 envs, 64 x 48 and hi = 4.  Not built with variance, visibility or follow_sensor.  latency=None,
+    the default: nothing of this is allocated, bound or called.
     Runs on the env's device and current stream; reads env.depth or the LiDAR's points, env.buffers["state" | "obs_state" | "done"] and writes nothing
     but its own tensors."""
     _prefix, _check = "pgtt_elevation", staticmethod(check)
 
     def __init__(self, env, grid: int = 64, res: float = 0.04, alpha: float = 1.0, self_half: Sequence[float] = (0.45, 0.25, 0.45),
                  source: str = "depth", fill: int = 0, dense: bool = False, follow_sensor: bool = False, variance=None, odometry=None,
-                 visibility=None, dense_bound: bool = False):
+                 visibility=None, dense_bound: bool = False, latency=None):
+        self.latency_cfg = latency_settings(latency)
+        if self.latency_cfg is not None:
+            for name, on in (("variance", variance), ("visibility", visibility), ("follow_sensor", follow_sensor)):
+                if on is not None and on is not False:
+                    raise ValueError(f"ElevationMap: latency with {name} is not built (the stamped tick is the plain tick's alone)")
         self.variance = variance_settings(variance)
         self.odometry = odometry_settings(odometry)
         self.visibility = visibility_settings(visibility, res)
@@ -337,6 +404,16 @@ class ElevationMap(_sidelib.Handle):
             if dense_bound:
                 self.bound = torch.full((n, self.grid, self.grid), float("nan"), dtype=torch.float32, device=dev)
         self.dense_bound = bool(dense_bound)
+        if self.latency_cfg is not None:
+            slots = self.latency_cfg["ticks"][1] + 1
+            check(self._lib.pgtt_elevation_check_latency(C.byref(latency_struct(**self.latency_cfg))))      # before the ring is sized by it
+            frame = tuple(env.lidar_scanner.points.shape[1:]) if source == "lidar" else tuple(env.depth.shape[1:])
+            self.ring = torch.zeros((slots, n) + frame, dtype=torch.float32, device=dev)
+            self.ring_pose = torch.zeros((slots, 7, n), dtype=torch.float32, device=dev)
+            self.latency = torch.zeros(n, dtype=torch.int32, device=dev)
+            self.latency_age = torch.zeros(n, dtype=torch.int32, device=dev)
+            self.fused = torch.zeros(n, dtype=torch.uint8, device=dev)
+            self.latency_counter = torch.zeros(1, dtype=torch.int64, device=dev)
         if self.follow_sensor:
             sensor = env.lidar_scanner if source == "lidar" else env.depth_camera
             self.sensor_counter, self.sensor_every = sensor.counter, int(sensor.config.every)
@@ -378,6 +455,11 @@ class ElevationMap(_sidelib.Handle):
             v = visibility_struct(**self.visibility, sensor_pos=self._sensor_pos, cleared=self.cleared.data_ptr(),
                                   bound_out=self.bound.data_ptr() if self.dense_bound else None)
             check(self._lib.pgtt_elevation_bind_visibility(self._h, C.byref(v)))
+        if self.latency_cfg is not None:
+            l = latency_struct(**self.latency_cfg, env_id_offset=self.env.env_id_offset, D=self.ring.shape[0],
+                               ring_data=self.ring.data_ptr(), ring_pose=self.ring_pose.data_ptr(), lat=self.latency.data_ptr(),
+                               age=self.latency_age.data_ptr(), fused=self.fused.data_ptr(), counter=self.latency_counter.data_ptr())
+            check(self._lib.pgtt_elevation_bind_latency(self._h, C.byref(l)))
 
     def tick(self, clear_mask: Optional[torch.Tensor] = None, clear_all: bool = False, use_done: bool = False, force: bool = False) -> torch.Tensor:
         """integrate the env's current image (or LiDAR points) under its current pose and sample the scan: one launch on the env's current stream,
@@ -388,7 +470,8 @@ class ElevationMap(_sidelib.Handle):
         the current pose.  `force` is not read without follow_sensor.
         With odometry the pose estimate is updated first (two small launches), with the same clear arguments: a cleared env's estimate is the
         truth again and its episode's scale error and gyro bias are drawn anew.
-        With visibility the clean-up is enqueued behind that and in front of the tick (one launch), with the same clear arguments."""
+        With visibility the clean-up is enqueued behind that and in front of the tick (one launch), with the same clear arguments.
+        With latency the tick is pgtt_elevation_delayed (three launches: the push into the ring, the tick on the frame that is due, the counter)."""
         mp = None
         if clear_mask is not None:
             self._mask = clear_mask.to(self.env.device, torch.uint8).contiguous()      # kept alive until the next tick: the launch is asynchronous
@@ -399,7 +482,9 @@ class ElevationMap(_sidelib.Handle):
             check(self._lib.pgtt_elevation_odometry(self._h, mp, int(bool(clear_all)), int(bool(use_done)), stream))
         if self.visibility is not None:
             check(self._lib.pgtt_elevation_visibility(self._h, mp, int(bool(clear_all)), int(bool(use_done)), stream))
-        if self.follow_sensor:
+        if self.latency_cfg is not None:
+            check(self._lib.pgtt_elevation_delayed(self._h, mp, int(bool(clear_all)), int(bool(use_done)), stream))
+        elif self.follow_sensor:
             check(self._lib.pgtt_elevation_follow(self._h, mp, int(bool(clear_all)), int(bool(use_done)), int(bool(force)), stream))
         elif self.variance is not None:
             fn = self._lib.pgtt_elevation_var_points if self.source == "lidar" else self._lib.pgtt_elevation_var

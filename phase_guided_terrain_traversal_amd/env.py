@@ -86,7 +86,13 @@ class Joystick:
         elevation=dict(visibility=True | dict(margin=..., end_guard=..., stride=..., sigmas=...), ...) cleans the map by visibility in front of every
         tick (pgtt_elevation_visibility; elevation.VISIBILITY_DEFAULTS): a cell that a ray passed below on its way to the ground is forgotten, which
         removes the ghosts a drifting pose leaves.  `env.elevation_cleared` [N] int32 is the number of cells the last step forgot.  With both sources
-        (a LiDAR on the torso); not with follow_sensor.  obs, state, reward, done and the sensors' outputs are what they are without it."""
+        (a LiDAR on the torso); not with follow_sensor.  obs, state, reward, done and the sensors' outputs are what they are without it.
+        elevation=dict(latency=K | (lo, hi) | dict(ticks=..., seed=...), ...) gives the sensor a latency (pgtt_elevation_delayed;
+        elevation.LATENCY_DEFAULTS): every frame is fused K steps after it was taken, under the pose of its capture, while the window and the scan
+        follow the current pose; (lo, hi) draws the latency per env per episode.  `env.elevation_latency` [N] int32 is each env's latency and
+        `env.elevation_fused` [N] uint8 whether the last step fused a frame: the first K steps of an episode fuse nothing.  With both sources, with
+        fill and odometry; not with variance, visibility or follow_sensor.  Latency 0 gives the bits of an env without the key; obs, state,
+        reward, done and the sensors' outputs are what they are without it."""
         if student is not None and depth is None:
             raise ValueError("Joystick(student=...) needs depth=dict(...): the student reads the onboard depth image")
         wants_map = elevation is not None and elevation is not False
@@ -110,6 +116,12 @@ class Joystick:
                 raise ValueError("Joystick(elevation=dict(variance=..., follow_sensor=True)): variance behind a slower sensor is not built yet")
             if variance is not True and not isinstance(variance, dict):
                 raise ValueError(f"Joystick(elevation=dict(variance=...)): variance must be True or a dict of settings, not {variance!r}")
+        latency = dict(elevation).get("latency") if wants_map and elevation is not True else None
+        if latency is not None and latency is not False:
+            for name in ("variance", "visibility", "follow_sensor"):
+                other = dict(elevation).get(name)
+                if other is not None and other is not False:
+                    raise ValueError(f"Joystick(elevation=dict(latency=..., {name}=...)): latency with {name} is not built")
         self.level_start = None
         if isinstance(terrain, (list, tuple)):
             terrain, self.level_start = _curriculum.stack_levels(terrain)
@@ -353,6 +365,16 @@ class Joystick:
         return None if odo is None else odo[:, :4]
 
     @property
+    def elevation_latency(self) -> Optional[torch.Tensor]:
+        """[N] int32: the steps between a frame's capture and its fusion into the elevation map, per env for this episode; None without latency"""
+        return getattr(self.elevation_map, "latency", None)
+
+    @property
+    def elevation_fused(self) -> Optional[torch.Tensor]:
+        """[N] uint8: 1 where the last tick of the elevation map fused a frame, 0 where the frame that was due predates the episode; None without latency"""
+        return getattr(self.elevation_map, "fused", None)
+
+    @property
     def elevation_cleared(self) -> Optional[torch.Tensor]:
         """[N] int32, a view: the cells the visibility clean-up forgot in front of the last tick of the elevation map; None without the clean-up"""
         return getattr(self.elevation_map, "cleared", None)
@@ -404,6 +426,8 @@ class Joystick:
             self.elevation_map.map.fill_(float("nan"))                # heights of the old terrain: the next tick starts from an empty map
             if getattr(self.elevation_map, "var", None) is not None:
                 self.elevation_map.var.fill_(float("nan"))            # the variance layer is NaN where the map is
+            if getattr(self.elevation_map, "latency_age", None) is not None:
+                self.elevation_map.latency_age.zero_()                # the ring's frames show the old terrain: none of them is due any more
 
     def _stream(self) -> int:
         return torch.cuda.current_stream(self.device).cuda_stream
