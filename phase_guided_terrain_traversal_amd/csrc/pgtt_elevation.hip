@@ -13,20 +13,26 @@
 //   phase E  lanes 0 .. 116 sample the scan, the minimum over the known points is a wave reduction and one LDS exchange; est, known.
 //   phase F  obs_out = obs with the scan rows replaced.
 // The phases are separated by workgroup barriers.  No global atomics, no scratch; nothing is shared between envs.
+// Written once, in front of the kernels ("what the kernels share"): phase A (stage_tick, from load_pose, stage_base, stage_camera, stage_yaw, cleared,
+// window_of / stage_window), phase B (mark_stale), phase E (scan_min_and_write), phase F (assemble), stored_origin and scan_slot.  Phases C and D -
+// the self filter, the window test, the unprojection, the image walk, the slot walk - are written out in every kernel that has them, and
+// visibility_kernel holds its own phase A and clear predicate as well: which products the compiler fuses there depends on the code around them, and
+// sharing these pieces moved outputs by an ulp.
 //
 // elevation_var_kernel<POINTS>, the variance tick (pgtt_elevation_var, pgtt_elevation_var_points): the same phases with a second pass over the pixels
 // (integer band sums in a 64-bit LDS word per slot) and a Kalman update per slot while `map` and `var` stream through; described at the kernel.
+// Phases A, B, E and F are the shared helpers'; phases C and D are its own.
 //
 // fill_kernel, the hole filling behind a tick: one workgroup of four waves per env again.  LDS holds the window in WINDOW order inside a border of one
 // cell, one key word (key_of the value; kNoKey = a hole or the border) and one byte `D` per cell: 5 (G + 2)^2 bytes, 48020 at G = 96, under the
 // 64 KB that need no launch attribute.  The border makes the window's edges edges and keeps every neighbour's index in range.
-//   load     the map streams in as in phase D (16-byte runs, dwords for an odd G), every slot to its window cell; lane 0 stages the base position, the
-//            yaw's sine and cosine and the window of the stored origin.
+//   load     the map streams in as in phase D (16-byte runs, dwords for an odd G), every slot to its window cell; lane 0 stages the base
+//            position, the yaw's sine and cosine (load_pose, stage_yaw) and the window of the stored origin (stored_origin, window_of).
 //   pass p   every hole takes the minimum key over its neighbours with D < p, and D = p.  A cell written in this pass reads as a hole or as a key
 //            with D = p or still 255, none of them a source, so one barrier per pass suffices and there are no atomics; a flag every lane reads
 //            alike ends the loop after a pass that filled nothing.
-//   sample   lanes 0 .. 116 read the key and D at the scan points (scan_slot, the tick's); the minimum over the covered points is taken on the keys.
-//   out      est, dist, obs_out (assemble, the tick's), map_out and dist_out in the map's slot layout.
+//   sample   lanes 0 .. 116 read the key and D at the scan points (scan_slot); the minimum over the covered points is taken on the keys.
+//   out      est, dist, obs_out (assemble), map_out and dist_out in the map's slot layout.
 // It writes nothing the tick reads.
 //
 // Following a slower sensor (pgtt_elevation_follow): two launches, of which one does the work.  Both read the sensor's counter on the device and
@@ -35,8 +41,8 @@
 //   elevation_hold_kernel           returns at once on a fresh call.  On a hold call it leaves the map alone and samples the scan at the current
 //            pose from the window the stored origin describes.  Two envs per workgroup, two waves per env; the map is not staged in LDS: a hold
 //            needs 117 of its cells, gathered from global memory.  Lane 0 of each env stages the pose and the window (and writes the origin of a
-//            cleared env); a cleared env's map goes out as NaN in 16-byte runs; the minimum is phase E's wave reduction and LDS exchange; est,
-//            known, obs_out.  No atomics.
+//            cleared env); a cleared env's map goes out as NaN in 16-byte runs; the minimum, est and known are scan_min_and_write's and obs_out is
+//            assemble's, both on the env's 128 lanes.  No atomics.
 //
 // Odometry drift (pgtt_elevation_odometry): odometry_kernel<POINTS> writes the estimated pose [7][N] the map may be bound to in place of `state`, and
 // with POINTS the world points re-registered at it; odometry_advance_kernel behind it advances the draws' epoch.  Described at the kernel.  It reads
@@ -92,11 +98,69 @@ __device__ __forceinline__ int floor_mod64(long long a, int g) { const int r = (
 __device__ __forceinline__ unsigned key_of(float z) { const unsigned b = __float_as_uint(z); return b ^ ((unsigned)((int)b >> 31) | 0x80000000u); }
 __device__ __forceinline__ float value_of(unsigned k) { return __uint_as_float(k ^ (((k >> 31) - 1u) | 0x80000000u)); }
 
-// the sine and cosine of the yaw of a normalised base quaternion
-__device__ __forceinline__ void yaw_sincos(float qw, float qx, float qy, float qz, float& sy, float& cy) {
-  const float yaw = atan2f(2.0f * (qw * qz + qx * qy), 1.0f - 2.0f * (qy * qy + qz * qz));
-  sincosf(yaw, &sy, &cy);
+// ---------------------------------------------------------------- what the kernels share: every phase is stated once, here
+// the seven pose rows of an env, S = its column of a [rows][N] array; NORMALISE: the quaternion divided by its norm
+struct Pose { float bx, by, bz, qw, qx, qy, qz; };
+template <bool NORMALISE = true>
+__device__ __forceinline__ Pose load_pose(const float* S, long N) {
+  const float bx = S[(PGTT_S_QPOS + 0) * N], by = S[(PGTT_S_QPOS + 1) * N], bz = S[(PGTT_S_QPOS + 2) * N];
+  float qw = S[(PGTT_S_QPOS + 3) * N], qx = S[(PGTT_S_QPOS + 4) * N], qy = S[(PGTT_S_QPOS + 5) * N], qz = S[(PGTT_S_QPOS + 6) * N];
+  if constexpr (NORMALISE) {
+    const float qn = sqrtf(qw * qw + qx * qx + qy * qy + qz * qz);
+    qw /= qn; qx /= qn; qy /= qn; qz /= qn;
+  }
+  return {bx, by, bz, qw, qx, qy, qz};
 }
+// the base position -> sh_p[base ..], the rows of the base rotation -> sh_p[P_RB ..]
+struct Rot { float r00, r01, r02, r10, r11, r12, r20, r21, r22; };
+__device__ __forceinline__ Rot stage_base(const Pose& p, int base, float* sh_p) {
+  const float qw = p.qw, qx = p.qx, qy = p.qy, qz = p.qz;
+  const float r00 = qw * qw + qx * qx - qy * qy - qz * qz, r01 = 2.f * (qx * qy - qw * qz), r02 = 2.f * (qx * qz + qw * qy);
+  const float r10 = 2.f * (qx * qy + qw * qz), r11 = qw * qw - qx * qx + qy * qy - qz * qz, r12 = 2.f * (qy * qz - qw * qx);
+  const float r20 = 2.f * (qx * qz - qw * qy), r21 = 2.f * (qy * qz + qw * qx), r22 = qw * qw - qx * qx - qy * qy + qz * qz;
+  sh_p[base + 0] = p.bx; sh_p[base + 1] = p.by; sh_p[base + 2] = p.bz;
+  sh_p[P_RB + 0] = r00; sh_p[P_RB + 1] = r01; sh_p[P_RB + 2] = r02; sh_p[P_RB + 3] = r10; sh_p[P_RB + 4] = r11; sh_p[P_RB + 5] = r12;
+  sh_p[P_RB + 6] = r20; sh_p[P_RB + 7] = r21; sh_p[P_RB + 8] = r22;
+  return {r00, r01, r02, r10, r11, r12, r20, r21, r22};
+}
+// the camera at mpos in the base frame -> sh_p[P_CAM ..]; camera = base * mount; fwd = its +x, up = its +z, right = fwd x up
+__device__ __forceinline__ void stage_camera(const Pose& p, const Rot& R, const float* mpos, const float* mquat, float* sh_p) {
+  sh_p[P_CAM + 0] = p.bx + R.r00 * mpos[0] + R.r01 * mpos[1] + R.r02 * mpos[2];
+  sh_p[P_CAM + 1] = p.by + R.r10 * mpos[0] + R.r11 * mpos[1] + R.r12 * mpos[2];
+  sh_p[P_CAM + 2] = p.bz + R.r20 * mpos[0] + R.r21 * mpos[1] + R.r22 * mpos[2];
+  const float qw = p.qw, qx = p.qx, qy = p.qy, qz = p.qz;
+  const float mw = mquat[0], mx = mquat[1], my = mquat[2], mz = mquat[3];
+  const float cw = qw * mw - qx * mx - qy * my - qz * mz, cx = qw * mx + qx * mw + qy * mz - qz * my;
+  const float cyq = qw * my - qx * mz + qy * mw + qz * mx, cz = qw * mz + qx * my - qy * mx + qz * mw;
+  const float fx = cw * cw + cx * cx - cyq * cyq - cz * cz, fy = 2.f * (cx * cyq + cw * cz), fz = 2.f * (cx * cz - cw * cyq);
+  const float ux = 2.f * (cx * cz + cw * cyq), uy = 2.f * (cyq * cz - cw * cx), uz = cw * cw - cx * cx - cyq * cyq + cz * cz;
+  sh_p[P_FWD + 0] = fx; sh_p[P_FWD + 1] = fy; sh_p[P_FWD + 2] = fz;
+  sh_p[P_UP + 0] = ux; sh_p[P_UP + 1] = uy; sh_p[P_UP + 2] = uz;
+  sh_p[P_RIGHT + 0] = fy * uz - fz * uy; sh_p[P_RIGHT + 1] = fz * ux - fx * uz; sh_p[P_RIGHT + 2] = fx * uy - fy * ux;
+}
+// the sine and cosine of the yaw of a normalised base quaternion -> sh_p[P_SY], sh_p[P_CY]
+__device__ __forceinline__ void stage_yaw(const Pose& p, float* sh_p) {
+  const float yaw = atan2f(2.0f * (p.qw * p.qz + p.qx * p.qy), 1.0f - 2.0f * (p.qy * p.qy + p.qz * p.qz));
+  float sy, cy;
+  sincosf(yaw, &sy, &cy);
+  sh_p[P_SY] = sy; sh_p[P_CY] = cy;
+}
+// does this call clear env e: the four fields every entry takes, in any of the argument structs
+template <class A>
+__device__ __forceinline__ bool cleared(const A& a, int e) {
+  return a.clear_all || (a.clear_mask && a.clear_mask[e]) || (a.use_done && a.done && a.done[e] != 0.f);
+}
+// the origin as the last tick left it; one outside the tick's clamp (a map never ticked) is as far away as the clamp
+__device__ __forceinline__ int2 stored_origin(const int32_t* origin, int e) {
+  return make_int2(min(max(origin[2 * (long)e], -(1 << 30)), 1 << 30), min(max(origin[2 * (long)e + 1], -(1 << 30)), 1 << 30));
+}
+// the window of G x G cells around origin cell (ox, oy): its first cell and that cell's slot, per axis; sh_i[I_LOX .. I_LMY]
+struct Window { int lox, loy, lmx, lmy; };
+__device__ __forceinline__ Window window_of(int ox, int oy, int G) {
+  const int lox = ox - G / 2, loy = oy - G / 2;
+  return {lox, loy, floor_mod(lox, G), floor_mod(loy, G)};
+}
+__device__ __forceinline__ void stage_window(const Window& w, int* sh_i) { sh_i[I_LOX] = w.lox; sh_i[I_LOY] = w.loy; sh_i[I_LMX] = w.lmx; sh_i[I_LMY] = w.lmy; }
 // the slot of the cell that contains scan point i = 9 r + c, or -1 outside the window.  pose: P_BASE, P_SY, P_CY; win: I_LOX .. I_LMY
 __device__ __forceinline__ int scan_slot(int i, const float* pose, const int* win, float sdx, float sdy, float res, int G) {
   const int r = i / PGTT_SCAN_W, c = i - r * PGTT_SCAN_W;
@@ -112,9 +176,38 @@ __device__ __forceinline__ int scan_slot(int i, const float* pose, const int* wi
   }
   return slot;
 }
-// env e's row of obs_out = its row of obs with the scan rows replaced by est (LDS)
-__device__ __forceinline__ void assemble(float* obs_out, const float* obs, const float* est, int e, int od, int row0, int tid) {
-  for (int k = tid; k < od; k += kLanes) {
+// phase B: lanes 0 .. 2G - 1 mark, per axis, the slots whose world cell moved.  Slot s holds world cell lo + ((s - lo) mod G) under the window that
+// starts at lo.  sh_stale [0, G): slot rows (x), [G, 2G): slot columns (y)
+__device__ __forceinline__ void mark_stale(const int* sh_i, unsigned char* sh_stale, int G, int tid) {
+  if (tid < 2 * G) {
+    const int ax = tid >= G, s = tid - ax * G;
+    const int lo_new = sh_i[I_LOX + ax], lo_old = sh_i[I_OLDX + ax];
+    unsigned char st = 1;
+    if (!sh_i[I_CLEAR]) st = (lo_new + floor_mod(s - lo_new, G)) != (lo_old + floor_mod(s - lo_old, G));
+    sh_stale[tid] = st;
+  }
+}
+// phase E behind the lookup.  Lane lt of the env's LANES lanes holds z, the height at scan point lt, and kn, whether it is known (false in the lanes
+// past the scan).  The minimum over the known points is a wave reduction and one exchange through sh_red[2], by the env's first two waves; est goes to
+// sh_est and out, known out.  live = false: a half workgroup without an env, which only keeps the barrier
+template <int LANES>
+__device__ __forceinline__ void scan_min_and_write(float z, bool kn, bool live, int e, int lt, float* sh_red, float* sh_est, float* est, uint8_t* known) {
+  float zmin = kn ? z : INFINITY;
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) zmin = fminf(zmin, __shfl_xor(zmin, off, 64));
+  if ((LANES == 128 || lt < 128) && (lt & 63) == 0) sh_red[lt >> 6] = zmin;
+  __syncthreads();
+  zmin = fminf(sh_red[0], sh_red[1]);
+  if (live && lt < PGTT_NSCAN) {
+    const float es = (kn && zmin < INFINITY) ? z - zmin : 0.f;
+    sh_est[lt] = es;
+    est[(long)e * PGTT_NSCAN + lt] = es;
+    known[(long)e * PGTT_NSCAN + lt] = kn ? 1 : 0;
+  }
+}
+// phase F: env e's row of obs_out = its row of obs with the scan rows replaced by est (LDS), by lane lt of the env's `lanes`
+__device__ __forceinline__ void assemble(float* obs_out, const float* obs, const float* est, int e, int od, int row0, int lt, int lanes) {
+  for (int k = lt; k < od; k += lanes) {
     const int j = k - row0;
     obs_out[(long)e * od + k] = (j >= 0 && j < PGTT_NSCAN) ? est[j] : obs[(long)e * od + k];
   }
@@ -124,6 +217,40 @@ __device__ __forceinline__ void assemble(float* obs_out, const float* obs, const
 __device__ __forceinline__ bool fresh_call(const int64_t* counter, int every, int force) {
   const long long c = counter[0] - 1;
   return force || (c >= 0 && (unsigned long long)c % (unsigned)every == 0);
+}
+
+// phase A of a tick, lane 0's: the sensor's pose (the base position to sh_p[P_SELF ..], the rotation, with an image the camera), then under the CURRENT
+// pose the yaw, the clear, the old and the new window, and the new origin written.  STAMPED (pgtt_elevation_delayed): the sensor's pose is that of
+// the due frame's capture, rows 0 .. 6 as the push kernel stored them in the ring (PGTT_S_QPOS = 0); without a frame the slot's rows are read all the
+// same and what is made of them is not, phase C is skipped.  Both poses go through the same load_pose: the same operations on the same rows when the
+// latency is 0, so the same bits
+template <bool POINTS, bool STAMPED>
+__device__ __forceinline__ void stage_tick(const ElevArgs& a, int e, float* sh_p, int* sh_i) {
+  constexpr int P_SELF = STAMPED ? P_CBASE : P_BASE;
+  const int G = a.G;
+  const long N = a.N;
+  const float* S = a.state + e;
+  if constexpr (STAMPED) {
+    const int frame = floor_mod64(a.lat_counter[0] - (long long)a.lat[e], a.D);
+    sh_i[I_FRAME] = a.fused[e] ? frame : -1;
+    S = a.ring_pose + (long)frame * 7 * N + e;
+  }
+  Pose p = load_pose(S, N);
+  const Rot R = stage_base(p, P_SELF, sh_p);
+  if constexpr (!POINTS) stage_camera(p, R, a.mpos, a.mquat, sh_p);
+  if constexpr (STAMPED) {
+    p = load_pose(a.state + e, N);
+    sh_p[P_BASE + 0] = p.bx; sh_p[P_BASE + 1] = p.by; sh_p[P_BASE + 2] = p.bz;
+  }
+  stage_yaw(p, sh_p);
+  const bool clear = cleared(a, e);
+  const int ox = cell_of(p.bx, a.res), oy = cell_of(p.by, a.res);
+  stage_window(window_of(ox, oy, G), sh_i);
+  // an old origin outside the clamp (a map never ticked, garbage in the buffer) is as far away as the clamp: everything is stale
+  const int px = a.origin[2 * (long)e], py = a.origin[2 * (long)e + 1];
+  const bool sane = px >= -(1 << 30) && px <= (1 << 30) && py >= -(1 << 30) && py <= (1 << 30);
+  sh_i[I_OLDX] = px - G / 2; sh_i[I_OLDY] = py - G / 2; sh_i[I_CLEAR] = (clear || !sane) ? 1 : 0;
+  a.origin[2 * (long)e] = ox; a.origin[2 * (long)e + 1] = oy;
 }
 
 // STAMPED (pgtt_elevation_delayed): phase C works under the pose of the frame's CAPTURE, read from the ring - the camera, the self filter's rotation
@@ -144,74 +271,12 @@ __global__ void __launch_bounds__(kLanes) elevation_kernel(ElevArgs a) {
   const long N = a.N;
 
   // ---- phase A: the poses (lane 0); the tick maximum starts empty
-  if (tid == 0) {
-    const float* S = a.state + e;
-    if constexpr (STAMPED) {
-      // the pose of the frame's capture: rows 0..6 as the push kernel stored them, PGTT_S_QPOS = 0.  Without a frame the slot's rows are read all
-      // the same and what is made of them is not: phase C is skipped
-      const int frame = floor_mod64(a.lat_counter[0] - (long long)a.lat[e], a.D);
-      sh_i[I_FRAME] = a.fused[e] ? frame : -1;
-      S = a.ring_pose + (long)frame * 7 * N + e;
-    }
-    float bx = S[(PGTT_S_QPOS + 0) * N], by = S[(PGTT_S_QPOS + 1) * N], bz = S[(PGTT_S_QPOS + 2) * N];
-    float qw = S[(PGTT_S_QPOS + 3) * N], qx = S[(PGTT_S_QPOS + 4) * N], qy = S[(PGTT_S_QPOS + 5) * N], qz = S[(PGTT_S_QPOS + 6) * N];
-    const float qn = sqrtf(qw * qw + qx * qx + qy * qy + qz * qz);
-    qw /= qn; qx /= qn; qy /= qn; qz /= qn;
-    // rows of the base rotation
-    const float r00 = qw * qw + qx * qx - qy * qy - qz * qz, r01 = 2.f * (qx * qy - qw * qz), r02 = 2.f * (qx * qz + qw * qy);
-    const float r10 = 2.f * (qx * qy + qw * qz), r11 = qw * qw - qx * qx + qy * qy - qz * qz, r12 = 2.f * (qy * qz - qw * qx);
-    const float r20 = 2.f * (qx * qz - qw * qy), r21 = 2.f * (qy * qz + qw * qx), r22 = qw * qw - qx * qx - qy * qy + qz * qz;
-    sh_p[P_SELF + 0] = bx; sh_p[P_SELF + 1] = by; sh_p[P_SELF + 2] = bz;
-    sh_p[P_RB + 0] = r00; sh_p[P_RB + 1] = r01; sh_p[P_RB + 2] = r02; sh_p[P_RB + 3] = r10; sh_p[P_RB + 4] = r11; sh_p[P_RB + 5] = r12;
-    sh_p[P_RB + 6] = r20; sh_p[P_RB + 7] = r21; sh_p[P_RB + 8] = r22;
-    if constexpr (!POINTS) {
-      sh_p[P_CAM + 0] = bx + r00 * a.mpos[0] + r01 * a.mpos[1] + r02 * a.mpos[2];
-      sh_p[P_CAM + 1] = by + r10 * a.mpos[0] + r11 * a.mpos[1] + r12 * a.mpos[2];
-      sh_p[P_CAM + 2] = bz + r20 * a.mpos[0] + r21 * a.mpos[1] + r22 * a.mpos[2];
-      // camera = base * mount; fwd = its +x, up = its +z, right = fwd x up
-      const float mw = a.mquat[0], mx = a.mquat[1], my = a.mquat[2], mz = a.mquat[3];
-      const float cw = qw * mw - qx * mx - qy * my - qz * mz, cx = qw * mx + qx * mw + qy * mz - qz * my;
-      const float cyq = qw * my - qx * mz + qy * mw + qz * mx, cz = qw * mz + qx * my - qy * mx + qz * mw;
-      const float fx = cw * cw + cx * cx - cyq * cyq - cz * cz, fy = 2.f * (cx * cyq + cw * cz), fz = 2.f * (cx * cz - cw * cyq);
-      const float ux = 2.f * (cx * cz + cw * cyq), uy = 2.f * (cyq * cz - cw * cx), uz = cw * cw - cx * cx - cyq * cyq + cz * cz;
-      sh_p[P_FWD + 0] = fx; sh_p[P_FWD + 1] = fy; sh_p[P_FWD + 2] = fz;
-      sh_p[P_UP + 0] = ux; sh_p[P_UP + 1] = uy; sh_p[P_UP + 2] = uz;
-      sh_p[P_RIGHT + 0] = fy * uz - fz * uy; sh_p[P_RIGHT + 1] = fz * ux - fx * uz; sh_p[P_RIGHT + 2] = fx * uy - fy * ux;
-    }
-    if constexpr (STAMPED) {
-      // from here on the CURRENT pose: the yaw, the clear and the window are the plain tick's.  The same operations on the same rows as above when
-      // the latency is 0, so the same bits
-      const float* T = a.state + e;
-      bx = T[(PGTT_S_QPOS + 0) * N]; by = T[(PGTT_S_QPOS + 1) * N]; bz = T[(PGTT_S_QPOS + 2) * N];
-      qw = T[(PGTT_S_QPOS + 3) * N]; qx = T[(PGTT_S_QPOS + 4) * N]; qy = T[(PGTT_S_QPOS + 5) * N]; qz = T[(PGTT_S_QPOS + 6) * N];
-      const float tn = sqrtf(qw * qw + qx * qx + qy * qy + qz * qz);
-      qw /= tn; qx /= tn; qy /= tn; qz /= tn;
-      sh_p[P_BASE + 0] = bx; sh_p[P_BASE + 1] = by; sh_p[P_BASE + 2] = bz;
-    }
-    float sy, cy; yaw_sincos(qw, qx, qy, qz, sy, cy);
-    sh_p[P_SY] = sy; sh_p[P_CY] = cy;
-    // clear, the old and the new window
-    const bool clear = a.clear_all || (a.clear_mask && a.clear_mask[e]) || (a.use_done && a.done && a.done[e] != 0.f);
-    const int ox = cell_of(bx, a.res), oy = cell_of(by, a.res);
-    const int lox = ox - G / 2, loy = oy - G / 2;
-    sh_i[I_LOX] = lox; sh_i[I_LOY] = loy; sh_i[I_LMX] = floor_mod(lox, G); sh_i[I_LMY] = floor_mod(loy, G);
-    // an old origin outside the clamp (a map never ticked, garbage in the buffer) is as far away as the clamp: everything is stale
-    const int px = a.origin[2 * (long)e], py = a.origin[2 * (long)e + 1];
-    const bool sane = px >= -(1 << 30) && px <= (1 << 30) && py >= -(1 << 30) && py <= (1 << 30);
-    sh_i[I_OLDX] = px - G / 2; sh_i[I_OLDY] = py - G / 2; sh_i[I_CLEAR] = (clear || !sane) ? 1 : 0;
-    a.origin[2 * (long)e] = ox; a.origin[2 * (long)e + 1] = oy;
-  }
+  if (tid == 0) stage_tick<POINTS, STAMPED>(a, e, sh_p, sh_i);
   for (int s = tid; s < GG; s += kLanes) sh_m[s] = 0u;
   __syncthreads();
 
-  // ---- phase B: per axis, the slots whose world cell moved.  Slot s holds world cell lo + ((s - lo) mod G) under the window that starts at lo.
-  if (tid < 2 * G) {
-    const int ax = tid >= G, s = tid - ax * G;
-    const int lo_new = sh_i[I_LOX + ax], lo_old = sh_i[I_OLDX + ax];
-    unsigned char st = 1;
-    if (!sh_i[I_CLEAR]) st = (lo_new + floor_mod(s - lo_new, G)) != (lo_old + floor_mod(s - lo_old, G));
-    sh_stale[tid] = st;
-  }
+  // ---- phase B: per axis, the slots whose world cell moved
+  mark_stale(sh_i, sh_stale, G, tid);
 
   // ---- phase C: the tick maximum
   if constexpr (POINTS) {
@@ -347,23 +412,12 @@ __global__ void __launch_bounds__(kLanes) elevation_kernel(ElevArgs a) {
       kn = z == z;
     }
   }
-  float zmin = kn ? z : INFINITY;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) zmin = fminf(zmin, __shfl_xor(zmin, off, 64));
-  if (tid < 128 && (tid & 63) == 0) sh_red[tid >> 6] = zmin;
-  __syncthreads();
-  zmin = fminf(sh_red[0], sh_red[1]);
-  if (tid < PGTT_NSCAN) {
-    const float es = (kn && zmin < INFINITY) ? z - zmin : 0.f;
-    sh_est[tid] = es;
-    a.est[(long)e * PGTT_NSCAN + tid] = es;
-    a.known[(long)e * PGTT_NSCAN + tid] = kn ? 1 : 0;
-  }
+  scan_min_and_write<kLanes>(z, kn, true, e, tid, sh_red, sh_est, a.est, a.known);
 
   // ---- phase F: obs_out = obs with the scan rows replaced
   if (a.obs_out) {
     __syncthreads();
-    assemble(a.obs_out, a.obs, sh_est, e, a.obs_dim, a.scan_row0, tid);
+    assemble(a.obs_out, a.obs, sh_est, e, a.obs_dim, a.scan_row0, tid, kLanes);
   }
 }
 
@@ -383,13 +437,13 @@ static_assert(12 * PGTT_ELEVATION_VAR_MAX_GRID * PGTT_ELEVATION_VAR_MAX_GRID + 2
 // elevation_var_kernel<POINTS>: the variance tick (include/pgtt_elevation.h, "Variance-weighted fusion"), one workgroup of four waves per env.
 // Dynamic LDS: sh_acc[G G], one 64-bit word (n << 40 | S) per slot, then sh_m[G G], the key word of elevation_kernel.  After phase D sh_m holds the
 // fused heights and the low half of each sh_acc word the slot's variance.
-//   phase A, B  elevation_kernel's; the lanes zero both arrays.
+//   phase A, B  stage_tick and mark_stale; the lanes zero both arrays.
 //   phase C  two passes over the same pixels (or points) by ONE loop body, so that a point and its slot are the same bits in both: pass 0 raises
 //            sh_m[slot] (ds_max_u32 on the key), pass 1 adds (1 << 40 | q) to sh_acc[slot] (ds_add_u64) for the pixels inside the band.  The point is
 //            recomputed in pass 1: a lane holds up to 256 pixels of a 256 x 256 image, which no register file keeps.
 //   phase D  `map` and `var` stream through in 16-byte runs (dwords for an odd G G): stale slots to NaN, predict, measurement and update per slot; a
 //            run of either array is written back only when one of its slots changed there.
-//   phase E, F  elevation_kernel's, with est_var next to est.
+//   phase E, F  scan_min_and_write and assemble, with est_var next to est.
 // Integer LDS atomics only; no global atomics, no scratch.
 template <bool POINTS>
 __global__ void __launch_bounds__(kLanes) elevation_var_kernel(VarArgs va) {
@@ -404,54 +458,13 @@ __global__ void __launch_bounds__(kLanes) elevation_var_kernel(VarArgs va) {
   const long N = a.N;
   unsigned* sh_m = reinterpret_cast<unsigned*>(sh_acc + GG);
 
-  // ---- phase A: the poses (lane 0), as in elevation_kernel; the tick maximum and the sums start empty
-  if (tid == 0) {
-    const float* S = a.state + e;
-    const float bx = S[(PGTT_S_QPOS + 0) * N], by = S[(PGTT_S_QPOS + 1) * N], bz = S[(PGTT_S_QPOS + 2) * N];
-    float qw = S[(PGTT_S_QPOS + 3) * N], qx = S[(PGTT_S_QPOS + 4) * N], qy = S[(PGTT_S_QPOS + 5) * N], qz = S[(PGTT_S_QPOS + 6) * N];
-    const float qn = sqrtf(qw * qw + qx * qx + qy * qy + qz * qz);
-    qw /= qn; qx /= qn; qy /= qn; qz /= qn;
-    const float r00 = qw * qw + qx * qx - qy * qy - qz * qz, r01 = 2.f * (qx * qy - qw * qz), r02 = 2.f * (qx * qz + qw * qy);
-    const float r10 = 2.f * (qx * qy + qw * qz), r11 = qw * qw - qx * qx + qy * qy - qz * qz, r12 = 2.f * (qy * qz - qw * qx);
-    const float r20 = 2.f * (qx * qz - qw * qy), r21 = 2.f * (qy * qz + qw * qx), r22 = qw * qw - qx * qx - qy * qy + qz * qz;
-    sh_p[P_BASE + 0] = bx; sh_p[P_BASE + 1] = by; sh_p[P_BASE + 2] = bz;
-    sh_p[P_RB + 0] = r00; sh_p[P_RB + 1] = r01; sh_p[P_RB + 2] = r02; sh_p[P_RB + 3] = r10; sh_p[P_RB + 4] = r11; sh_p[P_RB + 5] = r12;
-    sh_p[P_RB + 6] = r20; sh_p[P_RB + 7] = r21; sh_p[P_RB + 8] = r22;
-    if constexpr (!POINTS) {
-      sh_p[P_CAM + 0] = bx + r00 * a.mpos[0] + r01 * a.mpos[1] + r02 * a.mpos[2];
-      sh_p[P_CAM + 1] = by + r10 * a.mpos[0] + r11 * a.mpos[1] + r12 * a.mpos[2];
-      sh_p[P_CAM + 2] = bz + r20 * a.mpos[0] + r21 * a.mpos[1] + r22 * a.mpos[2];
-      const float mw = a.mquat[0], mx = a.mquat[1], my = a.mquat[2], mz = a.mquat[3];
-      const float cw = qw * mw - qx * mx - qy * my - qz * mz, cx = qw * mx + qx * mw + qy * mz - qz * my;
-      const float cyq = qw * my - qx * mz + qy * mw + qz * mx, cz = qw * mz + qx * my - qy * mx + qz * mw;
-      const float fx = cw * cw + cx * cx - cyq * cyq - cz * cz, fy = 2.f * (cx * cyq + cw * cz), fz = 2.f * (cx * cz - cw * cyq);
-      const float ux = 2.f * (cx * cz + cw * cyq), uy = 2.f * (cyq * cz - cw * cx), uz = cw * cw - cx * cx - cyq * cyq + cz * cz;
-      sh_p[P_FWD + 0] = fx; sh_p[P_FWD + 1] = fy; sh_p[P_FWD + 2] = fz;
-      sh_p[P_UP + 0] = ux; sh_p[P_UP + 1] = uy; sh_p[P_UP + 2] = uz;
-      sh_p[P_RIGHT + 0] = fy * uz - fz * uy; sh_p[P_RIGHT + 1] = fz * ux - fx * uz; sh_p[P_RIGHT + 2] = fx * uy - fy * ux;
-    }
-    float sy, cy; yaw_sincos(qw, qx, qy, qz, sy, cy);
-    sh_p[P_SY] = sy; sh_p[P_CY] = cy;
-    const bool clear = a.clear_all || (a.clear_mask && a.clear_mask[e]) || (a.use_done && a.done && a.done[e] != 0.f);
-    const int ox = cell_of(bx, a.res), oy = cell_of(by, a.res);
-    const int lox = ox - G / 2, loy = oy - G / 2;
-    sh_i[I_LOX] = lox; sh_i[I_LOY] = loy; sh_i[I_LMX] = floor_mod(lox, G); sh_i[I_LMY] = floor_mod(loy, G);
-    const int px = a.origin[2 * (long)e], py = a.origin[2 * (long)e + 1];
-    const bool sane = px >= -(1 << 30) && px <= (1 << 30) && py >= -(1 << 30) && py <= (1 << 30);
-    sh_i[I_OLDX] = px - G / 2; sh_i[I_OLDY] = py - G / 2; sh_i[I_CLEAR] = (clear || !sane) ? 1 : 0;
-    a.origin[2 * (long)e] = ox; a.origin[2 * (long)e + 1] = oy;
-  }
+  // ---- phase A: the poses (lane 0); the tick maximum and the sums start empty
+  if (tid == 0) stage_tick<POINTS, false>(a, e, sh_p, sh_i);
   for (int s = tid; s < GG; s += kLanes) { sh_acc[s] = 0ull; sh_m[s] = 0u; }
   __syncthreads();
 
   // ---- phase B: per axis, the slots whose world cell moved
-  if (tid < 2 * G) {
-    const int ax = tid >= G, s = tid - ax * G;
-    const int lo_new = sh_i[I_LOX + ax], lo_old = sh_i[I_OLDX + ax];
-    unsigned char st = 1;
-    if (!sh_i[I_CLEAR]) st = (lo_new + floor_mod(s - lo_new, G)) != (lo_old + floor_mod(s - lo_old, G));
-    sh_stale[tid] = st;
-  }
+  mark_stale(sh_i, sh_stale, G, tid);
 
   // ---- phase C: pass 0 the tick maximum, pass 1 the band sums.  `admit` is what both do with a point that step 3 admits into `slot`
   const float bpx = uni(sh_p[P_BASE + 0]), bpy = uni(sh_p[P_BASE + 1]), bpz = uni(sh_p[P_BASE + 2]);
@@ -622,24 +635,13 @@ __global__ void __launch_bounds__(kLanes) elevation_var_kernel(VarArgs va) {
       if (kn) zv = reinterpret_cast<const float*>(sh_acc)[2 * slot];
     }
   }
-  float zmin = kn ? z : INFINITY;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) zmin = fminf(zmin, __shfl_xor(zmin, off, 64));
-  if (tid < 128 && (tid & 63) == 0) sh_red[tid >> 6] = zmin;
-  __syncthreads();
-  zmin = fminf(sh_red[0], sh_red[1]);
-  if (tid < PGTT_NSCAN) {
-    const float es = (kn && zmin < INFINITY) ? z - zmin : 0.f;
-    sh_est[tid] = es;
-    a.est[(long)e * PGTT_NSCAN + tid] = es;
-    a.known[(long)e * PGTT_NSCAN + tid] = kn ? 1 : 0;
-    va.est_var[(long)e * PGTT_NSCAN + tid] = zv;
-  }
+  scan_min_and_write<kLanes>(z, kn, true, e, tid, sh_red, sh_est, a.est, a.known);
+  if (tid < PGTT_NSCAN) va.est_var[(long)e * PGTT_NSCAN + tid] = zv;
 
   // ---- phase F: obs_out = obs with the scan rows replaced
   if (a.obs_out) {
     __syncthreads();
-    assemble(a.obs_out, a.obs, sh_est, e, a.obs_dim, a.scan_row0, tid);
+    assemble(a.obs_out, a.obs, sh_est, e, a.obs_dim, a.scan_row0, tid, kLanes);
   }
 }
 
@@ -666,26 +668,19 @@ __global__ void __launch_bounds__(kLanes) elevation_hold_kernel(HoldArgs a) {
 
   // ---- the pose, the clear and the window (lane 0 of the env)
   if (live && lt == 0) {
-    const float* S = a.state + e;
-    const float bx = S[(PGTT_S_QPOS + 0) * N], by = S[(PGTT_S_QPOS + 1) * N];
-    float qw = S[(PGTT_S_QPOS + 3) * N], qx = S[(PGTT_S_QPOS + 4) * N], qy = S[(PGTT_S_QPOS + 5) * N], qz = S[(PGTT_S_QPOS + 6) * N];
-    const float qn = sqrtf(qw * qw + qx * qx + qy * qy + qz * qz);
-    qw /= qn; qx /= qn; qy /= qn; qz /= qn;
-    sh_p[half][P_BASE + 0] = bx; sh_p[half][P_BASE + 1] = by;
-    float sy, cy; yaw_sincos(qw, qx, qy, qz, sy, cy);
-    sh_p[half][P_SY] = sy; sh_p[half][P_CY] = cy;
-    const bool clear = a.clear_all || (a.clear_mask && a.clear_mask[e]) || (a.use_done && a.done && a.done[e] != 0.f);
-    int ox, oy;
+    const Pose p = load_pose(a.state + e, N);
+    sh_p[half][P_BASE + 0] = p.bx; sh_p[half][P_BASE + 1] = p.by;
+    stage_yaw(p, sh_p[half]);
+    const bool clear = cleared(a, e);
+    int2 o;
     if (clear) {
       // a cleared env takes the cell of its current base position, as a tick's clear does
-      ox = cell_of(bx, a.res); oy = cell_of(by, a.res);
-      a.origin[2 * (long)e] = ox; a.origin[2 * (long)e + 1] = oy;
+      o = make_int2(cell_of(p.bx, a.res), cell_of(p.by, a.res));
+      a.origin[2 * (long)e] = o.x; a.origin[2 * (long)e + 1] = o.y;
     } else {
-      // the origin as the last fresh call left it; one outside the tick's clamp is as far away as the clamp (fill_kernel's rule)
-      ox = min(max(a.origin[2 * (long)e], -(1 << 30)), 1 << 30); oy = min(max(a.origin[2 * (long)e + 1], -(1 << 30)), 1 << 30);
+      o = stored_origin(a.origin, e);                                  // as the last fresh call left it
     }
-    const int lox = ox - G / 2, loy = oy - G / 2;
-    sh_i[half][I_LOX] = lox; sh_i[half][I_LOY] = loy; sh_i[half][I_LMX] = floor_mod(lox, G); sh_i[half][I_LMY] = floor_mod(loy, G);
+    stage_window(window_of(o.x, o.y, G), sh_i[half]);
     sh_i[half][I_CLEAR] = clear ? 1 : 0;
   }
   __syncthreads();
@@ -713,29 +708,12 @@ __global__ void __launch_bounds__(kLanes) elevation_hold_kernel(HoldArgs a) {
   }
 
   // ---- the minimum over the known points, est and known: phase E
-  float zmin = kn ? z : INFINITY;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) zmin = fminf(zmin, __shfl_xor(zmin, off, 64));
-  if ((lt & 63) == 0) sh_red[half][lt >> 6] = zmin;
-  __syncthreads();
-  zmin = fminf(sh_red[half][0], sh_red[half][1]);
-  if (live && lt < PGTT_NSCAN) {
-    const float es = (kn && zmin < INFINITY) ? z - zmin : 0.f;
-    sh_est[half][lt] = es;
-    a.est[(long)e * PGTT_NSCAN + lt] = es;
-    a.known[(long)e * PGTT_NSCAN + lt] = kn ? 1 : 0;
-  }
+  scan_min_and_write<kHoldLanes>(z, kn, live, e, lt, sh_red[half], sh_est[half], a.est, a.known);
 
   // ---- obs_out = obs with the scan rows replaced: phase F
   if (a.obs_out) {
     __syncthreads();
-    if (live) {
-      const int od = a.obs_dim;
-      for (int k = lt; k < od; k += kHoldLanes) {
-        const int j = k - a.scan_row0;
-        a.obs_out[(long)e * od + k] = (j >= 0 && j < PGTT_NSCAN) ? sh_est[half][j] : a.obs[(long)e * od + k];
-      }
-    }
+    if (live) assemble(a.obs_out, a.obs, sh_est[half], e, a.obs_dim, a.scan_row0, lt, kHoldLanes);
   }
 }
 
@@ -759,27 +737,22 @@ __global__ void __launch_bounds__(kLanes) fill_kernel(FillArgs a) {
   const int e = blockIdx.x, tid = threadIdx.x, G = a.G, GG = G * G, S = G + 2;
   const long N = a.N;
   unsigned char* sh_d = reinterpret_cast<unsigned char*>(sh_k + S * S);
-  // the origin as the tick left it; one outside the tick's clamp (a map never ticked) is as far away as the clamp.  Every lane forms the window
-  // (two broadcast reads), so the load needs no barrier in front of it
-  const int ox = min(max(a.origin[2 * (long)e], -(1 << 30)), 1 << 30), oy = min(max(a.origin[2 * (long)e + 1], -(1 << 30)), 1 << 30);
-  const int lox = ox - G / 2, loy = oy - G / 2, lmx = floor_mod(lox, G), lmy = floor_mod(loy, G);
+  // the window of the origin as the tick left it.  Every lane forms it (two broadcast reads), so the load needs no barrier in front of it
+  const int2 o = stored_origin(a.origin, e);
+  const Window win = window_of(o.x, o.y, G);
   // slot (sx, sy) -> its place in the bordered window: row (sx - lmx) mod G, column (sy - lmy) mod G, both + 1
   auto place = [&](int sx, int sy) {
-    int wa = sx - lmx, wb = sy - lmy;
+    int wa = sx - win.lmx, wb = sy - win.lmy;
     wa += wa < 0 ? G : 0; wb += wb < 0 ? G : 0;
     return (wa + 1) * S + wb + 1;
   };
 
   // ---- load: the pose (lane 0); the border, which is never a source and never filled; the keys and D of the map's slots
   if (tid == 0) {
-    const float* St = a.state + e;
-    float qw = St[(PGTT_S_QPOS + 3) * N], qx = St[(PGTT_S_QPOS + 4) * N], qy = St[(PGTT_S_QPOS + 5) * N], qz = St[(PGTT_S_QPOS + 6) * N];
-    const float qn = sqrtf(qw * qw + qx * qx + qy * qy + qz * qz);
-    qw /= qn; qx /= qn; qy /= qn; qz /= qn;
-    sh_p[P_BASE + 0] = St[(PGTT_S_QPOS + 0) * N]; sh_p[P_BASE + 1] = St[(PGTT_S_QPOS + 1) * N];
-    float sy, cy; yaw_sincos(qw, qx, qy, qz, sy, cy);
-    sh_p[P_SY] = sy; sh_p[P_CY] = cy;
-    sh_i[I_LOX] = lox; sh_i[I_LOY] = loy; sh_i[I_LMX] = lmx; sh_i[I_LMY] = lmy;
+    const Pose p = load_pose(a.state + e, N);
+    sh_p[P_BASE + 0] = p.bx; sh_p[P_BASE + 1] = p.by;
+    stage_yaw(p, sh_p);
+    stage_window(win, sh_i);
     sh_any[0] = 0; sh_any[1] = 0; sh_any[2] = 0;
   }
   for (int i = tid; i < S; i += kLanes) {
@@ -901,7 +874,7 @@ __global__ void __launch_bounds__(kLanes) fill_kernel(FillArgs a) {
   }
   if (a.obs_out) {
     __syncthreads();
-    assemble(a.obs_out, a.obs, sh_est, e, a.obs_dim, a.scan_row0, tid);
+    assemble(a.obs_out, a.obs, sh_est, e, a.obs_dim, a.scan_row0, tid, kLanes);
   }
 }
 
@@ -933,11 +906,10 @@ constexpr int kOdoTile = 3 * kLanes;                           // floats of one 
 // env e's update in the header's order: reads its rows of `state` and `odo`, writes `odo` and its column of pose_est, leaves the transform in t
 __device__ __forceinline__ void odo_update(const OdoArgs& a, int e, float* t) {
   const long N = a.N;
-  const float* S = a.state + e;
-  const float bx = S[(PGTT_S_QPOS + 0) * N], by = S[(PGTT_S_QPOS + 1) * N], bz = S[(PGTT_S_QPOS + 2) * N];
-  const float qw = S[(PGTT_S_QPOS + 3) * N], qx = S[(PGTT_S_QPOS + 4) * N], qy = S[(PGTT_S_QPOS + 5) * N], qz = S[(PGTT_S_QPOS + 6) * N];
+  const Pose p = load_pose<false>(a.state + e, N);                      // the quaternion as it stands
+  const float bx = p.bx, by = p.by, bz = p.bz, qw = p.qw, qx = p.qx, qy = p.qy, qz = p.qz;
   float* o = a.odo + (size_t)e * PGTT_ELEVATION_ODO_WORDS;
-  const bool clear = a.clear_all || (a.clear_mask && a.clear_mask[e]) || (a.use_done && a.done && a.done[e] != 0.f);
+  const bool clear = cleared(a, e);
   unsigned w0 = a.gid0 + (unsigned)e, w1 = (unsigned)a.counter[0], w2 = PGTT_RS_ODOMETRY, w3 = clear ? 1u : 0u;
   philox4x32_10(a.k0, a.k1, w0, w1, w2, w3);
   const float k24 = 1.0f / 16777216.0f;
@@ -1049,7 +1021,7 @@ __global__ void __launch_bounds__(kLanes) latency_push_kernel(PushArgs a) {
   const long long c = a.counter[0];
   const int w = floor_mod64(c, a.D);
   if (tid == 0) {
-    const bool clear = a.clear_all || (a.clear_mask && a.clear_mask[e]) || (a.use_done && a.done && a.done[e] != 0.f);
+    const bool clear = cleared(a, e);
     int L = a.lat[e], age = a.age[e];
     if (clear) {
       unsigned w0 = a.gid0 + (unsigned)e, w1 = (unsigned)c, w2 = PGTT_RS_LATENCY, w3 = 0u;
@@ -1108,7 +1080,7 @@ __global__ void __launch_bounds__(kLanes) visibility_kernel(VisArgs a) {
   const float nanv = __uint_as_float(0x7fc00000u);
 
   // ---- skip: the tick behind this call will clear the env
-  if (a.clear_all || (a.clear_mask && a.clear_mask[e]) || (a.use_done && a.done && a.done[e] != 0.f)) {
+  if (a.clear_all || (a.clear_mask && a.clear_mask[e]) || (a.use_done && a.done && a.done[e] != 0.f)) {      // cleared(a, e), written out: DESIGN.md 31
     if (tid == 0) a.cleared[e] = 0;
     if (a.bound_out) {
       float* bo = a.bound_out + (long)e * GG;
@@ -1323,12 +1295,28 @@ struct pgtt_elevation_map {
 
 namespace {
 
-// what both bind calls ask of the buffers but the source
-int check_buffers(const PgttElevationBuffers* bufs, const char* who) {
+// what both bind calls ask of the buffers; need_depth: pgtt_elevation_bind's source, the depth image, is required with them
+int check_buffers(const PgttElevationBuffers* bufs, const char* who, bool need_depth) {
   const std::string p = std::string(who) + ": ";
-  if (!bufs->state || !bufs->map || !bufs->origin || !bufs->est || !bufs->known) return fail(PGTT_E_ARG, p + "state, map, origin, est and known are required");
+  if (!bufs->state || (need_depth && !bufs->depth) || !bufs->map || !bufs->origin || !bufs->est || !bufs->known)
+    return fail(PGTT_E_ARG, p + (need_depth ? "state, depth, map, origin, est and known are required" : "state, map, origin, est and known are required"));
   if (bufs->obs_out && !bufs->obs) return fail(PGTT_E_ARG, p + "obs is required with obs_out");
   return PGTT_OK;
+}
+
+// may `count` floats per env stream in 16-byte runs: every env's block then starts on a 16-byte boundary of p0 (and p1); a NULL pointer counts as
+// aligned, it is not streamed
+bool runs16(long count, const void* p0, const void* p1 = nullptr) { return count % 4 == 0 && ((uintptr_t)p0 & 15) == 0 && ((uintptr_t)p1 & 15) == 0; }
+
+// the config's camera and self filter as the kernels take them: ElevArgs and VisArgs, the same fields
+template <class A>
+void camera_args(const PgttElevationConfig& c, A& a) {
+  a.W = c.width; a.H = c.height;
+  a.self_on = (c.self_half[0] != 0.f || c.self_half[1] != 0.f || c.self_half[2] != 0.f) ? 1 : 0;
+  const double th = std::tan(0.5 * (double)c.fovy_deg * 3.14159265358979323846 / 180.0);
+  a.near_m = c.near; a.far_m = c.far; a.tu = (float)(th * c.width / c.height); a.tv = (float)th;
+  for (int i = 0; i < 3; i++) { a.mpos[i] = c.mount_pos[i]; a.self_half[i] = c.self_half[i]; }
+  for (int i = 0; i < 4; i++) a.mquat[i] = c.mount_quat[i];
 }
 
 // the kernel arguments of one tick on the handle's config and buffers
@@ -1338,17 +1326,12 @@ ElevArgs tick_args(const pgtt_elevation_map* h, const uint8_t* clear_mask, int c
   ElevArgs a{};
   a.state = b.state; a.depth = b.depth; a.obs = b.obs; a.done = b.done; a.clear_mask = clear_mask;
   a.map = b.map; a.origin = b.origin; a.est = b.est; a.known = b.known; a.obs_out = b.obs_out;
-  a.N = h->num_envs; a.W = c.width; a.H = c.height; a.G = c.grid; a.obs_dim = c.obs_dim; a.scan_row0 = c.scan_row0;
+  a.N = h->num_envs; a.G = c.grid; a.obs_dim = c.obs_dim; a.scan_row0 = c.scan_row0;
   a.clear_all = clear_all ? 1 : 0; a.use_done = use_done ? 1 : 0;
-  a.self_on = (c.self_half[0] != 0.f || c.self_half[1] != 0.f || c.self_half[2] != 0.f) ? 1 : 0;
-  // 16-byte runs need every env's block to start on a 16-byte boundary
-  a.vec_map = ((c.grid * c.grid) % 4 == 0 && ((uintptr_t)b.map & 15) == 0) ? 1 : 0;
-  a.vec_img = ((c.width * c.height) % 4 == 0 && ((uintptr_t)b.depth & 15) == 0) ? 1 : 0;
-  const double th = std::tan(0.5 * (double)c.fovy_deg * 3.14159265358979323846 / 180.0);
-  a.near_m = c.near; a.far_m = c.far; a.res = c.res; a.alpha = c.alpha; a.tu = (float)(th * c.width / c.height); a.tv = (float)th;
-  a.sdx = c.scan_dist_x; a.sdy = c.scan_dist_y;
-  for (int i = 0; i < 3; i++) { a.mpos[i] = c.mount_pos[i]; a.self_half[i] = c.self_half[i]; }
-  for (int i = 0; i < 4; i++) a.mquat[i] = c.mount_quat[i];
+  camera_args(c, a);
+  a.vec_map = runs16(c.grid * c.grid, b.map) ? 1 : 0;
+  a.vec_img = runs16(c.width * c.height, b.depth) ? 1 : 0;
+  a.res = c.res; a.alpha = c.alpha; a.sdx = c.scan_dist_x; a.sdy = c.scan_dist_y;
   a.points = h->points; a.P = h->P;
   return a;
 }
@@ -1406,8 +1389,7 @@ int launch_var(pgtt_elevation_map* h, bool points, const uint8_t* clear_mask, in
   const PgttElevationVar& v = h->var;
   VarArgs va{};
   va.a = tick_args(h, clear_mask, clear_all, use_done);
-  // map and var stream together: 16-byte runs need both to start on a 16-byte boundary
-  if (((uintptr_t)v.var & 15) != 0) va.a.vec_map = 0;
+  va.a.vec_map = runs16(c.grid * c.grid, h->buf.map, v.var) ? 1 : 0;      // map and var stream together
   va.var = v.var; va.est_var = v.est_var;
   va.s0sq = (float)((double)v.sigma0 * v.sigma0); va.srsq = (float)((double)v.sigma_rel * v.sigma_rel); va.gate2 = (float)((double)v.gate * v.gate);
   va.process = v.process; va.band = v.band; va.var_max = v.var_max; va.max_count = v.max_count;
@@ -1489,9 +1471,8 @@ int pgtt_elevation_delayed(pgtt_elevation_handle h, const uint8_t* clear_mask, i
   p.N = h->num_envs; p.D = l.D; p.F = points ? 3 * h->P : c.width * c.height;
   p.clear_all = a.clear_all; p.use_done = a.use_done; p.lat_lo = l.lat_lo; p.lat_hi = l.lat_hi;
   p.k0 = (unsigned)l.seed; p.k1 = (unsigned)(l.seed >> 32); p.gid0 = (unsigned)l.env_id_offset;
-  // 16-byte runs need every env's frame to start on a 16-byte boundary, in the source and in the ring
-  const bool ring16 = p.F % 4 == 0 && ((uintptr_t)l.ring_data & 15) == 0;
-  p.vec = (ring16 && ((uintptr_t)p.src & 15) == 0) ? 1 : 0;
+  const bool ring16 = runs16(p.F, l.ring_data);
+  p.vec = (ring16 && ((uintptr_t)p.src & 15) == 0) ? 1 : 0;            // the frame's runs: in the ring and in the source
   hipLaunchKernelGGL(latency_push_kernel, dim3(h->num_envs), dim3(kLanes), 0, (hipStream_t)stream, p);
   HIP_TRY(hipGetLastError());
   a.ring_data = l.ring_data; a.ring_pose = l.ring_pose; a.lat = l.lat; a.fused = l.fused; a.lat_counter = l.counter; a.D = l.D;
@@ -1531,18 +1512,13 @@ int pgtt_elevation_visibility(pgtt_elevation_handle h, const uint8_t* clear_mask
   VisArgs a{};
   a.state = b.state; a.depth = b.depth; a.done = b.done; a.clear_mask = clear_mask; a.points = h->points; a.origin = b.origin;
   a.map = b.map; a.var = h->has_var ? h->var.var : nullptr; a.cleared = v.cleared; a.bound_out = v.bound_out;
-  a.N = h->num_envs; a.W = c.width; a.H = c.height; a.G = c.grid; a.P = h->P; a.stride = v.stride;
+  a.N = h->num_envs; a.G = c.grid; a.P = h->P; a.stride = v.stride;
   a.clear_all = clear_all ? 1 : 0; a.use_done = use_done ? 1 : 0;
-  a.self_on = (c.self_half[0] != 0.f || c.self_half[1] != 0.f || c.self_half[2] != 0.f) ? 1 : 0;
-  // 16-byte runs need every env's block to start on a 16-byte boundary: map and var stream together
-  const bool quads = (c.grid * c.grid) % 4 == 0;
-  a.vec_map = (quads && ((uintptr_t)b.map & 15) == 0 && ((uintptr_t)a.var & 15) == 0) ? 1 : 0;
-  a.vec_out = (quads && ((uintptr_t)v.bound_out & 15) == 0) ? 1 : 0;
-  const double th = std::tan(0.5 * (double)c.fovy_deg * 3.14159265358979323846 / 180.0);
-  a.near_m = c.near; a.far_m = c.far; a.res = c.res; a.tu = (float)(th * c.width / c.height); a.tv = (float)th;
-  a.margin = v.margin; a.end_guard = v.end_guard; a.sigmas = v.sigmas;
-  for (int i = 0; i < 3; i++) { a.mpos[i] = c.mount_pos[i]; a.self_half[i] = c.self_half[i]; a.spos[i] = v.sensor_pos[i]; }
-  for (int i = 0; i < 4; i++) a.mquat[i] = c.mount_quat[i];
+  camera_args(c, a);
+  a.vec_map = runs16(c.grid * c.grid, b.map, a.var) ? 1 : 0;           // map and var stream together
+  a.vec_out = runs16(c.grid * c.grid, v.bound_out) ? 1 : 0;
+  a.res = c.res; a.margin = v.margin; a.end_guard = v.end_guard; a.sigmas = v.sigmas;
+  for (int i = 0; i < 3; i++) a.spos[i] = v.sensor_pos[i];
   const size_t lds = (size_t)c.grid * c.grid * sizeof(unsigned);
   if (points) hipLaunchKernelGGL(visibility_kernel<true>, dim3(h->num_envs), dim3(kLanes), lds, (hipStream_t)stream, a);
   else hipLaunchKernelGGL(visibility_kernel<false>, dim3(h->num_envs), dim3(kLanes), lds, (hipStream_t)stream, a);
@@ -1642,9 +1618,7 @@ int pgtt_elevation_destroy(pgtt_elevation_handle h) {
 
 int pgtt_elevation_bind(pgtt_elevation_handle h, const PgttElevationBuffers* bufs) {
   if (!h || !bufs) return fail(PGTT_E_ARG, "pgtt_elevation_bind: null argument");
-  if (!bufs->state || !bufs->depth || !bufs->map || !bufs->origin || !bufs->est || !bufs->known)
-    return fail(PGTT_E_ARG, "pgtt_elevation_bind: state, depth, map, origin, est and known are required");
-  if (bufs->obs_out && !bufs->obs) return fail(PGTT_E_ARG, "pgtt_elevation_bind: obs is required with obs_out");
+  if (int rc = check_buffers(bufs, "pgtt_elevation_bind", true)) return rc;
   h->buf = *bufs;
   h->bound = true;
   h->points = nullptr; h->P = 0;
@@ -1653,7 +1627,7 @@ int pgtt_elevation_bind(pgtt_elevation_handle h, const PgttElevationBuffers* buf
 
 int pgtt_elevation_bind_points(pgtt_elevation_handle h, const PgttElevationBuffers* bufs, const float* points, int P) {
   if (!h || !bufs) return fail(PGTT_E_ARG, "pgtt_elevation_bind_points: null argument");
-  if (int rc = check_buffers(bufs, "pgtt_elevation_bind_points")) return rc;
+  if (int rc = check_buffers(bufs, "pgtt_elevation_bind_points", false)) return rc;
   if (!points || P < 1) return fail(PGTT_E_ARG, "pgtt_elevation_bind_points: points is required, with P >= 1");
   h->buf = *bufs;
   h->bound = true;
@@ -1711,11 +1685,9 @@ int pgtt_elevation_fill(pgtt_elevation_handle h, void* stream) {
   a.state = h->buf.state; a.obs = h->buf.obs; a.map = h->buf.map; a.origin = h->buf.origin;
   a.est = o.est; a.dist = o.dist; a.obs_out = o.obs_out; a.map_out = o.map_out; a.dist_out = o.dist_out;
   a.N = h->num_envs; a.G = c.grid; a.obs_dim = c.obs_dim; a.scan_row0 = c.scan_row0; a.passes = h->passes;
-  // 16-byte (map, map_out) and 4-byte (dist_out) runs need every env's block to start on such a boundary
-  const bool quads = (c.grid * c.grid) % 4 == 0;
-  a.vec_map = (quads && ((uintptr_t)a.map & 15) == 0) ? 1 : 0;
-  a.vec_out = (quads && ((uintptr_t)o.map_out & 15) == 0) ? 1 : 0;
-  a.vec_dist = (quads && ((uintptr_t)o.dist_out & 3) == 0) ? 1 : 0;          // a NULL output counts as aligned: it is not written
+  a.vec_map = runs16(c.grid * c.grid, a.map) ? 1 : 0;
+  a.vec_out = runs16(c.grid * c.grid, o.map_out) ? 1 : 0;
+  a.vec_dist = ((c.grid * c.grid) % 4 == 0 && ((uintptr_t)o.dist_out & 3) == 0) ? 1 : 0;            // dist_out's runs are 4 bytes; NULL counts as aligned
   a.res = c.res; a.sdx = c.scan_dist_x; a.sdy = c.scan_dist_y;
   const size_t lds = (size_t)(c.grid + 2) * (c.grid + 2) * (sizeof(unsigned) + 1);
   hipLaunchKernelGGL(fill_kernel, dim3(h->num_envs), dim3(kLanes), lds, (hipStream_t)stream, a);

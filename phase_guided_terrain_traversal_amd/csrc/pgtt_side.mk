@@ -33,7 +33,7 @@ $(foreach l,$(LIBS),$(eval $(call ask_srchash,$(l))))
 
 all: $(OUTS)
 
-.PHONY: all clean resources FORCE
+.PHONY: all clean resources asm FORCE
 # the objects stay: a second run recompiles nothing
 .SECONDARY: $(OBJS)
 .SECONDEXPANSION:
@@ -52,6 +52,13 @@ resources: $(foreach l,$(LIBS),$(BUILD)/$(l)_resources.o)
 $(BUILD)/%_resources.o: pgtt_%.hip FORCE
 	@mkdir -p $(BUILD)
 	$(HIPCC) $(FLAGS) $(DEFS) --cuda-device-only -Rpass-analysis=kernel-resource-usage -c $< -o $@
+
+# the device assembly of $(LIBS), $(BUILD)/<lib>.s: what tools/side_isa_diff.py compares between two trees (no GPU needed)
+asm: $(foreach l,$(LIBS),$(BUILD)/$(l).s)
+
+$(BUILD)/%.s: pgtt_%.hip FORCE
+	@mkdir -p $(BUILD)
+	$(HIPCC) $(FLAGS) $(DEFS) --cuda-device-only -S $< -o $@
 
 FORCE:
 
