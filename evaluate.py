@@ -95,6 +95,16 @@ class VideoRecorder:
         self.camera = Camera("track", target=(0.0, 0.0, 0.0), distance=2.2, azimuth=120.0, elevation=-25.0, fovy=45.0)
         self.frames = []
         self.depth = None
+        # --video_elevation MODE: a second tile beside each env's RGB tile, the elevation map drawn from the same camera (Renderer.render_map)
+        self.elevation = getattr(args, "video_elevation", None)
+        if self.elevation is not None:
+            em = env.elevation_map
+            if em is None:
+                raise SystemExit("--video_elevation draws --elevation's map: give --elevation too")
+            if self.elevation == "var" and em.variance is None:
+                raise SystemExit("--video_elevation var draws the variance layer: give --elevation_variance too")
+            if self.elevation == "filled" and not em.dense:
+                raise SystemExit("--video_elevation filled draws the filled map: give --elevation_fill too")
         if getattr(args, "video_depth", False):
             # --video_depth: each env's onboard depth image (the sensor of depth.DEFAULTS, resolution included), grey, scaled to the tile by
             # nearest neighbour and put under its RGB tile
@@ -110,6 +120,11 @@ class VideoRecorder:
             p = scan_points(self.env, self.ids)
             markers = torch.cat([p, torch.full_like(p[..., :1], 0.012)], -1)
         rgb = self.renderer.render(self.ids, camera=self.camera, markers=markers)["rgb"]
+        if self.elevation is not None:
+            # height: the belief view; var / filled: tinted by the variance layer / by the pass that filled the cell; overlay: over the true terrain
+            kw = {"height": {}, "var": dict(tint="var"), "filled": dict(tint="dist"), "overlay": dict(terrain=True)}[self.elevation]
+            belief = self.renderer.render_map(self.ids, self.env.elevation_map, camera=self.camera, markers=markers, **kw)["rgb"]
+            rgb = torch.stack([rgb, belief], 1).flatten(0, 1)
         v, h, w, _ = rgb.shape
         frame = rgb.permute(1, 0, 2, 3).reshape(h, v * w, 3).clone()
         bar = max(1, h // 80)
@@ -117,7 +132,7 @@ class VideoRecorder:
         if self.depth is not None:
             d = self.depth.tick(force=True)[self.ids]
             grey = (255 * (1 - (d - self.depth.near) / (self.depth.far - self.depth.near))).clamp(0, 255).to(torch.uint8)
-            grey = resize_nearest(grey, h, w)
+            grey = resize_nearest(grey, h, w * (v // len(self.ids)))             # under the env's tiles, however many it has
             frame = torch.cat([frame, grey.permute(1, 0, 2).reshape(h, v * w, 1).expand(h, v * w, 3)], 0)
         self.frames.append(frame)
 
@@ -147,6 +162,15 @@ def sensor_kwargs(args):
         # depth image (the camera of depth.DEFAULTS) - instead of the privileged scan
         kw.update(depth=dict(noisy), student=args.student)
     elev = getattr(args, "elevation", None)
+    if getattr(args, "video_elevation", None) is not None:
+        if elev is None:
+            raise SystemExit("--video_elevation draws --elevation's map beside the scene: give --elevation too")
+        if not getattr(args, "video", None):
+            raise SystemExit("--video_elevation adds a tile to --video's frames: give --video too")
+        if args.video_elevation == "var" and getattr(args, "elevation_variance", None) is None:
+            raise SystemExit("--video_elevation var draws the variance layer: give --elevation_variance too")
+        if args.video_elevation == "filled" and getattr(args, "elevation_fill", None) is None:
+            raise SystemExit("--video_elevation filled draws the filled map: give --elevation_fill too")
     if noisy and elev is None and not getattr(args, "student", None):
         raise SystemExit("--sensor_noise is the noise of the sensor that feeds --elevation's map or --student: give one of them too")
     if getattr(args, "elevation_variance", None) is not None and elev is None:
@@ -174,6 +198,8 @@ def sensor_kwargs(args):
             if fill is not True and not 1 <= fill <= 95:                 # a caller that built the namespace without the parser
                 raise SystemExit(f"--elevation_fill {fill}: the number of passes must be in [1, 95]")
             given = dict({} if given is True else given, fill=fill)
+            if getattr(args, "video_elevation", None) == "filled":
+                given["dense"] = True                                      # the video draws the filled map itself, so the fill keeps it
         source = getattr(args, "elevation_source", "depth")
         # --sensor_every M: the sensor that feeds the map takes new data at one control step in M; for M > 1 the map follows it (follow_sensor):
         # it fuses on those steps and in between samples the held map at the current pose
@@ -459,6 +485,10 @@ def make_parser():
     ap.add_argument("--video_every", type=int, default=2, help="one frame every n control steps")
     ap.add_argument("--video_scan", action="store_true", help="overlay the 117 height-scan hits as marker spheres")
     ap.add_argument("--video_depth", action="store_true", help="tile each video env's onboard depth image (grey, near = white) under its RGB tile")
+    ap.add_argument("--video_elevation", type=str, nargs="?", const="height", default=None, choices=("height", "var", "filled", "overlay"),
+                    help="with --video and --elevation: tile the elevation map, drawn from the same camera, beside each env's RGB tile: coloured by "
+                         "height (default), by variance (needs --elevation_variance), the filled map by fill pass (needs --elevation_fill), or "
+                         "lifted 1 cm over the true terrain")
     add_sensor_args(ap)
     configs.add_push_args(ap)
     ap.add_argument("--terrain_files", type=str, default=None, help="comma-separated level files stacked into one table (as train.py --terrain_files); evaluated on --level")

@@ -21,6 +21,26 @@
  * visible = 0 when a shadow ray from hit + PGTT_RENDER_SHADOW_EPS * n toward l hits a box or a robot geom (markers and the plane cast no
  * shadow), 1 otherwise or with shadows off.  A miss takes the sky colour SKY_HORIZON + (SKY_ZENITH - SKY_HORIZON) * max(0, d.z).
  * Stored as round(255 * clamp(c, 0, 1)) (round half to even, no gamma), packed r | g << 8 | b << 16 | 255 << 24.
+ *
+ * The map call, pgtt_render_map(): the same views, with an env's elevation map drawn as a height field of cell columns.  This header does not
+ * include the elevation library's; it restates the layout that header's "Map" paragraph gives.  `map` is [N][G][G] heights, NaN = not drawn.
+ * For the view's env e, with lo = origin[e] - G/2 (integer division, G/2 rounded down; an origin outside +-2^30 is taken as +-2^30, as the
+ * map's hole filling takes it): the WINDOW cell (a, b), 0 <= a, b < G, is world cell (lo_x + a, lo_y + b) and is stored at slot
+ * [(lo_x + a) mod G][(lo_y + b) mod G] (floor-mod).  Any G from 1 to PGTT_RENDER_MAP_MAX_GRID is legal here.
+ * Scene of a map call.  A window cell whose height h is not NaN and with h + lift > floor_z is a COLUMN: the axis-aligned box
+ *     [(lo_x + a) res, (lo_x + a + 1) res] x [(lo_y + b) res, (lo_y + b + 1) res] x [floor_z, h + lift].
+ * A pixel's ray takes the nearest hit over: all columns, each by the box rule above (entry distance, t > 0, a ray that starts inside a column
+ * does not see it); the robot geoms; the markers; and, only with PGTT_RENDER_MAP_TERRAIN, the plane z = 0 and the env's terrain boxes.  That
+ * brute-force statement is the contract; the kernel walks the cells a ray crosses instead.  Without the terrain flag a ray that hits nothing
+ * takes the sky colour: a hole in the map shows sky.
+ * Column normal: the face's axis, signed against the ray.  Column albedo: COLD + (HOT - COLD) x, x = clamp((s - tint_lo) / (tint_hi - tint_lo),
+ * 0, 1), where s = tint[slot] when a tint layer is bound and the cell's height h (without lift) otherwise; NOVALUE when s is NaN.
+ * Shading as above; with PGTT_RENDER_SHADOWS columns cast and receive shadows: the shadow ray is occluded by any column, any robot geom and,
+ * with the terrain flag, any box.  Segmentation of a column: PGTT_SEG_CELL + a * G + b.  Depth as above.
+ * A view renders to the same bits whatever else is in the batch; nothing but the images and the workspace is written.  With no column drawn
+ * (all NaN, or every h + lift <= floor_z) and the terrain flag set, every output has the bits of pgtt_render() on the same views.
+ * Refused (PGTT_E_ARG): everything pgtt_render() refuses; a NULL PgttRenderMap, map or origin; grid outside [1, PGTT_RENDER_MAP_MAX_GRID];
+ * res not positive and finite; a non-finite floor_z, lift, tint_lo or tint_hi; tint_hi <= tint_lo; flag bits other than the one defined.
  */
 #ifndef PGTT_RENDER_H_
 #define PGTT_RENDER_H_
@@ -38,6 +58,7 @@ extern "C" {
 #define PGTT_RENDER_MAX_MARKER 128     /* marker spheres per view (the 117 height-scan hits fit) */
 #define PGTT_RENDER_MAX_DIM 4096       /* W and H */
 #define PGTT_RENDER_MAX_VIEWS 16384     /* views per call (the pixel grid's second dimension) */
+#define PGTT_RENDER_MAP_MAX_GRID 96    /* G of a map call: the window of heights is staged per pixel tile, 4 G G <= 36864 bytes */
 
 /* ---------------------------------------------------------------- shading constants (tests restate them) */
 #define PGTT_RENDER_LIGHT_X 0.4f       /* direction TOWARD the light, normalised in the kernel */
@@ -65,6 +86,15 @@ extern "C" {
 #define PGTT_RENDER_SKY_ZENITH_R 0.30f
 #define PGTT_RENDER_SKY_ZENITH_G 0.50f
 #define PGTT_RENDER_SKY_ZENITH_B 0.85f
+#define PGTT_RENDER_MAP_COLD_R 0.15f   /* map columns: albedo at tint_lo and below */
+#define PGTT_RENDER_MAP_COLD_G 0.35f
+#define PGTT_RENDER_MAP_COLD_B 0.85f
+#define PGTT_RENDER_MAP_HOT_R 0.95f    /* at tint_hi and above */
+#define PGTT_RENDER_MAP_HOT_G 0.25f
+#define PGTT_RENDER_MAP_HOT_B 0.10f
+#define PGTT_RENDER_MAP_NOVALUE_R 0.45f /* where the tint layer is NaN */
+#define PGTT_RENDER_MAP_NOVALUE_G 0.45f
+#define PGTT_RENDER_MAP_NOVALUE_B 0.45f
 
 /* ---------------------------------------------------------------- segmentation ids */
 #define PGTT_SEG_SKY (-1)
@@ -72,12 +102,14 @@ extern "C" {
 #define PGTT_SEG_BOX 1                 /* + box index b (0 .. B-1) */
 #define PGTT_SEG_GEOM 1000             /* + robot geom index g */
 #define PGTT_SEG_MARKER 2000           /* + marker index k */
+#define PGTT_SEG_CELL 10000            /* + a * G + b, the WINDOW cell (a, b) of a map call */
 
 enum { PGTT_RENDER_SPHERE = 0, PGTT_RENDER_CAPSULE = 1, PGTT_RENDER_BOX = 2 };
 /* FIXED: look-at = target (world).  TRACK: look-at = base position (qpos[0:3]) + target.  TRACK_YAW: as TRACK, and the azimuth is
  * azimuth_deg + the base yaw (atan2 of the normalised base quaternion, as the height scan takes it) in degrees. */
 enum { PGTT_CAM_FIXED = 0, PGTT_CAM_TRACK = 1, PGTT_CAM_TRACK_YAW = 2 };
 enum { PGTT_RENDER_SHADOWS = 1 };     /* PgttRenderViews.flags */
+enum { PGTT_RENDER_MAP_TERRAIN = 1 }; /* PgttRenderMap.flags: draw the plane and the terrain boxes too */
 
 /* A robot primitive rigidly attached to body `body` (0 .. PGTT_NBODY-1), pose in that body's frame.
  * size: sphere (radius, -, -); capsule (radius, half-length along the local z axis, -); box (half extents x, y, z). */
@@ -122,6 +154,19 @@ typedef struct PgttRenderViews {
   void* workspace;                     /* device, pgtt_render_workspace_bytes(V) bytes, 16-byte aligned */
 } PgttRenderViews;
 
+/* The height field of a map call (layout and scene: the head of this file).  All three pointers are DEVICE pointers, only read. */
+typedef struct PgttRenderMap {
+  const float* map;                    /* device [N][G][G], required: heights, NaN = not drawn */
+  const int32_t* origin;               /* device [N][2], required */
+  const float* tint;                   /* device [N][G][G] in the same layout, or NULL: the colour is then taken from the height */
+  int32_t grid;                        /* G, 1 .. PGTT_RENDER_MAP_MAX_GRID */
+  float res;                           /* cell size, > 0, finite */
+  float floor_z;                       /* finite: every column stands on this plane */
+  float lift;                          /* finite: added to every height when drawn (0 in the belief view; a centimetre over the true terrain) */
+  float tint_lo, tint_hi;              /* finite, tint_lo < tint_hi */
+  int32_t flags;                       /* PGTT_RENDER_MAP_TERRAIN */
+} PgttRenderMap;
+
 typedef struct pgtt_renderer* pgtt_render_handle;
 
 /* `model` gives the kinematic tree (body_pos, body_quat, jnt_axis, qpos0); `geoms` (host, ngeom <= PGTT_RENDER_MAX_GEOM) the robot
@@ -134,9 +179,12 @@ int pgtt_render_set_terrain(pgtt_render_handle h, const float* boxes_TxBx10, int
 /* bytes of the caller-owned workspace a call with `num_views` views needs (0 when num_views is out of range) */
 int64_t pgtt_render_workspace_bytes(int num_views);
 int pgtt_render(pgtt_render_handle h, const PgttRenderViews* v, void* stream);
+/* the views of `v` with the height field `m` drawn as columns: the same setup kernel and workspace, a pixel kernel of its own */
+int pgtt_render_map(pgtt_render_handle h, const PgttRenderViews* v, const PgttRenderMap* m, void* stream);
 int pgtt_render_sizeof_geom(void);
 int pgtt_render_sizeof_camera(void);
 int pgtt_render_sizeof_views(void);
+int pgtt_render_sizeof_map(void);
 /* "src=<SHA-256 of pgtt_render.hip and this header>;flavor=product" */
 const char* pgtt_render_build_info(void);
 const char* pgtt_render_last_error(void);

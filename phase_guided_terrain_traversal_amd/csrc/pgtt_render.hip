@@ -7,6 +7,9 @@
 //   render_pixel_kernel : grid (16x16 pixel tiles, views).  The prologue stages the view record, the env's terrain variant (ray-ready boxes)
 //                         and the view's markers into LDS; every lane then walks the same primitive list (wave-uniform bounds, LDS
 //                         broadcasts), takes the closest hit, casts one shadow ray toward the light and stores one packed RGBA dword.
+//                         pgtt_render() launches render_pixel_kernel<false>.  pgtt_render_map() launches render_pixel_kernel<true, MapArgs>
+//                         behind the same setup kernel: it also stages the env's window of elevation heights and walks the cell columns
+//                         a ray crosses (hit_columns).
 // Nothing is shared between views and nothing is atomic, so a view renders to the same bits whatever else is in the batch.
 #include <hip/hip_runtime.h>
 
@@ -165,14 +168,102 @@ __device__ __forceinline__ float hit_geom(V3 o, V3 d, const float* __restrict__ 
   return hit_box(o, d, bx, axis, sgn);
 }
 
+// ---------------------------------------------------------------- the columns of a map call (include/pgtt_render.h, "Scene of a map call")
+struct MapArgs {
+  const float* map;
+  const int32_t* origin;
+  const float* tint;
+  int G;
+  float res, floor_z, lift, tint_lo, tint_hi;
+  int terrain;
+};
+
+// Nearest column along the ray ol + t d, ol in WINDOW-LOCAL coordinates (cell (a, b) spans [a res, (a + 1) res] x [b res, (b + 1) res]; the
+// window's corner lo res is subtracted once per lane, so the rounding of a far-away window is paid once and not per cell).  hm is the window of
+// heights in window order, [G][G].  The ray is clipped to the window's box [0, G res]^2 x [floor_z, inf) and to t_stop (the best hit among the
+// other primitives), then walks the cells it crosses in order - a 2-D grid traversal, at most 2 G - 1 cells - and tests each column with the slab
+// rule in z against the cell's own xy crossing [t_in, t_out]: the first hit is the nearest.  The next border crossing is formed from the integer
+// cell index at every step (one multiply and one fused multiply-add per axis), not summed up from a tDelta, so that its rounding does not grow
+// with the number of steps either.  A direction component of magnitude below 1e-30 is a ray parallel to that axis: it crosses no border of it,
+// and no division by it decides anything.  -> t (INFINITY: none), cell = a G + b, axis = the face's axis.
+__device__ __forceinline__ float hit_columns(const float* __restrict__ hm, int G, float res, float floor_z, float lift, V3 ol, V3 d, float t_stop,
+                                             int& cell, int& axis) {
+  const float ext = (float)G * res;
+  const bool mx = fabsf(d.x) > 1e-30f, my = fabsf(d.y) > 1e-30f, mz = fabsf(d.z) > 1e-30f;
+  const float ivx = mx ? 1.f / d.x : 0.f, ivy = my ? 1.f / d.y : 0.f, ivz = mz ? 1.f / d.z : 0.f;
+  float t0 = 0.f, t1 = t_stop;
+  int ax = 2;                                    // the axis through which the ray entered the current cell; 2: it starts inside (or enters through the floor)
+  if (mx) {
+    const float ta = (0.f - ol.x) * ivx, tb = (ext - ol.x) * ivx;
+    const float lo = fminf(ta, tb);
+    if (lo > t0) { t0 = lo; ax = 0; }
+    t1 = fminf(t1, fmaxf(ta, tb));
+  } else if (ol.x < 0.f || ol.x > ext) return INFINITY;
+  if (my) {
+    const float ta = (0.f - ol.y) * ivy, tb = (ext - ol.y) * ivy;
+    const float lo = fminf(ta, tb);
+    if (lo > t0) { t0 = lo; ax = 1; }
+    t1 = fminf(t1, fmaxf(ta, tb));
+  } else if (ol.y < 0.f || ol.y > ext) return INFINITY;
+  if (mz) {
+    const float tf = (floor_z - ol.z) * ivz;
+    if (d.z > 0.f) { if (tf > t0) { t0 = tf; ax = 2; } }
+    else t1 = fminf(t1, tf);
+  } else if (ol.z < floor_z) return INFINITY;
+  if (!(t0 <= t1)) return INFINITY;
+  const float inv_res = 1.f / res;
+  int ix = min(max((int)floorf((ol.x + t0 * d.x) * inv_res), 0), G - 1);
+  int iy = min(max((int)floorf((ol.y + t0 * d.y) * inv_res), 0), G - 1);
+  const int sx = d.x > 0.f ? 1 : -1, sy = d.y > 0.f ? 1 : -1;
+  const int fx = d.x > 0.f ? 1 : 0, fy = d.y > 0.f ? 1 : 0;
+  float t_in = t0;
+  for (int it = 0; it < 2 * G; it++) {
+    const float tmx = mx ? ((float)(ix + fx) * res - ol.x) * ivx : INFINITY;
+    const float tmy = my ? ((float)(iy + fy) * res - ol.y) * ivy : INFINITY;
+    const float t_out = fminf(tmx, tmy);
+    const float h = hm[ix * G + iy], top = h + lift;
+    if (top > floor_z) {                         // false for NaN
+      float lo, hi;
+      if (mz) {
+        const float ta = (floor_z - ol.z) * ivz, tb = (top - ol.z) * ivz;
+        lo = fminf(ta, tb); hi = fmaxf(ta, tb);
+      } else {
+        lo = ol.z <= top ? -INFINITY : INFINITY; hi = INFINITY;
+      }
+      const float tn = fmaxf(t_in, lo), tf = fminf(t_out, hi);
+      if (tn <= tf && tn > 0.f) {
+        cell = ix * G + iy;
+        axis = lo > t_in ? 2 : ax;
+        return tn;
+      }
+    }
+    if (t_out >= t1) break;                      // the next cell begins behind the window, behind the floor or behind a nearer primitive
+    if (tmx < tmy) { ix += sx; ax = 0; if ((unsigned)ix >= (unsigned)G) break; }
+    else { iy += sy; ax = 1; if ((unsigned)iy >= (unsigned)G) break; }
+    t_in = t_out;
+  }
+  return INFINITY;
+}
+
 // ---------------------------------------------------------------- pixels
+// One template for both pixel kernels.  <false> with an empty pack is pgtt_render()'s kernel: the same arguments and, instruction for instruction,
+// the device code it had as a plain kernel (tools/side_isa_diff.py lists it under its new symbol; the bodies are equal).  <true, MapArgs> adds the
+// map call's staging (the env's window of heights, un-toroidalised once into window order), the column walk behind the other primitives, the
+// column's albedo (the tint layer is read from global memory once per pixel, at the hit cell) and the columns in the shadow ray.
+// LDS of <true>: 2624 + 6400 + 2048 + 36864 = 47936 bytes, under the 64 KB a launch gets without an attribute.
+__device__ __forceinline__ MapArgs map_args() { return MapArgs{}; }
+__device__ __forceinline__ MapArgs map_args(MapArgs ma) { return ma; }
+
+template <bool kMap, class... Map>
 __global__ void __launch_bounds__(kTile * kTile) render_pixel_kernel(const float* __restrict__ ws, const float* __restrict__ boxes, int B,
                                                                      const float* __restrict__ markers, int M, int ngeom, int W, int H, int tiles_x,
                                                                      int shadows, uint32_t* __restrict__ rgba, float* __restrict__ depth,
-                                                                     int32_t* __restrict__ seg) {
+                                                                     int32_t* __restrict__ seg, Map... map) {
   __shared__ float sh_view[kViewWords];
   __shared__ float sh_box[PGTT_MAX_BOX * kBoxWords];
   __shared__ float sh_mk[PGTT_RENDER_MAX_MARKER * 4];
+  __shared__ float sh_map[kMap ? PGTT_RENDER_MAP_MAX_GRID * PGTT_RENDER_MAP_MAX_GRID : 1];
+  const MapArgs ma = map_args(map...);
   const int vi = blockIdx.y, tid = threadIdx.x;
   const float* rec = ws + (size_t)vi * kViewWords;
   for (int i = tid; i < kHeadWords + ngeom * kGeomWords; i += blockDim.x) sh_view[i] = rec[i];
@@ -184,6 +275,28 @@ __global__ void __launch_bounds__(kTile * kTile) render_pixel_kernel(const float
   if (M > 0) {
     const float* src = markers + (size_t)vi * M * 4;
     for (int i = tid; i < M * 4; i += blockDim.x) sh_mk[i] = src[i];
+  }
+  // the map call: window cell (a, b) is world cell (lo + (a, b)) and lives at slot [(lo_x + a) mod G][(lo_y + b) mod G]
+  int G = 0, slot_x0 = 0, slot_y0 = 0;
+  size_t env_cells = 0;
+  float win_x = 0.f, win_y = 0.f;
+  if constexpr (kMap) {
+    G = ma.G;
+    const int e = __float_as_int(rec[13]);
+    const int lim = 1 << 30;
+    const int lo_x = min(max(ma.origin[2 * e], -lim), lim) - G / 2, lo_y = min(max(ma.origin[2 * e + 1], -lim), lim) - G / 2;
+    slot_x0 = lo_x % G; if (slot_x0 < 0) slot_x0 += G;
+    slot_y0 = lo_y % G; if (slot_y0 < 0) slot_y0 += G;
+    env_cells = (size_t)e * G * G;
+    win_x = (float)lo_x * ma.res; win_y = (float)lo_y * ma.res;
+    const float* src = ma.map + env_cells;
+    for (int i = tid; i < G * G; i += blockDim.x) {
+      const int a = i / G, b = i - a * G;
+      int sa = slot_x0 + a, sb = slot_y0 + b;
+      if (sa >= G) sa -= G;
+      if (sb >= G) sb -= G;
+      sh_map[i] = src[sa * G + sb];
+    }
   }
   __syncthreads();
 
@@ -200,7 +313,7 @@ __global__ void __launch_bounds__(kTile * kTile) render_pixel_kernel(const float
   float best = INFINITY;
   int id = PGTT_SEG_SKY;
   V3 n = v3(0.f, 0.f, 1.f);
-  if (d.z != 0.f) {
+  if ((!kMap || ma.terrain) && d.z != 0.f) {
     const float t = -o.z / d.z;
     if (t > 0.f) { best = t; id = PGTT_SEG_PLANE; }
   }
@@ -218,6 +331,15 @@ __global__ void __launch_bounds__(kTile * kTile) render_pixel_kernel(const float
   for (int k = 0; k < M; k++) {
     const float t = hit_sphere(o, d, ld3(sh_mk + 4 * k), sh_mk[4 * k + 3]);
     if (t < best) { best = t; id = PGTT_SEG_MARKER + k; }
+  }
+  if constexpr (kMap) {
+    int cell, axis;
+    const float t = hit_columns(sh_map, G, ma.res, ma.floor_z, ma.lift, v3(o.x - win_x, o.y - win_y, o.z), d, best, cell, axis);
+    if (t < best) {
+      best = t; id = PGTT_SEG_CELL + cell;
+      const float c = axis == 0 ? d.x : axis == 1 ? d.y : d.z, sgn = c < 0.f ? 1.f : -1.f;
+      n = v3(axis == 0 ? sgn : 0.f, axis == 1 ? sgn : 0.f, axis == 2 ? sgn : 0.f);
+    }
   }
 
   V3 col;
@@ -248,10 +370,26 @@ __global__ void __launch_bounds__(kTile * kTile) render_pixel_kernel(const float
         hit_box(o, d, bx, axis, sgn);
         n = sgn * ld3(G + 3 + 3 * axis);
       }
-    } else {
+    } else if (!kMap || id < PGTT_SEG_CELL) {
       const float* mk = sh_mk + 4 * (id - PGTT_SEG_MARKER);
       alb = v3(PGTT_RENDER_MARKER_R, PGTT_RENDER_MARKER_G, PGTT_RENDER_MARKER_B);
       n = (1.f / mk[3]) * (p - ld3(mk));
+    } else {
+      // a column: coloured by the tint layer at its slot, or by its own height
+      const int cell = id - PGTT_SEG_CELL;
+      float s = sh_map[cell];
+      if (ma.tint) {
+        const int a = cell / G, b = cell - a * G;
+        int sa = slot_x0 + a, sb = slot_y0 + b;
+        if (sa >= G) sa -= G;
+        if (sb >= G) sb -= G;
+        s = ma.tint[env_cells + sa * G + sb];
+      }
+      const float x = fminf(fmaxf((s - ma.tint_lo) / (ma.tint_hi - ma.tint_lo), 0.f), 1.f);
+      alb = s != s ? v3(PGTT_RENDER_MAP_NOVALUE_R, PGTT_RENDER_MAP_NOVALUE_G, PGTT_RENDER_MAP_NOVALUE_B)
+                   : v3(PGTT_RENDER_MAP_COLD_R + (PGTT_RENDER_MAP_HOT_R - PGTT_RENDER_MAP_COLD_R) * x,
+                        PGTT_RENDER_MAP_COLD_G + (PGTT_RENDER_MAP_HOT_G - PGTT_RENDER_MAP_COLD_G) * x,
+                        PGTT_RENDER_MAP_COLD_B + (PGTT_RENDER_MAP_HOT_B - PGTT_RENDER_MAP_COLD_B) * x);
     }
     if (dot(n, d) > 0.f) n = -1.f * n;
     V3 l = v3(PGTT_RENDER_LIGHT_X, PGTT_RENDER_LIGHT_Y, PGTT_RENDER_LIGHT_Z);
@@ -267,6 +405,13 @@ __global__ void __launch_bounds__(kTile * kTile) render_pixel_kernel(const float
         occ = hit_box(so, l, sh_box + b * kBoxWords, axis, sgn) < INFINITY;
       }
       for (int g = 0; g < ngeom && !occ; g++) occ = hit_geom(so, l, sh_view + kHeadWords + g * kGeomWords) < INFINITY;
+      if constexpr (kMap) {
+        // ... and the columns: the same walk, toward the light
+        if (!occ) {
+          int cell, axis;
+          occ = hit_columns(sh_map, G, ma.res, ma.floor_z, ma.lift, v3(so.x - win_x, so.y - win_y, so.z), l, INFINITY, cell, axis) < INFINITY;
+        }
+      }
       vis = occ ? 0.f : 1.f;
     }
     const float s = PGTT_RENDER_AMBIENT + PGTT_RENDER_DIFFUSE * ndl * vis;
@@ -294,6 +439,7 @@ PGTT_SIDE_EXPORTS(render, RENDER)
 int pgtt_render_sizeof_geom(void) { return (int)sizeof(PgttRenderGeom); }
 int pgtt_render_sizeof_camera(void) { return (int)sizeof(PgttRenderCamera); }
 int pgtt_render_sizeof_views(void) { return (int)sizeof(PgttRenderViews); }
+int pgtt_render_sizeof_map(void) { return (int)sizeof(PgttRenderMap); }
 
 int64_t pgtt_render_workspace_bytes(int num_views) {
   if (num_views < 1 || num_views > PGTT_RENDER_MAX_VIEWS) return 0;
@@ -324,25 +470,36 @@ int pgtt_render_set_terrain(pgtt_render_handle h, const float* boxes, int T, int
   return h->scene.set_terrain(boxes, T, B, "pgtt_render_set_terrain");
 }
 
-int pgtt_render(pgtt_render_handle h, const PgttRenderViews* v, void* stream) {
-  if (!h || !v) return fail(PGTT_E_ARG, "pgtt_render: null argument");
-  if (!v->state || !v->rgba || !v->workspace || !v->env_ids || !v->cameras) return fail(PGTT_E_ARG, "pgtt_render: state, rgba, workspace, env_ids and cameras are required");
-  if ((uintptr_t)v->workspace % 16 != 0) return fail(PGTT_E_ARG, "pgtt_render: workspace must be 16-byte aligned");
-  if (v->num_envs < 1) return fail(PGTT_E_ARG, "pgtt_render: num_envs must be >= 1");
-  if (v->num_views < 1 || v->num_views > PGTT_RENDER_MAX_VIEWS) return fail(PGTT_E_ARG, "pgtt_render: num_views outside [1, PGTT_RENDER_MAX_VIEWS]");
+}  // extern "C"
+
+namespace {
+
+// what both render entries refuse; `who` is the entry's name
+int check_views(pgtt_render_handle h, const PgttRenderViews* v, const char* who) {
+  const std::string p = std::string(who) + ": ";
+  if (!h || !v) return fail(PGTT_E_ARG, p + "null argument");
+  if (!v->state || !v->rgba || !v->workspace || !v->env_ids || !v->cameras) return fail(PGTT_E_ARG, p + "state, rgba, workspace, env_ids and cameras are required");
+  if ((uintptr_t)v->workspace % 16 != 0) return fail(PGTT_E_ARG, p + "workspace must be 16-byte aligned");
+  if (v->num_envs < 1) return fail(PGTT_E_ARG, p + "num_envs must be >= 1");
+  if (v->num_views < 1 || v->num_views > PGTT_RENDER_MAX_VIEWS) return fail(PGTT_E_ARG, p + "num_views outside [1, PGTT_RENDER_MAX_VIEWS]");
   if (v->width < 1 || v->height < 1 || v->width > PGTT_RENDER_MAX_DIM || v->height > PGTT_RENDER_MAX_DIM)
-    return fail(PGTT_E_ARG, "pgtt_render: width and height must be in [1, PGTT_RENDER_MAX_DIM]");
-  if (v->num_markers < 0 || v->num_markers > PGTT_RENDER_MAX_MARKER) return fail(PGTT_E_ARG, "pgtt_render: num_markers outside [0, PGTT_RENDER_MAX_MARKER]");
-  if (v->num_markers > 0 && !v->markers) return fail(PGTT_E_ARG, "pgtt_render: num_markers > 0 needs a markers buffer");
+    return fail(PGTT_E_ARG, p + "width and height must be in [1, PGTT_RENDER_MAX_DIM]");
+  if (v->num_markers < 0 || v->num_markers > PGTT_RENDER_MAX_MARKER) return fail(PGTT_E_ARG, p + "num_markers outside [0, PGTT_RENDER_MAX_MARKER]");
+  if (v->num_markers > 0 && !v->markers) return fail(PGTT_E_ARG, p + "num_markers > 0 needs a markers buffer");
   for (int i = 0; i < v->num_views; i++) {
-    if (v->env_ids[i] < 0 || v->env_ids[i] >= v->num_envs) return fail(PGTT_E_ARG, "pgtt_render: env id outside [0, num_envs)");
+    if (v->env_ids[i] < 0 || v->env_ids[i] >= v->num_envs) return fail(PGTT_E_ARG, p + "env id outside [0, num_envs)");
     const PgttRenderCamera& c = v->cameras[i];
-    if (c.mode < PGTT_CAM_FIXED || c.mode > PGTT_CAM_TRACK_YAW) return fail(PGTT_E_ARG, "pgtt_render: unknown camera mode");
-    if (!(c.distance > 0.f) || !std::isfinite(c.distance)) return fail(PGTT_E_ARG, "pgtt_render: camera distance must be positive");
-    if (!(c.fovy_deg > 0.f) || !(c.fovy_deg < 180.f)) return fail(PGTT_E_ARG, "pgtt_render: fovy must be in (0, 180) degrees");
+    if (c.mode < PGTT_CAM_FIXED || c.mode > PGTT_CAM_TRACK_YAW) return fail(PGTT_E_ARG, p + "unknown camera mode");
+    if (!(c.distance > 0.f) || !std::isfinite(c.distance)) return fail(PGTT_E_ARG, p + "camera distance must be positive");
+    if (!(c.fovy_deg > 0.f) || !(c.fovy_deg < 180.f)) return fail(PGTT_E_ARG, p + "fovy must be in (0, 180) degrees");
     if (!std::isfinite(c.azimuth_deg) || !std::isfinite(c.elevation_deg) || !std::isfinite(c.target[0]) || !std::isfinite(c.target[1]) || !std::isfinite(c.target[2]))
-      return fail(PGTT_E_ARG, "pgtt_render: camera angles and target must be finite");
+      return fail(PGTT_E_ARG, p + "camera angles and target must be finite");
   }
+  return PGTT_OK;
+}
+
+// both entries: the setup kernel over the views in chunks, then one pixel launch - the map call's when `m` is given
+int launch_views(pgtt_render_handle h, const PgttRenderViews* v, const PgttRenderMap* m, void* stream) {
   HIP_TRY(hipSetDevice(h->scene.device));
   hipStream_t st = (hipStream_t)stream;
   float* ws = (float*)v->workspace;
@@ -355,11 +512,42 @@ int pgtt_render(pgtt_render_handle h, const PgttRenderViews* v, void* stream) {
                        h->scene.d_model, h->scene.d_geoms, h->ngeom, ws, v->body_pose);
   }
   const int tiles_x = (v->width + kTile - 1) / kTile, tiles_y = (v->height + kTile - 1) / kTile;
-  hipLaunchKernelGGL(render_pixel_kernel, dim3(tiles_x * tiles_y, v->num_views), dim3(kTile * kTile), 0, st, ws, h->scene.d_boxes, h->scene.B, v->markers,
-                     v->num_markers, h->ngeom, v->width, v->height, tiles_x, (v->flags & PGTT_RENDER_SHADOWS) ? 1 : 0, v->rgba, v->depth,
-                     v->segmentation);
+  const dim3 grid(tiles_x * tiles_y, v->num_views), block(kTile * kTile);
+  const int shadows = (v->flags & PGTT_RENDER_SHADOWS) ? 1 : 0;
+  if (!m) {
+    hipLaunchKernelGGL((render_pixel_kernel<false>), grid, block, 0, st, ws, h->scene.d_boxes, h->scene.B, v->markers, v->num_markers, h->ngeom, v->width,
+                       v->height, tiles_x, shadows, v->rgba, v->depth, v->segmentation);
+  } else {
+    const int terrain = (m->flags & PGTT_RENDER_MAP_TERRAIN) ? 1 : 0;
+    const MapArgs ma = {m->map, m->origin, m->tint, m->grid, m->res, m->floor_z, m->lift, m->tint_lo, m->tint_hi, terrain};
+    hipLaunchKernelGGL((render_pixel_kernel<true, MapArgs>), grid, block, 0, st, ws, h->scene.d_boxes, terrain ? h->scene.B : 0, v->markers, v->num_markers,
+                       h->ngeom, v->width, v->height, tiles_x, shadows, v->rgba, v->depth, v->segmentation, ma);
+  }
   HIP_TRY(hipGetLastError());
   return PGTT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pgtt_render(pgtt_render_handle h, const PgttRenderViews* v, void* stream) {
+  if (int rc = check_views(h, v, "pgtt_render")) return rc;
+  return launch_views(h, v, nullptr, stream);
+}
+
+int pgtt_render_map(pgtt_render_handle h, const PgttRenderViews* v, const PgttRenderMap* m, void* stream) {
+  const std::string p = "pgtt_render_map: ";
+  if (int rc = check_views(h, v, "pgtt_render_map")) return rc;
+  if (!m) return fail(PGTT_E_ARG, p + "null PgttRenderMap");
+  if (!m->map || !m->origin) return fail(PGTT_E_ARG, p + "map and origin are required");
+  if (m->grid < 1 || m->grid > PGTT_RENDER_MAP_MAX_GRID) return fail(PGTT_E_ARG, p + "grid outside [1, PGTT_RENDER_MAP_MAX_GRID]");
+  if (!(m->res > 0.f) || !std::isfinite(m->res)) return fail(PGTT_E_ARG, p + "res must be positive and finite");
+  if (!std::isfinite(m->floor_z) || !std::isfinite(m->lift)) return fail(PGTT_E_ARG, p + "floor_z and lift must be finite");
+  if (!std::isfinite(m->tint_lo) || !std::isfinite(m->tint_hi)) return fail(PGTT_E_ARG, p + "tint_lo and tint_hi must be finite");
+  if (!(m->tint_lo < m->tint_hi)) return fail(PGTT_E_ARG, p + "tint_hi must be above tint_lo");
+  if (m->flags & ~PGTT_RENDER_MAP_TERRAIN) return fail(PGTT_E_ARG, p + "unknown flag bits");
+  return launch_views(h, v, m, stream);
 }
 
 }  // extern "C"

@@ -27,6 +27,10 @@ SPHERE, CAPSULE, BOX = 0, 1, 2
 CAM_MODES = {"fixed": 0, "track": 1, "track_yaw": 2}
 SHADOWS = 1
 SEG_SKY, SEG_PLANE, SEG_BOX, SEG_GEOM, SEG_MARKER = -1, 0, 1, 1000, 2000
+SEG_CELL = 10000                     # + a * G + b, the window cell (a, b) of a map call
+MAP_MAX_GRID, MAP_TERRAIN = 96, 1
+MAP_COLD, MAP_HOT, MAP_NOVALUE = (0.15, 0.35, 0.85), (0.95, 0.25, 0.10), (0.45, 0.45, 0.45)
+MAP_FLOOR_Z, MAP_HEIGHT_RANGE, MAP_OVERLAY_LIFT = -0.05, (-0.1, 1.0), 0.01      # render_map's defaults
 
 f, i32 = C.c_float, C.c_int32
 
@@ -46,7 +50,12 @@ class PgttRenderViews(C.Structure):
                 ("body_pose", C.c_void_p), ("workspace", C.c_void_p)]
 
 
-assert C.sizeof(PgttRenderGeom) == 60 and C.sizeof(PgttRenderCamera) == 32
+class PgttRenderMap(C.Structure):
+    _fields_ = [("map", C.c_void_p), ("origin", C.c_void_p), ("tint", C.c_void_p), ("grid", i32), ("res", f), ("floor_z", f), ("lift", f),
+                ("tint_lo", f), ("tint_hi", f), ("flags", i32)]
+
+
+assert C.sizeof(PgttRenderGeom) == 60 and C.sizeof(PgttRenderCamera) == 32 and C.sizeof(PgttRenderMap) == 3 * C.sizeof(C.c_void_p) + 7 * 4 + 4
 
 
 class RenderError(RuntimeError):
@@ -58,7 +67,9 @@ SIDE = _sidelib.SideLib("render", RenderError, {
     "pgtt_render_create": (None, [C.POINTER(abi.PgttModel), C.POINTER(PgttRenderGeom), C.c_int, C.c_int, C.POINTER(vp)]),
     "pgtt_render_destroy": (None, [vp]), "pgtt_render_set_terrain": (None, [vp, vp, C.c_int, C.c_int]),
     "pgtt_render_workspace_bytes": (C.c_int64, [C.c_int]), "pgtt_render": (None, [vp, C.POINTER(PgttRenderViews), vp]),
-}, {"pgtt_render_sizeof_geom": PgttRenderGeom, "pgtt_render_sizeof_camera": PgttRenderCamera, "pgtt_render_sizeof_views": PgttRenderViews})
+    "pgtt_render_map": (None, [vp, C.POINTER(PgttRenderViews), C.POINTER(PgttRenderMap), vp]),
+}, {"pgtt_render_sizeof_geom": PgttRenderGeom, "pgtt_render_sizeof_camera": PgttRenderCamera, "pgtt_render_sizeof_views": PgttRenderViews,
+    "pgtt_render_sizeof_map": PgttRenderMap})
 LIB_PATH, EXPORTS, lib, check, build_info = SIDE.path, SIDE.exports, SIDE.lib, SIDE.check, SIDE.build_info
 
 
@@ -240,6 +251,14 @@ class Renderer(_sidelib.Handle):
         -> {"rgba": [V, H, W, 4] uint8, "rgb": its first three channels, "depth": [V, H, W] float32, "segmentation": [V, H, W] int32,
         "body_pose": [V, 13, 7] float32} (the last three when asked for).  `outputs` may hold preallocated tensors under the same keys."""
         import torch
+        v, out, keep = self._views(env_ids, camera, markers, depth, segmentation, body_pose, outputs)
+        check(self._lib.pgtt_render(self._h, C.byref(v), torch.cuda.current_stream(self.env.device).cuda_stream))
+        out["rgb"] = out["rgba"][..., :3]
+        return out
+
+    def _views(self, env_ids, camera, markers, depth, segmentation, body_pose, outputs):
+        """the PgttRenderViews of a call, its output dict and what has to outlive the call (host arrays, the converted markers)"""
+        import torch
         env = self.env
         ids = [int(i) for i in (env_ids.tolist() if hasattr(env_ids, "tolist") else env_ids)]
         V, H, W = len(ids), self.height, self.width
@@ -273,7 +292,72 @@ class Renderer(_sidelib.Handle):
         for k in ("depth", "segmentation", "body_pose"):
             setattr(v, k, out[k].data_ptr() if k in out else None)
         v.workspace = self._workspace(V).data_ptr() if 1 <= V <= MAX_VIEWS else None
-        check(self._lib.pgtt_render(self._h, C.byref(v), torch.cuda.current_stream(dev).cuda_stream))
+        return v, out, (id_arr, cam_arr, mk)
+
+    def render_map(self, env_ids, map, camera: Union[Camera, Sequence[Camera], None] = None, markers=None, depth: bool = False,
+                   segmentation: bool = False, outputs: Optional[Dict] = None, terrain: bool = False, lift: Optional[float] = None,
+                   floor_z: Optional[float] = None, tint=None, tint_range=None) -> Dict:
+        """The views of render() with an elevation map drawn as a height field of cell columns (pgtt_render_map, include/pgtt_render.h): the
+        belief view, or with terrain=True the map lifted over the true scene.
+        map: an elevation.ElevationMap (its map, origin, grid and res), or dict(map=[N, G, G] float32, origin=[N, 2] int32, grid=G, res=) of
+        tensors on the env's device, in the map's slot layout; NaN = not drawn.
+        tint: None / "height" (the colour follows the height, over tint_range or (-0.1, 1.0)), "var" (an ElevationMap's variance layer, over
+        (0, var_max)), "dist" (a dense fill's distance layer over (0, passes), with the FILLED map as the heights), or any [N, G, G] float32
+        tensor in the same layout (over tint_range, or (0, 1)); a NaN tint shows MAP_NOVALUE.
+        floor_z: the plane every column stands on (-0.05 unless given); lift: added to every height when drawn (0, or 0.01 with terrain=True).
+        -> the dict render() returns."""
+        import torch
+        dev = self.env.device
+        if isinstance(map, dict):
+            missing = [k for k in ("map", "origin", "grid", "res") if k not in map]
+            if missing:
+                raise ValueError(f"render_map: the map dict lacks {missing}")
+            hmap, origin, G, res, emap = map["map"], map["origin"], int(map["grid"]), float(map["res"]), None
+        else:
+            hmap, origin, G, res, emap = map.map, map.origin, int(map.grid), float(map.res), map
+        lo_hi = None
+        if tint is None or (isinstance(tint, str) and tint == "height"):
+            layer, lo_hi = None, MAP_HEIGHT_RANGE
+        elif isinstance(tint, str):
+            if emap is None:
+                raise ValueError(f"render_map: tint={tint!r} names a layer of an ElevationMap; with a dict give the layer itself")
+            if tint == "var":
+                if getattr(emap, "variance", None) is None:
+                    raise ValueError("render_map: tint='var' needs a map made with variance=")
+                layer, lo_hi = emap.var, (0.0, float(emap.variance["var_max"]))
+            elif tint == "dist":
+                if not getattr(emap, "dense", False):
+                    raise ValueError("render_map: tint='dist' needs a map made with fill > 0 and dense=True")
+                hmap, layer, lo_hi = emap.filled_map, emap.filled_dist_map.to(torch.float32), (0.0, float(emap.passes))
+            else:
+                raise ValueError(f"render_map: tint must be None, 'height', 'var', 'dist' or a tensor, not {tint!r}")
+        else:
+            layer, lo_hi = tint, (0.0, 1.0)
+        if tint_range is not None:
+            lo_hi = (float(tint_range[0]), float(tint_range[1]))
+        if not 1 <= G <= MAP_MAX_GRID:
+            raise ValueError(f"render_map: grid must be in [1, {MAP_MAX_GRID}], not {G}")
+        n = self.env.num_envs
+        for name, t, shape, dtype in (("map", hmap, (n, G, G), torch.float32), ("origin", origin, (n, 2), torch.int32), ("tint", layer, (n, G, G), torch.float32)):
+            if t is None and name == "tint":
+                continue
+            if not isinstance(t, torch.Tensor):
+                raise ValueError(f"render_map: {name} must be a tensor")
+            if tuple(t.shape) != shape or t.dtype != dtype:
+                raise ValueError(f"render_map: {name} must be {list(shape)} {dtype}, not {list(t.shape)} {t.dtype}")
+            if t.device != dev:
+                raise ValueError(f"render_map: {name} is on {t.device}, the env on {dev}")
+            if not t.is_contiguous():
+                raise ValueError(f"render_map: {name} must be contiguous")
+        v, out, keep = self._views(env_ids, camera, markers, depth, segmentation, False, outputs)
+        m = PgttRenderMap()
+        m.map, m.origin, m.tint = hmap.data_ptr(), origin.data_ptr(), None if layer is None else layer.data_ptr()
+        m.grid, m.res = G, res
+        m.floor_z = MAP_FLOOR_Z if floor_z is None else float(floor_z)
+        m.lift = (MAP_OVERLAY_LIFT if terrain else 0.0) if lift is None else float(lift)
+        m.tint_lo, m.tint_hi = lo_hi
+        m.flags = MAP_TERRAIN if terrain else 0
+        check(self._lib.pgtt_render_map(self._h, C.byref(v), C.byref(m), torch.cuda.current_stream(dev).cuda_stream))
         out["rgb"] = out["rgba"][..., :3]
         return out
 
