@@ -110,7 +110,8 @@ class Rollout:
     """T steps of the env under a mix of the two drivers.  Per step: the teacher acts deterministically on the true observation (nothing stored, its
     raw head into `head`), `head` goes to row t of `labels` through the student's device-side row counter, the student acts on `obs` (its storage's
     "obs" rows record what it saw), the env gets the teacher's tanh(loc) where `mask` is set and the student's action elsewhere, the student
-    records.  No host read-back.  The steps are plain launches: the sensors' ticks inside env.step are not pinned under graph capture."""
+    records.  No host read-back.  The steps are plain launches; that env.step with its sensors' ticks, captured in a graph, replays the eager bits
+    is held by tests/test_gpu_stack.py (test_the_captured_step_is_the_eager_step)."""
 
     def __init__(self, env, teacher: PolicyMLP, obs: torch.Tensor, T: int, seed: int = 0, student_noise: bool = False, memory: int = 0):
         """memory = R > 0: the student is a recurrent_policy.RecurrentActor (the caller loads its weights); its storage has "obs", "mem0" and
