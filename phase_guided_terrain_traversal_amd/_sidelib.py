@@ -1,8 +1,8 @@
 """What the modules of the six side libraries share - render.py (libpgtt_render.so), depth.py (libpgtt_depth.so), perceive.py
 (libpgtt_perceive.so), elevation.py (libpgtt_elevation.so), learn.py (libpgtt_learn.so) and lidar.py (libpgtt_lidar.so): SideLib, which loads a side library through ctypes,
-turns its return codes into the module's exception and parses its build info; the terrain / close methods of a handle's owner; and the three env
-pointers the three ray casters read.  Imported by those modules only: env.py does not reach it unless a depth camera, a LiDAR, a student or an
-elevation map is asked for."""
+turns its return codes into the module's exception and parses its build info; the terrain / close methods of a handle's owner; the three env
+pointers the three ray casters read; and RaySensor, what the depth camera and the LiDAR both do around their own buffers.  Imported by those
+modules only: env.py does not reach it unless a depth camera, a LiDAR, a student or an elevation map is asked for."""
 from __future__ import annotations
 
 import ctypes as C
@@ -87,3 +87,43 @@ class Handle:
             self.close()
         except Exception:
             pass
+
+
+def fill_sensor_config(c, near, far, mount_body, mount_pos, mount_quat, every, see_robot, sigma, dropout, seed, env_id_offset):
+    """the fields PgttDepthConfig and PgttLidarConfig both have, set on `c`; no checks: the library makes its own"""
+    c.near, c.far, c.mount_body, c.every, c.see_robot = float(near), float(far), int(mount_body), int(every), int(bool(see_robot))
+    c.mount_pos[:] = [float(x) for x in mount_pos]
+    c.mount_quat[:] = [float(x) for x in mount_quat]
+    c.noise_sigma, c.dropout, c.seed, c.env_id_offset = float(sigma), float(dropout), int(seed) & (2 ** 64 - 1), int(env_id_offset)
+    return c
+
+
+def noise_args(noise: Optional[Dict]):
+    """-> (sigma, dropout, seed) of a sensor's `noise` setting, None or a dict"""
+    noise = dict(noise or {})
+    return noise.get("sigma", 0.0), noise.get("dropout", 0.0), noise.get("seed", 0)
+
+
+class RaySensor(Handle):
+    """a sensor mounted on every env of a Joystick, DepthCamera or LidarScanner: the subclass also sets _side (its module's SideLib), owns its
+    output buffers and binds them"""
+    _side: Optional[SideLib] = None
+
+    def _create(self, env, config, geoms, *pattern) -> None:
+        """pgtt_<x>_create(model, config, *pattern, geoms, ngeom, device, num_envs, &handle), the env's terrain, the tick counter"""
+        import torch
+        from . import render
+        self.env, self.config = env, config
+        self.geoms = list(render.default_robot_geoms(env.model) if geoms is None else geoms)
+        self._lib = self._side.lib()
+        self._ms = abi.model_struct(env.model)
+        self._h = C.c_void_p()
+        self._check(getattr(self._lib, self._prefix + "_create")(C.byref(self._ms), C.byref(config), *pattern, render.geom_array(self.geoms),
+                                                                 len(self.geoms), env.device.index or 0, env.num_envs, C.byref(self._h)))
+        self.set_terrain(env.terrain)
+        self.counter = torch.zeros(1, dtype=torch.int64, device=env.device)
+
+    def _tick(self, force: bool) -> None:
+        """pgtt_<x>(handle, force, stream) on the env's current stream"""
+        import torch
+        self._check(getattr(self._lib, self._prefix)(self._h, int(bool(force)), torch.cuda.current_stream(self.env.device).cuda_stream))

@@ -11,7 +11,7 @@
 //            un-normalised direction the slab parameter of a box IS the distance along the optical axis, and a record holds all that the
 //            slab test needs (the origin in the box frame, the box's axes, the half extents).  Every lane walks the same list (LDS
 //            broadcasts, wave-uniform trip count), takes the minimum with the plane, clamps, adds the noise and stores coalesced.
-// A tick that the sensor period skips returns at once in every workgroup (the decision reads counter[0] on the device); depth_advance_kernel,
+// A tick that the sensor period skips returns at once in every workgroup (the decision reads counter[0] on the device); sensor_advance_kernel,
 // enqueued behind it, adds one to the counter.  Nothing is shared between envs: an env's image does not depend on the batch.
 #include <hip/hip_runtime.h>
 
@@ -19,8 +19,7 @@
 #include <cstdint>
 
 #include "../../include/pgtt_depth.h"
-#include "pgtt_raycast.hip.h"
-#include "pgtt_raycast_host.h"
+#include "pgtt_sensor.hip.h"
 
 // experiment build (pgtt_side.mk, EXTRA=-DPGTT_DEPTH_NOCULL): every box and geom is kept; the figure DESIGN.md 14 compares against
 #ifdef PGTT_DEPTH_NOCULL
@@ -28,12 +27,6 @@
 #endif
 
 namespace {
-
-constexpr int kLanes = 256;             // lanes per workgroup = per env
-constexpr int kWaves = kLanes / 64;
-constexpr int kBoxWords = 16;           // LDS box, camera frame: ray origin in the box frame[3], axes r0 r1 r2 [9], half extents[3], pad
-constexpr int kGeomWords = 16;          // LDS geom, camera frame: centre[3], axes r0 r1 r2 [9], size[3], type
-static_assert(PGTT_MAX_BOX <= kLanes && PGTT_RENDER_MAX_GEOM <= 64, "one lane per box, the geoms in one wave");
 
 struct DepthArgs {
   const float* state;
@@ -52,18 +45,6 @@ struct DepthArgs {
   unsigned long long seed;
   long long env_off;
 };
-
-// Philox4x32-10, the env's generator (pgtt.h)
-__device__ __forceinline__ void philox4x32_10(unsigned k0, unsigned k1, unsigned& c0, unsigned& c1, unsigned& c2, unsigned& c3) {
-#pragma unroll
-  for (int r = 0; r < 10; r++) {
-    const unsigned h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
-    const unsigned h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
-    const unsigned n0 = h1 ^ c1 ^ k0, n2 = h0 ^ c3 ^ k1;
-    c0 = n0; c1 = l1; c2 = n2; c3 = l0;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-}
 
 // the camera: world vector -> camera frame (x right, y up, z forward)
 struct Cam { V3 o, right, up, fwd; };
@@ -96,26 +77,6 @@ __device__ __forceinline__ float hit_box(const float* __restrict__ r, float u, f
     tf = fminf(tf, fmaxf(t1, t2));
   }
   return (tn <= tf && tn > 0.f) ? tn : INFINITY;
-}
-// sphere / capsule for a ray from the origin along the UNIT direction d: t = distance along the ray
-__device__ __forceinline__ float hit_sphere(V3 oc, V3 d, float r) {
-  const float b = dot(oc, d), cc = dot(oc, oc) - r * r, disc = b * b - cc;
-  if (disc < 0.f) return INFINITY;
-  const float t = -b - sqrtf(disc);
-  return t > 0.f ? t : INFINITY;
-}
-// the cylinder's quadratic in its cross-product form; a <= 1e-12 baba, decided before h: the ray runs along the axis (see pgtt_raycast.hip.h)
-__device__ __forceinline__ float hit_capsule(V3 d, V3 c, V3 ax, float r, float hl) {
-  const V3 pa = c - hl * ax, ba = (2.f * hl) * ax, oa = -1.f * pa;
-  const V3 bd = cross(ba, d), bo = cross(ba, oa);
-  const float baba = dot(ba, ba), bard = dot(ba, d), baoa = dot(ba, oa);
-  const float a = dot(bd, bd), b = dot(bd, bo), cc = dot(bo, bo) - r * r * baba;
-  if (!(a > 1e-12f * baba)) return fminf(hit_sphere(oa, d, r), hit_sphere(oa - ba, d, r));
-  const float h = b * b - a * cc;
-  if (h < 0.f) return INFINITY;
-  const float t = (-b - sqrtf(h)) / a, y = baoa + t * bard;
-  if (y > 0.f && y < baba) return t > 0.f ? t : INFINITY;
-  return hit_sphere(y <= 0.f ? oa : oa - ba, d, r);
 }
 
 template <bool NOISE>
@@ -282,20 +243,9 @@ __global__ void __launch_bounds__(kLanes) depth_kernel(DepthArgs a) {
       }
     }
     float val = fminf(fmaxf(best, a.near_m), a.far_m);
-    if (NOISE) {
-      unsigned c0 = (unsigned)(a.env_off + e), c1 = (unsigned)tick, c2 = PGTT_RS_DEPTH, c3 = (unsigned)p;
-      philox4x32_10((unsigned)a.seed, (unsigned)(a.seed >> 32), c0, c1, c2, c3);
-      const float k24 = 1.0f / 16777216.0f;
-      const float u0 = (float)(c0 >> 8) * k24, u1 = (float)(c1 >> 8) * k24, u2 = (float)(c2 >> 8) * k24;
-      const float z = sqrtf(-2.f * logf(1.f - u1)) * cosf(6.283185307179586f * u2);
-      val = u0 < a.dropout ? a.far_m : fminf(fmaxf(val * (1.f + a.sigma * z), a.near_m), a.far_m);
-    }
+    if (NOISE) val = noisy(val, a.seed, a.env_off, e, tick, PGTT_RS_DEPTH, p, a.sigma, a.dropout, a.near_m, a.far_m);
     out[p] = val;
   }
-}
-
-__global__ void __launch_bounds__(64) depth_advance_kernel(int64_t* counter) {
-  if (threadIdx.x == 0 && blockIdx.x == 0) counter[0] = counter[0] + 1;
 }
 
 }  // namespace
@@ -323,23 +273,11 @@ int pgtt_depth_create(const PgttModel* model, const PgttDepthConfig* cfg, const 
   if (cfg->width < 1 || cfg->width > PGTT_DEPTH_MAX_DIM || cfg->height < 1 || cfg->height > PGTT_DEPTH_MAX_DIM)
     return fail(PGTT_E_ARG, "pgtt_depth_create: width and height must be in [1, PGTT_DEPTH_MAX_DIM]");
   if (!(cfg->fovy_deg > 0.f) || !(cfg->fovy_deg < 180.f)) return fail(PGTT_E_ARG, "pgtt_depth_create: fovy must be in (0, 180) degrees");
-  if (!(cfg->near > 0.f) || !(cfg->near < cfg->far) || !std::isfinite(cfg->far)) return fail(PGTT_E_ARG, "pgtt_depth_create: need 0 < near < far, finite");
-  if (cfg->mount_body < 0 || cfg->mount_body >= PGTT_NBODY) return fail(PGTT_E_ARG, "pgtt_depth_create: mount_body outside [0, PGTT_NBODY)");
-  if (cfg->every < 1) return fail(PGTT_E_ARG, "pgtt_depth_create: every must be >= 1");
-  if (cfg->see_robot != 0 && cfg->see_robot != 1) return fail(PGTT_E_ARG, "pgtt_depth_create: see_robot must be 0 or 1");
-  if (!(cfg->noise_sigma >= 0.f) || !std::isfinite(cfg->noise_sigma)) return fail(PGTT_E_ARG, "pgtt_depth_create: noise_sigma must be >= 0");
-  if (!(cfg->dropout >= 0.f) || !(cfg->dropout < 1.f)) return fail(PGTT_E_ARG, "pgtt_depth_create: dropout must be in [0, 1)");
-  double qn = 0.0;
-  for (int i = 0; i < 4; i++) qn += (double)cfg->mount_quat[i] * cfg->mount_quat[i];
-  qn = std::sqrt(qn);
-  if (!(qn > 0.0) || !std::isfinite(qn)) return fail(PGTT_E_ARG, "pgtt_depth_create: mount_quat must be a non-zero quaternion");
-  for (int i = 0; i < 3; i++)
-    if (!std::isfinite(cfg->mount_pos[i])) return fail(PGTT_E_ARG, "pgtt_depth_create: mount_pos must be finite");
+  if (int rc = check_sensor_config(cfg, "pgtt_depth_create")) return rc;
   if (int rc = check_geoms(geoms, ngeom, "pgtt_depth_create")) return rc;
   if (int rc = check_device(device, "pgtt_depth_create")) return rc;
   pgtt_depth_camera* h = new pgtt_depth_camera();
-  h->num_envs = num_envs; h->ngeom = ngeom; h->cfg = *cfg; h->scene.device = device;
-  for (int i = 0; i < 4; i++) h->cfg.mount_quat[i] = (float)(cfg->mount_quat[i] / qn);
+  h->num_envs = num_envs; h->ngeom = ngeom; h->cfg = with_unit_mount(*cfg); h->scene.device = device;
   if (int rc = h->scene.upload(model, geoms, ngeom)) { pgtt_depth_destroy(h); return rc; }
   *out = h;
   return PGTT_OK;
@@ -371,21 +309,10 @@ int pgtt_depth(pgtt_depth_handle h, int force, void* stream) {
   HIP_TRY(hipSetDevice(h->scene.device));
   const PgttDepthConfig& c = h->cfg;
   DepthArgs a{};
-  a.state = h->buf.state; a.params = h->buf.params; a.variant = h->buf.variant; a.depth = h->buf.depth; a.counter = h->buf.counter;
-  a.boxes = h->scene.d_boxes; a.model = h->scene.d_model; a.geoms = h->scene.d_geoms;
-  a.N = h->num_envs; a.T = h->scene.T; a.B = h->scene.B; a.ngeom = c.see_robot ? h->ngeom : 0;
-  a.W = c.width; a.H = c.height; a.mount_body = c.mount_body; a.every = c.every; a.force = force ? 1 : 0;
+  fill_sensor_args(a, c, h->buf, h->scene, h->num_envs, h->ngeom, force);
+  a.depth = h->buf.depth; a.W = c.width; a.H = c.height;
   a.tan_y = (float)std::tan(0.5 * (double)c.fovy_deg * 3.14159265358979323846 / 180.0);
-  a.near_m = c.near; a.far_m = c.far;
-  for (int i = 0; i < 3; i++) a.mpos[i] = c.mount_pos[i];
-  for (int i = 0; i < 4; i++) a.mquat[i] = c.mount_quat[i];
-  a.sigma = c.noise_sigma; a.dropout = c.dropout; a.seed = c.seed; a.env_off = c.env_id_offset;
-  hipStream_t st = (hipStream_t)stream;
-  if (c.noise_sigma > 0.f || c.dropout > 0.f) hipLaunchKernelGGL(depth_kernel<true>, dim3(h->num_envs), dim3(kLanes), 0, st, a);
-  else hipLaunchKernelGGL(depth_kernel<false>, dim3(h->num_envs), dim3(kLanes), 0, st, a);
-  hipLaunchKernelGGL(depth_advance_kernel, dim3(1), dim3(64), 0, st, h->buf.counter);
-  HIP_TRY(hipGetLastError());
-  return PGTT_OK;
+  return launch_sensor_tick(depth_kernel<true>, depth_kernel<false>, a, (hipStream_t)stream);
 }
 
 }  // extern "C"

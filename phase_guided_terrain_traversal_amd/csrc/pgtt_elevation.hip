@@ -62,6 +62,7 @@
 #include <cstdint>
 
 #include "../../include/pgtt_elevation.h"
+#include "pgtt_side_device.hip.h"
 #include "pgtt_side_host.h"
 
 namespace {
@@ -886,18 +887,6 @@ struct OdoArgs {
   unsigned k0, k1, gid0;                                       // the Philox key (seed lo, seed hi); (uint32) env_id_offset
   float dt, sigma_xy, sigma_z, sigma_yaw, yaw_bias, scale;
 };
-
-// Philox4x32-10, the env's generator (pgtt.h); this library's own copy, as pgtt_depth.hip and pgtt_lidar.hip have theirs
-__device__ __forceinline__ void philox4x32_10(unsigned k0, unsigned k1, unsigned& c0, unsigned& c1, unsigned& c2, unsigned& c3) {
-#pragma unroll
-  for (int r = 0; r < 10; r++) {
-    const unsigned h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
-    const unsigned h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
-    const unsigned n0 = h1 ^ c1 ^ k0, n2 = h0 ^ c3 ^ k1;
-    c0 = n0; c1 = l1; c2 = n2; c3 = l0;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-}
 
 // the transform of an env's points, T_est o T_true^-1: the cosine and sine of the new psi, the true base position, the new position error
 enum { T_COS = 0, T_SIN = 1, T_B = 2, T_E = 5, T_N = 8 };

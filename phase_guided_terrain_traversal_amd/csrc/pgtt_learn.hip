@@ -25,6 +25,7 @@
 #include <cstdint>
 
 #include "../../include/pgtt_learn.h"
+#include "pgtt_side_device.hip.h"
 #include "pgtt_side_host.h"
 
 namespace {
@@ -458,17 +459,6 @@ template <bool SAMPLE> struct TailK : RecurrentK { SampleK s; };
 template <> struct TailK<false> : RecurrentK {};
 
 __device__ __forceinline__ float softplus_t(float x) { return x > 20.f ? x : log1pf(expf(x)); }      // torch F.softplus (threshold 20)
-
-__device__ __forceinline__ void philox4x32_10(unsigned k0, unsigned k1, unsigned& c0, unsigned& c1, unsigned& c2, unsigned& c3) {
-#pragma unroll
-  for (int r = 0; r < 10; r++) {
-    const unsigned h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
-    const unsigned h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
-    const unsigned n0 = h1 ^ c1 ^ k0, n2 = h0 ^ c3 ^ k1;
-    c0 = n0; c1 = l1; c2 = n2; c3 = l0;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-}
 
 constexpr int kHead = 24, kAct = 12;
 

@@ -13,7 +13,7 @@
 // A pattern direction may be exactly perpendicular to a box axis, and hit_box states that case.  (So may a camera ray: with an odd width or
 // height the centre column or row of (u, v, 1) has u = 0 or v = 0.  The camera leaves it to rcp(0) = inf, which decides the slab the same way:
 // inside it no constraint, outside it a miss; tests/test_gpu_raycast_edges.py holds both kernels to that.)
-// A tick that the sensor period skips returns at once in every workgroup (the decision reads counter[0] on the device); lidar_advance_kernel,
+// A tick that the sensor period skips returns at once in every workgroup (the decision reads counter[0] on the device); sensor_advance_kernel,
 // enqueued behind it, adds one to the counter.  Nothing is shared between envs: an env's scan does not depend on the batch.
 #include <hip/hip_runtime.h>
 
@@ -22,16 +22,9 @@
 #include <vector>
 
 #include "../../include/pgtt_lidar.h"
-#include "pgtt_raycast.hip.h"
-#include "pgtt_raycast_host.h"
+#include "pgtt_sensor.hip.h"
 
 namespace {
-
-constexpr int kLanes = 256;             // lanes per workgroup = per env
-constexpr int kWaves = kLanes / 64;
-constexpr int kBoxWords = 16;           // LDS box, sensor frame: ray origin in the box frame[3], axes r0 r1 r2 [9], half extents[3], pad
-constexpr int kGeomWords = 16;          // LDS geom, sensor frame: centre[3], axes r0 r1 r2 [9], size[3], type
-static_assert(PGTT_MAX_BOX <= kLanes && PGTT_RENDER_MAX_GEOM <= 64, "one lane per box, the geoms in one wave");
 
 struct LidarArgs {
   const float* state;
@@ -52,18 +45,6 @@ struct LidarArgs {
   unsigned long long seed;
   long long env_off;
 };
-
-// Philox4x32-10, the env's generator (pgtt.h)
-__device__ __forceinline__ void philox4x32_10(unsigned k0, unsigned k1, unsigned& c0, unsigned& c1, unsigned& c2, unsigned& c3) {
-#pragma unroll
-  for (int r = 0; r < 10; r++) {
-    const unsigned h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
-    const unsigned h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
-    const unsigned n0 = h1 ^ c1 ^ k0, n2 = h0 ^ c3 ^ k1;
-    c0 = n0; c1 = l1; c2 = n2; c3 = l0;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-}
 
 // the sensor: world vector -> sensor frame (its own x, y, z axes)
 struct Sensor { V3 o, ax, ay, az; };
@@ -95,26 +76,6 @@ __device__ __forceinline__ float hit_box(const float* __restrict__ r, V3 d) {
     }
   }
   return (tn <= tf && tn > 0.f) ? tn : INFINITY;
-}
-// sphere / capsule for a ray from the origin along the UNIT direction d: t = distance along the ray
-__device__ __forceinline__ float hit_sphere(V3 oc, V3 d, float r) {
-  const float b = dot(oc, d), cc = dot(oc, oc) - r * r, disc = b * b - cc;
-  if (disc < 0.f) return INFINITY;
-  const float t = -b - sqrtf(disc);
-  return t > 0.f ? t : INFINITY;
-}
-// the cylinder's quadratic in its cross-product form; a <= 1e-12 baba, decided before h: the ray runs along the axis (see pgtt_raycast.hip.h)
-__device__ __forceinline__ float hit_capsule(V3 d, V3 c, V3 ax, float r, float hl) {
-  const V3 pa = c - hl * ax, ba = (2.f * hl) * ax, oa = -1.f * pa;
-  const V3 bd = cross(ba, d), bo = cross(ba, oa);
-  const float baba = dot(ba, ba), bard = dot(ba, d), baoa = dot(ba, oa);
-  const float a = dot(bd, bd), b = dot(bd, bo), cc = dot(bo, bo) - r * r * baba;
-  if (!(a > 1e-12f * baba)) return fminf(hit_sphere(oa, d, r), hit_sphere(oa - ba, d, r));
-  const float h = b * b - a * cc;
-  if (h < 0.f) return INFINITY;
-  const float t = (-b - sqrtf(h)) / a, y = baoa + t * bard;
-  if (y > 0.f && y < baba) return t > 0.f ? t : INFINITY;
-  return hit_sphere(y <= 0.f ? oa : oa - ba, d, r);
 }
 
 template <bool NOISE>
@@ -272,14 +233,7 @@ __global__ void __launch_bounds__(kLanes) lidar_kernel(LidarArgs a) {
       best = fminf(best, t);
     }
     float val = fminf(fmaxf(best, a.near_m), a.far_m);
-    if (NOISE) {
-      unsigned c0 = (unsigned)(a.env_off + e), c1 = (unsigned)tick, c2 = PGTT_RS_LIDAR, c3 = (unsigned)r;
-      philox4x32_10((unsigned)a.seed, (unsigned)(a.seed >> 32), c0, c1, c2, c3);
-      const float k24 = 1.0f / 16777216.0f;
-      const float u0 = (float)(c0 >> 8) * k24, u1 = (float)(c1 >> 8) * k24, u2 = (float)(c2 >> 8) * k24;
-      const float z = sqrtf(-2.f * logf(1.f - u1)) * cosf(6.283185307179586f * u2);
-      val = u0 < a.dropout ? a.far_m : fminf(fmaxf(val * (1.f + a.sigma * z), a.near_m), a.far_m);
-    }
+    if (NOISE) val = noisy(val, a.seed, a.env_off, e, tick, PGTT_RS_LIDAR, r, a.sigma, a.dropout, a.near_m, a.far_m);
     out[r] = val;
     if (pts) {
       const float nanv = __uint_as_float(0x7fc00000u);
@@ -291,25 +245,11 @@ __global__ void __launch_bounds__(kLanes) lidar_kernel(LidarArgs a) {
   }
 }
 
-__global__ void __launch_bounds__(64) lidar_advance_kernel(int64_t* counter) {
-  if (threadIdx.x == 0 && blockIdx.x == 0) counter[0] = counter[0] + 1;
-}
-
 // the checks of the config and of the pattern; `who` prefixes the message
 int resolve(const PgttLidarConfig* cfg, const float* dirs, int R, const char* who) {
   const std::string p = std::string(who) + ": ";
   if (!cfg) return fail(PGTT_E_ARG, p + "null config");
-  if (!(cfg->near > 0.f) || !(cfg->near < cfg->far) || !std::isfinite(cfg->far)) return fail(PGTT_E_ARG, p + "need 0 < near < far, finite");
-  if (cfg->mount_body < 0 || cfg->mount_body >= PGTT_NBODY) return fail(PGTT_E_ARG, p + "mount_body outside [0, PGTT_NBODY)");
-  if (cfg->every < 1) return fail(PGTT_E_ARG, p + "every must be >= 1");
-  if (cfg->see_robot != 0 && cfg->see_robot != 1) return fail(PGTT_E_ARG, p + "see_robot must be 0 or 1");
-  if (!(cfg->noise_sigma >= 0.f) || !std::isfinite(cfg->noise_sigma)) return fail(PGTT_E_ARG, p + "noise_sigma must be >= 0");
-  if (!(cfg->dropout >= 0.f) || !(cfg->dropout < 1.f)) return fail(PGTT_E_ARG, p + "dropout must be in [0, 1)");
-  double qn = 0.0;
-  for (int i = 0; i < 4; i++) qn += (double)cfg->mount_quat[i] * cfg->mount_quat[i];
-  if (!(qn > 0.0) || !std::isfinite(qn)) return fail(PGTT_E_ARG, p + "mount_quat must be a non-zero quaternion");
-  for (int i = 0; i < 3; i++)
-    if (!std::isfinite(cfg->mount_pos[i])) return fail(PGTT_E_ARG, p + "mount_pos must be finite");
+  if (int rc = check_sensor_config(cfg, who)) return rc;
   if (R < 1 || R > PGTT_LIDAR_MAX_RAYS) return fail(PGTT_E_ARG, p + "R must be in [1, PGTT_LIDAR_MAX_RAYS]");
   if (!dirs) return fail(PGTT_E_ARG, p + "null pattern");
   for (int r = 0; r < R; r++) {
@@ -350,11 +290,7 @@ int pgtt_lidar_create(const PgttModel* model, const PgttLidarConfig* cfg, const 
   if (int rc = check_geoms(geoms, ngeom, "pgtt_lidar_create")) return rc;
   if (int rc = check_device(device, "pgtt_lidar_create")) return rc;
   pgtt_lidar_scanner* h = new pgtt_lidar_scanner();
-  h->num_envs = num_envs; h->ngeom = ngeom; h->R = R; h->cfg = *cfg; h->scene.device = device;
-  double qn = 0.0;
-  for (int i = 0; i < 4; i++) qn += (double)cfg->mount_quat[i] * cfg->mount_quat[i];
-  qn = std::sqrt(qn);
-  for (int i = 0; i < 4; i++) h->cfg.mount_quat[i] = (float)(cfg->mount_quat[i] / qn);
+  h->num_envs = num_envs; h->ngeom = ngeom; h->R = R; h->cfg = with_unit_mount(*cfg); h->scene.device = device;
   // the pattern: unit rows (normalised in double), padded to 16 bytes
   std::vector<float> tab((size_t)R * 4, 0.f);
   for (int r = 0; r < R; r++) {
@@ -397,23 +333,10 @@ int pgtt_lidar(pgtt_lidar_handle h, int force, void* stream) {
   if (!h) return fail(PGTT_E_ARG, "pgtt_lidar: null handle");
   if (!h->bound) return fail(PGTT_E_STATE, "pgtt_lidar: no buffers bound (pgtt_lidar_bind first)");
   HIP_TRY(hipSetDevice(h->scene.device));
-  const PgttLidarConfig& c = h->cfg;
   LidarArgs a{};
-  a.state = h->buf.state; a.params = h->buf.params; a.variant = h->buf.variant; a.range = h->buf.range; a.points = h->buf.points;
-  a.counter = h->buf.counter;
-  a.boxes = h->scene.d_boxes; a.model = h->scene.d_model; a.geoms = h->scene.d_geoms; a.dirs = h->d_dirs;
-  a.N = h->num_envs; a.T = h->scene.T; a.B = h->scene.B; a.ngeom = c.see_robot ? h->ngeom : 0;
-  a.R = h->R; a.mount_body = c.mount_body; a.every = c.every; a.force = force ? 1 : 0;
-  a.near_m = c.near; a.far_m = c.far;
-  for (int i = 0; i < 3; i++) a.mpos[i] = c.mount_pos[i];
-  for (int i = 0; i < 4; i++) a.mquat[i] = c.mount_quat[i];
-  a.sigma = c.noise_sigma; a.dropout = c.dropout; a.seed = c.seed; a.env_off = c.env_id_offset;
-  hipStream_t st = (hipStream_t)stream;
-  if (c.noise_sigma > 0.f || c.dropout > 0.f) hipLaunchKernelGGL(lidar_kernel<true>, dim3(h->num_envs), dim3(kLanes), 0, st, a);
-  else hipLaunchKernelGGL(lidar_kernel<false>, dim3(h->num_envs), dim3(kLanes), 0, st, a);
-  hipLaunchKernelGGL(lidar_advance_kernel, dim3(1), dim3(64), 0, st, h->buf.counter);
-  HIP_TRY(hipGetLastError());
-  return PGTT_OK;
+  fill_sensor_args(a, h->cfg, h->buf, h->scene, h->num_envs, h->ngeom, force);
+  a.range = h->buf.range; a.points = h->buf.points; a.dirs = h->d_dirs; a.R = h->R;
+  return launch_sensor_tick(lidar_kernel<true>, lidar_kernel<false>, a, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -18,9 +18,21 @@
 //   6e-8 |ba| (one rounded product), which gives an a of about 1e-14 baba for a ray exactly along the axis, so the threshold has a margin of 100.
 //   It is decided BEFORE h = b^2 - a cc is looked at: the compiler may form ba x d twice, contracted differently, and multiply the two, so
 //   that an a at noise level, and with it h, comes out negative for a ray that meets the capsule.
-// Included by those three translation units only.  It does not include pgtt_common.hip.h (whose qrot(v, q) is the physics kernels' form): that
-// file is inside the physics source hash (srchash.py), and this one is inside the three side hashes only.  For the same reason the Philox copies
-// of pgtt_depth.hip, pgtt_lidar.hip and pgtt_policy.hip stay where they are.
+// The two onboard sensors, depth_kernel and lidar_kernel, are one shape, and what they state in common was tried piece by piece with hipcc for gfx950
+// and tools/side_isa_diff.py against the build before:
+//   moved into a shared header, text unchanged                              device code of depth_kernel<*>, lidar_kernel<*>
+//   Philox, hit_sphere, hit_capsule, the counter's advance kernel           identical, all four
+//   + the noise tail as a function                                          <false> identical; <true> one s_nop fewer and one select in its short
+//                                                                           encoding, every other opcode count equal; every buffer bit-identical
+//                                                                           on an MI355X (profiles/r34_ab_raycast.txt)
+//   + the body chain as a function (the args by reference, or plain         all four differ: 18 fewer fused multiply-adds, a 12-byte load split in
+//     pointers and scalars)                                                 two - bits would move
+//   + the placement of boxes and geoms with the compaction                  all four differ: another mix of packed fma / mul / add - bits would move
+// What was a __device__ function already moves freely; what stands inline in a kernel does not.  So pgtt_sensor.hip.h is the home of the pair's
+// common tests (hit_sphere, hit_capsule: the ray from the origin, a unit d), of the noise tail and of their common host code, and the chain, the
+// placement, hit_box (whose two forms differ on purpose), the culls and the loops keep their text in both kernels.
+// Included by those three translation units only (the sensors' through pgtt_sensor.hip.h).  It does not include pgtt_common.hip.h (whose qrot(v, q)
+// is the physics kernels' form): that file is inside the physics source hash (srchash.py), and this one is inside the three side hashes only.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -74,15 +74,11 @@ def pitch_quat(pitch_deg: float) -> np.ndarray:
 def config_struct(width, height, fovy, near, far, mount_body=0, mount_pos=(0.0, 0.0, 0.0), mount_quat=(1.0, 0.0, 0.0, 0.0), every=1,
                   see_robot=True, sigma=0.0, dropout=0.0, seed=0, env_id_offset=0) -> PgttDepthConfig:
     c = PgttDepthConfig()
-    c.width, c.height, c.fovy_deg, c.near, c.far = int(width), int(height), float(fovy), float(near), float(far)
-    c.mount_body, c.every, c.see_robot = int(mount_body), int(every), int(bool(see_robot))
-    c.mount_pos[:] = [float(x) for x in mount_pos]
-    c.mount_quat[:] = [float(x) for x in mount_quat]
-    c.noise_sigma, c.dropout, c.seed, c.env_id_offset = float(sigma), float(dropout), int(seed) & (2 ** 64 - 1), int(env_id_offset)
-    return c
+    c.width, c.height, c.fovy_deg = int(width), int(height), float(fovy)
+    return _sidelib.fill_sensor_config(c, near, far, mount_body, mount_pos, mount_quat, every, see_robot, sigma, dropout, seed, env_id_offset)
 
 
-class DepthCamera(_sidelib.Handle):
+class DepthCamera(_sidelib.RaySensor):
     """A depth camera rigidly mounted on body `mount_body` (0 = the torso) of every env of a Joystick, pose (mount_pos, mount_quat wxyz) in that
     body's frame: optical axis = the mount frame's +x, up = its +z.  `pitch_deg` instead of mount_quat pitches the camera down by that angle.
     every: the sensor period in ticks; see_robot: the robot's own primitives (`geoms`, default render.default_robot_geoms(model)) are in the
@@ -90,30 +86,20 @@ class DepthCamera(_sidelib.Handle):
     (seed, env.env_id_offset + env, tick counter, pixel) as the env's own streams are.
     The defaults of Joystick(depth=...) (depth.DEFAULTS) are placeholders for a Go2 head camera: settings, not facts.
     Runs on the env's device and current stream; writes nothing but `image` and `counter`."""
-    _prefix, _check = "pgtt_depth", staticmethod(check)
+    _side, _prefix, _check = SIDE, SIDE.prefix, staticmethod(check)
 
     def __init__(self, env, width: int, height: int, fovy: float, near: float, far: float, mount_body: int = 0,
                  mount_pos: Sequence[float] = (0.0, 0.0, 0.0), mount_quat: Optional[Sequence[float]] = None, pitch_deg: Optional[float] = None,
                  every: int = 1, see_robot: bool = True, noise: Optional[Dict] = None, geoms: Optional[Sequence[Dict]] = None):
         import torch
-        from . import render
         if mount_quat is not None and pitch_deg is not None:
             raise ValueError("DepthCamera: give mount_quat or pitch_deg, not both")
         if mount_quat is None:
             mount_quat = pitch_quat(pitch_deg or 0.0)
-        noise = dict(noise or {})
-        self.env, self.width, self.height, self.near, self.far, self.every = env, int(width), int(height), float(near), float(far), int(every)
-        self.geoms = list(render.default_robot_geoms(env.model) if geoms is None else geoms)
-        self.config = config_struct(width, height, fovy, near, far, mount_body, mount_pos, mount_quat, every, see_robot,
-                                    noise.get("sigma", 0.0), noise.get("dropout", 0.0), noise.get("seed", 0), env.env_id_offset)
-        self._lib = lib()
-        self._ms = abi.model_struct(env.model)
-        self._h = C.c_void_p()
-        check(self._lib.pgtt_depth_create(C.byref(self._ms), C.byref(self.config), render.geom_array(self.geoms), len(self.geoms),
-                                          env.device.index or 0, env.num_envs, C.byref(self._h)))
-        self.set_terrain(env.terrain)
+        self.width, self.height, self.near, self.far, self.every = int(width), int(height), float(near), float(far), int(every)
+        self._create(env, config_struct(width, height, fovy, near, far, mount_body, mount_pos, mount_quat, every, see_robot,
+                                        *_sidelib.noise_args(noise), env.env_id_offset), geoms)
         self.image = torch.zeros((env.num_envs, self.height, self.width), dtype=torch.float32, device=env.device)
-        self.counter = torch.zeros(1, dtype=torch.int64, device=env.device)
         self.bind()
 
     def bind(self) -> None:
@@ -125,6 +111,5 @@ class DepthCamera(_sidelib.Handle):
 
     def tick(self, force: bool = False):
         """one sensor tick: the image is recomputed when `force` or the counter is 0 modulo `every` (decided on the device), the counter advances"""
-        import torch
-        check(self._lib.pgtt_depth(self._h, int(bool(force)), torch.cuda.current_stream(self.env.device).cuda_stream))
+        self._tick(force)
         return self.image

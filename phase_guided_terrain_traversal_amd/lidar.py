@@ -85,11 +85,7 @@ def config_struct(near, far, mount_body=0, mount_pos=(0.0, 0.0, 0.0), mount_quat
                   dropout=0.0, seed=0, env_id_offset=0) -> PgttLidarConfig:
     """no checks: the library makes its own (pgtt_lidar_check)"""
     c = PgttLidarConfig()
-    c.near, c.far, c.mount_body, c.every, c.see_robot = float(near), float(far), int(mount_body), int(every), int(bool(see_robot))
-    c.mount_pos[:] = [float(x) for x in mount_pos]
-    c.mount_quat[:] = [float(x) for x in mount_quat]
-    c.noise_sigma, c.dropout, c.seed, c.env_id_offset = float(sigma), float(dropout), int(seed) & (2 ** 64 - 1), int(env_id_offset)
-    return c
+    return _sidelib.fill_sensor_config(c, near, far, mount_body, mount_pos, mount_quat, every, see_robot, sigma, dropout, seed, env_id_offset)
 
 
 def pattern_array(pattern) -> np.ndarray:
@@ -106,7 +102,7 @@ def check_settings(config: PgttLidarConfig, pattern) -> None:
     check(lib().pgtt_lidar_check(C.byref(config), p.ctypes.data if p.size else None, p.shape[0]))
 
 
-class LidarScanner(_sidelib.Handle):
+class LidarScanner(_sidelib.RaySensor):
     """A scanning range sensor rigidly mounted on body `mount_body` (0 = the torso) of every env of a Joystick, pose (mount_pos, mount_quat wxyz) in
     that body's frame.  pattern: [R, 3] ray directions in the sensor frame (normalised by the library), or n_az / n_el / az_deg / el_deg of
     spherical_pattern.  every: the sensor period in ticks; see_robot: the robot's own primitives (`geoms`, default
@@ -114,32 +110,21 @@ class LidarScanner(_sidelib.Handle):
     seed=0), the draws keyed by (seed, env.env_id_offset + env, tick counter, ray) as the env's own streams are.
     The defaults of Joystick(lidar=...) (lidar.DEFAULTS) are placeholders for a chin-mounted hemispherical scanner: settings, not facts.
     Runs on the env's device and current stream; writes nothing but `ranges`, `points` and `counter`."""
-    _prefix, _check = "pgtt_lidar", staticmethod(check)
+    _side, _prefix, _check = SIDE, SIDE.prefix, staticmethod(check)
 
     def __init__(self, env, near: float, far: float, pattern=None, n_az: Optional[int] = None, n_el: Optional[int] = None, az_deg=(-180.0, 180.0),
                  el_deg=(-85.0, 10.0), mount_body: int = 0, mount_pos: Sequence[float] = (0.0, 0.0, 0.0),
                  mount_quat: Sequence[float] = (1.0, 0.0, 0.0, 0.0), every: int = 1, see_robot: bool = True, noise: Optional[Dict] = None,
                  geoms: Optional[Sequence[Dict]] = None, points: bool = True):
         import torch
-        from . import render
         if (pattern is None) == (n_az is None or n_el is None):
             raise ValueError("LidarScanner: give pattern=[R, 3] or n_az and n_el, not both")
         self.pattern = pattern_array(spherical_pattern(n_az, n_el, az_deg, el_deg) if pattern is None else pattern)
-        noise = dict(noise or {})
-        self.env, self.near, self.far, self.every, self.num_rays = env, float(near), float(far), int(every), int(self.pattern.shape[0])
-        self.geoms = list(render.default_robot_geoms(env.model) if geoms is None else geoms)
-        self.config = config_struct(near, far, mount_body, mount_pos, mount_quat, every, see_robot, noise.get("sigma", 0.0),
-                                    noise.get("dropout", 0.0), noise.get("seed", 0), env.env_id_offset)
-        self._lib = lib()
-        self._ms = abi.model_struct(env.model)
-        self._h = C.c_void_p()
-        check(self._lib.pgtt_lidar_create(C.byref(self._ms), C.byref(self.config), self.pattern.ctypes.data if self.num_rays else None,
-                                          self.num_rays, render.geom_array(self.geoms), len(self.geoms), env.device.index or 0, env.num_envs,
-                                          C.byref(self._h)))
-        self.set_terrain(env.terrain)
+        self.near, self.far, self.every, self.num_rays = float(near), float(far), int(every), int(self.pattern.shape[0])
+        self._create(env, config_struct(near, far, mount_body, mount_pos, mount_quat, every, see_robot, *_sidelib.noise_args(noise), env.env_id_offset),
+                     geoms, self.pattern.ctypes.data if self.num_rays else None, self.num_rays)
         self.ranges = torch.zeros((env.num_envs, self.num_rays), dtype=torch.float32, device=env.device)
         self.points = torch.full((env.num_envs, self.num_rays, 3), float("nan"), dtype=torch.float32, device=env.device) if points else None
-        self.counter = torch.zeros(1, dtype=torch.int64, device=env.device)
         self.bind()
 
     def bind(self) -> None:
@@ -152,6 +137,5 @@ class LidarScanner(_sidelib.Handle):
 
     def tick(self, force: bool = False):
         """one sensor tick: the scan is recomputed when `force` or the counter is 0 modulo `every` (decided on the device), the counter advances"""
-        import torch
-        check(self._lib.pgtt_lidar(self._h, int(bool(force)), torch.cuda.current_stream(self.env.device).cuda_stream))
+        self._tick(force)
         return self.ranges

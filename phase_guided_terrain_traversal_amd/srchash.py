@@ -17,13 +17,15 @@ PHYSICS_SOURCES = ("pgtt_physics_inst.hip", "pgtt_physics.hip.h", "pgtt_physics_
 FLAGS_FRAGMENT = "flags.mk"
 # per side library: the unit and the shared headers in csrc/, then the public headers in include/ (every project file the unit includes)
 _PRELUDE = ("pgtt_side_host.h",)
+_DEVICE = ("pgtt_side_device.hip.h",)                       # Philox: the four libraries whose kernels draw
 _RAYCAST = ("pgtt_raycast.hip.h", "pgtt_raycast_host.h") + _PRELUDE
+_SENSOR = ("pgtt_sensor.hip.h",) + _DEVICE + _RAYCAST       # the two onboard ray sensors
 SIDE_SOURCES = {"render": (("pgtt_render.hip",) + _RAYCAST, ("pgtt_render.h", "pgtt.h")),
-                "depth": (("pgtt_depth.hip",) + _RAYCAST, ("pgtt_depth.h", "pgtt_render.h", "pgtt.h")),
+                "depth": (("pgtt_depth.hip",) + _SENSOR, ("pgtt_depth.h", "pgtt_render.h", "pgtt.h")),
                 "perceive": (("pgtt_perceive.hip",) + _PRELUDE, ("pgtt_perceive.h", "pgtt.h")),
-                "elevation": (("pgtt_elevation.hip",) + _PRELUDE, ("pgtt_elevation.h", "pgtt.h")),
-                "learn": (("pgtt_learn.hip",) + _PRELUDE, ("pgtt_learn.h", "pgtt.h")),
-                "lidar": (("pgtt_lidar.hip",) + _RAYCAST, ("pgtt_lidar.h", "pgtt_render.h", "pgtt.h"))}
+                "elevation": (("pgtt_elevation.hip",) + _DEVICE + _PRELUDE, ("pgtt_elevation.h", "pgtt.h")),
+                "learn": (("pgtt_learn.hip",) + _DEVICE + _PRELUDE, ("pgtt_learn.h", "pgtt.h")),
+                "lidar": (("pgtt_lidar.hip",) + _SENSOR, ("pgtt_lidar.h", "pgtt_render.h", "pgtt.h"))}
 
 
 def hashed_files(pkg: str = _HERE):

@@ -159,6 +159,42 @@ def test_check_refuses():
     lidar.check_settings(lidar.config_struct(**GOOD), pat)
 
 
+# one bad value of every field the LiDAR's config has in common with the camera's (the checks are stated once, csrc/pgtt_sensor.hip.h), in the
+# order of the checks, and the words libpgtt_lidar.so had for it before they were: byte for byte, behind the entry point's name
+SHARED_REFUSALS = [(dict(near=0.0), "need 0 < near < far, finite"), (dict(far=float("inf")), "need 0 < near < far, finite"),
+                   (dict(mount_body=13), "mount_body outside [0, PGTT_NBODY)"), (dict(every=0), "every must be >= 1"),
+                   (dict(see_robot=2), "see_robot must be 0 or 1"), (dict(sigma=-0.1), "noise_sigma must be >= 0"),
+                   (dict(sigma=float("inf")), "noise_sigma must be >= 0"), (dict(dropout=1.0), "dropout must be in [0, 1)"),
+                   (dict(mount_quat=(0.0, 0.0, 0.0, 0.0)), "mount_quat must be a non-zero quaternion"),
+                   (dict(mount_pos=(0.0, float("nan"), 0.0)), "mount_pos must be finite")]
+
+
+@needs_lib
+def test_check_refusal_texts():
+    """pgtt_lidar_check's exact message for each shared field, and for the LiDAR's own checks, which come last: a config that is bad in a
+    shared field AND has R = 0 is refused for the shared field"""
+    L = lidar.lib()
+    pat = lidar.pattern_array(lidar.spherical_pattern(8, 4))
+
+    def message(R=len(pat), dirs=pat, see_robot=True, **kw):
+        cfg = lidar.config_struct(**dict(GOOD, **kw))
+        cfg.see_robot = int(see_robot)                                            # config_struct makes it 0 or 1
+        assert L.pgtt_lidar_check(C.byref(cfg), None if dirs is None else dirs.ctypes.data, R) == -1, kw
+        return L.pgtt_lidar_last_error().decode()
+
+    for kw, text in SHARED_REFUSALS:
+        assert message(**kw) == "pgtt_lidar_check: " + text, kw
+        assert message(R=0, **kw) == "pgtt_lidar_check: " + text, kw
+    assert message(near=0.0, every=0, mount_pos=(float("inf"), 0.0, 0.0)) == "pgtt_lidar_check: need 0 < near < far, finite"
+    assert message(every=0, mount_pos=(float("inf"), 0.0, 0.0)) == "pgtt_lidar_check: every must be >= 1"
+    assert message(R=0) == "pgtt_lidar_check: R must be in [1, PGTT_LIDAR_MAX_RAYS]"
+    assert message(dirs=None) == "pgtt_lidar_check: null pattern"
+    zero_row = pat.copy()
+    zero_row[5] = 0.0
+    assert message(dirs=zero_row) == "pgtt_lidar_check: pattern row 5 is zero or not finite"
+    assert L.pgtt_lidar_check(None, pat.ctypes.data, len(pat)) == -1 and L.pgtt_lidar_last_error().decode() == "pgtt_lidar_check: null config"
+
+
 def test_joystick_refusals():
     """before anything touches a device"""
     from phase_guided_terrain_traversal_amd.env import Joystick

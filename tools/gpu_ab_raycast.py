@@ -1,12 +1,13 @@
-"""A/B check of two builds of the side libraries libpgtt_render.so and libpgtt_depth.so: the same seeded scenes, EVERY buffer the two
-libraries write compared bit for bit (renderer: rgba, depth, segmentation, body_pose; depth camera: the image).
+"""A/B check of two builds of the three ray casters libpgtt_render.so, libpgtt_depth.so and libpgtt_lidar.so: the same seeded scenes, EVERY buffer
+the three libraries write compared bit for bit (renderer: rgba, depth, segmentation, body_pose; depth camera: the image; LiDAR: ranges, points).
    usage: python tools/gpu_ab_raycast.py OLD_DIR NEW_DIR [--out profiles/NAME.txt]
-   (OLD_DIR / NEW_DIR hold the two .so files; each build runs in its own process, render.SIDE.path / depth.SIDE.path set before first use;
-   libpgtt.so is the checkout's in both)
+   (OLD_DIR / NEW_DIR hold the three .so files; each build runs in its own process, render.SIDE.path / depth.SIDE.path / lidar.SIDE.path set
+   before first use; libpgtt.so is the checkout's in both)
 Workloads, the smallest at which these kernels can go wrong: 8 envs on level4 with domain-randomised params (the qpos0 rows) and per-env
 variants, one label out of range, after 5 control steps of seeded small actions; 8 envs on flat ground without params.
 Renderer: fixed / track / track_yaw views at 40x30 (partial 16x16 tiles), shadows on and off, 5 markers.  Depth camera: 24x18 and 64x48,
-see_robot on and off, mounted on the torso and on a thigh, noise off and sigma = 0.02 / dropout = 0.1, every = 1."""
+see_robot on and off, mounted on the torso and on a thigh, noise off and sigma = 0.02 / dropout = 0.1, every = 1.  LiDAR: spherical_pattern(32, 8)
+(256 rays, one full pass of the workgroup) and a 300-ray table (a partial second pass), the same mounts, see_robot and noise settings, points on."""
 import os
 import subprocess
 import sys
@@ -20,12 +21,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def child(lib_dir, out):
     sys.path.insert(0, ROOT)
     import torch
-    from phase_guided_terrain_traversal_amd import abi, configs, depth, mjcf, render
+    from phase_guided_terrain_traversal_amd import abi, configs, depth, lidar, mjcf, render
     from phase_guided_terrain_traversal_amd.env import Joystick
     from phase_guided_terrain_traversal_amd.randomize import domain_randomize
     render.SIDE.path = os.path.join(lib_dir, "libpgtt_render.so")
     depth.SIDE.path = os.path.join(lib_dir, "libpgtt_depth.so")
-    res = {"info/render": np.frombuffer(render.build_info()["src"].encode(), np.uint8), "info/depth": np.frombuffer(depth.build_info()["src"].encode(), np.uint8)}
+    lidar.SIDE.path = os.path.join(lib_dir, "libpgtt_lidar.so")
+    res = {f"info/{m.SIDE.prefix[5:]}": np.frombuffer(m.build_info()["src"].encode(), np.uint8) for m in (render, depth, lidar)}
     n = 8
     for wl in ("level4", "flat"):
         if wl == "level4":
@@ -73,6 +75,19 @@ def child(lib_dir, out):
                         tag = f"{wl}/depth_{W}x{H}_robot{int(see)}_{mname}_noise{int(noise is not None)}"
                         res[tag + "/tick0"], res[tag + "/tick1"] = img.cpu().numpy(), img2.cpu().numpy()
                         cam.close()
+        # LiDAR
+        for pname, pattern in (("256", lidar.spherical_pattern(32, 8)), ("300", lidar.spherical_pattern(30, 10, (-180, 180), (-80, 25)))):
+            for see in (True, False):
+                for mname, mount in mounts.items():
+                    for noise in (None, dict(sigma=0.02, dropout=0.1, seed=11)):
+                        place = dict(mount_body=mount["mount_body"], mount_pos=mount["mount_pos"], mount_quat=depth.pitch_quat(mount.get("pitch_deg", 0.0)))
+                        lid = lidar.LidarScanner(env, **lidar.settings(dict(pattern=pattern, see_robot=see, noise=noise, every=1, **place)), points=True)
+                        tag = f"{wl}/lidar_{pname}_robot{int(see)}_{mname}_noise{int(noise is not None)}"
+                        for tick in (0, 1):                                # counter = 1: other noise draws
+                            lid.tick()
+                            torch.cuda.synchronize()
+                            res[f"{tag}/tick{tick}/ranges"], res[f"{tag}/tick{tick}/points"] = lid.ranges.cpu().numpy(), lid.points.cpu().numpy()
+                        lid.close()
         env.close()
     np.savez(out, **res)
 
@@ -94,9 +109,8 @@ def main():
         files.append(os.path.join(tmp, f"ab_{tag}.npz"))
         subprocess.run([sys.executable, os.path.abspath(__file__), "--child", d, files[-1]], check=True, cwd=ROOT)
     A, B = np.load(files[0]), np.load(files[1])
-    lines = ["# tools/gpu_ab_raycast.py: two builds of libpgtt_render.so / libpgtt_depth.so, every output buffer compared as uint32 / uint8",
-             f"# old: render src={bytes(A['info/render']).decode()} depth src={bytes(A['info/depth']).decode()}",
-             f"# new: render src={bytes(B['info/render']).decode()} depth src={bytes(B['info/depth']).decode()}"]
+    lines = ["# tools/gpu_ab_raycast.py: two builds of libpgtt_render.so / libpgtt_depth.so / libpgtt_lidar.so, every output buffer compared as uint32 / uint8"]
+    lines += [f"# {tag}: " + " ".join(f"{k} src={bytes(X['info/' + k]).decode()}" for k in ("render", "depth", "lidar")) for tag, X in (("old", A), ("new", B))]
     keys = sorted(k for k in A.files if not k.startswith("info/"))
     assert keys == sorted(k for k in B.files if not k.startswith("info/"))
     ndiff = 0

@@ -2,10 +2,11 @@
 from domain_randomize(seed=0), the default pattern of lidar.DEFAULTS, poses after 40 control steps of small random actions; device events around
 20 back-to-back calls after 5 warm-up calls, median [min, max] of 11 such windows, everything in one job.
 
-    python tools/gpu_lidar_time.py [--out profiles/NAME.txt] [--eval]
+    python tools/gpu_lidar_time.py [--out profiles/NAME.txt] [--eval] [--noise]
 
 (i) the LiDAR tick with the robot in the scene; (ii) without it; (iii) pgtt_elevation_points; and for scale, in the same job, (iv) the camera
 tick, (v) pgtt_elevation() and (vi) the env step (no sensor).  None of the figures is a pass criterion.
+--noise: both sensors with sigma = 0.02, dropout = 0.1, so (i), (ii) and (iv) time the kernels that hold the noise tail.
 --eval: evaluate.py's rollout of policy177 on level4, 1000 envs, full domain randomisation, one deterministic episode - on the true observation,
 on the depth-fused map and on the LiDAR-fused map, with the mean share of known scan points of the two maps."""
 import argparse
@@ -18,7 +19,7 @@ sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from phase_guided_terrain_traversal_amd import configs, elevation, lidar, mjcf, perceive  # noqa: E402
+from phase_guided_terrain_traversal_amd import configs, depth, elevation, lidar, mjcf, perceive  # noqa: E402
 from phase_guided_terrain_traversal_amd.env import Joystick  # noqa: E402
 from phase_guided_terrain_traversal_amd.randomize import domain_randomize  # noqa: E402
 
@@ -55,14 +56,16 @@ def main():
     ap.add_argument("--num_envs", type=int, default=4096)
     ap.add_argument("--out", type=str, default=None)
     ap.add_argument("--eval", action="store_true")
+    ap.add_argument("--noise", action="store_true")
     args = ap.parse_args()
     n = args.num_envs
     terrain = np.load(os.path.join(ROOT, "phase_guided_terrain_traversal_amd", "assets", "terrains", "level4.npy"))
     dr = domain_randomize(mjcf.load_model("stairs"), n, seed=0, terrain=terrain)
     kw = dict(params=torch.from_numpy(dr["params"]), variant=torch.from_numpy(dr["variant"]), box_friction=torch.from_numpy(dr["box_friction"]))
     cfg = configs.training_config()
-    env = Joystick("stairs", cfg, num_envs=n, terrain=terrain, device="cuda:0", lidar={}, elevation=dict(source="lidar"), **kw)
-    cam = Joystick("stairs", cfg, num_envs=n, terrain=terrain, device="cuda:0", depth={}, elevation=True, **kw)
+    sensor = dict(noise=dict(sigma=0.02, dropout=0.1)) if args.noise else {}
+    env = Joystick("stairs", cfg, num_envs=n, terrain=terrain, device="cuda:0", lidar=dict(sensor), elevation=dict(source="lidar"), **kw)
+    cam = Joystick("stairs", cfg, num_envs=n, terrain=terrain, device="cuda:0", depth=dict(sensor), elevation=True, **kw)
     plain = Joystick("stairs", cfg, num_envs=n, terrain=terrain, device="cuda:0", **kw)
     g = torch.Generator().manual_seed(1)
     for e in (env, cam, plain):
@@ -71,7 +74,7 @@ def main():
         act = (0.2 * torch.randn(n, 12, generator=g)).clamp(-1, 1).cuda()
         for e in (env, cam, plain):
             e.step(act)
-    blind = lidar.LidarScanner(env, **lidar.settings(dict(see_robot=False)))
+    blind = lidar.LidarScanner(env, **lidar.settings(dict(see_robot=False, **sensor)))
     torch.cuda.synchronize()
     lid, em = env.lidar_scanner, env.elevation_map
     rows = [("(i)   LiDAR tick (force), robot in the scene", window_us(lambda: lid.tick(force=True))),
@@ -85,7 +88,8 @@ def main():
     c, cc = em.config, cam.depth_camera.config
     lines = [f"{n} envs, level4, {lid.num_rays} rays (lidar.DEFAULTS), camera {cc.width}x{cc.height}, G = {c.grid}, res = {c.res:.3f}; us per call, median [min, max] of 11 windows "
              "of 20 calls",
-             f"libpgtt_lidar build: {lidar.build_info()}", f"libpgtt_elevation build: {elevation.build_info()}"]
+             f"libpgtt_lidar build: {lidar.build_info()}", f"libpgtt_depth build: {depth.build_info()}", f"libpgtt_elevation build: {elevation.build_info()}",
+             f"sensor noise: {sensor.get('noise')}"]
     lines += [f"{name:50s} {m:9.1f} [{lo:.1f}, {hi:.1f}]" for name, (m, lo, hi) in rows]
     lines.append(f"rays with a return inside (near, far): {returns:.3f}; (i) per ray {1e3 * rows[0][1][0] / (n * lid.num_rays):.3f} ns, (iv) per pixel "
                  f"{1e3 * rows[3][1][0] / (n * cc.width * cc.height):.3f} ns")
